@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - long-read all-vs-all overlaps/sec of the hot path on synthetic reads (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W [--workload C3|C2|...]
+    python bench.py --gpus N --steps K --warmup W [--workload C3|C2|...] [--full] [--dump-outputs DIR]
     N > 1: bench.py starts its N rank processes itself (one per GPU, before any GPU call: hylight_amd/launch.py); under an
     external launcher (python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...) it uses the ranks
     it was given.
@@ -20,11 +20,18 @@ the timed region starts (hlmi_job_open uploads them; `value_e2e` adds parsing + 
 the same for every N, so the line reports "scaling": "weak"; `value` = overlaps written by all ranks / time.
 `--workload C2` (configs[1], 10 000 reads) runs whole passes per step instead (`--slices 1`).
 
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what needs work of its own beside
+the timed steps: the untimed one-lane step (`roofline.one_lane`), the overlap graph of the pass and of the 1.44 M-row
+layout PAF (with the compiled reference beside it), and the CPU baseline with its parity check (`--no-graph` and
+`--no-cpu-baseline` leave parts of it out).  `--dump-outputs DIR` writes the rows of the last timed step as .npy files
+(`dump_outputs`).
+
 Prints ONE JSON line on rank 0 (fields: README.md / DESIGN.md section 7).
 """
 from __future__ import annotations
 
 import argparse
+import atexit
 import json
 import os
 import shutil
@@ -32,6 +39,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -303,6 +311,60 @@ def stage_bytes(st):
     return ava, flt
 
 
+# ---- --dump-outputs: what the last timed step computed, for comparing two builds -----------------------------------
+DUMP_LIMIT_BYTES = 64 << 20                      # all files of one dump together
+DUMP_SAMPLE_SEED = 20241008
+
+
+def _paf_field(s):
+    if s in ("+", "-"):
+        return 1.0 if s == "+" else -1.0
+    try:
+        return float(s)
+    except ValueError:
+        return float(zlib.crc32(s.encode()))
+
+
+def paf_arrays(path, budget_bytes, seed=DUMP_SAMPLE_SEED):
+    """The rows a stage call wrote (score-sorted PAF) as one float64 array, one row per PAF row: column 0 the row's index
+    in the file, then every PAF column (numbers as written, the strand as +1 / -1, names and tags as the CRC-32 of their
+    text), last the CRC-32 of the whole line.  When all rows do not fit `budget_bytes`, a seeded sample of them (the same
+    rows for the same file length), in file order."""
+    import numpy as np
+    with open(path, "rb") as f:
+        first = f.readline()
+        f.seek(0)
+        n = sum(1 for _ in f)
+    width = len(first.decode().rstrip("\n").rstrip("\t").split("\t")) + 2
+    cap = max(budget_bytes // (8 * width), 0)
+    keep = None
+    if n > cap:
+        keep = set(np.random.default_rng(seed).choice(n, size=cap, replace=False).tolist())
+    out = []
+    with open(path) as f:
+        for i, line in enumerate(f):
+            if keep is not None and i not in keep:
+                continue
+            line = line.rstrip("\n")
+            fields = line.rstrip("\t").split("\t")
+            if len(fields) + 2 != width:
+                raise ValueError(f"{path}: row {i} has {len(fields)} columns, the first row {width - 2}")
+            out.append([float(i)] + [_paf_field(s) for s in fields] + [float(zlib.crc32(line.encode()))])
+    return np.array(out, dtype=np.float64).reshape(len(out), width)
+
+
+def dump_outputs(out_dir, pafs, counts):
+    """--dump-outputs: `overlaps.npy` = the overlaps each stage call of the last timed step reported, `stage_rows.npy`
+    (`stage_rows_call<k>.npy` for a step's further calls) = its PAF rows as paf_arrays gives them; at most
+    DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "overlaps.npy"), np.array(counts, dtype=np.float64))
+    budget = (DUMP_LIMIT_BYTES - 4096 * (len(pafs) + 1)) // max(len(pafs), 1)
+    for k, paf in enumerate(pafs):
+        np.save(os.path.join(out_dir, "stage_rows" + (f"_call{k}" if k else "") + ".npy"), paf_arrays(paf, budget))
+
+
 def main():
     from hylight_amd import workloads as W
     ap = argparse.ArgumentParser()
@@ -315,8 +377,11 @@ def main():
     ap.add_argument("--slices", type=int, default=0, help="slices of the --nsplit chunks per pass (0: workload default)")
     ap.add_argument("--slice0", type=int, default=0, help="slice the first step takes (steps walk on from there; under the pair-once "
                     "rule a chunk's work grows with its index: the middle of the file is the mean)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the one-lane step, the overlap graphs and the CPU baseline (module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-graph", action="store_true", help="--full without the overlap graphs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows of the last timed step to DIR/*.npy (float64, at most 64 MB: dump_outputs)")
     args = ap.parse_args()
 
     from hylight_amd import launch
@@ -353,7 +418,10 @@ def main():
     if slices % world and slices > 1:
         raise SystemExit(f"--slices {slices} must be a multiple of the rank count {world}")
     shares = max(1, slices // world)                 # steps per complete pass
-    work = os.environ.get("HL_BENCH_DIR") or tempfile.mkdtemp(prefix="hl_bench_")
+    work = os.environ.get("HL_BENCH_DIR")
+    if not work:                            # a directory of this run's own (the C3 reads alone are 1 GB): gone at exit
+        work = tempfile.mkdtemp(prefix="hl_bench_")
+        atexit.register(shutil.rmtree, work, True)
     fa = os.path.join(work, f"{cfg['name']}.fa")
     short_fa, con_fa, remain_fa = (os.path.join(work, f"{cfg['name']}.{x}.fa") for x in ("short", "contigs", "remain"))
     if rank == 0 and not os.path.exists(fa):
@@ -392,6 +460,7 @@ def main():
     stage = runners[0][1]
     t_prepare = []
     step_stats = {}
+    step_out = []                           # (PAF, overlaps) of every call of the latest step
 
     def slice_paf(k):                       # every slice of a pass keeps its own file: together they are the stage output
         return out_paf if shares == 1 else f"{out_paf}.slice{k}"
@@ -406,8 +475,11 @@ def main():
             t_prepare.append(time.time() - t)
         n = 0
         step_stats.clear()
+        step_out.clear()
         for k, (rn, st) in enumerate(runners):
-            n += rn.run(slice_paf(i % shares) + (f".call{k}" if k else ""), share=(i % shares, shares), **st)
+            paf = slice_paf(i % shares) + (f".call{k}" if k else "")
+            step_out.append((paf, rn.run(paf, share=(i % shares, shares), **st)))
+            n += step_out[-1][1]
             for key, v in api.last_stats().items():          # (C4s: the counts and kernel times of both calls of the step)
                 step_stats[key] = step_stats.get(key, 0.0) + v
         return n
@@ -436,11 +508,13 @@ def main():
         share_load[(args.warmup + i) % shares if shares > 1 else 0] = (stats.get("anchors", 0.0), step_s[-1])
     fence()
     dt = time.time() - t0
+    if args.dump_outputs and rank == 0:     # (N > 1: rank 0's files hold every rank's rows)
+        dump_outputs(args.dump_outputs, [p for p, _ in step_out], [c for _, c in step_out])
     # Two query batches in flight (lanes) share the card: a kernel's HIP-event time in the timed steps includes
     # the waves of the other lane's kernels.  One more step of the last slice, untimed and with one lane, gives every kernel's
     # duration by itself - the figure earlier rounds reported and a serial rocprofv3 trace shows.
     stats_one_lane = None
-    if stats and stats.get("ava_lanes", 0) > len(runners) and not os.environ.get("HLMI_LANES"):
+    if args.full and stats and stats.get("ava_lanes", 0) > len(runners) and not os.environ.get("HLMI_LANES"):
         os.environ["HLMI_LANES"] = "1"
         try:
             step(args.warmup + args.steps - 1)
@@ -567,7 +641,7 @@ def main():
                 exchange=dict(world=(dist.get_world_size() if world > 1 else 1), backend=(backend if world > 1 else None), per_rank=per_rank),
                 stage_seconds={k: stats[k] for k in ("t_ava_s", "t_filter_s", "t_rows_to_text_s", "t_rows_download_s", "t_final_sort_s", "t_format_sort_write_s", "t_total_s") if k in stats})
     # second half of the BASELINE metric: overlap-graph build seconds (PAF on disk -> GFA on disk), not part of `value`
-    if not args.no_graph and not short_calls:
+    if args.full and not args.no_graph and not short_calls:
         try:
             if shares > 1:                  # the pass's output = the merge of its slices (utils.py:69)
                 have = [slice_paf(k) for k in range(shares) if os.path.exists(slice_paf(k))]
@@ -581,11 +655,11 @@ def main():
         except Exception as e:                                    # the stage number stays valid without it
             line["graph_build_s"] = None
             line["graph_error"] = str(e)[:200]
-    if not args.no_graph and not short_calls and rank == 0:
+    if args.full and not args.no_graph and not short_calls and rank == 0:
         line.update(graph_large(work))
     if os.environ.get("HL_BENCH_STATS"):
         sys.stderr.write("STATS " + json.dumps({k: round(v, 4) for k, v in sorted(stats.items())}) + "\n")
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         budget = float(os.environ.get("HL_CPU_BUDGET_S", "150"))
         if short_calls:      # the first of the two calls: short reads (queries) against the contig pieces (chunked targets)
             line["cpu_baseline"] = cpu_baseline(con_fa, short_fa, cfg["nsplit"], cfg["stage_short"], long_mode=False, budget_s=budget)

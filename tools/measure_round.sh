@@ -11,10 +11,10 @@ mkdir -p gpurun_out
 line() { wl=$1; shift; f=gpurun_out/${tag}_bench_$(echo $wl | tr A-Z a-z); python bench.py --workload $wl "$@" > $f.json 2> $f.err || echo "$wl BENCH FAILED"; tail -c 400 $f.json; }
 case $part in
 c3)   bash tools/profile_round.sh $tag C3 2>&1 | tail -5
-      line C3 --steps 20 --warmup 5
-      line C2 --steps 10 --warmup 3 ;;
+      line C3 --steps 20 --warmup 5 --full
+      line C2 --steps 10 --warmup 3 --full ;;
 c5)   bash tools/profile_round.sh $tag C5 2>&1 | tail -3
-      line C5 --slice0 26 --steps 8 --warmup 1 --no-graph; rm -f /tmp/hlb/C5* ;;
-rest) line C4s --steps 8 --warmup 1 --no-graph; rm -f /tmp/hlb/C4*
-      line C4 --slice0 30 --steps 4 --warmup 1 --no-graph ;;
+      line C5 --slice0 26 --steps 8 --warmup 1 --full --no-graph; rm -f /tmp/hlb/C5* ;;
+rest) line C4s --steps 8 --warmup 1 --full --no-graph; rm -f /tmp/hlb/C4*
+      line C4 --slice0 30 --steps 4 --warmup 1 --full --no-graph ;;
 esac
