@@ -32,6 +32,22 @@ class VqOverlap(C.Structure):
                 ("pad", C.c_char * 3)]
 
 
+class VqGraphOpts(C.Structure):
+    _fields_ = [("min_overlap_len", C.c_uint32), ("min_overlap_perc", C.c_uint32), ("min_read_len", C.c_uint32),
+                ("max_tip_len", C.c_uint32), ("remove_trans", C.c_uint32), ("edge_threshold", C.c_double),
+                ("ov_threshold", C.c_double), ("merge_contigs", C.c_double), ("mismatch", C.c_double),
+                ("ignore_inclusions", C.c_int), ("remove_tips", C.c_int), ("remove_branches", C.c_int),
+                ("remove_backedges", C.c_int), ("max_overlaps", C.c_uint64)]
+
+
+VQ_GRAPH_STATS = ("vertices", "candidates", "duplicates", "inclusions", "edges_built", "conflicts", "moved", "transitive",
+                  "tip_edges", "tip_reads", "branch_edges", "backedges", "edges_final")
+
+
+class VqGraphStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in VQ_GRAPH_STATS]
+
+
 ABI_VERSION = 5          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
@@ -65,6 +81,8 @@ SYMBOLS = {
                                            C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]),
     "hlmi_vq_overlap_scores": (C.c_int, [C.c_char_p, C.POINTER(VqOverlap), C.c_uint64, C.c_double, C.c_uint32, C.POINTER(C.c_double),
                                          C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "hlmi_vq_graph_opts_stageb": (None, [C.POINTER(VqGraphOpts)]),
+    "hlmi_vq_graph": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.c_char_p, C.POINTER(VqGraphStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -250,6 +268,29 @@ def vq_transitive_edges(n_vertices, src, dst, ovlen=None, remove_trans=1):
     _check(load().hlmi_vq_transitive_edges(n_vertices, n, a32(src), a32(dst), a32(ovlen) if ovlen is not None else None,
                                            remove_trans, flags, C.byref(cnt)))
     return list(flags[:n]), cnt.value
+
+
+def vq_graph_opts_stageb():
+    """hlmi_vq_graph_opts_stageb: the options of HyLight's first stage-b iteration, as a dict."""
+    o = VqGraphOpts()
+    load().hlmi_vq_graph_opts_stageb(C.byref(o))
+    return {k: getattr(o, k) for k, _ in VqGraphOpts._fields_}
+
+
+def vq_graph(singles_fastq, overlaps, out_dir, **opts):
+    """ViralQuasispecies --graph_only: the oriented, reduced overlap graph of `overlaps` over the reads
+    of `singles_fastq`, written into out_dir (created if missing).  Options: the fields of hlmi_vq_graph_opts, the
+    stage-b values by default.  -> dict of the stats (hlmi_vq_graph_stats)."""
+    o = VqGraphOpts()
+    load().hlmi_vq_graph_opts_stageb(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(VqGraphOpts._fields_):
+            raise TypeError(f"vq_graph: unknown option {k!r}")
+        setattr(o, k, int(v) if isinstance(v, bool) else v)
+    os.makedirs(out_dir, exist_ok=True)
+    st = VqGraphStats()
+    _check(load().hlmi_vq_graph(_b(singles_fastq), _b(overlaps), C.byref(o), _b(out_dir), C.byref(st)))
+    return {k: getattr(st, k) for k in VQ_GRAPH_STATS}
 
 
 DEVICE = "cuda"          # where the buffers that cross the C ABI live (stage.py allocates them with torch)

@@ -9,6 +9,7 @@
 #include "paf_io.h"
 #include "stage.h"
 #include "textpass.h"
+#include "vq_internal.h"
 
 namespace hlmi {
 void init_device(int device, int threads);
@@ -313,6 +314,19 @@ int hlmi_vq_overlap_scores(const char *fastq_singles, const hlmi_vq_overlap *ov,
         if (!fastq_singles || (n && (!ov || !score || !mismatch_rate || !pos3))) fail(HLMI_EINVAL, "hlmi_vq_overlap_scores: NULL argument");
         require_device();
         vq_overlap_scores(fastq_singles, ov, n, mismatch, min_read_len, score, mismatch_rate, pos3);
+    });
+}
+
+void hlmi_vq_graph_opts_stageb(hlmi_vq_graph_opts *o) {
+    if (o) vq_graph_opts_stageb(o);
+}
+
+int hlmi_vq_graph(const char *singles_fastq, const char *overlaps, const hlmi_vq_graph_opts *o, const char *out_dir,
+                  hlmi_vq_graph_stats *st) {
+    return guarded([&] {
+        if (!singles_fastq || !overlaps || !o || !out_dir || !st) fail(HLMI_EINVAL, "hlmi_vq_graph: NULL argument");
+        require_device();
+        vq_graph_run(singles_fastq, overlaps, *o, out_dir, st);
     });
 }
 

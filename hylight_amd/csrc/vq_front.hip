@@ -3,9 +3,10 @@
 //   * the text of record: which lines of the overlaps file become edge candidates (EdgeCalculator.cpp:561-666 in front
 //     of process_overlaps, Overlap.h:37-72,196-203) - host, integer and string rules only;
 //   * transitive edges by intersection of sorted adjacency lists (GraphAlgos.cpp:746-795,938-993) - device.
-// Between the two the reference scores every candidate from the reads' bases and qualities (EdgeCalculator.cpp:26-139,
-// log / pow / exp thresholds) and orients it (Edge.h): not built.  The reference needs Boost and cannot be compiled in
-// this image, so both pieces are checked against oracle/vq.py only: PARITY UNPINNED.
+// and the quality-aware score of every candidate (EdgeCalculator.cpp:26-139, further down).  The graph built from them
+// (orientation, reductions, writers) is vq_graph.hip / vq_graph_host.cpp, which share the transitive-edge kernels through
+// vq_internal.h.  The reference needs Boost and cannot be compiled in this image, so everything is checked against
+// oracle/vq.py only: PARITY UNPINNED.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,8 +21,10 @@
 #include "dev_prims.h"
 #include "graph.h"
 #include "paf_io.h"
+#include "vq_internal.h"
 
 namespace hlmi {
+using namespace vqk;
 
 // ---------------------------------------------------------------------------------------------
 // 13-column overlaps -> edge candidates
@@ -35,6 +38,12 @@ static std::string without(std::string s, const char *drop) {
 
 void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, int relax_pe, uint64_t max_overlaps,
                        hlmi_vq_overlap *out, uint64_t cap, uint64_t *n_out, uint64_t *n_nonedge, uint64_t *n_skipped) {
+    vq_parse_overlaps(path, min_len, min_perc, relax_pe, max_overlaps, out, cap, n_out, n_nonedge, n_skipped, nullptr);
+}
+
+void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, int relax_pe, uint64_t max_overlaps,
+                       hlmi_vq_overlap *out, uint64_t cap, uint64_t *n_out, uint64_t *n_nonedge, uint64_t *n_skipped,
+                       std::vector<hlmi_vq_overlap> *nonedges) {
     const std::string data = read_file(path);
     uint64_t kept = 0, nonedge = 0, skipped = 0, i = 0;
     size_t pos = 0;
@@ -82,7 +91,11 @@ void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, in
         if (o.len1 >= min_len && ss) { decided = true; edge = perc >= min_perc; }
         else if ((double)o.len1 >= 0.5 * (double)min_len && (double)o.len2 >= 0.5 * (double)min_len && anyp) { decided = true; edge = perc >= min_perc; }
         else if (relax_pe && o.len1 + o.len2 >= min_len && anyp) { decided = true; edge = perc >= min_perc; }
-        if (!decided) { ++nonedge; continue; }                // written back to nonedge_overlaps.txt
+        if (!decided) {                                       // written back to nonedge_overlaps.txt
+            ++nonedge;
+            if (nonedges) nonedges->push_back(o);
+            continue;
+        }
         if (!edge) { ++skipped; continue; }                   // long enough, identity too low: dropped without a trace
         if (out && kept < cap) out[kept] = o;
         ++kept;
@@ -93,12 +106,8 @@ void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, in
 // ---------------------------------------------------------------------------------------------
 // transitive edges
 // ---------------------------------------------------------------------------------------------
-namespace {
-constexpr int WG = 256;
-constexpr int WAVES = WG / 64;
-constexpr uint32_t SET_CAP = 2048;                 // LDS hash slots per wave: vertices with up to SET_CAP / 2 out-edges
-constexpr uint32_t EMPTY = 0xffffffffu;
-inline dim3 grid1(size_t n) { return dim3((unsigned)cdiv(n ? n : 1, (size_t)WG)); }
+// edge_keys_kernel, offsets_kernel, trans_kernel and trans_big_kernel are shared with vq_graph.hip (vq_internal.h)
+namespace vqk {
 
 __global__ void edge_keys_kernel(const uint32_t *a, const uint32_t *b, const uint32_t *ids, size_t n, uint64_t *key, uint32_t *val) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -205,6 +214,8 @@ __global__ __launch_bounds__(WG) void trans_big_kernel(const uint64_t *okey, con
         }
     }
 }
+}  // namespace vqk
+namespace {
 __global__ void spread_flags_kernel(const uint8_t *flag_sub, const uint32_t *ids, size_t n, uint8_t *out) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i < n && flag_sub[i]) out[ids[i]] |= 1;

@@ -1,0 +1,119 @@
+// vq_internal.h - what vq_front.hip (the front of the SAVAGE overlap-graph assembler) shares with
+// vq_graph.hip / vq_graph_host.cpp (the oriented overlap graph built from it): the parser's non-edge rows, and the
+// transitive-edge kernels (GraphAlgos.cpp:746-795), which both files launch on the library's stream.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "common.h"
+
+namespace hlmi {
+
+// vq_parse_overlaps (graph.h) that also keeps the rows the reference writes back to nonedge_overlaps.txt (too short for an
+// edge: EdgeCalculator.cpp:628-631), in file order
+void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, int relax_pe, uint64_t max_overlaps,
+                       hlmi_vq_overlap *out, uint64_t cap, uint64_t *n_out, uint64_t *n_nonedge, uint64_t *n_skipped,
+                       std::vector<hlmi_vq_overlap> *nonedges);
+
+namespace vqk {
+constexpr int WG = 256;
+constexpr int WAVES = WG / 64;
+constexpr uint32_t SET_CAP = 2048;                 // LDS hash slots per wave: vertices with up to SET_CAP / 2 out-edges
+constexpr uint32_t EMPTY = 0xffffffffu;
+inline dim3 grid1(size_t n) { return dim3((unsigned)cdiv(n ? n : 1, (size_t)WG)); }
+
+// key[i] = a[k] << 32 | b[k], val[i] = k for k = ids[i] (ids NULL: k = i)
+__global__ void edge_keys_kernel(const uint32_t *a, const uint32_t *b, const uint32_t *ids, size_t n, uint64_t *key, uint32_t *val);
+// off[v] = first position whose key's high word is >= v, for v = 0 .. n_vertices
+__global__ void offsets_kernel(const uint64_t *key, size_t n, uint32_t n_vertices, uint32_t *off);
+// flag[oval[k]] = 1 when out-edge k of (okey, ooff) is transitive (an in-neighbour of its target is an out-neighbour of its
+// source), 0 otherwise; one wave per source vertex, vertices with more than SET_CAP / 2 out-edges go to big_list
+__global__ void trans_kernel(const uint64_t *okey, const uint32_t *oval, const uint32_t *ooff, const uint64_t *ikey,
+                             const uint32_t *ioff, uint32_t n_vertices, uint8_t *flag, uint32_t *big_list, uint32_t *n_big);
+__global__ void trans_big_kernel(const uint64_t *okey, const uint32_t *oval, const uint32_t *ooff, const uint64_t *ikey,
+                                 const uint32_t *ioff, const uint32_t *big_list, uint32_t n_big, uint8_t *flag);
+}  // namespace vqk
+
+}  // namespace hlmi
+
+namespace hlmi {
+
+// ---- vq_graph.hip / vq_graph_host.cpp: the oriented overlap graph (ViralQuasispecies --graph_only) -----------------------
+// One edge of the graph: the fields of Edge.h a single-end overlap uses.  Reads and vertices are one to one, so read1 /
+// read2 are implied by v1 / v2 (Edge::swap_reads and switch_edge_orientation swap both together).
+struct VqEdge {
+    uint32_t v1, v2;                   // out-vertex, in-vertex
+    int32_t pos1, pos2, pos3, pos4;    // pos3 = |read1| - pos1 - |read2| (set_extra_pos), pos4 = 0
+    uint8_t ori1, ori2, pad[2];        // 1: '+'
+    int32_t len;                       // overlap length (get_len(0) = column 10)
+    int32_t perc;                      // Overlap::get_perc
+    uint32_t cand;                     // file index of the candidate it came from
+    double score, mr;                  // overlap score, mismatch rate
+};
+
+// Edge::switch_edge_orientation (Edge.h) for a single-end edge; returns true when the edge changes direction
+__host__ __device__ inline bool switch_orientation(VqEdge &e) {
+    int32_t t = e.pos1; e.pos1 = e.pos3; e.pos3 = t;
+    t = e.pos2; e.pos2 = e.pos4; e.pos4 = t;
+    e.ori1 = !e.ori1;
+    e.ori2 = !e.ori2;
+    if (e.pos1 < 0 || (e.pos1 == 0 && e.v1 > e.v2)) {
+        uint32_t v = e.v1; e.v1 = e.v2; e.v2 = v;
+        uint8_t o = e.ori1; e.ori1 = e.ori2; e.ori2 = o;
+        e.pos1 = -e.pos1;
+        if (e.pos2 < 0) e.pos2 = -e.pos2;
+        return true;
+    }
+    if (e.pos2 < 0) e.pos2 = -e.pos2;
+    return false;
+}
+// (the move branch leaves pos3 / pos4 as swapped: Edge.h negates nothing there)
+
+// Edge selection (EdgeCalculator.cpp:428-532) on the device: winners[] = the candidate index that holds each (min vertex,
+// max vertex, ori1 == ori2) key at the end of process_overlaps, ascending; incl[v] = 1 for the vertices the first candidate
+// of a key marks as included (only with ignore_inclusions).
+void vq_select_edges(const std::vector<VqEdge> &cand, uint32_t n_vertices, bool ignore_inclusions,
+                     std::vector<uint32_t> &winners, std::vector<uint8_t> &incl);
+
+// The check pass of labelVertices (GraphAlgos.cpp:295-348) over the edges in adjacency-list order, kept on the device
+// across the tries of vertexLabellingHeuristic: cls[k] = 0 edge agrees with the labels, 1 contradiction (to be deleted),
+// 2 flipped and moved to the other endpoint's list (left unchanged here), 3 flipped in place (applied here, and kept for
+// the later tries, as the reference's in-place Edge::switch_edge_orientation is).
+class VqLabelPass {
+public:
+    explicit VqLabelPass(const std::vector<VqEdge> &edges);
+    void run(const std::vector<uint8_t> &orient, std::vector<uint8_t> &cls);
+    std::vector<VqEdge> state() const;
+private:
+    DBuf<VqEdge> d_edges_;
+    DBuf<uint8_t> d_orient_, d_cls_;
+    size_t n_;
+};
+
+// removeInclusions (GraphAlgos.cpp:20-48): positions of the adjacency lists (src[p] -> dst[p], lists in off[]) that stay.
+// Every out- and in-edge pair of an included vertex goes, one edge per pair: removeEdge takes the first u -> v of u's list.
+void vq_inclusion_keep(uint32_t n_vertices, const std::vector<uint32_t> &off, const std::vector<uint32_t> &src,
+                       const std::vector<uint32_t> &dst, const std::vector<uint8_t> &incl, std::vector<uint32_t> &kept);
+// findTransEdges repeated `rounds` times (GraphAlgos.cpp:746-776, 956-966): flags[p] = 1 for the edges of the last round's
+// set (transitive, double transitive, ...); returns their number.  The kernels are vq_front.hip's.
+uint64_t vq_trans_flags(uint32_t n_vertices, const std::vector<uint32_t> &src, const std::vector<uint32_t> &dst, int rounds,
+                        std::vector<uint8_t> &flags);
+// removeTips (GraphAlgos.cpp:543-637): one wave per vertex over its out-list and its in-list.  ext_fwd[p] / ext_bwd[p] =
+// Edge::ext_len(true / false) of the edge at position p.  removed[p] = 1 for the edges that go, tip[v] = 1 for the reads
+// marked as tips.
+void vq_tips(uint32_t n_vertices, const std::vector<uint32_t> &off, const std::vector<uint32_t> &dst,
+             const std::vector<uint32_t> &in_off, const std::vector<uint32_t> &in_src, const std::vector<uint32_t> &ext_fwd,
+             const std::vector<uint32_t> &ext_bwd, uint32_t max_tip_len, std::vector<uint8_t> &removed, std::vector<uint8_t> &tip);
+// removeBranches (GraphAlgos.cpp:835-936): comp[v] = a component label of the branch-free graph; only equality is meant.
+// join[p] = 1 for the non-transitive edges; an edge joins its endpoints only when its source keeps its out-list and its
+// target its in-list (the one-sided clearing of :855-901).
+void vq_branch_components(uint32_t n_vertices, const std::vector<uint32_t> &src, const std::vector<uint32_t> &dst,
+                          const std::vector<uint8_t> &trans, std::vector<uint32_t> &comp);
+
+// vq_graph_host.cpp: hlmi_vq_graph_opts_stageb / hlmi_vq_graph (include/hylight_mi.h)
+void vq_graph_opts_stageb(hlmi_vq_graph_opts *o);
+void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st);
+
+}  // namespace hlmi

@@ -148,9 +148,11 @@ int hlmi_miniasm(const char *paf, const char *reads_fa, int bub_dist, int n_roun
 int hlmi_sfo2overlaps(const char *in_sfo, const char *out_savage, int num_singles, int num_pairs);
 
 /* ---- f3 (STARTED): front end of the SAVAGE overlap-graph assembler ------ */
-/* tools/HaploConduct/src (ViralQuasispecies) needs Boost and cannot be built here: these two entry points restate its
- * text of record and are checked against oracle/vq.py only (parity unpinned).  Not built: the quality-aware overlap score
- * (EdgeCalculator.cpp:26-139, log / pow / exp thresholds), edge orientation (Edge.h), everything after the graph. */
+/* tools/HaploConduct/src (ViralQuasispecies) needs Boost and cannot be built here: the entry points below restate its
+ * text of record and are checked against oracle/vq.py and tests/vq_graph_model.py only (parity unpinned).  Built: the
+ * parser, the quality-aware overlap score, transitive edges, and the oriented, reduced overlap graph of a --graph_only run
+ * (hlmi_vq_graph).  Not built: what reads that graph - SRBuilder (merging along edges, cliques), FindNextOverlaps and the
+ * stage-b iteration of pipeline_per_stage.py. */
 typedef struct {
     uint64_t id1, id2;                 /* strtoul(..., 0) of columns 1, 2                        (Overlap.h:39-40, Types.h:99)  */
     uint32_t pos1, pos2, perc1, perc2, len1, len2;   /* atoi; pos2 = perc2 = len2 = 0 when column 4 is "-" (Overlap.h:53-57) */
@@ -186,6 +188,51 @@ int hlmi_vq_transitive_edges(uint32_t n_vertices, uint64_t n_edges, const uint32
  * the reference's.  Reads are looked up by the integer id of their "@<id>" line (strtoul base 0, FastqStorage.cpp:109-117). */
 int hlmi_vq_overlap_scores(const char *fastq_singles, const hlmi_vq_overlap *ov, uint64_t n, double mismatch,
                            uint32_t min_read_len, double *score, double *mismatch_rate, int64_t *pos3);
+
+/* ViralQuasispecies --graph_only=true (ViralQuasispecies.cpp:250-398) on single-end reads: the options it reads. */
+typedef struct {
+    uint32_t min_overlap_len, min_overlap_perc, min_read_len, max_tip_len, remove_trans;
+    double edge_threshold, ov_threshold, merge_contigs, mismatch;
+    int ignore_inclusions, remove_tips, remove_branches, remove_backedges;
+    uint64_t max_overlaps;
+} hlmi_vq_graph_opts;
+/* The values HyLight's first stage-b iteration passes (HyLight.py:320-324 -> pipeline_per_stage.py:170-200):
+ * min_overlap_len 300, min_overlap_perc 0, edge_threshold 1, merge_contigs 0, remove_trans 1, remove_branches 1,
+ * ignore_inclusions 1, max_tip_len 1000; the rest ViralQuasispecies' defaults (ViralQuasispecies.cpp:55-100):
+ * ov_threshold 0.9, mismatch 0, min_read_len 0, remove_tips 1, remove_backedges 1 (error_correction false),
+ * max_overlaps 1e8. */
+void hlmi_vq_graph_opts_stageb(hlmi_vq_graph_opts *o);
+typedef struct {
+    uint64_t vertices;      /* reads of singles_fastq (vertex = position in the file)                                   */
+    uint64_t candidates;    /* scored candidates that passed the edge rule (score > edge_threshold, or mismatch rate
+                               <= merge_contigs)                                                                         */
+    uint64_t duplicates;    /* candidates - edges_built: candidates of a (pair, orientation class) already in the graph */
+    uint64_t inclusions;    /* candidates with perc 100 (the reference's inclusion_count)                               */
+    uint64_t edges_built;   /* edges after process_overlaps: one per (pair, orientation class)                          */
+    uint64_t conflicts;     /* edges deleted by the orientation labelling (its best try)                                */
+    uint64_t moved;         /* edges the labelling moved to the other endpoint's list                                   */
+    uint64_t transitive;    /* edges removeTransitiveEdges removed                                                      */
+    uint64_t tip_edges;     /* edges removeTips removed                                                                 */
+    uint64_t tip_reads;     /* reads it marked as tips (the lines of tips.txt)                                          */
+    uint64_t branch_edges;  /* edges removeBranches removed                                                             */
+    uint64_t backedges;     /* back edges of the best DFS (the lines of cycles.txt)                                     */
+    uint64_t edges_final;   /* edges of the final graph (the lines of digraph.txt)                                      */
+} hlmi_vq_graph_stats;
+/* Builds and reduces the overlap graph of `overlaps` (13 columns, single-end rows) over the reads of singles_fastq the way
+ * ViralQuasispecies --graph_only=true --threads 1 does, and writes into out_dir (which must exist), byte for byte in the
+ * reference's formats: nonedge_overlaps.txt, graph.gfa (after transitive-edge removal), graph.txt, graph_trimmed.gfa,
+ * digraph.txt, cycles.txt (only when there are back edges: the reference removes it and writes it back edge by edge), and
+ * the project's own tips.txt (ascending ids of the vertices whose reads removeTips marked as tips).  When no edge is
+ * built, the reference stops after nonedge_overlaps.txt (and removes graph.txt); so does this call.
+ * The contract is the sequential reference: with several threads the reference adds each chunk's edges in the order its
+ * critical sections run (EdgeCalculator.cpp:395-419), so the first candidate of a (pair, orientation class) - the only
+ * one that can mark an inclusion - may differ between its multi-thread runs.
+ * Refused with HLMI_ESTATE (not on HyLight's path): an edge candidate of type 'p' (HyLight runs --num_pairs 0),
+ * remove_branches with remove_trans != 1 (the reference asserts).  add_duplicates, resolve_orientations = false and
+ * branch_reduction are not options here: this call always resolves orientations by labelling and never reduces branches
+ * by read evidence.  remove_trans > 3 is HLMI_EINVAL. */
+int hlmi_vq_graph(const char *singles_fastq, const char *overlaps, const hlmi_vq_graph_opts *o, const char *out_dir,
+                  hlmi_vq_graph_stats *st);
 
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
