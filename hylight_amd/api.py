@@ -48,6 +48,19 @@ class VqGraphStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in VQ_GRAPH_STATS]
 
 
+class ClusterOpts(C.Structure):
+    _fields_ = [("size", C.c_int64), ("threads", C.c_int32), ("pad", C.c_int32), ("window_bytes", C.c_uint64)]
+
+
+CLUSTER_STATS = ("names", "rows", "chunks", "sessions", "windows", "survivors", "strict_rejects", "unions", "clusters_ge20",
+                 "reads_sliced", "files")
+CLUSTER_MS = ("ms_fastq", "ms_paf", "ms_prefilter", "ms_union", "ms_refresh", "ms_group", "ms_demux", "ms_write", "ms_total")
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in CLUSTER_STATS] + [(k, C.c_double) for k in CLUSTER_MS]
+
+
 ABI_VERSION = 5          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
@@ -83,6 +96,8 @@ SYMBOLS = {
                                          C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "hlmi_vq_graph_opts_stageb": (None, [C.POINTER(VqGraphOpts)]),
     "hlmi_vq_graph": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.c_char_p, C.POINTER(VqGraphStats)]),
+    "hlmi_cluster_opts_default": (None, [C.POINTER(ClusterOpts)]),
+    "hlmi_cluster_short": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(ClusterOpts), C.c_char_p, C.POINTER(ClusterStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -291,6 +306,24 @@ def vq_graph(singles_fastq, overlaps, out_dir, **opts):
     st = VqGraphStats()
     _check(load().hlmi_vq_graph(_b(singles_fastq), _b(overlaps), C.byref(o), _b(out_dir), C.byref(st)))
     return {k: getattr(st, k) for k in VQ_GRAPH_STATS}
+
+
+def cluster_short(paf, fastq, out_dir, size=15000, threads=20, **opts):
+    """HyLight's short-read clustering (HyLight.py:215-226): readnames.txt, HiStrain_max<size>_final_clusters_grouped.json
+    and fq_<size>/<cid>/<cid>.{1,2}.fq in out_dir (created if missing), byte for byte as the reference scripts leave them.
+    `size`, `threads`: HyLight --size and -t.  Options: window_bytes (PAF bytes per upload; 1 = one session per window).
+    -> dict of the stats (hlmi_cluster_stats)."""
+    o = ClusterOpts()
+    load().hlmi_cluster_opts_default(C.byref(o))
+    o.size, o.threads = int(size), int(threads)
+    for k, v in opts.items():
+        if k != "window_bytes":
+            raise TypeError(f"cluster_short: unknown option {k!r}")
+        o.window_bytes = int(v)
+    os.makedirs(out_dir, exist_ok=True)
+    st = ClusterStats()
+    _check(load().hlmi_cluster_short(_b(paf), _b(fastq), C.byref(o), _b(out_dir), C.byref(st)))
+    return {k: getattr(st, k) for k in CLUSTER_STATS + CLUSTER_MS}
 
 
 DEVICE = "cuda"          # where the buffers that cross the C ABI live (stage.py allocates them with torch)

@@ -13,6 +13,7 @@
 
 namespace hlmi {
 void init_device(int device, int threads);
+void cluster_run(const char *paf, const char *fastq, const hlmi_cluster_opts &o, const char *out_dir, hlmi_cluster_stats *st);
 void shutdown_device();
 const std::string &last_error();
 }  // namespace hlmi
@@ -327,6 +328,19 @@ int hlmi_vq_graph(const char *singles_fastq, const char *overlaps, const hlmi_vq
         if (!singles_fastq || !overlaps || !o || !out_dir || !st) fail(HLMI_EINVAL, "hlmi_vq_graph: NULL argument");
         require_device();
         vq_graph_run(singles_fastq, overlaps, *o, out_dir, st);
+    });
+}
+
+void hlmi_cluster_opts_default(hlmi_cluster_opts *o) {
+    if (o) *o = hlmi_cluster_opts{15000, 20, 0, 0};            // HyLight.py --size, -t
+}
+
+int hlmi_cluster_short(const char *paf, const char *fastq, const hlmi_cluster_opts *o, const char *out_dir,
+                       hlmi_cluster_stats *st) {
+    return guarded([&] {
+        if (!paf || !fastq || !o || !out_dir || !st) fail(HLMI_EINVAL, "hlmi_cluster_short: NULL argument");
+        require_device();
+        cluster_run(paf, fastq, *o, out_dir, st);
     });
 }
 

@@ -23,9 +23,15 @@
 #include "dev_prims.h"
 #include "graph.h"
 #include "paf_io.h"
+#include "text_dev.h"
 #include "wave_ops.h"
 
 namespace hlmi {
+
+__global__ void line_start_kernel(const uint8_t *txt, size_t base, size_t n, uint8_t *flag) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) flag[i] = (base + i == 0 || txt[base + i - 1] == '\n') ? 1 : 0;
+}
 
 namespace {
 constexpr int WG = 256;
@@ -41,11 +47,6 @@ struct PafRow {                 // one parsed line (paf.h:21-25)
     uint32_t rev;
 };
 
-// flags of the window txt[base .. base + n): 1 where a line starts
-__global__ void line_start_kernel(const uint8_t *txt, size_t base, size_t n, uint8_t *flag) {
-    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i < n) flag[i] = (base + i == 0 || txt[base + i - 1] == '\n') ? 1 : 0;
-}
 __global__ void add_base_kernel(const uint32_t *rel, size_t n, uint64_t base, uint64_t *out) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i < n) out[i] = base + rel[i];
@@ -119,13 +120,7 @@ __global__ void name_hash_kernel(const uint8_t *txt, const PafRow *rows, const u
     uint64_t off;
     uint32_t len;
     occ_name(rows, kept, (uint32_t)o, off, len);
-    uint64_t h = seed ^ (0x9e3779b97f4a7c15ull * (len + 1));
-    for (uint32_t i = 0; i < len; ++i) {
-        h = (h ^ txt[off + i]) * 0x100000001b3ull;
-        h ^= h >> 29;
-    }
-    h ^= h >> 32;
-    hash[o] = h * 0xd6e8feb86659fd93ull;
+    hash[o] = name_hash64(txt, off, len, seed);
     occ_id[o] = (uint32_t)o;
 }
 // sorted by hash (stable: occurrences ascending inside a group).  head[i] = first of its group; every other member is
@@ -141,9 +136,7 @@ __global__ void name_group_kernel(const uint8_t *txt, const PafRow *rows, const 
     uint32_t l1, l2;
     occ_name(rows, kept, occ_sorted[i - 1], o1, l1);
     occ_name(rows, kept, occ_sorted[i], o2, l2);
-    bool same = l1 == l2;
-    for (uint32_t k = 0; same && k < l1; ++k) same = txt[o1 + k] == txt[o2 + k];
-    if (!same) *collision = 1;
+    if (!bytes_equal(txt, o1, l1, txt, o2, l2)) *collision = 1;
 }
 // first[o] = 1 where occurrence o is the first one of its name
 __global__ void name_first_kernel(const uint32_t *occ_sorted, const uint8_t *head, size_t n_occ, uint8_t *first) {

@@ -14,6 +14,12 @@ sfo2overlaps; the consumers of that file - short-read clustering, POLYTE and the
 with EXIT_NO_FINAL (3) and everything up to tmp/stageb/sfoverlap.out.savage in place (`--stop_after savage` declares
 that partial run and exits 0).  The text passes (filter_non_atcg, gfa2fa, pick_up) are the library's native ones.
 
+The short-read branch (HyLight.py:211-275) is opt-in: `--stop_after clusters` runs the clustering of HyLight.py:215-226
+(hlmi_cluster_short: readnames.txt, the grouped JSON and fq_<size>/ in tmp/) and exits 0; `--polyte_cmd PREFIX`, without
+`--short_contigs`, also runs POLYTE per cluster through PREFIX (the reference's polyte.tune_params.py, external), collects
+tmp/all.contigs_<size>.fasta, extends it into short_stageb.fa (with `--stageb_cmd`) and builds all_contigs.fa from it and
+long_con_polished.fa.  Without these flags the run is the same as before.
+
 `--gpus N` (extension): every split_reads2 call is sharded over N GPUs of the node, chunk i -> rank i % N, the way the
 reference fans its chunks out with `xargs -P` (script/utils.py:44-69).  The process starts N - 1 further copies of
 itself before it touches the GPU (hylight_amd/launch.py); rank 0 runs the pipeline (text passes, graph builds, external
@@ -157,8 +163,10 @@ def build_parser():
     p.add_argument("--insert_size", dest="insert_size", default=450, type=int)
     p.add_argument("--average_read_len", dest="average_read_len", default=250, type=int)
     p.add_argument("--version", "-v", action="version", version="%(prog)s version: " + __version__)
-    p.add_argument("--stop_after", choices=["overlap", "contigs1", "polish", "savage", "stageb_graph"], default=None,
-                   help="(extension) stop after the named stage (savage: the contig overlap file of extend_con; "
+    p.add_argument("--stop_after", choices=["overlap", "contigs1", "polish", "clusters", "savage", "stageb_graph"],
+                   default=None,
+                   help="(extension) stop after the named stage (clusters: the short-read clustering into tmp/ - "
+                        "readnames.txt, the grouped JSON, fq_<size>/; savage: the contig overlap file of extend_con; "
                         "stageb_graph: also the overlap graph of the stage-b merge in tmp/stageb/ - graph.gfa, "
                         "graph.txt, graph_trimmed.gfa, digraph.txt, cycles.txt, tips.txt - then exit status 3)")
     p.add_argument("--device", type=int, default=0, help="(extension) GPU index of a single-GPU run")
@@ -166,9 +174,67 @@ def build_parser():
                    help="(extension) shard every overlap stage over this many GPUs of the node (one process per GPU)")
     p.add_argument("--short_contigs", default=None,
                    help="(extension) contigs of the short-read branch (POLYTE, run elsewhere) to merge with the long-read contigs")
+    p.add_argument("--polyte_cmd", default=None,
+                   help="(extension) command prefix of the reference's polyte.tune_params.py, if installed: without "
+                        "--short_contigs, cluster the short reads and run it per cluster (HyLight.py:215-275)")
     p.add_argument("--stageb_cmd", default=None,
                    help="(extension) command prefix of the reference's pipeline_per_stage.py, if installed")
     return p
+
+
+def polyte_lines(tmp, size, polyte_cmd, insert_size, average_read_len):
+    """HyLight.py:228-242: one POLYTE command per cluster directory of tmp/fq_<size>/, `polyte_cmd` in place of
+    `python <bin>/polyte.tune_params.py`."""
+    outdir2 = os.path.join(tmp, f"fq_{size}")
+    lines = []
+    for i in sorted(os.listdir(outdir2)):
+        fq1, fq2, folder = f"{outdir2}/{i}/{i}.1.fq", f"{outdir2}/{i}/{i}.2.fq", f"{outdir2}/{i}"
+        lines.append(f"cd {folder}; {polyte_cmd} -p1 {fq1} -p2 {fq2}  -m 50 -m_EC 60 -t 1 --hap_cov 10 --insert_size  "
+                     f"{insert_size} --stddev 27  --mismatch_rate 0 --min_clique_size 2 --average_read_len "
+                     f"{average_read_len} --edge1 0.93 --edge2 1.0 --no_EC > log.txt 2>&1")
+    return lines
+
+
+def _short_branch(args, tmp, outdir, long_con3):
+    """HyLight.py:228-275 after the clustering: POLYTE per cluster (external, `--polyte_cmd`), the cluster contigs, their
+    stage-b extension (short_stageb.fa) and all_contigs.fa; then the final extend_con as on the other path."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    size = args.size
+    lines = polyte_lines(tmp, size, args.polyte_cmd, args.insert_size, args.average_read_len)
+    with open(os.path.join(tmp, "cmd_polyte.sh"), "w") as f:
+        f.writelines(line + "\n" for line in lines)
+    with ThreadPoolExecutor(max_workers=max(1, args.threads)) as ex:    # `xargs -i -P threads bash -c "{}"`
+        list(ex.map(lambda line: subprocess.run(["bash", "-c", line]), lines))
+    outdir2 = os.path.join(tmp, f"fq_{size}")
+    ids = sorted(os.listdir(outdir2))
+    for i in ids:                                               # HyLight.py:248-256
+        folder = f"{outdir2}/{i}/"
+        if not os.path.isfile(folder + "contigs.fasta"):
+            print(f"You need to rerun polyte in {folder} or decrease the size of cluster and rerun the whole steps")
+    fname = os.path.join(tmp, f"all.contigs_{size}.fasta")
+    with open(fname, "wb") as o:                                # `cat fq_<size>/*/contigs.fasta` (C-locale glob order)
+        for i in ids:
+            p = f"{outdir2}/{i}/contigs.fasta"
+            if os.path.isfile(p):
+                with open(p, "rb") as f:
+                    shutil.copyfileobj(f, o)
+    short_con = os.path.join(outdir, "short_stageb.fa")
+    extend_con(fname, tmp, short_con, threads=30, len_c=500000, stageb_cmd=args.stageb_cmd)
+    all_con = os.path.join(outdir, "all_contigs.fa")
+    first = short_con if os.path.exists(short_con) and os.path.getsize(short_con) else fname     # HyLight.py:266-275
+    with open(all_con, "wb") as o:
+        for p in (first, long_con3):
+            with open(p, "rb") as f:
+                shutil.copyfileobj(f, o)
+    final = os.path.join(outdir, "final_contigs.fa")
+    n_con = extend_con(all_con, tmp, final, threads=30, stageb_cmd=args.stageb_cmd)
+    if not os.path.exists(final):
+        sys.stderr.write(f"hylight-mi: {n_con} contigs, their overlaps are in tmp/stageb/sfoverlap.out.savage; the stage-b merge "
+                         "(pipeline_per_stage.py / ViralQuasispecies, HyLight.py:320-324) is not built here, so "
+                         f"final_contigs.fa was not written (pass --stageb_cmd to run the reference's): exit status {EXIT_NO_FINAL}\n")
+        return EXIT_NO_FINAL
+    return 0
 
 
 def _init_rank(args, world, local):
@@ -284,8 +350,15 @@ def _pipeline(args, pool):
     long_con3 = os.path.join(outdir, "long_con_polished.fa")
     _run(f"{racon} --no-trimming -u -t 30 {short_reads} {ov_short} {long_con2} > {long_con3}", cwd=outdir)
     remain_short = pick_up(ov_short, tmp, short_reads)
+    shortr2 = os.devnull                                       # no reads remain: the clustering sees no rows
     if os.path.exists(remain_short) and os.path.getsize(remain_short):
-        stage(short_reads, remain_short, nsplit, tmp + "shortr2.paf", 70, 3, iden, long=False)
+        shortr2 = stage(short_reads, remain_short, nsplit, tmp + "shortr2.paf", 70, 3, iden, long=False)
+    if args.stop_after == "clusters" or (args.polyte_cmd and not args.short_contigs):
+        st = api.cluster_short(shortr2, short_reads, tmp, size=args.size, threads=args.threads)    # HyLight.py:215-226
+        sys.stderr.write(f"hylight-mi: {st['files'] // 2} short-read clusters in tmp/fq_{args.size}/\n")
+        if args.stop_after == "clusters":
+            return 0
+        return _short_branch(args, tmp, outdir, long_con3)
     # HyLight.py:211-262 (read clustering, POLYTE per cluster) is the short-read branch: not part of this path.  Its
     # contigs can be handed in; the contig-overlap half of extend_con runs either way (HyLight.py:264-280).
     sys.stderr.write("hylight-mi: short-read clustering and POLYTE (HyLight.py:211-262) are outside this implementation"

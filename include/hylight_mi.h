@@ -234,6 +234,53 @@ typedef struct {
 int hlmi_vq_graph(const char *singles_fastq, const char *overlaps, const hlmi_vq_graph_opts *o, const char *out_dir,
                   hlmi_vq_graph_stats *st);
 
+/* ---- short-read clustering (HyLight.py:215-226: get_readnames.py, bin_pointer_limited_filechunks_shortpath2.py,
+ * getclusters.py, get_fq_cluster.py with cwd = tmp/ and run id HiStrain).  Parity pinned: tests/golden/fxH_cluster_*.json
+ * hold what the reference scripts themselves wrote. */
+typedef struct {
+    int64_t size;             /* HyLight --size: the cluster size cap (default 15000)                                   */
+    int32_t threads;          /* HyLight -t: chunks per session and the slicing of getclusters.py (default 20), 1..100  */
+    int32_t pad;
+    uint64_t window_bytes;    /* PAF bytes uploaded per window of whole sessions (0: 512 MiB; at most 2 GiB; a window
+                                 holds one session at least, so 1 gives one session per window)                          */
+} hlmi_cluster_opts;
+void hlmi_cluster_opts_default(hlmi_cluster_opts *o);
+typedef struct {
+    uint64_t names;           /* lines of readnames.txt (nodes)                                                          */
+    uint64_t rows;            /* PAF rows                                                                                */
+    uint64_t chunks;          /* chunkify's byte chunks of 2 600 000 bytes to the end of a line                         */
+    uint64_t sessions;        /* groups of `threads` chunks                                                              */
+    uint64_t windows;         /* PAF windows uploaded                                                                    */
+    uint64_t survivors;       /* rows kept by the prefilter (different clusters, size1 + size2 < size at session start)  */
+    uint64_t strict_rejects;  /* rows refused only because size1 + size2 == size at session start                        */
+    uint64_t unions;          /* merges of the sequential pass                                                           */
+    uint64_t clusters_ge20;   /* final clusters of size >= 20                                                            */
+    uint64_t reads_sliced;    /* reads of clusters >= 20 dropped by getclusters' slicing                                 */
+    uint64_t files;           /* .fq files written (2 per JSON key)                                                      */
+    double ms_fastq, ms_paf, ms_prefilter, ms_union, ms_refresh, ms_group, ms_demux, ms_write, ms_total;
+} hlmi_cluster_stats;
+/* Clusters the short reads of `fastq` by the overlap rows of `paf` (the scored 14-column shortr2.paf, LF line ends) and
+ * writes into out_dir (which must exist), byte for byte as the reference leaves it after its cmd_rm: readnames.txt,
+ * HiStrain_max<size>_final_clusters_grouped.json and fq_<size>/<cid>/<cid>.1.fq and .2.fq for every JSON key (both always
+ * created; fq_<size>/ exists even when there is no key).  Nothing else is left behind; an existing fq_<size>/ is replaced
+ * whole.  Rules (script line numbers in DESIGN.md):
+ *   names      FASTQ line i % 4 == 0 holding "/1" anywhere -> line[1:-3]; node id = rank; lookup key = that after rstrip
+ *   rows       PAF columns 1 and 6 minus their last two characters
+ *   sessions   2 600 000-byte chunks to the end of a line, `threads` chunks per session; every row of a session is
+ *              tested against the state frozen at its start (kept iff the cluster ids differ and size1 + size2 < size),
+ *              the kept ones are merged in file order against the live state (size1 + size2 <= size); the root with the
+ *              shorter path hangs under the other, ties hang root 1 under root 2; cluster id = rank of the root
+ *   grouping   nodes of clusters >= 20 in readnames order; only the first min(threads, 60) * int(K / threads) survive;
+ *              JSON keys: slice 0's ids ascending, then each later slice's new ids ascending (json.dump defaults)
+ *   demux      record -> cluster of re.split('[@/]', header)[-2]; .1.fq if the header matches /1$, else .2.fq
+ * Refused with HLMI_EINVAL (the reference would crash, truncate a chunk silently, or parse the text otherwise), before
+ * anything is written: threads < 1 or > 100, size < 1; an empty FASTQ, a FASTA input, a FASTQ header line without '@',
+ * '\r' or a byte >= 0x80 in the FASTQ; a duplicate readnames name or one with '"'; in the PAF '\r', a byte >= 0x80,
+ * '"' or another str.splitlines() separator (\v \f \x1c-\x1e), a row with fewer than 12 columns, an endpoint whose
+ * name is not in readnames. */
+int hlmi_cluster_short(const char *paf, const char *fastq, const hlmi_cluster_opts *o, const char *out_dir,
+                       hlmi_cluster_stats *st);
+
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
  * reads into a caller-owned device buffer (16 B per minimizer: two uint64), the caller
