@@ -199,6 +199,9 @@ void read_paf(const char *path, PafText &out, bool need_tie_rank) {
         r.cig_off = out.ops.size();
         if (lf == "*") {
             r.flags |= PF_STAR;
+        } else if (lf == "cg:Z:*") {
+            // the bare row format_ava_row writes for a stub candidate: no ops.  Not the "*" of slr2:318 - the reference
+            // splits it into no ops as well, so the row keeps its interval and its place as the pair's first row
         } else if (lf.size() > 5 && lf.substr(0, 5) == "cg:Z:") {
             uint64_t num = 0;
             bool have = false;
