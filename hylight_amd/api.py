@@ -48,6 +48,20 @@ class VqGraphStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in VQ_GRAPH_STATS]
 
 
+class VqMergeOpts(C.Structure):
+    _fields_ = [("first_it", C.c_int), ("keep_singletons", C.c_uint32), ("store_tips_separately", C.c_int),
+                ("min_clique_size", C.c_uint32)]
+
+
+VQ_MERGE_STATS = ("pairs", "merged", "dropped_empty", "dropped_n", "trivial", "trivial_reverse", "short_reads", "n_reads",
+                  "inclusion_reads", "tip_reads", "bases_in", "bytes_out")
+VQ_MERGE_MS = ("ms_merge",)
+
+
+class VqMergeStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in VQ_MERGE_STATS] + [(k, C.c_double) for k in VQ_MERGE_MS]
+
+
 class ClusterOpts(C.Structure):
     _fields_ = [("size", C.c_int64), ("threads", C.c_int32), ("pad", C.c_int32), ("window_bytes", C.c_uint64)]
 
@@ -61,7 +75,7 @@ class ClusterStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in CLUSTER_STATS] + [(k, C.c_double) for k in CLUSTER_MS]
 
 
-ABI_VERSION = 5          # include/hylight_mi.h: HLMI_ABI_VERSION
+ABI_VERSION = 6          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -96,6 +110,11 @@ SYMBOLS = {
                                          C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "hlmi_vq_graph_opts_stageb": (None, [C.POINTER(VqGraphOpts)]),
     "hlmi_vq_graph": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.c_char_p, C.POINTER(VqGraphStats)]),
+    "hlmi_vq_merge_opts_stageb": (None, [C.POINTER(VqMergeOpts)]),
+    "hlmi_vq_merge": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqMergeOpts), C.c_char_p,
+                                C.POINTER(VqGraphStats), C.POINTER(VqMergeStats)]),
+    "hlmi_vq_consensus_pair": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32,
+                                         C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
     "hlmi_cluster_opts_default": (None, [C.POINTER(ClusterOpts)]),
     "hlmi_cluster_short": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(ClusterOpts), C.c_char_p, C.POINTER(ClusterStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
@@ -306,6 +325,47 @@ def vq_graph(singles_fastq, overlaps, out_dir, **opts):
     st = VqGraphStats()
     _check(load().hlmi_vq_graph(_b(singles_fastq), _b(overlaps), C.byref(o), _b(out_dir), C.byref(st)))
     return {k: getattr(st, k) for k in VQ_GRAPH_STATS}
+
+
+def vq_merge_opts_stageb():
+    """hlmi_vq_merge_opts_stageb: the SRBuilder options of HyLight's first stage-b iteration, as a dict."""
+    o = VqMergeOpts()
+    load().hlmi_vq_merge_opts_stageb(C.byref(o))
+    return {k: getattr(o, k) for k, _ in VqMergeOpts._fields_}
+
+
+def vq_merge(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
+    """hlmi_vq_merge: the graph of vq_graph (same files) and then SRBuilder::mergeAlongEdges - singles.fastq, subreads.txt,
+    removed_tip_sequences.fastq (appended to) and superread_map.txt in out_dir (created if missing).  Options: the fields
+    of hlmi_vq_graph_opts and of hlmi_vq_merge_opts, the stage-b values by default; subreads_in: the previous iteration's
+    subreads.txt when first_it is off.  -> (graph stats, merge stats) as dicts."""
+    go, mo = VqGraphOpts(), VqMergeOpts()
+    load().hlmi_vq_graph_opts_stageb(C.byref(go))
+    load().hlmi_vq_merge_opts_stageb(C.byref(mo))
+    for k, v in opts.items():
+        target = go if k in dict(VqGraphOpts._fields_) else mo if k in dict(VqMergeOpts._fields_) else None
+        if target is None:
+            raise TypeError(f"vq_merge: unknown option {k!r}")
+        setattr(target, k, int(v) if isinstance(v, bool) else v)
+    os.makedirs(out_dir, exist_ok=True)
+    gst, mst = VqGraphStats(), VqMergeStats()
+    _check(load().hlmi_vq_merge(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
+                                C.byref(go), C.byref(mo), _b(out_dir), C.byref(gst), C.byref(mst)))
+    return ({k: getattr(gst, k) for k in VQ_GRAPH_STATS},
+            {k: getattr(mst, k) for k in VQ_MERGE_STATS + VQ_MERGE_MS})
+
+
+def vq_consensus_pair(seq1, qual1, seq2, qual2, pos):
+    """hlmi_vq_consensus_pair: SRBuilder::consensus of two oriented sequences (str or bytes), the second `pos` bases behind
+    the first -> (sequence, qualities) as str; ("", "") where the reference returns an empty consensus."""
+    if pos < 0 or pos >= 1 << 30:
+        raise ValueError(f"vq_consensus_pair: pos {pos} is outside 0 .. 2^30")
+    s1, q1, s2, q2 = (x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in (seq1, qual1, seq2, qual2))
+    cap = max(len(s1), pos + len(s2), 1)
+    out_s, out_q = C.create_string_buffer(cap), C.create_string_buffer(cap)
+    n = C.c_uint32(0)
+    _check(load().hlmi_vq_consensus_pair(s1, q1, len(s1), len(q1), s2, q2, len(s2), len(q2), pos, out_s, out_q, C.byref(n)))
+    return out_s.raw[:n.value].decode("latin-1"), out_q.raw[:n.value].decode("latin-1")
 
 
 def cluster_short(paf, fastq, out_dir, size=15000, threads=20, **opts):

@@ -331,6 +331,30 @@ int hlmi_vq_graph(const char *singles_fastq, const char *overlaps, const hlmi_vq
     });
 }
 
+void hlmi_vq_merge_opts_stageb(hlmi_vq_merge_opts *o) {
+    if (o) vq_merge_opts_stageb(o);
+}
+
+int hlmi_vq_merge(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                  const hlmi_vq_merge_opts *mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst) {
+    return guarded([&] {
+        if (!singles_fastq || !overlaps || !go || !mo || !out_dir || !gst || !mst) fail(HLMI_EINVAL, "hlmi_vq_merge: NULL argument");
+        require_device();
+        vq_merge_run(singles_fastq, overlaps, subreads_in, *go, *mo, out_dir, gst, mst);
+    });
+}
+
+int hlmi_vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2,
+                           const char *qual2, uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual,
+                           uint32_t *out_len) {
+    return guarded([&] {
+        if (!out_len || (len1 && !seq1) || (qlen1 && !qual1) || (len2 && !seq2) || (qlen2 && !qual2) || !out_seq || !out_qual)
+            fail(HLMI_EINVAL, "hlmi_vq_consensus_pair: NULL argument");
+        require_device();
+        vq_consensus_pair(seq1, qual1, len1, qlen1, seq2, qual2, len2, qlen2, pos, out_seq, out_qual, out_len);
+    });
+}
+
 void hlmi_cluster_opts_default(hlmi_cluster_opts *o) {
     if (o) *o = hlmi_cluster_opts{15000, 20, 0, 0};            // HyLight.py --size, -t
 }

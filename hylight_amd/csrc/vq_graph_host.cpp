@@ -32,10 +32,12 @@ namespace {
 // ---- reads: singles.fastq, vertex = position in the file (FastqStorage.cpp:92-150, ViralQuasispecies.cpp:262-276) ------
 struct Singles {
     std::vector<std::string> seq;                      // upper-cased
+    std::vector<std::string> qual;                     // the quality line as it stands
+    std::vector<uint64_t> id;                          // read id per vertex
     std::unordered_map<uint64_t, uint32_t> index_of;   // read id (strtoul base 0 of the first word) -> vertex
 };
 
-Singles read_singles(const char *path) {
+Singles read_singles(const char *path, bool keep_text) {
     const std::string data = read_file(path);
     Singles r;
     size_t pos = 0, line = 0;
@@ -65,6 +67,10 @@ Singles read_singles(const char *path) {
                 if (cur.empty()) fail(HLMI_EINVAL, "%s: single read %llu has an empty sequence", path, (unsigned long long)id);
                 r.index_of[id] = (uint32_t)r.seq.size();
                 r.seq.push_back(cur);
+                if (keep_text) {                          // only the merge reads these
+                    r.qual.emplace_back(l);
+                    r.id.push_back(id);
+                }
                 break;
         }
     }
@@ -219,7 +225,7 @@ std::vector<uint32_t> vertices_by_indegree(const Graph &g) {
 }
 
 // ---- vertexLabellingHeuristic (GraphAlgos.cpp:178-248) -----------------------------------------------------------------
-struct Labelling { size_t conflicts = 0, moved = 0; };
+struct Labelling { size_t conflicts = 0, moved = 0; std::vector<uint8_t> orient; };   // orient: vertex_orientations (:247)
 
 Labelling label_vertices(Graph &g) {
     const uint32_t V = g.V;
@@ -293,6 +299,7 @@ Labelling label_vertices(Graph &g) {
         if (n_del < delete_count) {                                     // the first try with the fewest deletions wins
             record();
             delete_count = n_del;
+            opt = cur;                                                  // opt_orientations = orientations (:211)
         }
     }
     // the in-place flips of every try stay (Edge::switch_edge_orientation on the listed edge, :341)
@@ -310,6 +317,7 @@ Labelling label_vertices(Graph &g) {
     Labelling r;
     r.conflicts = delete_count;
     r.moved = best_moved.size();
+    r.orient = std::move(opt);
     return r;
 }
 
@@ -438,12 +446,17 @@ void vq_graph_opts_stageb(hlmi_vq_graph_opts *o) {
     o->max_overlaps = 100000000;
 }
 
-void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st) {
+void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st,
+                  VqGraphState *keep) {
     if (o.remove_trans > 3) fail(HLMI_EINVAL, "vq_graph: remove_trans must be 0 .. 3");
     if (o.remove_branches && o.remove_trans != 1)
         fail(HLMI_ESTATE, "vq_graph: remove_branches needs remove_trans 1 (findBranchfreeGraph asserts it, GraphAlgos.cpp:716)");
     *st = hlmi_vq_graph_stats{};
-    const Singles reads = read_singles(fastq);
+    Singles reads = read_singles(fastq, keep != nullptr);
+    if (keep) {
+        *keep = VqGraphState{};
+        vq_merge_check_reads(reads.seq, reads.qual);      // refused inputs are refused before a file is written
+    }
     if (reads.seq.size() >= (1u << 31)) fail(HLMI_EINVAL, "vq_graph: more than 2^31 reads");
     Graph g;
     g.V = (uint32_t)reads.seq.size();
@@ -612,6 +625,19 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
         write_text(join(out_dir, "tips.txt"), s);
     }
     st->edges_final = g.edge_count();
+    if (keep) {                                           // what SRBuilder reads (vq_merge_host.cpp)
+        sort_edges(g);                                    // ViralQuasispecies.cpp:434, in front of mergeAlongEdges
+        keep->built = true;
+        keep->out.resize(g.V);
+        for (uint32_t u = 0; u < g.V; ++u)
+            for (uint32_t e : g.out[u]) keep->out[u].push_back(g.pool[e]);
+        keep->orient = lab.orient;
+        keep->incl = incl;
+        keep->tip = tip;
+        keep->seq = std::move(reads.seq);
+        keep->qual = std::move(reads.qual);
+        keep->id = std::move(reads.id);
+    }
 }
 
 }  // namespace hlmi

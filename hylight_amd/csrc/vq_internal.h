@@ -114,6 +114,72 @@ void vq_branch_components(uint32_t n_vertices, const std::vector<uint32_t> &src,
 
 // vq_graph_host.cpp: hlmi_vq_graph_opts_stageb / hlmi_vq_graph (include/hylight_mi.h)
 void vq_graph_opts_stageb(hlmi_vq_graph_opts *o);
-void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st);
+// What SRBuilder reads of the finished graph (keep != NULL): the reads, the out-lists after the sortEdges of
+// ViralQuasispecies.cpp:434, the vertex orientations of the winning labelling, the inclusions and the tip reads.  built is
+// false when the run stopped for want of an edge (ViralQuasispecies.cpp:282-291).
+struct VqGraphState {
+    bool built = false;
+    std::vector<std::string> seq, qual;
+    std::vector<uint64_t> id;
+    std::vector<std::vector<VqEdge>> out;
+    std::vector<uint8_t> orient, incl, tip;
+};
+void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st,
+                  VqGraphState *keep = nullptr);
+
+}  // namespace hlmi
+
+namespace hlmi {
+
+// ---- vq_merge.hip / vq_merge_host.cpp: super-reads along the edges of the graph (SRBuilder::mergeAlongEdges) --------------
+namespace vqm {
+constexpr int WG = 256;
+constexpr int WAVE = 64;
+constexpr int SPAN = 4096;                       // output positions per workgroup step (a span of the position space, not a read)
+constexpr int NQ = 94;                           // phred 0 .. 93 ('!' .. '~')
+constexpr int CNT_SLOTS = 256;                   // N counters in LDS per span; a span with more records counts the rest in global memory
+constexpr uint32_t NONE = 0xffffffffu;
+// The answers of SRBuilder::consensus_pos as 16-bit entries, low byte = quality character.
+//   single[c][q]      one base c (A C G T N = 0 .. 4): high byte = the base written
+//   with_n[c][q]      base c (0 .. 3) against an N of any quality: high byte = the base written
+//   same[q1][q2]      twice one base: high byte 1 = that base, 0 = N
+//   diff[q1][q2]      two different bases: 0 = N, 1 = the first, 2 = the second
+// The host evaluates every (base, quality) pair and builds same / diff only if the answer is the same whichever bases they
+// are (it depends on them through the order of the four terms of total_prob alone); otherwise the call fails.
+constexpr int T_SINGLE = 0, T_WITH_N = T_SINGLE + 5 * NQ, T_SAME = T_WITH_N + 4 * NQ, T_DIFF = T_SAME + NQ * NQ,
+              T_ALL = T_DIFF + NQ * NQ;
+constexpr uint32_t F_REV_A = 1, F_REV_B = 2, F_CONS = 4;
+struct Rec {                                     // one FASTQ record of the output
+    uint32_t a, b;                               // reads: a at 0, b (NONE: a copy of a) at p
+    uint32_t p, len;                             // len = output bases
+    uint32_t flags, id;                          // F_*; id = the number after '@'
+};
+}  // namespace vqm
+
+// The device side of a merge over resident reads: bases / quals concatenated, read r at [off[r], off[r + 1]).
+class VqMergeDev {
+public:
+    VqMergeDev(const std::vector<std::string> &seq, const std::vector<std::string> &qual, const std::vector<uint16_t> &tables);
+    std::vector<uint32_t> read_n_counts();                                  // 'N's per read
+    std::vector<uint32_t> count_n(const std::vector<vqm::Rec> &recs);       // 'N's each record would hold
+    // the records' FASTQ text, one after the other; start[r] = first byte of record r, start[n] = the size
+    std::string write(const std::vector<vqm::Rec> &recs, std::vector<uint64_t> &start);
+private:
+    void layout(const std::vector<vqm::Rec> &recs, DBuf<vqm::Rec> &d_rec, DBuf<uint64_t> &pos0, DBuf<uint64_t> &byte0);
+    DBuf<uint8_t> d_bases_, d_quals_;
+    DBuf<uint64_t> d_off_;
+    DBuf<uint16_t> d_tab_;
+    size_t n_reads_;
+};
+
+// what hlmi_vq_merge refuses in a read (HLMI_EINVAL): a base outside A C G T N, a quality outside '!' .. '~', a quality line
+// of another length than the sequence
+void vq_merge_check_reads(const std::vector<std::string> &seq, const std::vector<std::string> &qual);
+// vq_merge_host.cpp: hlmi_vq_merge_opts_stageb / hlmi_vq_merge / hlmi_vq_consensus_pair (include/hylight_mi.h)
+void vq_merge_opts_stageb(hlmi_vq_merge_opts *o);
+void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                  const hlmi_vq_merge_opts &mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
+void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2, const char *qual2,
+                       uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual, uint32_t *out_len);
 
 }  // namespace hlmi

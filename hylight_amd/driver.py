@@ -97,13 +97,15 @@ def contig_ava_opts():
     return o
 
 
-def extend_con(input_con, outdir1, out_file, threads=30, len_c=50000000, stageb_cmd=None, stageb_graph=False):
+def extend_con(input_con, outdir1, out_file, threads=30, len_c=50000000, stageb_cmd=None, stageb_graph=False, stageb_merge=False):
     """HyLight.extend_con (script/HyLight.py:282-326) up to the SAVAGE overlap file.  Returns the number of contigs
     written to contigs_b.fastq.  `stageb_cmd`: command prefix of the reference's stage-b script
     (`python .../pipeline_per_stage.py`) for installations that have it; without it the merge itself is skipped.
     `stageb_graph`: also build the overlap graph of the first stage-b iteration (ViralQuasispecies --graph_only,
     hlmi_vq_graph with the stage-b options) into outdir1/stageb/ - graph.gfa, graph.txt, graph_trimmed.gfa,
-    digraph.txt, cycles.txt, tips.txt, nonedge_overlaps.txt."""
+    digraph.txt, cycles.txt, tips.txt, nonedge_overlaps.txt.  `stageb_merge`: that graph and the super-reads merged along
+    its edges (ViralQuasispecies --cliques=false up to findNextOverlaps, hlmi_vq_merge with the stage-b options) -
+    singles.fastq, subreads.txt, removed_tip_sequences.fastq, superread_map.txt in outdir1/stageb/."""
     conb = os.path.join(outdir1, "contigs_b.fastq")
     if os.path.exists(conb):
         os.remove(conb)
@@ -128,7 +130,9 @@ def extend_con(input_con, outdir1, out_file, threads=30, len_c=50000000, stageb_
     else:
         for p in (raw, sfo, savage):
             open(p, "w").close()
-    if stageb_graph and n:
+    if stageb_merge and n:
+        api.vq_merge(os.path.join(sb, "fastq", "singles.fastq"), savage, sb)
+    elif stageb_graph and n:
         api.vq_graph(os.path.join(sb, "fastq", "singles.fastq"), savage, sb)
     if stageb_cmd and n:                                       # HyLight.py:320-324
         _run(f"{stageb_cmd} --no_error_correction --remove_branches true --stage b --min_overlap_len 300 "
@@ -163,12 +167,14 @@ def build_parser():
     p.add_argument("--insert_size", dest="insert_size", default=450, type=int)
     p.add_argument("--average_read_len", dest="average_read_len", default=250, type=int)
     p.add_argument("--version", "-v", action="version", version="%(prog)s version: " + __version__)
-    p.add_argument("--stop_after", choices=["overlap", "contigs1", "polish", "clusters", "savage", "stageb_graph"],
+    p.add_argument("--stop_after", choices=["overlap", "contigs1", "polish", "clusters", "savage", "stageb_graph", "stageb_merge"],
                    default=None,
                    help="(extension) stop after the named stage (clusters: the short-read clustering into tmp/ - "
                         "readnames.txt, the grouped JSON, fq_<size>/; savage: the contig overlap file of extend_con; "
                         "stageb_graph: also the overlap graph of the stage-b merge in tmp/stageb/ - graph.gfa, "
-                        "graph.txt, graph_trimmed.gfa, digraph.txt, cycles.txt, tips.txt - then exit status 3)")
+                        "graph.txt, graph_trimmed.gfa, digraph.txt, cycles.txt, tips.txt - then exit status 3; stageb_merge: "
+                        "that graph and the super-reads merged along its edges - singles.fastq, subreads.txt, "
+                        "removed_tip_sequences.fastq, superread_map.txt in tmp/stageb/ - then exit status 3)")
     p.add_argument("--device", type=int, default=0, help="(extension) GPU index of a single-GPU run")
     p.add_argument("--gpus", type=int, default=1,
                    help="(extension) shard every overlap stage over this many GPUs of the node (one process per GPU)")
@@ -374,6 +380,13 @@ def _pipeline(args, pool):
         sys.stderr.write(f"hylight-mi: {n_con} contigs; the overlap graph of the stage-b merge is in tmp/stageb/ (graph.gfa, "
                          "graph.txt, graph_trimmed.gfa, digraph.txt, cycles.txt, tips.txt); merging along it (SRBuilder) is "
                          f"not built here, so final_contigs.fa was not written: exit status {EXIT_NO_FINAL}\n")
+        return EXIT_NO_FINAL
+    if args.stop_after == "stageb_merge":
+        n_con = extend_con(all_con, tmp, final, threads=30, stageb_merge=True)
+        sys.stderr.write(f"hylight-mi: {n_con} contigs; the super-reads of the first stage-b iteration are in tmp/stageb/ "
+                         "(singles.fastq, subreads.txt, superread_map.txt, removed_tip_sequences.fastq); the overlaps between "
+                         "them (FindNextOverlaps) and the iteration are not built here, so final_contigs.fa was not written: "
+                         f"exit status {EXIT_NO_FINAL}\n")
         return EXIT_NO_FINAL
     n_con = extend_con(all_con, tmp, final, threads=30, stageb_cmd=None if args.stop_after == "savage" else args.stageb_cmd)
     if args.stop_after == "savage":

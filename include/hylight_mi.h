@@ -34,10 +34,11 @@ extern "C" {
 /* Select the HIP device used by this process (one process per GPU).  device < 0 keeps the
  * current device.  host_threads bounds host-side helper threads (text formatting, sorting,
  * the output writer); <= 0: the CPUs this process may run on, 16 at most. */
-/* ABI version: bumped whenever a public struct grows or an entry point changes (5: hlmi_ava_opts ends in zdrop).  A caller
+/* ABI version: bumped whenever a public struct grows or an entry point changes (5: hlmi_ava_opts ends in zdrop; 6:
+ * hlmi_vq_merge, hlmi_vq_consensus_pair).  A caller
  * compares hlmi_abi_version() with the HLMI_ABI_VERSION of the header it was built against BEFORE passing structs: a caller of
  * an older header would hand over a shorter hlmi_ava_opts than the library reads. */
-#define HLMI_ABI_VERSION 5
+#define HLMI_ABI_VERSION 6
 int         hlmi_abi_version(void);
 int         hlmi_init(int device, int host_threads);
 void        hlmi_shutdown(void);
@@ -151,8 +152,8 @@ int hlmi_sfo2overlaps(const char *in_sfo, const char *out_savage, int num_single
 /* tools/HaploConduct/src (ViralQuasispecies) needs Boost and cannot be built here: the entry points below restate its
  * text of record and are checked against oracle/vq.py and tests/vq_graph_model.py only (parity unpinned).  Built: the
  * parser, the quality-aware overlap score, transitive edges, and the oriented, reduced overlap graph of a --graph_only run
- * (hlmi_vq_graph).  Not built: what reads that graph - SRBuilder (merging along edges, cliques), FindNextOverlaps and the
- * stage-b iteration of pipeline_per_stage.py. */
+ * (hlmi_vq_graph), and the step that reads it with --cliques=false: SRBuilder::mergeAlongEdges, the super-reads of the next
+ * iteration (hlmi_vq_merge).  Not built: cliques, FindNextOverlaps and the stage-b iteration of pipeline_per_stage.py. */
 typedef struct {
     uint64_t id1, id2;                 /* strtoul(..., 0) of columns 1, 2                        (Overlap.h:39-40, Types.h:99)  */
     uint32_t pos1, pos2, perc1, perc2, len1, len2;   /* atoi; pos2 = perc2 = len2 = 0 when column 4 is "-" (Overlap.h:53-57) */
@@ -233,6 +234,87 @@ typedef struct {
  * by read evidence.  remove_trans > 3 is HLMI_EINVAL. */
 int hlmi_vq_graph(const char *singles_fastq, const char *overlaps, const hlmi_vq_graph_opts *o, const char *out_dir,
                   hlmi_vq_graph_stats *st);
+
+/* ---- SRBuilder with --cliques=false --error_correction=false --threads 1 (ViralQuasispecies.cpp:413-447,
+ * SRBuilder::mergeAlongEdges, SRBuilder.cpp:1238-1384): the contigs of the next stage-b iteration ---------------------- */
+/* SRBuilder::consensus with error_correction = false (SRBuilder.cpp:406-533) and consensus_pos (:297-402) for two sequences
+ * that are already oriented, the second one `pos` bases behind the first; computed by the device kernel hlmi_vq_merge
+ * uses.  seq1 / seq2 hold len1 / len2 bases of A C G T N, qual1 / qual2 hold qlen1 / qlen2 quality characters '!' .. '~'
+ * (anything else: HLMI_EINVAL; the reference asserts).  out_seq / out_qual need room for max(len1, pos + len2) bytes (no
+ * NUL is added); *out_len = that length, or 0 where the reference returns an empty consensus: a position without an active
+ * base (pos > len1: the loop of :453-521 meets :498), or a read whose position reaches the end of its sequence or of its
+ * quality string while it is active (:478: an empty sequence, a quality string shorter than its sequence).  pos == len1
+ * is NOT empty: read 1 goes inactive at its last base (:487-492) and read 2 becomes active at position pos (:455-459).
+ * minQual is the reference's default 0.9 (ViralQuasispecies.cpp:62 -> SRBuilder.h:89; HyLight's path does not pass
+ * --min_qual).  Per position (:297-402): log10 / pow / round are the host's libm in the reference's expression order, kept
+ * in tables by (bases, qualities) - the device only looks up.  A position with ONE active base goes through consensus_pos
+ * too: the base comes back with its quality except that Q0 and Q1 give another base (the three others score higher: an A
+ * becomes T, a T, C or G becomes A; quality '#' for Q0, '"' for Q1), and an N comes back as N with quality '$' (:354-357).
+ * Two different bases of equal quality give N '$': each has probability 1/2 < minQual. */
+int hlmi_vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2,
+                           const char *qual2, uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual,
+                           uint32_t *out_len);
+typedef struct {
+    int first_it;               /* --first_it: every read is its own original (OverlapGraph::buildOriginalsDict, :772-798) */
+    uint32_t keep_singletons;   /* --keep_singletons: an unmerged read shorter than this is not kept (:1286)               */
+    int store_tips_separately;  /* --separate_tips: an unmerged tip read goes to removed_tip_sequences.fastq (:1305)       */
+    uint32_t min_clique_size;   /* --min_clique_size: read for parity only - a pair never exceeds 3 * min_clique_size
+                                   (:721) and without error correction the minimum support is not applied (:420-437)     */
+} hlmi_vq_merge_opts;
+/* pipeline_per_stage.py:170-203 on HyLight's path: keep_singletons = max(min_overlap_len, min_read_len) = 300,
+ * separate_tips true, min_clique_size 2, first_it true */
+void hlmi_vq_merge_opts_stageb(hlmi_vq_merge_opts *o);
+typedef struct {
+    uint64_t pairs;             /* edges taken by getEdgesForMerging                                                        */
+    uint64_t merged;            /* super-reads written from them                                                            */
+    uint64_t dropped_empty;     /* pairs whose consensus is empty                                                           */
+    uint64_t dropped_n;         /* pairs whose consensus fails test_N_rate                                                  */
+    uint64_t trivial;           /* unmerged reads written as they are                                                       */
+    uint64_t trivial_reverse;   /* ... of them reverse-complemented                                                         */
+    uint64_t short_reads;       /* unmerged reads left out: shorter than keep_singletons                                    */
+    uint64_t n_reads;           /* ... too many N                                                                           */
+    uint64_t inclusion_reads;   /* ... included in another read (to removed_tip_sequences.fastq)                            */
+    uint64_t tip_reads;         /* ... tips (to removed_tip_sequences.fastq)                                                */
+    uint64_t bases_in;          /* bases of singles_fastq                                                                   */
+    uint64_t bytes_out;         /* bytes of the new singles.fastq                                                           */
+    double ms_merge;            /* wall time of the step after the graph                                                    */
+} hlmi_vq_merge_stats;
+/* hlmi_vq_graph (same code, same files in out_dir) and then the reference's next step.  subreads_in: the subreads.txt of
+ * the previous iteration when first_it is 0 (buildOriginalsDict, OverlapGraph.cpp:799-845), NULL when first_it is set.
+ * Written into out_dir in the reference's formats:
+ *   singles.fastq   the merged super-reads, ids from 0 in merge-list order (writeSinglesToFile, :1471-1507), then the
+ *                   unmerged reads in ascending vertex order (writeTrivialsToFile, :1416-1469); a read whose vertex
+ *                   orientation is reverse is written reverse-complemented with its qualities reversed (:1331-1368)
+ *   subreads.txt    per new read: "<id>" and per original read "\t<original>:<+|->:<index>:<length>" (:1449-1463, :1489-1503)
+ *   removed_tip_sequences.fastq   only when a read goes there (writeTipsToFile, :1386-1414): the unmerged inclusions and
+ *                   tips in vertex order, forward, ids from 0.  The reference APPENDS to this file; so does this call
+ *   superread_map.txt   the project's own: per vertex "vertex<TAB>new id or -1<TAB>offset of the read in its super-read
+ *                   <TAB>+|-" - what visited, nodes_to_new_IDs and the subread map hold for findNextOverlaps
+ * Rules:
+ *   merge list   getEdgesForMerging (GraphAlgos.cpp:112-148): vertices ascending, each free vertex with its first free
+ *                out-neighbour in the order sortEdges leaves (ViralQuasispecies.cpp:434)
+ *   placement    the smaller vertex is the base (constructSuperread, :658-679); the edge is getEdgeInfo(base, other): base ->
+ *                other if there is one, else other -> base; the other read lies at +pos1 when the base is the edge's read 1,
+ *                else at -pos1 (sort_vertices, :87-148), so the edge's read 1 starts the super-read and its read 2 lies pos1
+ *                behind; reads are reverse-complemented by their vertex orientation; length = base + left + right
+ *                extension (:224-252)
+ *   drops        an empty consensus, or Read::test_N_rate (Read.h:214-233: kept when N_count < 0.05 * length, compared as
+ *                doubles); the vertices of a dropped pair stay unvisited and come back as unmerged reads
+ *   unmerged     in this order (:1282-1372): shorter than keep_singletons; N rate; inclusion (with ignore_inclusions);
+ *                tip (with store_tips_separately); else written, forward as it is or reversed with its originals mirrored
+ *   originals    calcSubreadInfo (:536-595) and :750-806: first_it: index = offset of the read in the super-read; else a
+ *                forward read adds its offset, a reverse read gives |read| + offset - (length + index); the base vertex's
+ *                entry wins where both reads hold one original
+ * Deviations (stated): the contract is --threads 1 (with more, the reference concatenates per-thread results in the order
+ * their critical sections run, :1004-1011).  The entries of a subreads.txt line are in ascending original id (the reference:
+ * iteration order of a libstdc++ unordered_map; its only reader puts them back into a map).  Paired reads are not built:
+ * HLMI_ESTATE as for hlmi_vq_graph; the empty paired1.fastq / paired2.fastq the reference leaves behind are not written,
+ * nor merge_self_overlap / filter_subreads (a pair never exceeds 3 * min_clique_size).  A read with a character outside
+ * A C G T N, a quality outside '!' .. '~' or a quality line of another length than its sequence is HLMI_EINVAL (the
+ * reference asserts on the first two and would drop every merge of the third).  When the graph has no edge the reference
+ * returns before this step (ViralQuasispecies.cpp:282-291): so does this call, and none of the four files is written. */
+int hlmi_vq_merge(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                  const hlmi_vq_merge_opts *mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
 
 /* ---- short-read clustering (HyLight.py:215-226: get_readnames.py, bin_pointer_limited_filechunks_shortpath2.py,
  * getclusters.py, get_fq_cluster.py with cwd = tmp/ and run id HiStrain).  Parity pinned: tests/golden/fxH_cluster_*.json
