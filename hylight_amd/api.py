@@ -62,6 +62,19 @@ class VqMergeStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in VQ_MERGE_STATS] + [(k, C.c_double) for k in VQ_MERGE_MS]
 
 
+class VqNextOpts(C.Structure):
+    _fields_ = [("no_inclusion_overlaps", C.c_int)]
+
+
+VQ_NEXT_STATS = ("src_graph", "src_branching", "src_nonedge", "nonedge_skipped", "src_induced", "copied", "u2sr", "v2sr", "sr2sr",
+                 "claims_failed", "lines")
+VQ_NEXT_MS = ("ms_next",)
+
+
+class VqNextStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in VQ_NEXT_STATS] + [(k, C.c_double) for k in VQ_NEXT_MS]
+
+
 class ClusterOpts(C.Structure):
     _fields_ = [("size", C.c_int64), ("threads", C.c_int32), ("pad", C.c_int32), ("window_bytes", C.c_uint64)]
 
@@ -75,7 +88,7 @@ class ClusterStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in CLUSTER_STATS] + [(k, C.c_double) for k in CLUSTER_MS]
 
 
-ABI_VERSION = 6          # include/hylight_mi.h: HLMI_ABI_VERSION
+ABI_VERSION = 7          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -113,6 +126,10 @@ SYMBOLS = {
     "hlmi_vq_merge_opts_stageb": (None, [C.POINTER(VqMergeOpts)]),
     "hlmi_vq_merge": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqMergeOpts), C.c_char_p,
                                 C.POINTER(VqGraphStats), C.POINTER(VqMergeStats)]),
+    "hlmi_vq_next_opts_stageb": (None, [C.POINTER(VqNextOpts)]),
+    "hlmi_vq_iteration": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqMergeOpts),
+                                    C.POINTER(VqNextOpts), C.c_char_p, C.POINTER(VqGraphStats), C.POINTER(VqMergeStats),
+                                    C.POINTER(VqNextStats)]),
     "hlmi_vq_consensus_pair": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32,
                                          C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
     "hlmi_cluster_opts_default": (None, [C.POINTER(ClusterOpts)]),
@@ -353,6 +370,28 @@ def vq_merge(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
                                 C.byref(go), C.byref(mo), _b(out_dir), C.byref(gst), C.byref(mst)))
     return ({k: getattr(gst, k) for k in VQ_GRAPH_STATS},
             {k: getattr(mst, k) for k in VQ_MERGE_STATS + VQ_MERGE_MS})
+
+
+def vq_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
+    """hlmi_vq_iteration: one stage-b iteration - the files of vq_merge, then overlaps.txt (SRBuilder::findNextOverlaps) and one
+    line appended to stats.txt, in out_dir (created if missing).  The inputs may lie in out_dir under the names written: they
+    are read first.  Options: the fields of hlmi_vq_graph_opts, hlmi_vq_merge_opts and hlmi_vq_next_opts, the stage-b values
+    by default.  -> (graph stats, merge stats, next stats) as dicts."""
+    go, mo, no = VqGraphOpts(), VqMergeOpts(), VqNextOpts()
+    load().hlmi_vq_graph_opts_stageb(C.byref(go))
+    load().hlmi_vq_merge_opts_stageb(C.byref(mo))
+    load().hlmi_vq_next_opts_stageb(C.byref(no))
+    for k, v in opts.items():
+        target = next((t for t in (go, mo, no) if k in dict(type(t)._fields_)), None)
+        if target is None:
+            raise TypeError(f"vq_iteration: unknown option {k!r}")
+        setattr(target, k, int(v) if isinstance(v, bool) else v)
+    os.makedirs(out_dir, exist_ok=True)
+    gst, mst, nst = VqGraphStats(), VqMergeStats(), VqNextStats()
+    _check(load().hlmi_vq_iteration(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
+                                    C.byref(go), C.byref(mo), C.byref(no), _b(out_dir), C.byref(gst), C.byref(mst), C.byref(nst)))
+    return ({k: getattr(gst, k) for k in VQ_GRAPH_STATS}, {k: getattr(mst, k) for k in VQ_MERGE_STATS + VQ_MERGE_MS},
+            {k: getattr(nst, k) for k in VQ_NEXT_STATS + VQ_NEXT_MS})
 
 
 def vq_consensus_pair(seq1, qual1, seq2, qual2, pos):

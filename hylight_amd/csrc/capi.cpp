@@ -344,6 +344,21 @@ int hlmi_vq_merge(const char *singles_fastq, const char *overlaps, const char *s
     });
 }
 
+void hlmi_vq_next_opts_stageb(hlmi_vq_next_opts *o) {
+    if (o) vq_next_opts_stageb(o);
+}
+
+int hlmi_vq_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                      const hlmi_vq_merge_opts *mo, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
+                      hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst) {
+    return guarded([&] {
+        if (!singles_fastq || !overlaps || !go || !mo || !no || !out_dir || !gst || !mst || !nst)
+            fail(HLMI_EINVAL, "hlmi_vq_iteration: NULL argument");
+        require_device();
+        vq_iteration_run(singles_fastq, overlaps, subreads_in, *go, *mo, *no, out_dir, gst, mst, nst);
+    });
+}
+
 int hlmi_vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2,
                            const char *qual2, uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual,
                            uint32_t *out_len) {

@@ -447,11 +447,12 @@ void vq_graph_opts_stageb(hlmi_vq_graph_opts *o) {
 }
 
 void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st,
-                  VqGraphState *keep) {
+                  VqGraphState *keep, bool for_next) {
     if (o.remove_trans > 3) fail(HLMI_EINVAL, "vq_graph: remove_trans must be 0 .. 3");
     if (o.remove_branches && o.remove_trans != 1)
         fail(HLMI_ESTATE, "vq_graph: remove_branches needs remove_trans 1 (findBranchfreeGraph asserts it, GraphAlgos.cpp:716)");
     *st = hlmi_vq_graph_stats{};
+    if (for_next && !keep) fail(HLMI_EINVAL, "vq_graph: for_next needs a state to keep what findNextOverlaps reads");
     Singles reads = read_singles(fastq, keep != nullptr);
     if (keep) {
         *keep = VqGraphState{};
@@ -484,6 +485,7 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
     // otherwise kept as a non-edge when score > ov_threshold
     std::vector<VqEdge> edges;
     std::string ne_text;
+    std::vector<const hlmi_vq_overlap *> ne_rows;        // for_next: the rows of nonedge_overlaps.txt in file order
     for (uint64_t k = 0; k < n_cand; ++k) {
         const hlmi_vq_overlap &c = cand[k];
         if (score[k] > o.edge_threshold || (mr[k] != -1 && mr[k] <= o.merge_contigs)) {
@@ -496,6 +498,7 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
             e.len = (int32_t)c.len1;
             e.perc = (int32_t)(c.perc2 > 0 ? (unsigned)(0.5 * (double)(c.perc1 + c.perc2)) : c.perc1);
             e.cand = (uint32_t)k;
+            e.pad[0] = (uint8_t)c.ord;
             e.score = score[k]; e.mr = mr[k];
             if (e.pos1 == 0 && e.v1 > e.v2) {            // :443-448: an overlap at position 0 goes from the smaller vertex
                 std::swap(e.v1, e.v2);
@@ -507,11 +510,31 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
             edges.push_back(e);
         } else if (score[k] > o.ov_threshold && mr[k] != -1) {
             overlap_line(ne_text, c);
+            if (for_next) ne_rows.push_back(&c);
         }
     }
     // nonedge_overlaps.txt (:533-541, :654-661): each chunk of 1e6 candidates appends its scored non-edges, in candidate
     // order, and the parser's non-edges follow at the end - so all scored non-edges in file order, then the parser's
     for (const auto &c : nonedge) overlap_line(ne_text, c);
+    if (for_next) {                                       // FindNextOverlaps.cpp:661-691: a score-0 edge per row
+        for (const auto &c : nonedge) ne_rows.push_back(&c);
+        for (const hlmi_vq_overlap *c : ne_rows) {
+            if (c->type1 != 's' || c->type2 != 's')
+                fail(HLMI_ESTATE, "vq_iteration: a non-edge overlap row has a paired-end read; HyLight builds none (--num_pairs 0)");
+            const auto i1 = reads.index_of.find(c->id1), i2 = reads.index_of.find(c->id2);
+            if (i1 == reads.index_of.end() || i2 == reads.index_of.end())
+                fail(HLMI_EINVAL, "vq_iteration: a non-edge overlap row names a read that is not in %s", fastq);
+            VqSrcEdge s{};
+            s.v1 = i1->second; s.v2 = i2->second;
+            s.pos1 = (int32_t)c->pos1; s.pos2 = (int32_t)c->pos2;
+            s.len1 = (int32_t)c->len1; s.len2 = (int32_t)c->len2;
+            s.perc = (int32_t)(c->perc2 > 0 ? (unsigned)(0.5 * (double)(c->perc1 + c->perc2)) : c->perc1);   // Overlap::get_perc
+            s.ori1 = c->ori1 == '+'; s.ori2 = c->ori2 == '+';
+            s.score0 = 1;
+            s.ord = c->ord;
+            keep->nonedge.push_back(s);
+        }
+    }
     write_text(join(out_dir, "nonedge_overlaps.txt"), ne_text);
     st->candidates = edges.size();
 
@@ -539,6 +562,18 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
 
     std::vector<uint32_t> off, src, dst, eid, kept;
     if (o.ignore_inclusions) {                            // removeInclusions
+        if (for_next) {                                   // inclusion_edges (GraphAlgos.cpp:26-42): out-edges, then getEdgeInfo per in-neighbour
+            const std::vector<std::vector<uint32_t>> in = g.adj_in();
+            keep->incl_off.push_back(0);
+            for (uint32_t v = 0; v < g.V; ++v) {
+                if (!incl[v]) continue;
+                for (uint32_t e : g.out[v]) keep->incl_edges.push_back(vq_src_edge(g.pool[e]));
+                for (uint32_t u : in[v])
+                    for (uint32_t e : g.out[u])
+                        if (g.pool[e].v2 == v) { keep->incl_edges.push_back(vq_src_edge(g.pool[e])); break; }
+                keep->incl_off.push_back((uint32_t)keep->incl_edges.size());
+            }
+        }
         g.flatten(off, src, dst, eid);
         vq_inclusion_keep(g.V, off, src, dst, incl, kept);
         g.keep(kept, src, eid);
@@ -577,6 +612,14 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
         kept.clear();
         for (uint32_t p = 0; p < removed.size(); ++p) if (!removed[p]) kept.push_back(p);
         st->tip_edges = removed.size() - kept.size();
+        if (for_next) {                                   // :630-636: a std::set of (source, target), one removeEdge each
+            std::vector<uint32_t> gone;
+            for (uint32_t p = 0; p < removed.size(); ++p) if (removed[p]) gone.push_back(p);
+            std::stable_sort(gone.begin(), gone.end(), [&](uint32_t a, uint32_t b) {
+                return src[a] != src[b] ? src[a] < src[b] : dst[a] < dst[b];
+            });
+            for (uint32_t p : gone) keep->branching.push_back(vq_src_edge(g.pool[eid[p]]));
+        }
         g.keep(kept, src, eid);
     }
     for (uint8_t t : tip) st->tip_reads += t;
@@ -591,6 +634,9 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
         kept.clear();                                     // the cross-component edges of the current graph go (:917-931)
         for (uint32_t p = 0; p < src.size(); ++p) if (comp[src[p]] == comp[dst[p]]) kept.push_back(p);
         st->branch_edges = src.size() - kept.size();
+        if (for_next)                                     // :918-931: vertices ascending, list order
+            for (uint32_t p = 0; p < src.size(); ++p)
+                if (comp[src[p]] != comp[dst[p]]) keep->branching.push_back(vq_src_edge(g.pool[eid[p]]));
         g.keep(kept, src, eid);
     }
 
@@ -610,7 +656,12 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
         if (!best.empty()) {
             std::string s;
             for (const auto &pr : best) {
-                if (o.remove_backedges) g.erase_first(pr.first, pr.second, -1);
+                if (o.remove_backedges) {
+                    if (for_next)                         // reportCycle (OverlapGraph.cpp:548-560) pushes the removed edge
+                        for (uint32_t e : g.out[pr.first])
+                            if (g.pool[e].v2 == pr.second) { keep->branching.push_back(vq_src_edge(g.pool[e])); break; }
+                    g.erase_first(pr.first, pr.second, -1);
+                }
                 s += std::to_string(pr.first); s += '\t'; s += std::to_string(pr.second); s += '\n';
             }
             write_text(cyc, s);

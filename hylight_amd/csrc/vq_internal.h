@@ -52,6 +52,7 @@ struct VqEdge {
     uint32_t cand;                     // file index of the candidate it came from
     double score, mr;                  // overlap score, mismatch rate
 };
+// (pad[0] carries Edge::ord, the overlap row's column 5: findNextOverlaps copies it)
 
 // Edge::switch_edge_orientation (Edge.h) for a single-end edge; returns true when the edge changes direction
 __host__ __device__ inline bool switch_orientation(VqEdge &e) {
@@ -117,15 +118,41 @@ void vq_graph_opts_stageb(hlmi_vq_graph_opts *o);
 // What SRBuilder reads of the finished graph (keep != NULL): the reads, the out-lists after the sortEdges of
 // ViralQuasispecies.cpp:434, the vertex orientations of the winning labelling, the inclusions and the tip reads.  built is
 // false when the run stopped for want of an edge (ViralQuasispecies.cpp:282-291).
+// One source edge of findNextOverlaps: what updateOverlap reads of an Edge (FindNextOverlaps.cpp:25-72)
+struct VqSrcEdge {
+    uint32_t v1, v2;
+    int32_t pos1, pos2, len1, len2, perc;
+    uint8_t ori1, ori2;                // 1: '+'
+    uint8_t score0;                    // get_score() == 0: a non-edge overlap (:34)
+    char ord;
+};
+// what findNextOverlaps reads of a graph edge; single-end: get_len(1) = len, get_len(2) = 0
+inline VqSrcEdge vq_src_edge(const VqEdge &e) {
+    VqSrcEdge s{};
+    s.v1 = e.v1; s.v2 = e.v2;
+    s.pos1 = e.pos1; s.pos2 = e.pos2;
+    s.len1 = e.len; s.len2 = 0;
+    s.perc = e.perc;
+    s.ori1 = e.ori1; s.ori2 = e.ori2;
+    s.score0 = e.score == 0;
+    s.ord = (char)e.pad[0];
+    return s;
+}
 struct VqGraphState {
     bool built = false;
     std::vector<std::string> seq, qual;
     std::vector<uint64_t> id;
     std::vector<std::vector<VqEdge>> out;
     std::vector<uint8_t> orient, incl, tip;
+    // for findNextOverlaps (for_next): OverlapGraph::branching_edges in push order, the rows of nonedge_overlaps.txt in file
+    // order as the edges of FindNextOverlaps.cpp:661-691, and inclusion_edges (GraphAlgos.cpp:26-42): list l = incl_edges
+    // [incl_off[l], incl_off[l + 1])
+    std::vector<VqSrcEdge> branching, nonedge, incl_edges;
+    std::vector<uint32_t> incl_off;
 };
+// for_next: also keep what findNextOverlaps reads, and refuse a paired-end non-edge row before a file is written
 void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st,
-                  VqGraphState *keep = nullptr);
+                  VqGraphState *keep = nullptr, bool for_next = false);
 
 }  // namespace hlmi
 
@@ -181,5 +208,31 @@ void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_
                   const hlmi_vq_merge_opts &mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
 void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2, const char *qual2,
                        uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual, uint32_t *out_len);
+
+}  // namespace hlmi
+
+namespace hlmi {
+
+// ---- vq_next.hip: the overlaps of the next iteration (SRBuilder::findNextOverlaps, FNO 1) --------------------------------
+namespace vqn {
+constexpr int WG = 256;
+constexpr uint32_t NONE = 0xffffffffu;
+constexpr uint32_t LINE_WIDTH = 64;              // lines up to this many bytes are ordered on the device (8 words of 8 bytes)
+constexpr int SEARCH_STEPS = 33;                 // a binary search over fewer than 2^32 entries ends within this many steps
+}  // namespace vqn
+// What the merge leaves per vertex (the columns of superread_map.txt and the new reads' lengths)
+struct VqNextTables {
+    std::vector<uint32_t> ent;                   // new id of the read or of its super-read; NONE: visited without a super-read
+    std::vector<uint8_t> in_sr;                  // 1: ent is a super-read
+    std::vector<uint32_t> off;                   // offset of the read in it (0 for a copied read)
+    std::vector<uint32_t> len;                   // length of the new read `ent`
+};
+void vq_next_opts_stageb(hlmi_vq_next_opts *o);
+// -> the image of overlaps.txt
+std::string vq_next_run(const VqGraphState &g, const VqNextTables &t, double edge_threshold, const hlmi_vq_next_opts &no,
+                        hlmi_vq_next_stats *st);
+void vq_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                      const hlmi_vq_merge_opts &mo, const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst,
+                      hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst);
 
 }  // namespace hlmi

@@ -234,19 +234,24 @@ void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint3
     *out_len = (uint32_t)total;
 }
 
-void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                  const hlmi_vq_merge_opts &mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst) {
+// hlmi_vq_merge (no == NULL) and hlmi_vq_iteration: one path.  With `no` the call goes on to findNextOverlaps, and reads
+// subreads_in in front of the graph's first write: the iteration loop runs in place, its inputs under the names written here.
+static void merge_and_next(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                           const hlmi_vq_merge_opts &mo, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
+                           hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst) {
     *mst = hlmi_vq_merge_stats{};
+    if (nst) *nst = hlmi_vq_next_stats{};
     if (!mo.first_it && !subreads_in) fail(HLMI_EINVAL, "vq_merge: first_it is off and there is no subreads file");
+    std::map<uint64_t, Originals> dict;
+    if (no && !mo.first_it) dict = read_subreads(subreads_in);
     VqGraphState g;
-    vq_graph_run(fastq, overlaps, go, out_dir, gst, &g);       // the graph and its files: one path for both entry points
+    vq_graph_run(fastq, overlaps, go, out_dir, gst, &g, no != nullptr);   // the graph and its files: one path for all entry points
     if (!g.built) return;                                        // ViralQuasispecies.cpp:282-291: nothing to be done
     const double t0 = now_ms();
     const uint32_t V = (uint32_t)g.seq.size();
     for (uint32_t v = 0; v < V; ++v) mst->bases_in += g.seq[v].size();       // (checked by vq_graph_run: vq_merge_check_reads)
     // original_ID_dict (buildOriginalsDict): first_it: every read is its own original at index 0, forward
-    std::map<uint64_t, Originals> dict;
-    if (!mo.first_it) dict = read_subreads(subreads_in);
+    if (!no && !mo.first_it) dict = read_subreads(subreads_in);
     auto originals_of = [&](uint32_t v) -> Originals {
         if (mo.first_it) return Originals{{g.id[v], Orig{true, 0, (int)g.seq[v].size()}}};
         auto it = dict.find(g.id[v]);
@@ -394,7 +399,35 @@ void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_
     }
     write_file(join(out_dir, "superread_map.txt"), map.data(), map.size(), "wb");
     mst->ms_merge = now_ms() - t0;
+    if (no) {                                                    // ViralQuasispecies.cpp:449-479
+        const double t1 = now_ms();
+        VqNextTables t;
+        t.ent.resize(V); t.in_sr = visited; t.off = offset; t.len.assign(V, 0);
+        for (uint32_t v = 0; v < V; ++v) {
+            t.ent[v] = new_id[v] < 0 ? vqn::NONE : (uint32_t)new_id[v];
+            if (new_id[v] >= 0) t.len[v] = recs[(size_t)new_id[v]].len;
+        }
+        const std::string image = vq_next_run(g, t, go.edge_threshold, *no, nst);
+        write_file(join(out_dir, "overlaps.txt"), image.data(), image.size(), "wb");
+        const std::string line = std::to_string(gst->vertices) + "\t" + std::to_string(gst->edges_final) + "\t" +
+                                 std::to_string(nst->lines) + "\n";
+        write_file(join(out_dir, "stats.txt"), line.data(), line.size(), "ab");
+        nst->ms_next = now_ms() - t1;
+    }
     ktimer_flush();
+}
+
+void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                  const hlmi_vq_merge_opts &mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst) {
+    merge_and_next(fastq, overlaps, subreads_in, go, mo, nullptr, out_dir, gst, mst, nullptr);
+}
+
+void vq_next_opts_stageb(hlmi_vq_next_opts *o) { *o = hlmi_vq_next_opts{}; }
+
+void vq_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                      const hlmi_vq_merge_opts &mo, const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst,
+                      hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst) {
+    merge_and_next(fastq, overlaps, subreads_in, go, mo, &no, out_dir, gst, mst, nst);
 }
 
 }  // namespace hlmi

@@ -97,7 +97,8 @@ def contig_ava_opts():
     return o
 
 
-def extend_con(input_con, outdir1, out_file, threads=30, len_c=50000000, stageb_cmd=None, stageb_graph=False, stageb_merge=False):
+def extend_con(input_con, outdir1, out_file, threads=30, len_c=50000000, stageb_cmd=None, stageb_graph=False, stageb_merge=False,
+               stageb_native=False):
     """HyLight.extend_con (script/HyLight.py:282-326) up to the SAVAGE overlap file.  Returns the number of contigs
     written to contigs_b.fastq.  `stageb_cmd`: command prefix of the reference's stage-b script
     (`python .../pipeline_per_stage.py`) for installations that have it; without it the merge itself is skipped.
@@ -105,7 +106,8 @@ def extend_con(input_con, outdir1, out_file, threads=30, len_c=50000000, stageb_
     hlmi_vq_graph with the stage-b options) into outdir1/stageb/ - graph.gfa, graph.txt, graph_trimmed.gfa,
     digraph.txt, cycles.txt, tips.txt, nonedge_overlaps.txt.  `stageb_merge`: that graph and the super-reads merged along
     its edges (ViralQuasispecies --cliques=false up to findNextOverlaps, hlmi_vq_merge with the stage-b options) -
-    singles.fastq, subreads.txt, removed_tip_sequences.fastq, superread_map.txt in outdir1/stageb/."""
+    singles.fastq, subreads.txt, removed_tip_sequences.fastq, superread_map.txt in outdir1/stageb/.  `stageb_native`: the
+    whole stage-b loop in outdir1/stageb/ (hylight_amd.vq_stageb) and out_file from its last singles.fastq."""
     conb = os.path.join(outdir1, "contigs_b.fastq")
     if os.path.exists(conb):
         os.remove(conb)
@@ -134,6 +136,12 @@ def extend_con(input_con, outdir1, out_file, threads=30, len_c=50000000, stageb_
         api.vq_merge(os.path.join(sb, "fastq", "singles.fastq"), savage, sb)
     elif stageb_graph and n:
         api.vq_graph(os.path.join(sb, "fastq", "singles.fastq"), savage, sb)
+    if stageb_native and n:                                    # HyLight.py:320-324 with the library's own stage b
+        from . import vq_stageb
+        vq_stageb.run(os.path.join(sb, "fastq"), savage, sb)
+        merged = os.path.join(sb, "singles.fastq")             # absent when no two contigs overlap: they are the result
+        vq_stageb.fastq2fasta(merged if os.path.exists(merged) else os.path.join(sb, "fastq", "singles.fastq"), out_file)
+        return n
     if stageb_cmd and n:                                       # HyLight.py:320-324
         _run(f"{stageb_cmd} --no_error_correction --remove_branches true --stage b --min_overlap_len 300 "
              f"--min_overlap_perc 0 --edge_threshold 1 --overlaps ./sfoverlap.out.savage --fastq ./fastq --max_tip_len 1000 "
@@ -185,6 +193,9 @@ def build_parser():
                         "--short_contigs, cluster the short reads and run it per cluster (HyLight.py:215-275)")
     p.add_argument("--stageb_cmd", default=None,
                    help="(extension) command prefix of the reference's pipeline_per_stage.py, if installed")
+    p.add_argument("--stageb_native", action="store_true",
+                   help="(extension) run stage b with the library (hylight_amd.vq_stageb: ViralQuasispecies' merge iterations on "
+                        "the GPU) and write final_contigs.fa - the contigs themselves when no two of them overlap")
     return p
 
 
@@ -226,7 +237,7 @@ def _short_branch(args, tmp, outdir, long_con3):
                 with open(p, "rb") as f:
                     shutil.copyfileobj(f, o)
     short_con = os.path.join(outdir, "short_stageb.fa")
-    extend_con(fname, tmp, short_con, threads=30, len_c=500000, stageb_cmd=args.stageb_cmd)
+    extend_con(fname, tmp, short_con, threads=30, len_c=500000, stageb_cmd=args.stageb_cmd, stageb_native=args.stageb_native)
     all_con = os.path.join(outdir, "all_contigs.fa")
     first = short_con if os.path.exists(short_con) and os.path.getsize(short_con) else fname     # HyLight.py:266-275
     with open(all_con, "wb") as o:
@@ -234,11 +245,12 @@ def _short_branch(args, tmp, outdir, long_con3):
             with open(p, "rb") as f:
                 shutil.copyfileobj(f, o)
     final = os.path.join(outdir, "final_contigs.fa")
-    n_con = extend_con(all_con, tmp, final, threads=30, stageb_cmd=args.stageb_cmd)
+    n_con = extend_con(all_con, tmp, final, threads=30, stageb_cmd=args.stageb_cmd, stageb_native=args.stageb_native)
     if not os.path.exists(final):
         sys.stderr.write(f"hylight-mi: {n_con} contigs, their overlaps are in tmp/stageb/sfoverlap.out.savage; the stage-b merge "
-                         "(pipeline_per_stage.py / ViralQuasispecies, HyLight.py:320-324) is not built here, so "
-                         f"final_contigs.fa was not written (pass --stageb_cmd to run the reference's): exit status {EXIT_NO_FINAL}\n")
+                         "(pipeline_per_stage.py / ViralQuasispecies, HyLight.py:320-324) was not asked for, so final_contigs.fa "
+                         "was not written (pass --stageb_native to run the library's, or --stageb_cmd for the reference's): "
+                         f"exit status {EXIT_NO_FINAL}\n")
         return EXIT_NO_FINAL
     return 0
 
@@ -378,23 +390,25 @@ def _pipeline(args, pool):
     if args.stop_after == "stageb_graph":
         n_con = extend_con(all_con, tmp, final, threads=30, stageb_graph=True)
         sys.stderr.write(f"hylight-mi: {n_con} contigs; the overlap graph of the stage-b merge is in tmp/stageb/ (graph.gfa, "
-                         "graph.txt, graph_trimmed.gfa, digraph.txt, cycles.txt, tips.txt); merging along it (SRBuilder) is "
-                         f"not built here, so final_contigs.fa was not written: exit status {EXIT_NO_FINAL}\n")
+                         "graph.txt, graph_trimmed.gfa, digraph.txt, cycles.txt, tips.txt); the run stops there as asked, so "
+                         f"final_contigs.fa was not written (--stageb_native runs all of stage b): exit status {EXIT_NO_FINAL}\n")
         return EXIT_NO_FINAL
     if args.stop_after == "stageb_merge":
         n_con = extend_con(all_con, tmp, final, threads=30, stageb_merge=True)
         sys.stderr.write(f"hylight-mi: {n_con} contigs; the super-reads of the first stage-b iteration are in tmp/stageb/ "
-                         "(singles.fastq, subreads.txt, superread_map.txt, removed_tip_sequences.fastq); the overlaps between "
-                         "them (FindNextOverlaps) and the iteration are not built here, so final_contigs.fa was not written: "
+                         "(singles.fastq, subreads.txt, superread_map.txt, removed_tip_sequences.fastq); the run stops there as "
+                         "asked, so final_contigs.fa was not written (--stageb_native runs all of stage b): "
                          f"exit status {EXIT_NO_FINAL}\n")
         return EXIT_NO_FINAL
-    n_con = extend_con(all_con, tmp, final, threads=30, stageb_cmd=None if args.stop_after == "savage" else args.stageb_cmd)
+    n_con = extend_con(all_con, tmp, final, threads=30, stageb_cmd=None if args.stop_after == "savage" else args.stageb_cmd,
+                       stageb_native=args.stageb_native and args.stop_after != "savage")
     if args.stop_after == "savage":
         return 0
     if not os.path.exists(final):
         sys.stderr.write(f"hylight-mi: {n_con} contigs, their overlaps are in tmp/stageb/sfoverlap.out.savage; the stage-b merge "
-                         "(pipeline_per_stage.py / ViralQuasispecies, HyLight.py:320-324) is not built here, so "
-                         f"final_contigs.fa was not written (pass --stageb_cmd to run the reference's): exit status {EXIT_NO_FINAL}\n")
+                         "(pipeline_per_stage.py / ViralQuasispecies, HyLight.py:320-324) was not asked for, so final_contigs.fa "
+                         "was not written (pass --stageb_native to run the library's, or --stageb_cmd for the reference's): "
+                         f"exit status {EXIT_NO_FINAL}\n")
         return EXIT_NO_FINAL
     return 0
 

@@ -38,7 +38,7 @@ extern "C" {
  * hlmi_vq_merge, hlmi_vq_consensus_pair).  A caller
  * compares hlmi_abi_version() with the HLMI_ABI_VERSION of the header it was built against BEFORE passing structs: a caller of
  * an older header would hand over a shorter hlmi_ava_opts than the library reads. */
-#define HLMI_ABI_VERSION 6
+#define HLMI_ABI_VERSION 7
 int         hlmi_abi_version(void);
 int         hlmi_init(int device, int host_threads);
 void        hlmi_shutdown(void);
@@ -153,7 +153,8 @@ int hlmi_sfo2overlaps(const char *in_sfo, const char *out_savage, int num_single
  * text of record and are checked against oracle/vq.py and tests/vq_graph_model.py only (parity unpinned).  Built: the
  * parser, the quality-aware overlap score, transitive edges, and the oriented, reduced overlap graph of a --graph_only run
  * (hlmi_vq_graph), and the step that reads it with --cliques=false: SRBuilder::mergeAlongEdges, the super-reads of the next
- * iteration (hlmi_vq_merge).  Not built: cliques, FindNextOverlaps and the stage-b iteration of pipeline_per_stage.py. */
+ * iteration (hlmi_vq_merge), and SRBuilder::findNextOverlaps behind it (hlmi_vq_iteration: one whole stage-b iteration; the
+ * loop of pipeline_per_stage.py is hylight_amd/vq_stageb.py).  Not built: cliques, FindNextOverlaps3, BranchReduction. */
 typedef struct {
     uint64_t id1, id2;                 /* strtoul(..., 0) of columns 1, 2                        (Overlap.h:39-40, Types.h:99)  */
     uint32_t pos1, pos2, perc1, perc2, len1, len2;   /* atoi; pos2 = perc2 = len2 = 0 when column 4 is "-" (Overlap.h:53-57) */
@@ -315,6 +316,59 @@ typedef struct {
  * returns before this step (ViralQuasispecies.cpp:282-291): so does this call, and none of the four files is written. */
 int hlmi_vq_merge(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
                   const hlmi_vq_merge_opts *mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
+
+/* ---- SRBuilder::findNextOverlaps with --FNO=1 --optimize=false --cliques=false --error_correction=false --threads 1, to the
+ * end of main (FindNextOverlaps.cpp:25-327 updateOverlap, :331-347 findCliqueIndex, :351-565 computeOverlapData - the S-S
+ * branch :357-385 only -, :605-631 reconsiderEdgeOverlaps, :635-697 reconsiderNonedgeOverlaps, :816-887
+ * findInclusionOverlaps, :890-958 findNextOverlaps, ViralQuasispecies.cpp:449-479): the overlaps of the next iteration. */
+typedef struct {
+    int no_inclusion_overlaps;  /* --no_inclusion_overlaps: lines with percentage 100 are left out (:68, :145, :223, :320)  */
+} hlmi_vq_next_opts;
+/* pipeline_per_stage.py does not pass the option: 0 */
+void hlmi_vq_next_opts_stageb(hlmi_vq_next_opts *o);
+typedef struct {
+    uint64_t src_graph;         /* source edges: the final graph's out-lists (:612-623)                                     */
+    uint64_t src_branching;     /* ... branching_edges: tip edges, removeBranches' edges, back edges (:628-629)            */
+    uint64_t src_nonedge;       /* ... rows of nonedge_overlaps.txt that were kept (:697)                                   */
+    uint64_t nonedge_skipped;   /* rows left out because checkEdge(v1, v2, reverse allowed) > 0 (:694-696)                  */
+    uint64_t src_induced;       /* ... edges induced through an included vertex and kept: checkEdge == -1 (:876-879)        */
+    uint64_t copied, u2sr, v2sr, sr2sr;   /* the reference's four counters: lines per case, before identical lines collapse  */
+    uint64_t claims_failed;     /* owners of a key whose computeOverlapData failed (new_pos1 >= len, :378-384)              */
+    uint64_t lines;             /* distinct lines = the lines of overlaps.txt = the third column of the stats.txt line      */
+    double ms_next;             /* wall time of the step after the merge                                                    */
+} hlmi_vq_next_stats;
+/* One stage-b iteration: hlmi_vq_merge (same code, same files in out_dir), then overlaps.txt - the std::set<std::string> of
+ * :918-948 in ascending byte order, one '\n' per line - and one line APPENDED to stats.txt: "<vertices>\t<edges of the final
+ * graph>\t<lines>\n" (ViralQuasispecies.cpp:472-479).  All inputs are read before any output is written: the iteration loop
+ * calls this with singles_fastq, overlaps and subreads_in lying in out_dir under the names it writes.  When the graph has
+ * no edge the call stops where hlmi_vq_merge stops: no overlaps.txt, no stats.txt line.
+ * Source edges, in this order (the order decides which one owns a key):
+ *   1  the final graph: vertices ascending, each out-list in the order of the sortEdges of ViralQuasispecies.cpp:434
+ *   2  branching_edges in push order: the tip edges in ascending (source, target) (GraphAlgos.cpp:630-636), the edges
+ *      removeBranches removed (:918-931), the back edges reportCycle removed (OverlapGraph.cpp:548-560), each as it stood
+ *   3  the rows of nonedge_overlaps.txt in file order as score-0 edges (:661-691), a row left out when
+ *      checkEdge(v1, v2, true) > 0: the score of the first v1 -> v2 of v1's list, else of the first v2 -> v1
+ *   4  per included vertex (ascending; its out-edges, then per in-neighbour the first edge from it: GraphAlgos.cpp:26-42,
+ *      copied after the labelling) every pair i < j of the list that chains through it (:841-865): score = edge_threshold,
+ *      len = min(|r1| - pos1, |r2|), perc = floor(100 * len / min(|r1|, |r2|)) in integers; kept when checkEdge == -1
+ * Per source edge u -> v (updateOverlap): both unvisited: the edge is copied with the new ids, its own positions, perc and
+ * lengths (:47-72); a vertex in a super-read stands for that super-read, lying at its offset (:73-326): new_pos1 = pos1 +
+ * offset(u) - offset(v); negative: the second entity comes first, new_pos1 = -new_pos1, len = its length; overlap length =
+ * min(len - new_pos1, len1, len2); percentage = (int)floor(max(ol / float(len1), ol / float(len2)) * 100) with the
+ * division and the product rounded to float one after the other; no line when new_pos1 >= len.  A vertex that is visited
+ * but in no super-read (too short, N rate, inclusion, tip: SRBuilder.cpp:1286-1311) gives nothing; the same super-read on
+ * both sides is skipped (:255).  A case with a super-read first claims (min id, max id) in overlaps_found (:84-97, :162-175,
+ * :261-273): the first source edge in the order above owns the pair, later ones are dropped, and when the owner's
+ * computeOverlapData fails the pair gets no line.  Copied edges never consult the table.  ori1 / ori2: for a score-0 edge
+ * '+' where the edge's orientation equals the vertex label, else '-' (:34-37); '+' for every other edge.
+ * Device: one thread per source edge for case and key, a stable radix sort of (key, sequence number) and its run heads for
+ * the claims, one thread per line for the text, LSD radix passes over the lines' 8-byte big-endian words for the order (a
+ * line padded with zero bytes orders as the string does) - lines longer than 64 bytes make the call order on the host.
+ * Refused with HLMI_ESTATE before anything is written: a paired-end row ('p') among the candidates or the non-edge rows.
+ * add_duplicates and resolve_orientations = false are not options; FindNextOverlaps3 and cliques are not built. */
+int hlmi_vq_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                      const hlmi_vq_merge_opts *mo, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
+                      hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst);
 
 /* ---- short-read clustering (HyLight.py:215-226: get_readnames.py, bin_pointer_limited_filechunks_shortpath2.py,
  * getclusters.py, get_fq_cluster.py with cwd = tmp/ and run id HiStrain).  Parity pinned: tests/golden/fxH_cluster_*.json
