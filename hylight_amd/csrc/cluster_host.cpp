@@ -19,6 +19,7 @@
 #include <unistd.h>
 
 #include "cluster_internal.h"
+#include "paf_io.h"
 
 namespace hlmi {
 
@@ -29,10 +30,6 @@ constexpr uint64_t CHUNK = 2600000;                 // bin_pointer:30
 constexpr uint64_t WINDOW_DEFAULT = 512ull << 20;
 constexpr uint64_t WINDOW_MAX = 2ull << 30;         // 32-bit line offsets inside a window
 const char *RUN_ID = "HiStrain";                    // HyLight.py:69
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 std::vector<uint8_t> read_all(const char *path) {
     FILE *f = fopen(path, "rb");

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include <charconv>
+#include <chrono>
 
 #include <algorithm>
 #include <thread>
@@ -44,6 +45,23 @@ std::string read_file(const char *path) {
     while ((n = fread(buf, 1, sizeof buf, f)) > 0) s.append(buf, n);
     fclose(f);
     return s;
+}
+
+void write_file(const std::string &path, const char *data, size_t n, const char *mode) {
+    FILE *f = fopen(path.c_str(), mode);
+    if (!f) fail(HLMI_EIO, "cannot write %s: %s", path.c_str(), strerror(errno));
+    const bool ok = fwrite(data, 1, n, f) == n;
+    if (fclose(f) != 0 || !ok) fail(HLMI_EIO, "cannot write %s", path.c_str());
+}
+
+std::string join_path(const char *dir, const char *name) {
+    std::string p(dir);
+    if (!p.empty() && p.back() != '/') p += '/';
+    return p + name;
+}
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 void write_lines(const char *path, const std::vector<std::string> &lines) {

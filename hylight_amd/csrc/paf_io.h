@@ -69,5 +69,9 @@ void sort_scored_lines(std::vector<std::string_view> &lines, const std::vector<u
 void write_lines(const char *path, const std::vector<std::string> &lines);
 void write_lines(const char *path, const std::vector<std::string_view> &lines);
 std::string read_file(const char *path);
+// the whole of data[0, n) into path as fopen's `mode` opens it ("ab": appended); HLMI_EIO when it cannot be opened or written
+void write_file(const std::string &path, const char *data, size_t n, const char *mode = "wb");
+std::string join_path(const char *dir, const char *name);      // dir + '/' + name (no second '/' behind one)
+double now_ms();                                               // steady clock, for the ms_* fields of the stats
 
 }  // namespace hlmi

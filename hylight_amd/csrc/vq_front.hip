@@ -3,12 +3,14 @@
 //   * the text of record: which lines of the overlaps file become edge candidates (EdgeCalculator.cpp:561-666 in front
 //     of process_overlaps, Overlap.h:37-72,196-203) - host, integer and string rules only;
 //   * transitive edges by intersection of sorted adjacency lists (GraphAlgos.cpp:746-795,938-993) - device.
-// and the quality-aware score of every candidate (EdgeCalculator.cpp:26-139, further down).  The graph built from them
-// (orientation, reductions, writers) is vq_graph.hip / vq_graph_host.cpp, which share the transitive-edge kernels through
-// vq_internal.h.  The reference needs Boost and cannot be compiled in this image, so everything is checked against
+// and the quality-aware score of every candidate (EdgeCalculator.cpp:26-139, further down), with the one reader of
+// singles.fastq in front of it.  The graph built from them (orientation, reductions, writers) is vq_graph.hip /
+// vq_graph_host.cpp, which call the same parsers and the same rounds of the transitive-edge pass (vq_trans_rounds) as the
+// entry points here.  The reference needs Boost and cannot be compiled in this image, so everything is checked against
 // oracle/vq.py only: PARITY UNPINNED.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <unordered_map>
@@ -37,15 +39,11 @@ static std::string without(std::string s, const char *drop) {
 }
 
 void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, int relax_pe, uint64_t max_overlaps,
-                       hlmi_vq_overlap *out, uint64_t cap, uint64_t *n_out, uint64_t *n_nonedge, uint64_t *n_skipped) {
-    vq_parse_overlaps(path, min_len, min_perc, relax_pe, max_overlaps, out, cap, n_out, n_nonedge, n_skipped, nullptr);
-}
-
-void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, int relax_pe, uint64_t max_overlaps,
-                       hlmi_vq_overlap *out, uint64_t cap, uint64_t *n_out, uint64_t *n_nonedge, uint64_t *n_skipped,
-                       std::vector<hlmi_vq_overlap> *nonedges) {
+                       std::vector<hlmi_vq_overlap> &edges, std::vector<hlmi_vq_overlap> *nonedges, uint64_t *n_nonedge,
+                       uint64_t *n_skipped) {
+    edges.clear();
     const std::string data = read_file(path);
-    uint64_t kept = 0, nonedge = 0, skipped = 0, i = 0;
+    uint64_t nonedge = 0, skipped = 0, i = 0;
     size_t pos = 0;
     std::vector<std::string> f;
     while (pos < data.size() && i < max_overlaps) {          // (getline: a last line without '\n' counts)
@@ -85,7 +83,7 @@ void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, in
         o.len1 = (uint32_t)len1; o.len2 = (uint32_t)len2;
         o.ord = ord[0]; o.ori1 = ori1[0]; o.ori2 = ori2[0]; o.type1 = ty1[0]; o.type2 = ty2[0];
         if (o.id1 == o.id2) { ++skipped; continue; }
-        const unsigned perc = o.perc2 > 0 ? (unsigned)(0.5 * (double)(o.perc1 + o.perc2)) : o.perc1;     // Overlap.h:196-203
+        const uint32_t perc = vq_perc(o);
         const bool ss = o.type1 == 's' && o.type2 == 's', anyp = o.type1 == 'p' || o.type2 == 'p';
         bool edge = false, decided = false;
         if (o.len1 >= min_len && ss) { decided = true; edge = perc >= min_perc; }
@@ -97,16 +95,25 @@ void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, in
             continue;
         }
         if (!edge) { ++skipped; continue; }                   // long enough, identity too low: dropped without a trace
-        if (out && kept < cap) out[kept] = o;
-        ++kept;
+        edges.push_back(o);
     }
-    *n_out = kept; *n_nonedge = nonedge; *n_skipped = skipped;
+    *n_nonedge = nonedge; *n_skipped = skipped;
+}
+
+// the C entry point's form (graph.h): the first `cap` candidates into out, the number of all of them into n_out
+void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, int relax_pe, uint64_t max_overlaps,
+                       hlmi_vq_overlap *out, uint64_t cap, uint64_t *n_out, uint64_t *n_nonedge, uint64_t *n_skipped) {
+    std::vector<hlmi_vq_overlap> edges;
+    vq_parse_overlaps(path, min_len, min_perc, relax_pe, max_overlaps, edges, nullptr, n_nonedge, n_skipped);
+    if (out) std::copy_n(edges.begin(), std::min<uint64_t>(cap, edges.size()), out);
+    *n_out = edges.size();
 }
 
 // ---------------------------------------------------------------------------------------------
 // transitive edges
 // ---------------------------------------------------------------------------------------------
-// edge_keys_kernel, offsets_kernel, trans_kernel and trans_big_kernel are shared with vq_graph.hip (vq_internal.h)
+// the rounds are vq_trans_rounds, further down, for the entry point here and for vq_graph.hip; vq_next.hip builds its keys
+// with edge_keys_kernel too (vq_internal.h)
 namespace vqk {
 
 __global__ void edge_keys_kernel(const uint32_t *a, const uint32_t *b, const uint32_t *ids, size_t n, uint64_t *key, uint32_t *val) {
@@ -237,29 +244,14 @@ __global__ void branch_mark_kernel(const uint32_t *src, const uint32_t *dst, con
 }
 }  // namespace
 
-void vq_transitive_edges(uint32_t n_vertices, uint64_t n_edges, const uint32_t *src, const uint32_t *dst, const uint32_t *ovlen,
-                         int remove_trans, uint8_t *flags, uint64_t *n_transitive) {
-    if (remove_trans < 1 || remove_trans > 3) fail(HLMI_EINVAL, "remove_trans must be 1, 2 or 3");
-    if (n_edges >= (1ull << 32)) fail(HLMI_EINVAL, "more than 2^32 edges");
-    *n_transitive = 0;
-    if (!n_edges) return;
-    for (uint64_t k = 0; k < n_edges; ++k)
-        if (src[k] >= n_vertices || dst[k] >= n_vertices) fail(HLMI_EINVAL, "edge %llu names a vertex >= n_vertices", (unsigned long long)k);
-    const size_t E = (size_t)n_edges;
-    DBuf<uint32_t> d_src, d_dst;
-    d_src.upload(src, E);
-    d_dst.upload(dst, E);
-    DBuf<uint8_t> result(E);
-    result.zero();
-    DBuf<uint32_t> ids;                    // edges of the current graph (round 1: all)
-    size_t n_cur = E;
-    size_t found = 0;
-    for (int round = 1; round <= remove_trans && n_cur; ++round) {
+size_t vq_trans_rounds(uint32_t n_vertices, const uint32_t *d_src, const uint32_t *d_dst, size_t E, int rounds, DBuf<uint32_t> &ids) {
+    size_t n_cur = E, found = 0;           // the edges of the current round's graph: ids[0, n_cur) (round 1: all)
+    for (int round = 1; round <= rounds && n_cur; ++round) {
         DBuf<uint64_t> okey(n_cur), ikey(n_cur);
         DBuf<uint32_t> oval(n_cur), ival(n_cur), ooff((size_t)n_vertices + 1), ioff((size_t)n_vertices + 1);
         const uint32_t *cur = round == 1 ? nullptr : ids.p;
-        hipLaunchKernelGGL(edge_keys_kernel, grid1(n_cur), dim3(WG), 0, stream(), d_src.p, d_dst.p, cur, n_cur, okey.p, oval.p);
-        hipLaunchKernelGGL(edge_keys_kernel, grid1(n_cur), dim3(WG), 0, stream(), d_dst.p, d_src.p, cur, n_cur, ikey.p, ival.p);
+        hipLaunchKernelGGL(edge_keys_kernel, grid1(n_cur), dim3(WG), 0, stream(), d_src, d_dst, cur, n_cur, okey.p, oval.p);
+        hipLaunchKernelGGL(edge_keys_kernel, grid1(n_cur), dim3(WG), 0, stream(), d_dst, d_src, cur, n_cur, ikey.p, ival.p);
         sort_pairs_u64_u32(okey, oval, n_cur, 0, 64);
         sort_pairs_u64_u32(ikey, ival, n_cur, 0, 64);
         hipLaunchKernelGGL(offsets_kernel, grid1((size_t)n_vertices + 1), dim3(WG), 0, stream(), okey.p, n_cur, n_vertices, ooff.p);
@@ -269,9 +261,8 @@ void vq_transitive_edges(uint32_t n_vertices, uint64_t n_edges, const uint32_t *
         fl.zero();
         DBuf<uint32_t> big(n_vertices ? n_vertices : 1), n_big(1);
         n_big.zero();
-        const unsigned nb = (unsigned)std::min<size_t>(cdiv((size_t)n_vertices, (size_t)WAVES), 256 * 16);
-        hipLaunchKernelGGL(trans_kernel, dim3(nb ? nb : 1), dim3(WG), 0, stream(), okey.p, oval.p, ooff.p, ikey.p, ioff.p, n_vertices,
-                           fl.p, big.p, n_big.p);
+        hipLaunchKernelGGL(trans_kernel, dim3(waves_grid(n_vertices)), dim3(WG), 0, stream(), okey.p, oval.p, ooff.p, ikey.p, ioff.p,
+                           n_vertices, fl.p, big.p, n_big.p);
         HIP_CHECK(hipGetLastError());
         const uint32_t hb = download_one(n_big.p);
         if (hb) hipLaunchKernelGGL(trans_big_kernel, dim3(256 * 8), dim3(WG), 0, stream(), okey.p, oval.p, ooff.p, ikey.p, ioff.p,
@@ -283,6 +274,24 @@ void vq_transitive_edges(uint32_t n_vertices, uint64_t n_edges, const uint32_t *
         ids = std::move(next);
         n_cur = found;
     }
+    return found;
+}
+
+void vq_transitive_edges(uint32_t n_vertices, uint64_t n_edges, const uint32_t *src, const uint32_t *dst, const uint32_t *ovlen,
+                         int remove_trans, uint8_t *flags, uint64_t *n_transitive) {
+    if (remove_trans < 1 || remove_trans > 3) fail(HLMI_EINVAL, "remove_trans must be 1, 2 or 3");
+    if (n_edges >= (1ull << 32)) fail(HLMI_EINVAL, "more than 2^32 edges");
+    *n_transitive = 0;
+    if (!n_edges) return;
+    for (uint64_t k = 0; k < n_edges; ++k)
+        if (src[k] >= n_vertices || dst[k] >= n_vertices) fail(HLMI_EINVAL, "edge %llu names a vertex >= n_vertices", (unsigned long long)k);
+    const size_t E = (size_t)n_edges;
+    DBuf<uint32_t> d_src, d_dst, ids;
+    d_src.upload(src, E);
+    d_dst.upload(dst, E);
+    DBuf<uint8_t> result(E);
+    result.zero();
+    const size_t found = vq_trans_rounds(n_vertices, d_src.p, d_dst.p, E, remove_trans, ids);
     if (found) {
         DBuf<uint8_t> ones(found);
         ones.fill_ff();
@@ -354,53 +363,69 @@ __global__ void vq_score_kernel(const uint8_t *seq, const uint8_t *qual, const V
 }
 }  // namespace
 
-void vq_overlap_scores(const char *fastq, const hlmi_vq_overlap *ov, uint64_t n, double mismatch, uint32_t min_read_len,
-                       double *score, double *mismatch_rate, int64_t *pos3) {
-    // singles.fastq: 4-line records, id = strtoul of the first word behind '@', bases upper-cased (FastqStorage.cpp:92-150)
-    const std::string data = read_file(fastq);
-    std::vector<VqReadRef> reads;
-    std::unordered_map<uint64_t, uint32_t> index_of;
-    std::string seq, qual;
-    {
-        size_t pos = 0, line = 0;
-        uint64_t id = 0;
-        std::string cur_seq;
-        while (pos < data.size()) {
-            size_t e = data.find('\n', pos);
-            if (e == std::string::npos) e = data.size();
-            const std::string_view l(data.data() + pos, e - pos);
-            pos = e + 1;
-            switch (line++ % 4) {
-                case 0: {
-                    if (l.empty() || l[0] != '@') fail(HLMI_EINVAL, "%s: read id does not start with @ (line %zu)", fastq, line);
-                    size_t b = 1;
-                    while (b < l.size() && isspace((unsigned char)l[b])) ++b;
-                    size_t w = b;
-                    while (w < l.size() && !isspace((unsigned char)l[w])) ++w;
-                    id = strtoul(std::string(l.substr(b, w - b)).c_str(), nullptr, 0);
-                    break;
-                }
-                case 1:
-                    cur_seq.assign(l);
-                    for (char &c : cur_seq) c = (char)toupper((unsigned char)c);
-                    break;
-                case 2: break;
-                case 3: {
-                    if (cur_seq.empty()) fail(HLMI_EINVAL, "%s: single read %llu has an empty sequence", fastq, (unsigned long long)id);
-                    if (l.size() != cur_seq.size()) fail(HLMI_EINVAL, "%s: read %llu: %zu bases, %zu qualities", fastq, (unsigned long long)id, cur_seq.size(), l.size());
-                    index_of[id] = (uint32_t)reads.size();
-                    reads.push_back(VqReadRef{(uint64_t)seq.size(), (uint32_t)cur_seq.size(), 0});
-                    seq += cur_seq;
-                    for (char c : l) {
-                        const int q = (int)(unsigned char)c - 33;
-                        if (q < 0 || q >= NQ) fail(HLMI_EINVAL, "%s: read %llu: quality character outside '!'..'~'", fastq, (unsigned long long)id);
-                        qual.push_back((char)q);
-                    }
-                    break;
-                }
+// singles.fastq: 4-line records, id = strtoul of the first word behind '@', bases upper-cased (FastqStorage.cpp:92-150)
+Singles read_singles(const char *path) {
+    const std::string data = read_file(path);
+    Singles r;
+    r.path = path;
+    size_t pos = 0, line = 0;
+    uint64_t id = 0;
+    std::string cur;
+    while (pos < data.size()) {
+        size_t e = data.find('\n', pos);
+        if (e == std::string::npos) e = data.size();
+        const std::string_view l(data.data() + pos, e - pos);
+        pos = e + 1;
+        switch (line++ % 4) {
+            case 0: {
+                if (l.empty() || l[0] != '@') fail(HLMI_EINVAL, "%s: read id does not start with @ (line %zu)", path, line);
+                size_t b = 1;
+                while (b < l.size() && isspace((unsigned char)l[b])) ++b;
+                size_t w = b;
+                while (w < l.size() && !isspace((unsigned char)l[w])) ++w;
+                id = strtoul(std::string(l.substr(b, w - b)).c_str(), nullptr, 0);
+                break;
             }
+            case 1:
+                cur.assign(l);
+                for (char &c : cur) c = (char)toupper((unsigned char)c);
+                break;
+            case 2: break;
+            case 3:
+                if (cur.empty()) fail(HLMI_EINVAL, "%s: single read %llu has an empty sequence", path, (unsigned long long)id);
+                r.index_of[id] = (uint32_t)r.seq.size();
+                r.seq.push_back(cur);
+                r.qual.emplace_back(l);
+                r.id.push_back(id);
+                break;
         }
     }
+    return r;
+}
+
+void vq_overlap_scores(const char *fastq, const hlmi_vq_overlap *ov, uint64_t n, double mismatch, uint32_t min_read_len,
+                       double *score, double *mismatch_rate, int64_t *pos3) {
+    vq_score_overlaps(read_singles(fastq), ov, n, mismatch, min_read_len, score, mismatch_rate, pos3);
+}
+
+void vq_score_overlaps(const Singles &in, const hlmi_vq_overlap *ov, uint64_t n, double mismatch, uint32_t min_read_len,
+                       double *score, double *mismatch_rate, int64_t *pos3) {
+    // every read, named by an overlap or not: bases and phred values (character - 33) one after the other
+    const char *fastq = in.path.c_str();
+    std::vector<VqReadRef> reads;
+    std::string seq, qual;
+    for (size_t v = 0; v < in.seq.size(); ++v) {
+        const std::string &s = in.seq[v], &l = in.qual[v];
+        if (l.size() != s.size()) fail(HLMI_EINVAL, "%s: read %llu: %zu bases, %zu qualities", fastq, (unsigned long long)in.id[v], s.size(), l.size());
+        reads.push_back(VqReadRef{(uint64_t)seq.size(), (uint32_t)s.size(), 0});
+        seq += s;
+        for (char c : l) {
+            const int q = (int)(unsigned char)c - 33;
+            if (q < 0 || q >= NQ) fail(HLMI_EINVAL, "%s: read %llu: quality character outside '!'..'~'", fastq, (unsigned long long)in.id[v]);
+            qual.push_back((char)q);
+        }
+    }
+    const auto &index_of = in.index_of;
     if (!n) return;
     // p per quality pair, in the reference's order of operations (EdgeCalculator.cpp:41-49, :62-66)
     std::vector<double> P(NQ), lm((size_t)NQ * NQ), lx((size_t)NQ * NQ);

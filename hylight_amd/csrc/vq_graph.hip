@@ -1,7 +1,8 @@
 // vq_graph.hip - SURVEY 8f rank 3: the device side of the oriented overlap graph of ViralQuasispecies --graph_only
 // (tools/HaploConduct/src, ViralQuasispecies.cpp:250-398).  The per-edge and per-vertex steps run here; the order-dependent
 // ones (sortEdges, the labelling BFS, the cycle DFS, the writers) are in vq_graph_host.cpp, the same split as graph_dev.hip /
-// graph_host.cpp.  Everything runs on the library's stream with its allocator.  PARITY UNPINNED (see vq_front.hip).
+// graph_host.cpp.  The transitive edges come from vq_front.hip's vq_trans_rounds.  Everything runs on the library's stream
+// with its allocator.  PARITY UNPINNED (see vq_front.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,8 +17,6 @@ namespace hlmi {
 using namespace vqk;
 
 namespace {
-inline unsigned waves_grid(size_t n_items) { return (unsigned)std::max<size_t>(1, std::min<size_t>(cdiv(n_items, (size_t)WAVES), 256 * 16)); }
-
 // ---------------------------------------------------------------------------------------------
 // edge selection (EdgeCalculator.cpp:428-532)
 // ---------------------------------------------------------------------------------------------
@@ -257,67 +256,37 @@ void VqLabelPass::run(const std::vector<uint8_t> &orient, std::vector<uint8_t> &
 }
 std::vector<VqEdge> VqLabelPass::state() const { return n_ ? d_edges_.download(n_) : std::vector<VqEdge>(); }
 
-static std::vector<uint32_t> kept_positions(const DBuf<uint8_t> &keep, size_t n) {
-    DBuf<uint32_t> idx(n ? n : 1);
-    const size_t k = n ? select_flagged_indices(keep.p, idx.p, n) : 0;
-    return k ? idx.download(k) : std::vector<uint32_t>();
-}
-
-void vq_inclusion_keep(uint32_t n_vertices, const std::vector<uint32_t> &off, const std::vector<uint32_t> &src,
-                       const std::vector<uint32_t> &dst, const std::vector<uint8_t> &incl, std::vector<uint32_t> &kept) {
+void vq_inclusion_removed(const std::vector<uint32_t> &off, const std::vector<uint32_t> &src, const std::vector<uint32_t> &dst,
+                          const std::vector<uint8_t> &incl, std::vector<uint8_t> &removed) {
     const size_t n = dst.size();
-    kept.clear();
+    removed.clear();
     if (!n) return;
     DBuf<uint32_t> d_off, d_src, d_dst;
     DBuf<uint8_t> d_incl, keep(n);
     d_off.upload(off); d_src.upload(src); d_dst.upload(dst); d_incl.upload(incl);
     hipLaunchKernelGGL(inclusion_keep_kernel, grid1(n), dim3(WG), 0, stream(), d_off.p, d_src.p, d_dst.p, n, d_incl.p, keep.p);
     HIP_CHECK(hipGetLastError());
-    kept = kept_positions(keep, n);
-    (void)n_vertices;
+    removed = keep.download(n);
+    for (uint8_t &f : removed) f = !f;
+}
+
+// vq_trans_flags over resident edges
+static uint64_t trans_flags(uint32_t n_vertices, const DBuf<uint32_t> &d_src, const DBuf<uint32_t> &d_dst, size_t E, int rounds,
+                            std::vector<uint8_t> &flags) {
+    flags.assign(E, 0);
+    DBuf<uint32_t> ids;
+    const size_t found = vq_trans_rounds(n_vertices, d_src.p, d_dst.p, E, rounds, ids);
+    if (found)
+        for (uint32_t k : ids.download(found)) flags[k] = 1;
+    return found;
 }
 
 uint64_t vq_trans_flags(uint32_t n_vertices, const std::vector<uint32_t> &src, const std::vector<uint32_t> &dst, int rounds,
                         std::vector<uint8_t> &flags) {
-    const size_t E = src.size();
-    flags.assign(E, 0);
-    if (!E) return 0;
     DBuf<uint32_t> d_src, d_dst;
     d_src.upload(src);
     d_dst.upload(dst);
-    DBuf<uint32_t> ids;                                 // the current round's graph (round 1: every edge)
-    size_t n_cur = E, found = 0;
-    for (int round = 1; round <= rounds && n_cur; ++round) {
-        DBuf<uint64_t> okey(n_cur), ikey(n_cur);
-        DBuf<uint32_t> oval(n_cur), ival(n_cur), ooff((size_t)n_vertices + 1), ioff((size_t)n_vertices + 1);
-        const uint32_t *cur = round == 1 ? nullptr : ids.p;
-        hipLaunchKernelGGL(edge_keys_kernel, grid1(n_cur), dim3(WG), 0, stream(), d_src.p, d_dst.p, cur, n_cur, okey.p, oval.p);
-        hipLaunchKernelGGL(edge_keys_kernel, grid1(n_cur), dim3(WG), 0, stream(), d_dst.p, d_src.p, cur, n_cur, ikey.p, ival.p);
-        sort_pairs_u64_u32(okey, oval, n_cur, 0, 64);
-        sort_pairs_u64_u32(ikey, ival, n_cur, 0, 64);
-        hipLaunchKernelGGL(offsets_kernel, grid1((size_t)n_vertices + 1), dim3(WG), 0, stream(), okey.p, n_cur, n_vertices, ooff.p);
-        hipLaunchKernelGGL(offsets_kernel, grid1((size_t)n_vertices + 1), dim3(WG), 0, stream(), ikey.p, n_cur, n_vertices, ioff.p);
-        DBuf<uint8_t> fl(E);
-        fl.zero();
-        DBuf<uint32_t> big(n_vertices ? n_vertices : 1), n_big(1);
-        n_big.zero();
-        hipLaunchKernelGGL(trans_kernel, dim3(waves_grid(n_vertices)), dim3(WG), 0, stream(), okey.p, oval.p, ooff.p, ikey.p, ioff.p,
-                           n_vertices, fl.p, big.p, n_big.p);
-        HIP_CHECK(hipGetLastError());
-        const uint32_t hb = download_one(n_big.p);
-        if (hb) hipLaunchKernelGGL(trans_big_kernel, dim3(256 * 8), dim3(WG), 0, stream(), okey.p, oval.p, ooff.p, ikey.p, ioff.p,
-                                   big.p, hb, fl.p);
-        HIP_CHECK(hipGetLastError());
-        DBuf<uint32_t> next(E);
-        found = select_flagged_indices(fl.p, next.p, E);
-        ids = std::move(next);
-        n_cur = found;
-    }
-    if (found) {
-        const std::vector<uint32_t> h = ids.download(found);
-        for (uint32_t k : h) flags[k] = 1;
-    }
-    return found;
+    return trans_flags(n_vertices, d_src, d_dst, src.size(), rounds, flags);
 }
 
 void vq_tips(uint32_t n_vertices, const std::vector<uint32_t> &off, const std::vector<uint32_t> &dst,
@@ -340,14 +309,17 @@ void vq_tips(uint32_t n_vertices, const std::vector<uint32_t> &off, const std::v
 }
 
 void vq_branch_components(uint32_t n_vertices, const std::vector<uint32_t> &src, const std::vector<uint32_t> &dst,
-                          const std::vector<uint8_t> &trans, std::vector<uint32_t> &comp) {
+                          std::vector<uint32_t> &comp) {
     const size_t n = src.size();
     comp.resize(n_vertices);
     for (uint32_t v = 0; v < n_vertices; ++v) comp[v] = v;
     if (!n || !n_vertices) return;
     DBuf<uint32_t> d_src, d_dst, outdeg(n_vertices), indeg(n_vertices), parent(n_vertices), d_comp(n_vertices);
     DBuf<uint8_t> d_tr;
-    d_src.upload(src); d_dst.upload(dst); d_tr.upload(trans);
+    d_src.upload(src); d_dst.upload(dst);
+    std::vector<uint8_t> trans;
+    trans_flags(n_vertices, d_src, d_dst, n, 1, trans);
+    d_tr.upload(trans);
     outdeg.zero();
     indeg.zero();
     hipLaunchKernelGGL(degree_kernel, grid1(n), dim3(WG), 0, stream(), d_src.p, d_dst.p, d_tr.p, n, outdeg.p, indeg.p);

@@ -1,7 +1,8 @@
 // vq_graph_host.cpp - SURVEY 8f rank 3: the oriented, reduced overlap graph of ViralQuasispecies --graph_only=true
-// (tools/HaploConduct/src, ViralQuasispecies.cpp:250-398) for HyLight's stage b.  Host side: reads, candidates and their
-// order, the order-dependent steps (sortEdges, sortAdjOut, the labelling BFS, the cycle DFS) and the writers.  The
-// per-edge / per-vertex steps are in vq_graph.hip.  The contract is the sequential reference (--threads 1).
+// (tools/HaploConduct/src, ViralQuasispecies.cpp:250-398) for HyLight's stage b.  Host side: the candidates and their
+// order, the order-dependent steps (sortEdges, sortAdjOut, the labelling BFS, the cycle DFS) and the writers.  The two
+// input files are parsed by vq_front.hip (read_singles, vq_parse_overlaps), each once per call; the per-edge / per-vertex
+// steps are in vq_graph.hip.  The contract is the sequential reference (--threads 1).
 // PARITY UNPINNED: the reference needs Boost and cannot be built here; tests/vq_graph_model.py restates it.
 //
 // The adjacency lists hold edge ids (the reference's std::list<Edge>); adj_in is rebuilt from them where it is read:
@@ -10,13 +11,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <set>
 #include <string>
-#include <string_view>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -28,67 +27,6 @@
 
 namespace hlmi {
 namespace {
-
-// ---- reads: singles.fastq, vertex = position in the file (FastqStorage.cpp:92-150, ViralQuasispecies.cpp:262-276) ------
-struct Singles {
-    std::vector<std::string> seq;                      // upper-cased
-    std::vector<std::string> qual;                     // the quality line as it stands
-    std::vector<uint64_t> id;                          // read id per vertex
-    std::unordered_map<uint64_t, uint32_t> index_of;   // read id (strtoul base 0 of the first word) -> vertex
-};
-
-Singles read_singles(const char *path, bool keep_text) {
-    const std::string data = read_file(path);
-    Singles r;
-    size_t pos = 0, line = 0;
-    uint64_t id = 0;
-    std::string cur;
-    while (pos < data.size()) {
-        size_t e = data.find('\n', pos);
-        if (e == std::string::npos) e = data.size();
-        const std::string_view l(data.data() + pos, e - pos);
-        pos = e + 1;
-        switch (line++ % 4) {
-            case 0: {
-                if (l.empty() || l[0] != '@') fail(HLMI_EINVAL, "%s: read id does not start with @ (line %zu)", path, line);
-                size_t b = 1;
-                while (b < l.size() && isspace((unsigned char)l[b])) ++b;
-                size_t w = b;
-                while (w < l.size() && !isspace((unsigned char)l[w])) ++w;
-                id = strtoul(std::string(l.substr(b, w - b)).c_str(), nullptr, 0);
-                break;
-            }
-            case 1:
-                cur.assign(l);
-                for (char &c : cur) c = (char)toupper((unsigned char)c);
-                break;
-            case 2: break;
-            case 3:
-                if (cur.empty()) fail(HLMI_EINVAL, "%s: single read %llu has an empty sequence", path, (unsigned long long)id);
-                r.index_of[id] = (uint32_t)r.seq.size();
-                r.seq.push_back(cur);
-                if (keep_text) {                          // only the merge reads these
-                    r.qual.emplace_back(l);
-                    r.id.push_back(id);
-                }
-                break;
-        }
-    }
-    return r;
-}
-
-std::string join(const char *dir, const char *name) {
-    std::string p(dir);
-    if (!p.empty() && p.back() != '/') p += '/';
-    return p + name;
-}
-
-void write_text(const std::string &path, const std::string &text) {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) fail(HLMI_EIO, "cannot write %s: %s", path.c_str(), strerror(errno));
-    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
-    if (fclose(f) != 0 || !ok) fail(HLMI_EIO, "cannot write %s", path.c_str());
-}
 
 // Overlap::get_overlap_line (Overlap.h:222-225)
 void overlap_line(std::string &s, const hlmi_vq_overlap &o) {
@@ -150,10 +88,15 @@ struct Graph {
         }
         off[V] = (uint32_t)eid.size();
     }
-    // keep the positions `kept` (ascending) of a flatten(): every list keeps its order
-    void keep(const std::vector<uint32_t> &kept, const std::vector<uint32_t> &src, const std::vector<uint32_t> &eid) {
+    // drop the positions p of a flatten() with gone[p] != 0: every list keeps its order.  -> how many went
+    size_t drop(const std::vector<uint8_t> &gone, const std::vector<uint32_t> &src, const std::vector<uint32_t> &eid) {
+        size_t n_gone = 0;
         for (auto &l : out) l.clear();
-        for (uint32_t p : kept) out[src[p]].push_back(eid[p]);
+        for (size_t p = 0; p < gone.size(); ++p) {
+            if (gone[p]) ++n_gone;
+            else out[src[p]].push_back(eid[p]);
+        }
+        return n_gone;
     }
     // adj_in as sortEdges rebuilds it (OverlapGraph.cpp:753-763): sources in vertex order, then list order
     std::vector<std::vector<uint32_t>> adj_in() const {
@@ -392,7 +335,7 @@ void write_gfa(const Graph &g, const Singles &reads, const std::string &path) {
             s += std::to_string(g.pool[e].len); s += "M\n";
         }
     }
-    write_text(path, s);
+    write_file(path, s.data(), s.size());
 }
 
 // writeGraphToFile: undirected edge lines for quick-cliques.  An included vertex and edges into one are left out; an edge
@@ -416,14 +359,52 @@ void write_graph_txt(const Graph &g, const std::vector<uint8_t> &incl, const std
             ++count;
         }
     }
-    write_text(path, std::to_string(g.V) + "\n" + std::to_string(2 * count) + "\n" + body);
+    const std::string s = std::to_string(g.V) + "\n" + std::to_string(2 * count) + "\n" + body;
+    write_file(path, s.data(), s.size());
 }
 
 void write_digraph(const Graph &g, const std::string &path) {
     std::string s;
     for (uint32_t i = 0; i < g.V; ++i)
         for (uint32_t e : g.out[i]) { s += std::to_string(i); s += '\t'; s += std::to_string(g.pool[e].v2); s += '\n'; }
-    write_text(path, s);
+    write_file(path, s.data(), s.size());
+}
+
+// ---- what findNextOverlaps reads beside the graph (for_next) -----------------------------------------------------------
+// FindNextOverlaps.cpp:661-691: a score-0 source edge per row of nonedge_overlaps.txt.  A paired-end row is refused.
+std::vector<VqSrcEdge> nonedge_src_edges(const std::vector<const hlmi_vq_overlap *> &rows, const Singles &reads) {
+    std::vector<VqSrcEdge> r;
+    for (const hlmi_vq_overlap *c : rows) {
+        if (c->type1 != 's' || c->type2 != 's')
+            fail(HLMI_ESTATE, "vq_iteration: a non-edge overlap row has a paired-end read; HyLight builds none (--num_pairs 0)");
+        const auto i1 = reads.index_of.find(c->id1), i2 = reads.index_of.find(c->id2);
+        if (i1 == reads.index_of.end() || i2 == reads.index_of.end())
+            fail(HLMI_EINVAL, "vq_iteration: a non-edge overlap row names a read that is not in %s", reads.path.c_str());
+        VqSrcEdge s{};
+        s.v1 = i1->second; s.v2 = i2->second;
+        s.pos1 = (int32_t)c->pos1; s.pos2 = (int32_t)c->pos2;
+        s.len1 = (int32_t)c->len1; s.len2 = (int32_t)c->len2;
+        s.perc = (int32_t)vq_perc(*c);
+        s.ori1 = c->ori1 == '+'; s.ori2 = c->ori2 == '+';
+        s.score0 = 1;
+        s.ord = c->ord;
+        r.push_back(s);
+    }
+    return r;
+}
+
+// inclusion_edges (GraphAlgos.cpp:26-42) per included vertex: its out-edges, then getEdgeInfo per in-neighbour
+void inclusion_src_edges(const Graph &g, const std::vector<uint8_t> &incl, VqGraphState &keep) {
+    const std::vector<std::vector<uint32_t>> in = g.adj_in();
+    keep.incl_off.push_back(0);
+    for (uint32_t v = 0; v < g.V; ++v) {
+        if (!incl[v]) continue;
+        for (uint32_t e : g.out[v]) keep.incl_edges.push_back(vq_src_edge(g.pool[e]));
+        for (uint32_t u : in[v])
+            for (uint32_t e : g.out[u])
+                if (g.pool[e].v2 == v) { keep.incl_edges.push_back(vq_src_edge(g.pool[e])); break; }
+        keep.incl_off.push_back((uint32_t)keep.incl_edges.size());
+    }
 }
 
 }  // namespace
@@ -453,7 +434,7 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
         fail(HLMI_ESTATE, "vq_graph: remove_branches needs remove_trans 1 (findBranchfreeGraph asserts it, GraphAlgos.cpp:716)");
     *st = hlmi_vq_graph_stats{};
     if (for_next && !keep) fail(HLMI_EINVAL, "vq_graph: for_next needs a state to keep what findNextOverlaps reads");
-    Singles reads = read_singles(fastq, keep != nullptr);
+    Singles reads = read_singles(fastq);
     if (keep) {
         *keep = VqGraphState{};
         vq_merge_check_reads(reads.seq, reads.qual);      // refused inputs are refused before a file is written
@@ -466,12 +447,10 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
     st->vertices = g.V;
 
     // candidates (EdgeCalculator.cpp:561-666): HyLight's path has no paired-end reads (--num_pairs 0, relax_PE_edges off)
-    uint64_t n_cand = 0, n_nonedge = 0, n_skipped = 0;
-    vq_parse_overlaps(overlaps, o.min_overlap_len, o.min_overlap_perc, 0, o.max_overlaps, nullptr, 0, &n_cand, &n_nonedge, &n_skipped);
-    std::vector<hlmi_vq_overlap> cand(n_cand);
-    std::vector<hlmi_vq_overlap> nonedge;
-    vq_parse_overlaps(overlaps, o.min_overlap_len, o.min_overlap_perc, 0, o.max_overlaps, cand.data(), n_cand, &n_cand, &n_nonedge,
-                      &n_skipped, &nonedge);
+    uint64_t n_nonedge = 0, n_skipped = 0;
+    std::vector<hlmi_vq_overlap> cand, nonedge;
+    vq_parse_overlaps(overlaps, o.min_overlap_len, o.min_overlap_perc, 0, o.max_overlaps, cand, &nonedge, &n_nonedge, &n_skipped);
+    const uint64_t n_cand = cand.size();
     for (uint64_t k = 0; k < n_cand; ++k)
         if (cand[k].type1 != 's' || cand[k].type2 != 's')
             fail(HLMI_ESTATE, "vq_graph: overlap candidate %llu has a paired-end read; HyLight builds no paired-end edges "
@@ -479,7 +458,7 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
     if (n_cand >= (1ull << 32)) fail(HLMI_EINVAL, "vq_graph: more than 2^32 candidates");
     std::vector<double> score(n_cand), mr(n_cand);
     std::vector<int64_t> pos3(n_cand);
-    if (n_cand) vq_overlap_scores(fastq, cand.data(), n_cand, o.mismatch, o.min_read_len, score.data(), mr.data(), pos3.data());
+    if (n_cand) vq_score_overlaps(reads, cand.data(), n_cand, o.mismatch, o.min_read_len, score.data(), mr.data(), pos3.data());
 
     // process_overlaps (:389-419): edge when score > edge_threshold, or when the mismatch rate is known and <= merge_contigs;
     // otherwise kept as a non-edge when score > ov_threshold
@@ -496,7 +475,7 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
             e.pos3 = (int32_t)pos3[k]; e.pos4 = 0;
             e.ori1 = c.ori1 == '+'; e.ori2 = c.ori2 == '+';
             e.len = (int32_t)c.len1;
-            e.perc = (int32_t)(c.perc2 > 0 ? (unsigned)(0.5 * (double)(c.perc1 + c.perc2)) : c.perc1);
+            e.perc = (int32_t)vq_perc(c);
             e.cand = (uint32_t)k;
             e.pad[0] = (uint8_t)c.ord;
             e.score = score[k]; e.mr = mr[k];
@@ -516,26 +495,11 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
     // nonedge_overlaps.txt (:533-541, :654-661): each chunk of 1e6 candidates appends its scored non-edges, in candidate
     // order, and the parser's non-edges follow at the end - so all scored non-edges in file order, then the parser's
     for (const auto &c : nonedge) overlap_line(ne_text, c);
-    if (for_next) {                                       // FindNextOverlaps.cpp:661-691: a score-0 edge per row
+    if (for_next) {
         for (const auto &c : nonedge) ne_rows.push_back(&c);
-        for (const hlmi_vq_overlap *c : ne_rows) {
-            if (c->type1 != 's' || c->type2 != 's')
-                fail(HLMI_ESTATE, "vq_iteration: a non-edge overlap row has a paired-end read; HyLight builds none (--num_pairs 0)");
-            const auto i1 = reads.index_of.find(c->id1), i2 = reads.index_of.find(c->id2);
-            if (i1 == reads.index_of.end() || i2 == reads.index_of.end())
-                fail(HLMI_EINVAL, "vq_iteration: a non-edge overlap row names a read that is not in %s", fastq);
-            VqSrcEdge s{};
-            s.v1 = i1->second; s.v2 = i2->second;
-            s.pos1 = (int32_t)c->pos1; s.pos2 = (int32_t)c->pos2;
-            s.len1 = (int32_t)c->len1; s.len2 = (int32_t)c->len2;
-            s.perc = (int32_t)(c->perc2 > 0 ? (unsigned)(0.5 * (double)(c->perc1 + c->perc2)) : c->perc1);   // Overlap::get_perc
-            s.ori1 = c->ori1 == '+'; s.ori2 = c->ori2 == '+';
-            s.score0 = 1;
-            s.ord = c->ord;
-            keep->nonedge.push_back(s);
-        }
+        keep->nonedge = nonedge_src_edges(ne_rows, reads);
     }
-    write_text(join(out_dir, "nonedge_overlaps.txt"), ne_text);
+    write_file(join_path(out_dir, "nonedge_overlaps.txt"), ne_text.data(), ne_text.size());
     st->candidates = edges.size();
 
     std::vector<uint32_t> winners;
@@ -544,7 +508,7 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
     st->edges_built = winners.size();
     st->duplicates = st->candidates - st->edges_built;
     if (winners.empty()) {                                // ViralQuasispecies.cpp:282-291: nothing to be done
-        remove(join(out_dir, "graph.txt").c_str());
+        remove(join_path(out_dir, "graph.txt").c_str());
         return;
     }
     // adjacency order: a replacement removes the old edge and appends the new one (:522-530), so each list holds its
@@ -560,23 +524,14 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
     st->conflicts = lab.conflicts;
     st->moved = lab.moved;
 
-    std::vector<uint32_t> off, src, dst, eid, kept;
+    // the reductions: the lists flattened, the positions that go flagged on the device, the lists without them
+    std::vector<uint32_t> off, src, dst, eid;
+    std::vector<uint8_t> gone;
     if (o.ignore_inclusions) {                            // removeInclusions
-        if (for_next) {                                   // inclusion_edges (GraphAlgos.cpp:26-42): out-edges, then getEdgeInfo per in-neighbour
-            const std::vector<std::vector<uint32_t>> in = g.adj_in();
-            keep->incl_off.push_back(0);
-            for (uint32_t v = 0; v < g.V; ++v) {
-                if (!incl[v]) continue;
-                for (uint32_t e : g.out[v]) keep->incl_edges.push_back(vq_src_edge(g.pool[e]));
-                for (uint32_t u : in[v])
-                    for (uint32_t e : g.out[u])
-                        if (g.pool[e].v2 == v) { keep->incl_edges.push_back(vq_src_edge(g.pool[e])); break; }
-                keep->incl_off.push_back((uint32_t)keep->incl_edges.size());
-            }
-        }
+        if (for_next) inclusion_src_edges(g, incl, *keep);
         g.flatten(off, src, dst, eid);
-        vq_inclusion_keep(g.V, off, src, dst, incl, kept);
-        g.keep(kept, src, eid);
+        vq_inclusion_removed(off, src, dst, incl, gone);
+        g.drop(gone, src, eid);
     } else {
         std::fill(incl.begin(), incl.end(), 0);
     }
@@ -584,16 +539,13 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
     if (o.remove_trans) {                                 // removeTransitiveEdges (GraphAlgos.cpp:938-1077)
         sort_adj_out(g);
         g.flatten(off, src, dst, eid);
-        std::vector<uint8_t> tr;
-        st->transitive = vq_trans_flags(g.V, src, dst, (int)o.remove_trans, tr);
+        st->transitive = vq_trans_flags(g.V, src, dst, (int)o.remove_trans, gone);
         // the reference rebuilds adj_out when more than half of the edges go and erases them one by one otherwise; both
         // leave the sortAdjOut order minus the transitive edges (each listed target is matched once, and two edges to one
         // target are both listed), so one compaction stands for both
-        kept.clear();
-        for (uint32_t p = 0; p < tr.size(); ++p) if (!tr[p]) kept.push_back(p);
-        g.keep(kept, src, eid);
+        g.drop(gone, src, eid);
     }
-    write_gfa(g, reads, join(out_dir, "graph.gfa"));
+    write_gfa(g, reads, join_path(out_dir, "graph.gfa"));
 
     std::vector<uint8_t> tip(g.V, 0);
     if (o.remove_tips) {                                  // removeTips
@@ -607,37 +559,30 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
             fwd[p] = (uint32_t)std::max((int)g.rlen[e.v2] - e.len, 0);   // Edge::ext_len(true), single-end
             bwd[p] = (uint32_t)(e.pos1 + e.pos2);                         // Edge::ext_len(false), ord '-'
         }
-        std::vector<uint8_t> removed;
-        vq_tips(g.V, off, dst, in_off, in_src, fwd, bwd, o.max_tip_len, removed, tip);
-        kept.clear();
-        for (uint32_t p = 0; p < removed.size(); ++p) if (!removed[p]) kept.push_back(p);
-        st->tip_edges = removed.size() - kept.size();
+        vq_tips(g.V, off, dst, in_off, in_src, fwd, bwd, o.max_tip_len, gone, tip);
         if (for_next) {                                   // :630-636: a std::set of (source, target), one removeEdge each
-            std::vector<uint32_t> gone;
-            for (uint32_t p = 0; p < removed.size(); ++p) if (removed[p]) gone.push_back(p);
-            std::stable_sort(gone.begin(), gone.end(), [&](uint32_t a, uint32_t b) {
+            std::vector<uint32_t> order;
+            for (uint32_t p = 0; p < gone.size(); ++p) if (gone[p]) order.push_back(p);
+            std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
                 return src[a] != src[b] ? src[a] < src[b] : dst[a] < dst[b];
             });
-            for (uint32_t p : gone) keep->branching.push_back(vq_src_edge(g.pool[eid[p]]));
+            for (uint32_t p : order) keep->branching.push_back(vq_src_edge(g.pool[eid[p]]));
         }
-        g.keep(kept, src, eid);
+        st->tip_edges = g.drop(gone, src, eid);
     }
     for (uint8_t t : tip) st->tip_reads += t;
 
     if (o.remove_branches) {                              // removeBranches
         sort_adj_out(g);
         g.flatten(off, src, dst, eid);
-        std::vector<uint8_t> tr;
-        vq_trans_flags(g.V, src, dst, 1, tr);
         std::vector<uint32_t> comp;
-        vq_branch_components(g.V, src, dst, tr, comp);
-        kept.clear();                                     // the cross-component edges of the current graph go (:917-931)
-        for (uint32_t p = 0; p < src.size(); ++p) if (comp[src[p]] == comp[dst[p]]) kept.push_back(p);
-        st->branch_edges = src.size() - kept.size();
+        vq_branch_components(g.V, src, dst, comp);
+        gone.assign(src.size(), 0);                       // the cross-component edges of the current graph go (:917-931)
+        for (size_t p = 0; p < src.size(); ++p) gone[p] = comp[src[p]] != comp[dst[p]];
         if (for_next)                                     // :918-931: vertices ascending, list order
-            for (uint32_t p = 0; p < src.size(); ++p)
-                if (comp[src[p]] != comp[dst[p]]) keep->branching.push_back(vq_src_edge(g.pool[eid[p]]));
-        g.keep(kept, src, eid);
+            for (size_t p = 0; p < src.size(); ++p)
+                if (gone[p]) keep->branching.push_back(vq_src_edge(g.pool[eid[p]]));
+        st->branch_edges = g.drop(gone, src, eid);
     }
 
     sort_edges(g);                                        // ViralQuasispecies.cpp:352
@@ -651,7 +596,7 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
         }
         st->backedges = best.size();
         // cycles.txt: findCycles removes it, reportCycle appends the winning set in std::set order
-        const std::string cyc = join(out_dir, "cycles.txt");
+        const std::string cyc = join_path(out_dir, "cycles.txt");
         remove(cyc.c_str());
         if (!best.empty()) {
             std::string s;
@@ -664,16 +609,16 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
                 }
                 s += std::to_string(pr.first); s += '\t'; s += std::to_string(pr.second); s += '\n';
             }
-            write_text(cyc, s);
+            write_file(cyc, s.data(), s.size());
         }
     }
-    write_graph_txt(g, incl, join(out_dir, "graph.txt"));
-    write_gfa(g, reads, join(out_dir, "graph_trimmed.gfa"));
-    write_digraph(g, join(out_dir, "digraph.txt"));
+    write_graph_txt(g, incl, join_path(out_dir, "graph.txt"));
+    write_gfa(g, reads, join_path(out_dir, "graph_trimmed.gfa"));
+    write_digraph(g, join_path(out_dir, "digraph.txt"));
     {
         std::string s;
         for (uint32_t v = 0; v < g.V; ++v) if (tip[v]) { s += std::to_string(v); s += '\n'; }
-        write_text(join(out_dir, "tips.txt"), s);
+        write_file(join_path(out_dir, "tips.txt"), s.data(), s.size());
     }
     st->edges_final = g.edge_count();
     if (keep) {                                           // what SRBuilder reads (vq_merge_host.cpp)

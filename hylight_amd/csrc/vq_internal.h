@@ -1,21 +1,49 @@
-// vq_internal.h - what vq_front.hip (the front of the SAVAGE overlap-graph assembler) shares with
-// vq_graph.hip / vq_graph_host.cpp (the oriented overlap graph built from it): the parser's non-edge rows, and the
-// transitive-edge kernels (GraphAlgos.cpp:746-795), which both files launch on the library's stream.
+// vq_internal.h - what the stage-b sources (the SAVAGE / ViralQuasispecies overlap-graph assembler) share,
+// in the order of the pipeline:
+//   front  vq_front.hip                          the two input files (singles.fastq, the 13-column overlaps), the overlap
+//                                                score, and the rounds of findTransEdges (GraphAlgos.cpp:746-795)
+//   graph  vq_graph.hip / vq_graph_host.cpp      the oriented, reduced overlap graph (ViralQuasispecies --graph_only)
+//   merge  vq_merge.hip / vq_merge_host.cpp      super-reads along its edges (SRBuilder::mergeAlongEdges)
+//   next   vq_next.hip                           the overlaps of the next iteration (SRBuilder::findNextOverlaps)
+// Everything on the device runs on the library's stream.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "common.h"
 
 namespace hlmi {
 
-// vq_parse_overlaps (graph.h) that also keeps the rows the reference writes back to nonedge_overlaps.txt (too short for an
-// edge: EdgeCalculator.cpp:628-631), in file order
+// ---- front: vq_front.hip -------------------------------------------------------------------------------------------------
+// singles.fastq: 4-line records, vertex = position in the file (FastqStorage.cpp:92-150, ViralQuasispecies.cpp:262-276)
+struct Singles {
+    std::string path;                                  // for messages
+    std::vector<std::string> seq;                      // upper-cased
+    std::vector<std::string> qual;                     // the quality line as it stands
+    std::vector<uint64_t> id;                          // read id per vertex
+    std::unordered_map<uint64_t, uint32_t> index_of;   // read id (strtoul base 0 of the first word) -> vertex
+};
+// refuses (HLMI_EINVAL) an id line without '@' and an empty sequence; the qualities are checked by whoever reads them
+// (vq_score_overlaps, vq_merge_check_reads)
+Singles read_singles(const char *path);
+
+// The rows of a 13-column overlaps file (EdgeCalculator.cpp:561-666, Overlap.h:37-72): `edges` = the edge candidates in
+// file order; `nonedges` (may be NULL) = the rows the reference writes back to nonedge_overlaps.txt (too short for an edge,
+// :628-631), in file order.  Only the first max_overlaps lines are looked at.
 void vq_parse_overlaps(const char *path, uint32_t min_len, uint32_t min_perc, int relax_pe, uint64_t max_overlaps,
-                       hlmi_vq_overlap *out, uint64_t cap, uint64_t *n_out, uint64_t *n_nonedge, uint64_t *n_skipped,
-                       std::vector<hlmi_vq_overlap> *nonedges);
+                       std::vector<hlmi_vq_overlap> &edges, std::vector<hlmi_vq_overlap> *nonedges, uint64_t *n_nonedge,
+                       uint64_t *n_skipped);
+// Overlap::get_perc (Overlap.h:196-203)
+inline uint32_t vq_perc(const hlmi_vq_overlap &o) { return o.perc2 > 0 ? (uint32_t)(0.5 * (double)(o.perc1 + o.perc2)) : o.perc1; }
+
+// vq_overlap_scores (graph.h) over reads that are already parsed.  Refuses (HLMI_EINVAL) a quality line of another length
+// than its sequence and a quality character outside '!' .. '~' in ANY read, then an overlap that names a read not there.
+void vq_score_overlaps(const Singles &reads, const hlmi_vq_overlap *ov, uint64_t n, double mismatch, uint32_t min_read_len,
+                       double *score, double *mismatch_rate, int64_t *pos3);
 
 namespace vqk {
 constexpr int WG = 256;
@@ -23,6 +51,8 @@ constexpr int WAVES = WG / 64;
 constexpr uint32_t SET_CAP = 2048;                 // LDS hash slots per wave: vertices with up to SET_CAP / 2 out-edges
 constexpr uint32_t EMPTY = 0xffffffffu;
 inline dim3 grid1(size_t n) { return dim3((unsigned)cdiv(n ? n : 1, (size_t)WG)); }
+// blocks of a one-wave-per-item kernel that strides over its items
+inline unsigned waves_grid(size_t n_items) { return (unsigned)std::max<size_t>(1, std::min<size_t>(cdiv(n_items, (size_t)WAVES), 256 * 16)); }
 
 // key[i] = a[k] << 32 | b[k], val[i] = k for k = ids[i] (ids NULL: k = i)
 __global__ void edge_keys_kernel(const uint32_t *a, const uint32_t *b, const uint32_t *ids, size_t n, uint64_t *key, uint32_t *val);
@@ -36,11 +66,11 @@ __global__ void trans_big_kernel(const uint64_t *okey, const uint32_t *oval, con
                                  const uint32_t *ioff, const uint32_t *big_list, uint32_t n_big, uint8_t *flag);
 }  // namespace vqk
 
-}  // namespace hlmi
+// rounds of findTransEdges over the edges (d_src[k] -> d_dst[k]), k < E, both resident; ids receives the edge numbers
+// of the last round's set (ascending); returns their count
+size_t vq_trans_rounds(uint32_t n_vertices, const uint32_t *d_src, const uint32_t *d_dst, size_t E, int rounds, DBuf<uint32_t> &ids);
 
-namespace hlmi {
-
-// ---- vq_graph.hip / vq_graph_host.cpp: the oriented overlap graph (ViralQuasispecies --graph_only) -----------------------
+// ---- graph: vq_graph.hip / vq_graph_host.cpp (ViralQuasispecies --graph_only) ----------------------------------------------
 // One edge of the graph: the fields of Edge.h a single-end overlap uses.  Reads and vertices are one to one, so read1 /
 // read2 are implied by v1 / v2 (Edge::swap_reads and switch_edge_orientation swap both together).
 struct VqEdge {
@@ -93,12 +123,13 @@ private:
     size_t n_;
 };
 
-// removeInclusions (GraphAlgos.cpp:20-48): positions of the adjacency lists (src[p] -> dst[p], lists in off[]) that stay.
-// Every out- and in-edge pair of an included vertex goes, one edge per pair: removeEdge takes the first u -> v of u's list.
-void vq_inclusion_keep(uint32_t n_vertices, const std::vector<uint32_t> &off, const std::vector<uint32_t> &src,
-                       const std::vector<uint32_t> &dst, const std::vector<uint8_t> &incl, std::vector<uint32_t> &kept);
-// findTransEdges repeated `rounds` times (GraphAlgos.cpp:746-776, 956-966): flags[p] = 1 for the edges of the last round's
-// set (transitive, double transitive, ...); returns their number.  The kernels are vq_front.hip's.
+// The reductions below all speak of the positions of Graph::flatten (vq_graph_host.cpp): src[p] -> dst[p], lists in off[].
+// removeInclusions (GraphAlgos.cpp:20-48): removed[p] = 1 for the positions that go.  Every out- and in-edge pair of an
+// included vertex goes, one edge per pair: removeEdge takes the first u -> v of u's list.
+void vq_inclusion_removed(const std::vector<uint32_t> &off, const std::vector<uint32_t> &src, const std::vector<uint32_t> &dst,
+                          const std::vector<uint8_t> &incl, std::vector<uint8_t> &removed);
+// findTransEdges repeated `rounds` times (GraphAlgos.cpp:746-776, 956-966, vq_trans_rounds): flags[p] = 1 for the edges of
+// the last round's set (transitive, double transitive, ...); returns their number
 uint64_t vq_trans_flags(uint32_t n_vertices, const std::vector<uint32_t> &src, const std::vector<uint32_t> &dst, int rounds,
                         std::vector<uint8_t> &flags);
 // removeTips (GraphAlgos.cpp:543-637): one wave per vertex over its out-list and its in-list.  ext_fwd[p] / ext_bwd[p] =
@@ -108,16 +139,14 @@ void vq_tips(uint32_t n_vertices, const std::vector<uint32_t> &off, const std::v
              const std::vector<uint32_t> &in_off, const std::vector<uint32_t> &in_src, const std::vector<uint32_t> &ext_fwd,
              const std::vector<uint32_t> &ext_bwd, uint32_t max_tip_len, std::vector<uint8_t> &removed, std::vector<uint8_t> &tip);
 // removeBranches (GraphAlgos.cpp:835-936): comp[v] = a component label of the branch-free graph; only equality is meant.
-// join[p] = 1 for the non-transitive edges; an edge joins its endpoints only when its source keeps its out-list and its
-// target its in-list (the one-sided clearing of :855-901).
+// A non-transitive edge joins its endpoints only when its source keeps its out-list and its target its in-list (the
+// one-sided clearing of :855-901).
+// The non-transitive edges are those vq_trans_flags(.., 1, ..) leaves unflagged: one upload of src / dst serves both passes.
 void vq_branch_components(uint32_t n_vertices, const std::vector<uint32_t> &src, const std::vector<uint32_t> &dst,
-                          const std::vector<uint8_t> &trans, std::vector<uint32_t> &comp);
+                          std::vector<uint32_t> &comp);
 
 // vq_graph_host.cpp: hlmi_vq_graph_opts_stageb / hlmi_vq_graph (include/hylight_mi.h)
 void vq_graph_opts_stageb(hlmi_vq_graph_opts *o);
-// What SRBuilder reads of the finished graph (keep != NULL): the reads, the out-lists after the sortEdges of
-// ViralQuasispecies.cpp:434, the vertex orientations of the winning labelling, the inclusions and the tip reads.  built is
-// false when the run stopped for want of an edge (ViralQuasispecies.cpp:282-291).
 // One source edge of findNextOverlaps: what updateOverlap reads of an Edge (FindNextOverlaps.cpp:25-72)
 struct VqSrcEdge {
     uint32_t v1, v2;
@@ -138,6 +167,9 @@ inline VqSrcEdge vq_src_edge(const VqEdge &e) {
     s.ord = (char)e.pad[0];
     return s;
 }
+// What SRBuilder reads of the finished graph (keep != NULL): the reads, the out-lists after the sortEdges of
+// ViralQuasispecies.cpp:434, the vertex orientations of the winning labelling, the inclusions and the tip reads.  built is
+// false when the run stopped for want of an edge (ViralQuasispecies.cpp:282-291).
 struct VqGraphState {
     bool built = false;
     std::vector<std::string> seq, qual;
@@ -154,11 +186,7 @@ struct VqGraphState {
 void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st,
                   VqGraphState *keep = nullptr, bool for_next = false);
 
-}  // namespace hlmi
-
-namespace hlmi {
-
-// ---- vq_merge.hip / vq_merge_host.cpp: super-reads along the edges of the graph (SRBuilder::mergeAlongEdges) --------------
+// ---- merge: vq_merge.hip / vq_merge_host.cpp (SRBuilder::mergeAlongEdges) -------------------------------------------------
 namespace vqm {
 constexpr int WG = 256;
 constexpr int WAVE = 64;
@@ -209,11 +237,7 @@ void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_
 void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2, const char *qual2,
                        uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual, uint32_t *out_len);
 
-}  // namespace hlmi
-
-namespace hlmi {
-
-// ---- vq_next.hip: the overlaps of the next iteration (SRBuilder::findNextOverlaps, FNO 1) --------------------------------
+// ---- next: vq_next.hip (SRBuilder::findNextOverlaps, FNO 1) ---------------------------------------------------------------
 namespace vqn {
 constexpr int WG = 256;
 constexpr uint32_t NONE = 0xffffffffu;

@@ -7,8 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cerrno>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -112,19 +110,6 @@ const std::vector<uint16_t> &consensus_tables() {
     return tab;
 }
 
-std::string join(const char *dir, const char *name) {
-    std::string p(dir);
-    if (!p.empty() && p.back() != '/') p += '/';
-    return p + name;
-}
-
-void write_file(const std::string &path, const char *data, size_t n, const char *mode) {
-    FILE *f = fopen(path.c_str(), mode);
-    if (!f) fail(HLMI_EIO, "cannot write %s: %s", path.c_str(), strerror(errno));
-    const bool ok = fwrite(data, 1, n, f) == n;
-    if (fclose(f) != 0 || !ok) fail(HLMI_EIO, "cannot write %s", path.c_str());
-}
-
 void check_read(const char *seq, size_t len, const char *qual, size_t qlen, const char *what, size_t k) {
     for (size_t i = 0; i < len; ++i) {
         const char c = seq[i];
@@ -185,10 +170,6 @@ void subreads_line(std::string &s, uint64_t id, const Originals &o) {
         s += std::to_string(kv.second.index); s += ':'; s += std::to_string(kv.second.len);
     }
     s += '\n';
-}
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 }  // namespace
@@ -388,16 +369,16 @@ static void merge_and_next(const char *fastq, const char *overlaps, const char *
     const std::string text = dev.write(recs, start);
     const uint64_t cut = start[n_singles];
     mst->bytes_out = cut;
-    write_file(join(out_dir, "singles.fastq"), text.data(), cut, "wb");                  // (the reference removes it first, :1245)
-    write_file(join(out_dir, "subreads.txt"), subreads.data(), subreads.size(), "wb");
+    write_file(join_path(out_dir, "singles.fastq"), text.data(), cut);                  // (the reference removes it first, :1245)
+    write_file(join_path(out_dir, "subreads.txt"), subreads.data(), subreads.size());
     if (!tips.empty())                                                                   // writeTipsToFile APPENDS (:1391)
-        write_file(join(out_dir, "removed_tip_sequences.fastq"), text.data() + cut, text.size() - cut, "ab");
+        write_file(join_path(out_dir, "removed_tip_sequences.fastq"), text.data() + cut, text.size() - cut, "ab");
     std::string map;
     for (uint32_t v = 0; v < V; ++v) {
         map += std::to_string(v); map += '\t'; map += std::to_string(new_id[v]); map += '\t';
         map += std::to_string(offset[v]); map += '\t'; map += g.orient[v] ? '+' : '-'; map += '\n';
     }
-    write_file(join(out_dir, "superread_map.txt"), map.data(), map.size(), "wb");
+    write_file(join_path(out_dir, "superread_map.txt"), map.data(), map.size());
     mst->ms_merge = now_ms() - t0;
     if (no) {                                                    // ViralQuasispecies.cpp:449-479
         const double t1 = now_ms();
@@ -408,10 +389,10 @@ static void merge_and_next(const char *fastq, const char *overlaps, const char *
             if (new_id[v] >= 0) t.len[v] = recs[(size_t)new_id[v]].len;
         }
         const std::string image = vq_next_run(g, t, go.edge_threshold, *no, nst);
-        write_file(join(out_dir, "overlaps.txt"), image.data(), image.size(), "wb");
+        write_file(join_path(out_dir, "overlaps.txt"), image.data(), image.size());
         const std::string line = std::to_string(gst->vertices) + "\t" + std::to_string(gst->edges_final) + "\t" +
                                  std::to_string(nst->lines) + "\n";
-        write_file(join(out_dir, "stats.txt"), line.data(), line.size(), "ab");
+        write_file(join_path(out_dir, "stats.txt"), line.data(), line.size(), "ab");
         nst->ms_next = now_ms() - t1;
     }
     ktimer_flush();
