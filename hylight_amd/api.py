@@ -88,6 +88,19 @@ class ClusterStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in CLUSTER_STATS] + [(k, C.c_double) for k in CLUSTER_MS]
 
 
+class PolishOpts(C.Structure):
+    _fields_ = [("min_len", C.c_int), ("min_iden", C.c_double), ("min_cov", C.c_int), ("include_unpolished", C.c_int)]
+
+
+POLISH_STATS = ("rows", "rows_selected", "contigs", "contigs_polished", "substituted", "deleted", "inserted_bases", "slots_opened",
+                "ins_long", "ins_edge")
+POLISH_MS = ("ms_device", "ms_total")
+
+
+class PolishStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in POLISH_STATS] + [(k, C.c_double) for k in POLISH_MS]
+
+
 ABI_VERSION = 7          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
@@ -134,6 +147,8 @@ SYMBOLS = {
                                          C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
     "hlmi_cluster_opts_default": (None, [C.POINTER(ClusterOpts)]),
     "hlmi_cluster_short": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(ClusterOpts), C.c_char_p, C.POINTER(ClusterStats)]),
+    "hlmi_polish_opts_default": (None, [C.POINTER(PolishOpts)]),
+    "hlmi_polish": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PolishOpts), C.c_char_p, C.POINTER(PolishStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -423,6 +438,22 @@ def cluster_short(paf, fastq, out_dir, size=15000, threads=20, **opts):
     st = ClusterStats()
     _check(load().hlmi_cluster_short(_b(paf), _b(fastq), C.byref(o), _b(out_dir), C.byref(st)))
     return {k: getattr(st, k) for k in CLUSTER_STATS + CLUSTER_MS}
+
+
+def polish(contigs, reads, paf, out_fa, **opts):
+    """hlmi_polish: the pile-up consensus of `contigs` (FASTA / FASTQ) under the rows of `paf` (cg:Z: CIGARs in = X I D, as
+    api.ava writes them) of `reads`, written to out_fa - the native stand-in for `racon --no-trimming -u` (a function of
+    this project's own: include/hylight_mi.h states it, tests/polish_model.py is its contract).  Options: the fields of
+    hlmi_polish_opts (min_len 0, min_iden 0.0, min_cov 3, include_unpolished 1).  -> dict of the stats (hlmi_polish_stats)."""
+    o = PolishOpts()
+    load().hlmi_polish_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(PolishOpts._fields_):
+            raise TypeError(f"polish: unknown option {k!r}")
+        setattr(o, k, int(v) if isinstance(v, bool) else v)
+    st = PolishStats()
+    _check(load().hlmi_polish(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(out_fa), C.byref(st)))
+    return {k: getattr(st, k) for k in POLISH_STATS + POLISH_MS}
 
 
 DEVICE = "cuda"          # where the buffers that cross the C ABI live (stage.py allocates them with torch)

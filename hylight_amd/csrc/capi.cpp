@@ -14,6 +14,8 @@
 namespace hlmi {
 void init_device(int device, int threads);
 void cluster_run(const char *paf, const char *fastq, const hlmi_cluster_opts &o, const char *out_dir, hlmi_cluster_stats *st);
+void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
+                hlmi_polish_stats *st);
 void shutdown_device();
 const std::string &last_error();
 }  // namespace hlmi
@@ -380,6 +382,19 @@ int hlmi_cluster_short(const char *paf, const char *fastq, const hlmi_cluster_op
         if (!paf || !fastq || !o || !out_dir || !st) fail(HLMI_EINVAL, "hlmi_cluster_short: NULL argument");
         require_device();
         cluster_run(paf, fastq, *o, out_dir, st);
+    });
+}
+
+void hlmi_polish_opts_default(hlmi_polish_opts *o) {
+    if (o) *o = hlmi_polish_opts{0, 0.0, 3, 1};
+}
+
+int hlmi_polish(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts *o, const char *out_fa,
+                hlmi_polish_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish: NULL argument");
+        require_device();
+        polish_run(contigs, reads, paf, *o, out_fa, st);
     });
 }
 

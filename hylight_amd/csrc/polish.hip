@@ -1,0 +1,262 @@
+// polish.hip - the device part of hlmi_polish (include/hylight_mi.h): column votes of the selected rows' CIGARs, the
+// decisions per position and per slot, and the new contigs' bases.
+//   count pass   a workgroup owns one tile of POLISH_TILE positions of one contig: eight 32-bit counters per position in LDS
+//                (A C G T del, non-voting columns, row starts, inserting rows); its waves walk the CIGARs of the rows that
+//                overlap the tile, 64 ops at a time with DPP prefix sums for the target and query columns; the tile then
+//                decides its positions and slots itself and writes one decision byte and one slot flag per position - no
+//                counter ever reaches global memory, and no global atomic is needed
+//   slot passes  opened slots are few: a wave per row walks its CIGAR once more and votes with global atomics into the 16
+//                length counters of each opened slot, then, the lengths decided, into the 16 x 4 base counters
+//   write        a thread per position: output length, a device scan for the offsets, one kernel for the bytes
+// Every counter is 32 bits wide: coverage needs no overflow path.  Every loop is bounded by a count known at its head.
+#include <hip/hip_runtime.h>
+
+#include "common.h"
+#include "dev_prims.h"
+#include "polish_internal.h"
+#include "wave_ops.h"
+
+namespace hlmi {
+namespace pol {
+namespace {
+
+constexpr int POLISH_WG = 256, POLISH_WAVES = POLISH_WG / 64;
+constexpr int C_OTHER = 5, C_START = 6, C_INS = 7, POLISH_CNT = 8;     // counters behind the five symbols
+constexpr uint32_t SHORT_RUN = 16;         // a lane votes a run of up to this many columns itself; longer ones take the wave
+constexpr uint32_t NO_SLOT = 0xffffffffu;
+
+// symbol of alignment column `col` of row r: 0..3, or C_OTHER for anything that is not A C G T
+__device__ __forceinline__ uint32_t column_symbol(const PolRow &r, const uint8_t *__restrict__ reads, uint32_t col) {
+    if (col >= r.qn) return C_OTHER;                                   // (validated on the host: never)
+    const uint8_t c = reads[r.read_off + (r.rev ? r.qn - 1 - col : col)] & 0xdfu;      // upper case
+    const uint32_t k = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : (uint32_t)C_OTHER;
+    return r.rev && k < 4 ? 3u - k : k;
+}
+
+// One wave walks the CIGAR of r: f(code, len, first target position, first query column) for every op, lane = op; stops
+// in front of the first 64 ops that start at t_stop or behind it.  All 64 lanes call f together.
+template <typename F>
+__device__ __forceinline__ void walk_row(const PolRow &r, const uint32_t *__restrict__ ops, int lane, uint32_t t_stop, F &&f) {
+    uint32_t tb = r.ts, qb = 0;
+    const uint32_t *o = ops + r.cig_off;
+    for (uint32_t k0 = 0; k0 < r.cig_n && tb < t_stop; k0 += 64) {
+        const uint32_t idx = k0 + (uint32_t)lane;
+        const uint32_t op = idx < r.cig_n ? o[idx] : 0u;
+        const uint32_t len = op >> 4, code = op & 15u;
+        const uint32_t tl = code == OP_I ? 0u : len, ql = code == OP_D ? 0u : len;
+        const uint32_t te = wave_prefix_sum_incl_dpp(tl), qe = wave_prefix_sum_incl_dpp(ql);
+        f(code, len, tb + te - tl, qb + qe - ql);
+        tb += (uint32_t)__builtin_amdgcn_readlane((int)te, 63);
+        qb += (uint32_t)__builtin_amdgcn_readlane((int)qe, 63);
+    }
+}
+
+__global__ __launch_bounds__(POLISH_WG) void polish_count_kernel(const PolRow *__restrict__ rows, const uint32_t *__restrict__ ops,
+                                                                 const uint8_t *__restrict__ reads, const uint8_t *__restrict__ contig,
+                                                                 const PolTile *__restrict__ tiles, int min_cov,
+                                                                 uint8_t *__restrict__ sym, uint8_t *__restrict__ open) {
+    __shared__ uint32_t s_cnt[POLISH_CNT][POLISH_TILE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const PolTile t = tiles[blockIdx.x];
+    const uint32_t t_end = t.t0 + t.n_pos;
+    for (int i = tid; i < POLISH_CNT * POLISH_TILE; i += POLISH_WG) (&s_cnt[0][0])[i] = 0;
+    __syncthreads();
+    for (uint32_t k = t.row_lo + (uint32_t)wave; k < t.row_hi; k += POLISH_WAVES) {
+        const PolRow r = rows[k];
+        if (r.te <= t.t0 || r.ts >= t_end) continue;
+        if (lane == 0 && r.ts >= t.t0) atomicAdd(&s_cnt[C_START][r.ts - t.t0], 1u);
+        auto vote = [&](uint32_t p, uint32_t code, uint32_t tp0, uint32_t qc0) {
+            const uint32_t s = code == OP_D ? (uint32_t)SYM_DEL : column_symbol(r, reads, qc0 + (p - tp0));
+            atomicAdd(&s_cnt[s][p - t.t0], 1u);
+        };
+        walk_row(r, ops, lane, t_end, [&](uint32_t code, uint32_t len, uint32_t tp0, uint32_t qc0) {
+            if (code == OP_I && len >= 1 && len <= (uint32_t)POLISH_INS_CAP && tp0 > r.ts && tp0 < r.te && tp0 >= t.t0 && tp0 < t_end)
+                atomicAdd(&s_cnt[C_INS][tp0 - t.t0], 1u);
+            // the columns of this op inside the tile
+            uint32_t a = 0, b = 0;
+            if (code == OP_EQ || code == OP_X || code == OP_D) {
+                a = max(tp0, t.t0);
+                b = max(a, min(tp0 + len, t_end));
+            }
+            const uint32_t n = b - a;
+            if (n <= SHORT_RUN)
+                for (uint32_t p = a; p < b; ++p) vote(p, code, tp0, qc0);
+            unsigned long long longs = __ballot(n > SHORT_RUN);
+            for (int it = 0; it < 64 && longs; ++it) {                 // the long runs, one after the other, 64 columns a step
+                const int src = __ffsll(longs) - 1;
+                longs &= longs - 1;
+                const uint32_t a2 = (uint32_t)__shfl((int)a, src), b2 = (uint32_t)__shfl((int)b, src);
+                const uint32_t code2 = (uint32_t)__shfl((int)code, src), tp2 = (uint32_t)__shfl((int)tp0, src),
+                               qc2 = (uint32_t)__shfl((int)qc0, src);
+                for (uint32_t p = a2 + (uint32_t)lane; p < b2; p += 64) vote(p, code2, tp2, qc2);
+            }
+        });
+    }
+    __syncthreads();
+    for (uint32_t i = (uint32_t)tid; i < t.n_pos; i += POLISH_WG) {
+        uint32_t v[5], c = 0, top = 0;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { v[k] = s_cnt[k][i]; c += v[k]; top = max(top, v[k]); }
+        const size_t g = (size_t)t.cbase + t.t0 + i;
+        uint8_t d = SYM_KEEP;
+        if (c >= (uint32_t)min_cov) {
+            const uint8_t own = contig[g] & 0xdfu;
+            const int ko = own == 'A' ? 0 : own == 'C' ? 1 : own == 'G' ? 2 : own == 'T' ? 3 : -1;
+            if (ko >= 0 && v[ko] == top) d = (uint8_t)ko;
+            else d = v[0] == top ? 0 : v[1] == top ? 1 : v[2] == top ? 2 : v[3] == top ? 3 : SYM_DEL;
+        }
+        sym[g] = d;
+        // rows that cover the position, less the ones that start on it, span the slot in front of it
+        const uint32_t span = c + s_cnt[C_OTHER][i] - s_cnt[C_START][i], ins = s_cnt[C_INS][i];
+        open[g] = span >= (uint32_t)min_cov && 2ull * ins > span;
+    }
+}
+
+__global__ void slot_index_kernel(const uint32_t *__restrict__ open_pos, uint32_t n_open, uint32_t *__restrict__ slot_of) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < n_open) slot_of[open_pos[s]] = s;
+}
+
+// MODE 0: the length every inserting row votes for at its opened slots; MODE 1: its bases, where its length won
+template <int MODE>
+__global__ __launch_bounds__(POLISH_WG) void polish_slot_kernel(const PolRow *__restrict__ rows, uint32_t n_rows,
+                                                                const uint32_t *__restrict__ ops, const uint8_t *__restrict__ reads,
+                                                                const uint32_t *__restrict__ slot_of, const uint8_t *__restrict__ win_len,
+                                                                uint32_t *__restrict__ len_cnt, uint32_t *__restrict__ base_cnt) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t w = blockIdx.x * POLISH_WAVES + (threadIdx.x >> 6);
+    if (w >= n_rows) return;
+    const PolRow r = rows[w];
+    walk_row(r, ops, lane, 0xffffffffu, [&](uint32_t code, uint32_t len, uint32_t tp0, uint32_t qc0) {
+        if (code != OP_I || len < 1 || len > (uint32_t)POLISH_INS_CAP || tp0 <= r.ts || tp0 >= r.te) return;
+        const uint32_t s = slot_of[(size_t)r.cbase + tp0];
+        if (s == NO_SLOT) return;
+        if (MODE == 0) atomicAdd(&len_cnt[(size_t)s * POLISH_INS_CAP + len - 1], 1u);
+        else if (win_len[s] == len)
+            for (uint32_t j = 0; j < len; ++j) {
+                const uint32_t k = column_symbol(r, reads, qc0 + j);
+                if (k < 4) atomicAdd(&base_cnt[((size_t)s * POLISH_INS_CAP + j) * 4 + k], 1u);
+            }
+    });
+}
+
+__global__ void slot_len_kernel(const uint32_t *__restrict__ len_cnt, uint32_t n_open, uint8_t *__restrict__ win_len) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_open) return;
+    uint32_t best = 0, n = 0;
+    for (int l = 0; l < POLISH_INS_CAP; ++l) {
+        const uint32_t c = len_cnt[(size_t)s * POLISH_INS_CAP + l];
+        if (c > best) { best = c; n = (uint32_t)l + 1; }               // (a tie keeps the smaller length)
+    }
+    win_len[s] = (uint8_t)n;
+}
+
+// bytes position g adds to its contig: the slot in front of it, then itself; entry n (behind the last position): 0
+__global__ void out_len_kernel(const uint8_t *__restrict__ sym, const uint32_t *__restrict__ slot_of, const uint8_t *__restrict__ win_len,
+                               size_t n, uint32_t *__restrict__ out_len) {
+    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (g > n) return;
+    uint32_t l = 0;
+    if (g < n) {
+        l = sym[g] != SYM_DEL;
+        const uint32_t s = slot_of[g];
+        if (s != NO_SLOT) l += win_len[s];
+    }
+    out_len[g] = l;
+}
+
+__global__ void write_kernel(const uint8_t *__restrict__ sym, const uint32_t *__restrict__ slot_of, const uint8_t *__restrict__ win_len,
+                             const uint32_t *__restrict__ base_cnt, const uint8_t *__restrict__ contig, const uint64_t *__restrict__ off,
+                             size_t n, uint8_t *__restrict__ out) {
+    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    uint64_t o = off[g];
+    const uint32_t s = slot_of[g];
+    if (s != NO_SLOT) {
+        const uint32_t len = min((uint32_t)win_len[s], (uint32_t)POLISH_INS_CAP);
+        for (uint32_t j = 0; j < len; ++j) {
+            const uint32_t *c = base_cnt + ((size_t)s * POLISH_INS_CAP + j) * 4;
+            uint32_t best = 0;
+            uint8_t b = 'N';
+            for (int k = 0; k < 4; ++k)
+                if (c[k] > best) { best = c[k]; b = (uint8_t)"ACGT"[k]; }
+            out[o++] = b;
+        }
+    }
+    const uint8_t d = sym[g];
+    if (d != SYM_DEL) out[o] = d == SYM_KEEP ? contig[g] : (uint8_t)"ACGT"[d];
+}
+
+__global__ void gather_off_kernel(const uint64_t *__restrict__ off, const uint32_t *__restrict__ at, uint32_t n, uint64_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = off[at[i]];
+}
+
+}  // namespace
+
+void polish_device(const PolDevIn &in, PolDevOut &out) {
+    const size_t G = in.contigs.size();
+    out = PolDevOut{};
+    out.start.assign(in.cbase.size(), 0);
+    if (!G) return;
+    constexpr int B = 256;
+    DBuf<uint8_t> d_contig, d_reads, d_sym(G), d_open(G);
+    DBuf<PolRow> d_rows;
+    DBuf<uint32_t> d_ops, d_cbase;
+    DBuf<PolTile> d_tiles;
+    d_contig.upload((const uint8_t *)in.contigs.data(), G);
+    d_reads.upload((const uint8_t *)in.reads.data(), in.reads.size());
+    d_rows.upload(in.rows);
+    d_ops.upload(in.ops);
+    d_tiles.upload(in.tiles);
+    d_cbase.upload(in.cbase);
+    HIP_CHECK(hipMemsetAsync(d_sym.p, SYM_KEEP, G, stream()));
+    d_open.zero();
+    if (!in.tiles.empty()) {
+        KTimer kt("polish_count");
+        hipLaunchKernelGGL(polish_count_kernel, dim3((unsigned)in.tiles.size()), dim3(POLISH_WG), 0, stream(), d_rows.p, d_ops.p,
+                           d_reads.p, d_contig.p, d_tiles.p, in.min_cov, d_sym.p, d_open.p);
+        HIP_CHECK(hipGetLastError());
+    }
+    DBuf<uint32_t> d_open_pos(G), d_slot_of(G);
+    const size_t n_open = select_flagged_indices(d_open.p, d_open_pos.p, G);
+    d_slot_of.fill_ff();
+    DBuf<uint32_t> d_len_cnt(std::max<size_t>(n_open, 1) * POLISH_INS_CAP), d_base_cnt(std::max<size_t>(n_open, 1) * POLISH_INS_CAP * 4);
+    DBuf<uint8_t> d_win_len(std::max<size_t>(n_open, 1));
+    if (n_open) {
+        KTimer kt("polish_slots");
+        const uint32_t n_rows = (uint32_t)in.rows.size();
+        d_len_cnt.zero();
+        d_base_cnt.zero();
+        hipLaunchKernelGGL(slot_index_kernel, dim3(cdiv(n_open, B)), dim3(B), 0, stream(), d_open_pos.p, (uint32_t)n_open, d_slot_of.p);
+        hipLaunchKernelGGL(polish_slot_kernel<0>, dim3(cdiv(n_rows, POLISH_WAVES)), dim3(POLISH_WG), 0, stream(), d_rows.p, n_rows,
+                           d_ops.p, d_reads.p, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
+        hipLaunchKernelGGL(slot_len_kernel, dim3(cdiv(n_open, B)), dim3(B), 0, stream(), d_len_cnt.p, (uint32_t)n_open, d_win_len.p);
+        hipLaunchKernelGGL(polish_slot_kernel<1>, dim3(cdiv(n_rows, POLISH_WAVES)), dim3(POLISH_WG), 0, stream(), d_rows.p, n_rows,
+                           d_ops.p, d_reads.p, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
+        HIP_CHECK(hipGetLastError());
+    }
+    DBuf<uint32_t> d_out_len(G + 1);
+    DBuf<uint64_t> d_off(G + 1), d_start(in.cbase.size());
+    hipLaunchKernelGGL(out_len_kernel, dim3(cdiv(G + 1, B)), dim3(B), 0, stream(), d_sym.p, d_slot_of.p, d_win_len.p, G, d_out_len.p);
+    exclusive_scan_u32_to_u64(d_out_len.p, d_off.p, G + 1);
+    const uint64_t total = download_one(d_off.p + G);
+    DBuf<uint8_t> d_out(std::max<uint64_t>(total, 1));
+    {
+        KTimer kt("polish_write");
+        hipLaunchKernelGGL(write_kernel, dim3(cdiv(G, B)), dim3(B), 0, stream(), d_sym.p, d_slot_of.p, d_win_len.p, d_base_cnt.p,
+                           d_contig.p, d_off.p, G, d_out.p);
+        hipLaunchKernelGGL(gather_off_kernel, dim3(cdiv(in.cbase.size(), B)), dim3(B), 0, stream(), d_off.p, d_cbase.p,
+                           (uint32_t)in.cbase.size(), d_start.p);
+        HIP_CHECK(hipGetLastError());
+    }
+    out.start = d_start.download();
+    const std::vector<uint8_t> bytes = d_out.download((size_t)total);
+    out.bases.assign((const char *)bytes.data(), bytes.size());
+    out.sym = d_sym.download();
+    out.open_pos = d_open_pos.download(n_open);
+    out.open_len = d_win_len.download(n_open);
+}
+
+}  // namespace pol
+}  // namespace hlmi

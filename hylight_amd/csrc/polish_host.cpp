@@ -1,0 +1,215 @@
+// polish_host.cpp - the host part of hlmi_polish (include/hylight_mi.h): reading, the refusals, row selection, the rows and
+// tiles the device works on (sorted by contig and start), the statistics, the headers and the file.  The votes, the
+// decisions and the bases are polish.hip's.
+// PARITY UNPINNED: racon is not part of the reference tree; tests/polish_model.py is the contract.
+#include <algorithm>
+#include <cstdio>
+#include <string>
+#include <string_view>
+#include <unordered_map>
+#include <vector>
+
+#include "common.h"
+#include "paf_io.h"
+#include "polish_internal.h"
+
+namespace hlmi {
+
+using namespace pol;
+
+namespace {
+
+// name -> first record of that name
+std::unordered_map<std::string_view, uint32_t> first_records(const SeqSet &s, const char *path) {
+    std::unordered_map<std::string_view, uint32_t> m;
+    m.reserve(s.size() * 2);
+    for (size_t i = 0; i < s.size(); ++i) {
+        if (s.len(i) >= MAX_SEQ) fail(HLMI_EINVAL, "hlmi_polish: %s: %s has 2^28 bases or more", path, s.names[i].c_str());
+        m.emplace(s.names[i], (uint32_t)i);
+    }
+    return m;
+}
+
+struct Sel {
+    size_t line;            // 0-based PAF line
+    uint32_t contig, read;
+};
+
+}  // namespace
+
+void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
+                hlmi_polish_stats *st) {
+    const double t_begin = now_ms();
+    *st = hlmi_polish_stats{};
+    if (o.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish: min_cov %d (< 1)", o.min_cov);
+    SeqSet cs, rs;
+    read_seqs(contigs, cs);
+    read_seqs(reads, rs);
+    const auto contig_named = first_records(cs, contigs), read_named = first_records(rs, reads);
+    PafText pt;
+    read_paf(paf, pt, false);
+    const size_t n = pt.recs.size();
+    st->rows = n;
+    st->contigs = cs.size();
+
+    // what read_paf lets through and this call does not: a row of 11 columns, a CIGAR that ends in a number
+    std::vector<uint8_t> has_tag(n), is_star(n);
+    for (size_t i = 0; i < n; ++i) {
+        const std::string_view L = pt.line(i);
+        if (std::count(L.begin(), L.end(), '\t') < 11) fail(HLMI_EINVAL, "%s:%zu: PAF row has 11 columns (< 12)", paf, i + 1);
+        const std::string_view lf = L.substr(L.rfind('\t') + 1);
+        has_tag[i] = lf.substr(0, 5) == "cg:Z:";
+        is_star[i] = lf == "cg:Z:*";
+        if (has_tag[i] && lf.back() >= '0' && lf.back() <= '9') fail(HLMI_EINVAL, "%s:%zu: cg:Z: ends in a number", paf, i + 1);
+    }
+    std::vector<int64_t> contig_of(pt.dict.names.size()), read_of(pt.dict.names.size());
+    for (size_t k = 0; k < pt.dict.names.size(); ++k) {
+        const auto c = contig_named.find(pt.dict.names[k]);
+        const auto r = read_named.find(pt.dict.names[k]);
+        contig_of[k] = c == contig_named.end() ? -1 : (int64_t)c->second;
+        read_of[k] = r == read_named.end() ? -1 : (int64_t)r->second;
+    }
+
+    // the refusals, row by row, and the selection
+    std::unordered_map<uint32_t, Sel> best;                  // query name -> its row so far
+    for (size_t i = 0; i < n; ++i) {
+        const PafRec &r = pt.recs[i];
+        const uint32_t *op = pt.ops.data() + r.cig_off;
+        if (!has_tag[i]) fail(HLMI_EINVAL, "%s:%zu: no cg:Z: tag in the last column", paf, i + 1);
+        uint64_t n_t = 0, n_q = 0, n_eq = 0, n_all = 0;
+        bool other = is_star[i] != 0;
+        for (uint32_t k = 0; k < r.cig_n; ++k) {
+            const uint64_t len = op[k] >> 4;
+            const uint32_t code = op[k] & 15u;
+            other |= code == OP_OTHER;
+            n_all += len;
+            if (code != OP_I) n_t += len;
+            if (code != OP_D) n_q += len;
+            if (code == OP_EQ) n_eq += len;
+        }
+        if (other) fail(HLMI_EINVAL, "%s:%zu: a CIGAR op other than = X I D", paf, i + 1);
+        if (read_of[r.qid] < 0) fail(HLMI_EINVAL, "%s:%zu: query %s is not among the reads", paf, i + 1, pt.dict.names[r.qid].c_str());
+        if (contig_of[r.tid] < 0) fail(HLMI_EINVAL, "%s:%zu: target %s is not among the contigs", paf, i + 1, pt.dict.names[r.tid].c_str());
+        const uint32_t ci = (uint32_t)contig_of[r.tid], ri = (uint32_t)read_of[r.qid];
+        if (r.qs > r.qe || r.qe > rs.len(ri) || r.ts > r.te || r.te > cs.len(ci))
+            fail(HLMI_EINVAL, "%s:%zu: coordinates outside the sequences (read of %u, contig of %u bases)", paf, i + 1, rs.len(ri), cs.len(ci));
+        if (n_t != (uint64_t)(r.te - r.ts)) fail(HLMI_EINVAL, "%s:%zu: the CIGAR has %llu target columns, te - ts = %u", paf, i + 1, (unsigned long long)n_t, r.te - r.ts);
+        if (n_q != (uint64_t)(r.qe - r.qs)) fail(HLMI_EINVAL, "%s:%zu: the CIGAR has %llu query columns, qe - qs = %u", paf, i + 1, (unsigned long long)n_q, r.qe - r.qs);
+        const uint32_t span = r.te - r.ts;
+        if (r.qid == r.tid || span == 0 || (int64_t)span < (int64_t)o.min_len) continue;
+        if ((double)n_eq / (double)n_all < o.min_iden) continue;
+        const auto it = best.find(r.qid);
+        if (it == best.end()) best.emplace(r.qid, Sel{i, ci, ri});
+        else if (span > pt.recs[it->second.line].te - pt.recs[it->second.line].ts) it->second = Sel{i, ci, ri};
+    }
+    std::vector<Sel> sel;
+    sel.reserve(best.size());
+    for (const auto &kv : best) sel.push_back(kv.second);
+    std::sort(sel.begin(), sel.end(), [&](const Sel &a, const Sel &b) {      // by (contig, start), the line last
+        if (a.contig != b.contig) return a.contig < b.contig;
+        const uint32_t sa = pt.recs[a.line].ts, sb = pt.recs[b.line].ts;
+        return sa != sb ? sa < sb : a.line < b.line;
+    });
+    st->rows_selected = sel.size();
+
+    // the device's input: polished contigs side by side, the aligned stretch of every read, compact CIGARs, tiles
+    PolDevIn in;
+    in.min_cov = o.min_cov;
+    std::vector<uint32_t> rc(cs.size(), 0), slot_of_contig(cs.size(), 0);
+    for (const Sel &s : sel) ++rc[s.contig];
+    std::vector<uint32_t> polished;
+    for (uint32_t c = 0; c < cs.size(); ++c)
+        if (rc[c]) {
+            slot_of_contig[c] = (uint32_t)polished.size();
+            polished.push_back(c);
+            if (in.contigs.size() + cs.len(c) >= (1ull << 31)) fail(HLMI_EINVAL, "hlmi_polish: 2^31 contig bases or more to polish in one call");
+            in.cbase.push_back((uint32_t)in.contigs.size());
+            in.contigs.append(cs.bases, cs.off[c], cs.len(c));
+        }
+    in.cbase.push_back((uint32_t)in.contigs.size());
+    st->contigs_polished = polished.size();
+    in.rows.reserve(sel.size());
+    for (const Sel &s : sel) {
+        const PafRec &r = pt.recs[s.line];
+        const uint32_t *op = pt.ops.data() + r.cig_off;
+        PolRow row{};
+        row.read_off = in.reads.size();
+        row.cig_off = in.ops.size();
+        row.ts = r.ts; row.te = r.te; row.qn = r.qe - r.qs;
+        row.rev = (r.flags & PF_REV) ? 1u : 0u;
+        row.cbase = in.cbase[slot_of_contig[s.contig]];
+        in.reads.append(rs.bases, rs.off[s.read] + r.qs, row.qn);
+        uint32_t p = r.ts;
+        for (uint32_t k = 0; k < r.cig_n; ++k) {
+            const uint32_t len = op[k] >> 4, code = op[k] & 15u;
+            if (!len) continue;
+            if (code == OP_I) {
+                if (p == r.ts || p == r.te) ++st->ins_edge;
+                if (in.ops.size() > row.cig_off && (in.ops.back() & 15u) == OP_I) {       // the same slot: one op
+                    in.ops.back() += len << 4;
+                    continue;
+                }
+            } else p += len;
+            in.ops.push_back(op[k]);
+        }
+        row.cig_n = (uint32_t)(in.ops.size() - row.cig_off);
+        p = r.ts;
+        for (uint32_t k = 0; k < row.cig_n; ++k) {
+            const uint32_t w = in.ops[row.cig_off + k];
+            if ((w & 15u) != OP_I) p += w >> 4;
+            else if (p != r.ts && p != r.te && (w >> 4) > (uint32_t)POLISH_INS_CAP) ++st->ins_long;
+        }
+        in.rows.push_back(row);
+    }
+    for (size_t r0 = 0; r0 < in.rows.size();) {
+        size_t r1 = r0;
+        while (r1 < in.rows.size() && in.rows[r1].cbase == in.rows[r0].cbase) ++r1;
+        const uint32_t cbase = in.rows[r0].cbase;
+        const uint32_t len = *std::upper_bound(in.cbase.begin(), in.cbase.end(), cbase) - cbase;
+        size_t lo = r0, hi = r0;
+        for (uint32_t t0 = 0; t0 < len; t0 += POLISH_TILE) {
+            const uint32_t n_pos = std::min<uint32_t>(POLISH_TILE, len - t0);
+            while (hi < r1 && in.rows[hi].ts < t0 + n_pos) ++hi;
+            while (lo < hi && in.rows[lo].te <= t0) ++lo;        // (rows behind lo that ended too are passed over by the kernel)
+            if (lo < hi) in.tiles.push_back(PolTile{t0, n_pos, (uint32_t)lo, (uint32_t)hi, cbase});
+        }
+        r0 = r1;
+    }
+
+    const double t_dev = now_ms();
+    PolDevOut out;
+    polish_device(in, out);
+    st->ms_device = now_ms() - t_dev;
+
+    st->slots_opened = out.open_pos.size();
+    for (uint8_t l : out.open_len) st->inserted_bases += l;
+    std::vector<std::string> lines;
+    for (uint32_t c = 0; c < cs.size(); ++c) {
+        if (!rc[c]) {
+            if (o.include_unpolished && cs.len(c)) {
+                lines.push_back(">" + cs.names[c]);
+                lines.push_back(cs.bases.substr(cs.off[c], cs.len(c)));
+            }
+            continue;
+        }
+        const uint32_t j = slot_of_contig[c], b = in.cbase[j], L = cs.len(c);
+        uint64_t covered = 0;
+        for (uint32_t p = 0; p < L; ++p) {
+            const uint8_t d = out.sym[b + p];
+            if (d == SYM_KEEP) continue;
+            ++covered;
+            if (d == SYM_DEL) ++st->deleted;
+            else if ("ACGT"[d] != (char)((unsigned char)in.contigs[b + p] & 0xdfu)) ++st->substituted;
+        }
+        const uint64_t new_len = out.start[j + 1] - out.start[j];
+        if (!new_len) continue;
+        char head[96];
+        snprintf(head, sizeof head, " LN:i:%llu RC:i:%u XC:f:%.6f", (unsigned long long)new_len, rc[c], (double)covered / (double)L);
+        lines.push_back(">" + cs.names[c] + head);
+        lines.push_back(out.bases.substr(out.start[j], new_len));
+    }
+    write_lines(out_fa, lines);
+    st->ms_total = now_ms() - t_begin;
+}
+
+}  // namespace hlmi

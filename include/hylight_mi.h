@@ -417,6 +417,57 @@ typedef struct {
 int hlmi_cluster_short(const char *paf, const char *fastq, const hlmi_cluster_opts *o, const char *out_dir,
                        hlmi_cluster_stats *st);
 
+/* ---- contig polishing (replaces the external `racon --no-trimming -u` of HyLight.py:152,182,203) ------------------------
+ * A function of the project's own, NOT racon's: racon re-aligns with a partial-order aligner; this call only counts the
+ * columns of the CIGARs the overlapper wrote.  Parity unpinned; tests/polish_model.py is the contract, byte for byte. */
+typedef struct {
+    int min_len;              /* rows with te - ts below this are dropped                                                 */
+    double min_iden;          /* rows with (sum of '=' lengths) / (sum of all op lengths) below this are dropped         */
+    int min_cov;              /* votes a position needs to be decided, rows a slot needs to be opened (>= 1)              */
+    int include_unpolished;   /* racon's -u: a contig without a selected row is written as it is                          */
+} hlmi_polish_opts;
+void hlmi_polish_opts_default(hlmi_polish_opts *o);   /* 0, 0.0, 3, 1 */
+typedef struct {
+    uint64_t rows;              /* PAF rows                                                                                 */
+    uint64_t rows_selected;     /* rows that vote (one per read at most)                                                    */
+    uint64_t contigs;           /* records of `contigs`                                                                     */
+    uint64_t contigs_polished;  /* ... with a selected row                                                                  */
+    uint64_t substituted;       /* positions decided as a base other than the contig's own (upper-cased)                    */
+    uint64_t deleted;           /* positions decided as `del`                                                               */
+    uint64_t inserted_bases;    /* bases written at opened slots                                                            */
+    uint64_t slots_opened;
+    uint64_t ins_long;          /* (row, slot) pairs whose insertion is longer than 16 bases: the row spans, it does not insert */
+    uint64_t ins_edge;          /* I ops at the very start or end of a selected row's CIGAR: they belong to no slot         */
+    double ms_device;           /* wall time of the device part: uploads, kernels, read-backs                               */
+    double ms_total;
+} hlmi_polish_stats;
+/* contigs, reads: FASTA or FASTQ; paf: rows of >= 12 columns whose LAST field is a cg:Z: CIGAR in = X I D (what hlmi_ava
+ * writes).  Writes the polished contigs to out_fa (under a temporary name, renamed on success).
+ * Refused with HLMI_EINVAL before anything is written (the message names the 1-based PAF line; malformed rows - columns,
+ * integers, strand, CIGAR numbers - of the whole file are reported before the following): no cg:Z: tag; an op other than
+ * = X I D; a query name not in `reads`; a target name not in `contigs`; coordinates outside the sequences (the sequences'
+ * own lengths count, not columns 2 and 7); sum(= X D) != te - ts; sum(= X I) != qe - qs.  Also min_cov < 1, and a
+ * sequence of 2^28 bases or more.  A name that occurs twice means its first record.  An op of length 0 is no op.
+ * Row selection, in this order: rows with qname == tname are skipped; rows with te == ts or te - ts < min_len are dropped;
+ * rows with (double)n_eq / (double)n_all < min_iden are dropped; per query name the row with the largest te - ts stays,
+ * the earliest line on a tie (one row per read is racon's rule as well).
+ * Votes: alignment column i of a row reads read[qs + i] on strand '+' and the complement of read[qe - 1 - i] on '-',
+ * upper-cased.  Position p in [ts, te): an = or X column votes its base if that is A, C, G or T and nothing otherwise; a D
+ * column votes `del`.  Slot p, ts < p < te, is the gap in front of position p: every selected row with ts < p < te spans
+ * it; the I ops the row has there (none of = X D between them) are concatenated; a row with 1..16 bases there inserts
+ * them, one with more spans without inserting (ins_long); I ops at p == ts or p == te belong to no slot (ins_edge).
+ * Decisions: position: c = its votes; c < min_cov: the contig's byte stays, case included; else the symbol with the most
+ * votes, on a tie the contig's own upper-cased base if it is among the tied ones, else the first of A, C, G, T, del; del
+ * omits the position.  Slot: s spanning rows, i inserting rows; opened when s >= min_cov and 2 i > s; its length is the
+ * most frequent one among the inserting rows (tie: the smallest), base j the most frequent of A, C, G, T at index j among
+ * the rows that insert exactly that length (tie: the first of A, C, G, T; none: N).
+ * Output: the contigs in file order, two lines each: ">name LN:i:<new length> RC:i:<rows selected on it> XC:f:<share of
+ * its positions with c >= min_cov, %.6f>"; a contig without a selected row is written as ">name" and its bytes when
+ * include_unpolished is set, else left out; a contig whose consensus is empty is not written.
+ * Device: every counter is 32 bits wide, so coverage has no limit below 2^32 rows. */
+int hlmi_polish(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts *o, const char *out_fa,
+                hlmi_polish_stats *st);
+
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
  * reads into a caller-owned device buffer (16 B per minimizer: two uint64), the caller
