@@ -62,6 +62,21 @@ class VqMergeStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in VQ_MERGE_STATS] + [(k, C.c_double) for k in VQ_MERGE_MS]
 
 
+class VqCliqueOpts(C.Structure):
+    _fields_ = [("min_clique_size", C.c_uint32), ("error_correction", C.c_int), ("first_it", C.c_int),
+                ("keep_singletons", C.c_uint32)]
+
+
+VQ_CLIQUE_STATS = ("cliques_read", "singletons", "below_min", "taken", "filtered", "superreads", "dropped_empty", "dropped_n",
+                   "dropped_support", "trivial", "trivial_reverse", "short_reads", "n_reads", "columns", "columns_host",
+                   "bases_in", "bytes_out")
+VQ_CLIQUE_MS = ("ms_cliques",)
+
+
+class VqCliqueStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in VQ_CLIQUE_STATS] + [(k, C.c_double) for k in VQ_CLIQUE_MS]
+
+
 class VqNextOpts(C.Structure):
     _fields_ = [("no_inclusion_overlaps", C.c_int)]
 
@@ -139,6 +154,10 @@ SYMBOLS = {
     "hlmi_vq_merge_opts_stageb": (None, [C.POINTER(VqMergeOpts)]),
     "hlmi_vq_merge": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqMergeOpts), C.c_char_p,
                                 C.POINTER(VqGraphStats), C.POINTER(VqMergeStats)]),
+    "hlmi_vq_clique_opts_polyte": (None, [C.POINTER(VqCliqueOpts), C.c_int]),
+    "hlmi_vq_cliques_of_graph": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "hlmi_vq_cliques": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqCliqueOpts), C.c_char_p,
+                                  C.POINTER(VqGraphStats), C.POINTER(VqCliqueStats)]),
     "hlmi_vq_next_opts_stageb": (None, [C.POINTER(VqNextOpts)]),
     "hlmi_vq_iteration": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqMergeOpts),
                                     C.POINTER(VqNextOpts), C.c_char_p, C.POINTER(VqGraphStats), C.POINTER(VqMergeStats),
@@ -385,6 +404,43 @@ def vq_merge(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
                                 C.byref(go), C.byref(mo), _b(out_dir), C.byref(gst), C.byref(mst)))
     return ({k: getattr(gst, k) for k in VQ_GRAPH_STATS},
             {k: getattr(mst, k) for k in VQ_MERGE_STATS + VQ_MERGE_MS})
+
+
+def vq_clique_opts_polyte(error_correction=False):
+    """hlmi_vq_clique_opts_polyte: the SRBuilder options POLYTE passes with --cliques=true, as a dict.  POLYTE also passes
+    --min_qual=0, which is not built: hlmi_vq_cliques keeps minQual 0.9, so disagreeing columns become N (see the header)."""
+    o = VqCliqueOpts()
+    load().hlmi_vq_clique_opts_polyte(C.byref(o), int(bool(error_correction)))
+    return {k: getattr(o, k) for k, _ in VqCliqueOpts._fields_}
+
+
+def vq_cliques_of_graph(graph_txt, cliques_out):
+    """hlmi_vq_cliques_of_graph: the maximal cliques of a graph.txt, written as the reference's enumerator prints them (its
+    two text lines, then one clique per line).  Host code: needs no GPU.  -> the number of cliques."""
+    n = C.c_uint64(0)
+    _check(load().hlmi_vq_cliques_of_graph(_b(graph_txt), _b(cliques_out), C.byref(n)))
+    return n.value
+
+
+def vq_cliques(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
+    """hlmi_vq_cliques: the graph of vq_graph (same files) and then ViralQuasispecies' --cliques=true step for single-end reads -
+    cliques.txt, singles.fastq, subreads.txt and clique_map.txt in out_dir (created if missing).  Options: the fields of
+    hlmi_vq_graph_opts (the stage-b values by default; what POLYTE passes beside them is written down in the header) and of
+    hlmi_vq_clique_opts (hlmi_vq_clique_opts_polyte for the error_correction given).  -> (graph stats, clique stats)."""
+    go, co = VqGraphOpts(), VqCliqueOpts()
+    load().hlmi_vq_graph_opts_stageb(C.byref(go))
+    load().hlmi_vq_clique_opts_polyte(C.byref(co), int(bool(opts.get("error_correction", False))))
+    for k, v in opts.items():
+        target = go if k in dict(VqGraphOpts._fields_) else co if k in dict(VqCliqueOpts._fields_) else None
+        if target is None:
+            raise TypeError(f"vq_cliques: unknown option {k!r}")
+        setattr(target, k, int(v) if isinstance(v, bool) else v)
+    os.makedirs(out_dir, exist_ok=True)
+    gst, cst = VqGraphStats(), VqCliqueStats()
+    _check(load().hlmi_vq_cliques(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
+                                  C.byref(go), C.byref(co), _b(out_dir), C.byref(gst), C.byref(cst)))
+    return ({k: getattr(gst, k) for k in VQ_GRAPH_STATS},
+            {k: getattr(cst, k) for k in VQ_CLIQUE_STATS + VQ_CLIQUE_MS})
 
 
 def vq_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):

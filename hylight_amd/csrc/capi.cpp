@@ -372,6 +372,26 @@ int hlmi_vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, u
     });
 }
 
+void hlmi_vq_clique_opts_polyte(hlmi_vq_clique_opts *o, int error_correction) {
+    if (o) vq_clique_opts_polyte(o, error_correction);
+}
+
+int hlmi_vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uint64_t *n_cliques) {
+    return guarded([&] {                                       // host code: no device is asked for
+        if (!graph_txt || !cliques_out || !n_cliques) fail(HLMI_EINVAL, "hlmi_vq_cliques_of_graph: NULL argument");
+        vq_cliques_of_graph(graph_txt, cliques_out, n_cliques);
+    });
+}
+
+int hlmi_vq_cliques(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                    const hlmi_vq_clique_opts *co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst) {
+    return guarded([&] {
+        if (!singles_fastq || !overlaps || !go || !co || !out_dir || !gst || !cst) fail(HLMI_EINVAL, "hlmi_vq_cliques: NULL argument");
+        require_device();
+        vq_cliques_run(singles_fastq, overlaps, subreads_in, *go, *co, out_dir, gst, cst);
+    });
+}
+
 void hlmi_cluster_opts_default(hlmi_cluster_opts *o) {
     if (o) *o = hlmi_cluster_opts{15000, 20, 0, 0};            // HyLight.py --size, -t
 }

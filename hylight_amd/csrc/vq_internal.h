@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -211,6 +212,7 @@ struct Rec {                                     // one FASTQ record of the outp
 };
 }  // namespace vqm
 
+namespace vqc { struct Pile; struct Entry; struct Result; }
 // The device side of a merge over resident reads: bases / quals concatenated, read r at [off[r], off[r + 1]).
 class VqMergeDev {
 public:
@@ -219,6 +221,11 @@ public:
     std::vector<uint32_t> count_n(const std::vector<vqm::Rec> &recs);       // 'N's each record would hold
     // the records' FASTQ text, one after the other; start[r] = first byte of record r, start[n] = the size
     std::string write(const std::vector<vqm::Rec> &recs, std::vector<uint64_t> &start);
+    // vq_clique.hip: SRBuilder::consensus of every pile-up, one wave each.  bases / quals receive the piles' columns (pile k
+    // at col0), a quality byte of 0 marks a column the host has to redo (vqc::MARGIN); res[k] as vqc::Result says
+    void consensus_piles(const std::vector<vqc::Pile> &piles, const std::vector<vqc::Entry> &entries, uint32_t min_support,
+                         bool error_correction, std::vector<uint8_t> &bases, std::vector<uint8_t> &quals,
+                         std::vector<vqc::Result> &res);
 private:
     void layout(const std::vector<vqm::Rec> &recs, DBuf<vqm::Rec> &d_rec, DBuf<uint64_t> &pos0, DBuf<uint64_t> &byte0);
     DBuf<uint8_t> d_bases_, d_quals_;
@@ -236,6 +243,59 @@ void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_
                   const hlmi_vq_merge_opts &mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
 void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2, const char *qual2,
                        uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual, uint32_t *out_len);
+
+// SRBuilder::consensus_pos (:297-402) of n >= 1 nucleotides (A C G T N) with their phreds, in the reference's expression order
+// with the host's libm -> (base << 8) | quality character
+uint16_t vq_consensus_pos(const char *nuc, const int *phred, int n);
+const std::vector<uint16_t> &vq_consensus_tables();            // the vqm::T_* tables, built once
+
+// ---- originals: vq_clique_host.cpp (what subreads.txt holds; shared by the merge and the clique step) ---------------------
+// OriginalIndex of a single-end original (Types.h): forward, index1, len1
+struct VqOrig { bool forward; long index; int len; };
+using VqOriginals = std::map<uint64_t, VqOrig>;                // ascending original id: the order the lines are written in
+// buildOriginalsDict, the branch that reads subreads.txt (OverlapGraph.cpp:799-845), over the file's text
+std::map<uint64_t, VqOriginals> vq_parse_subreads(const std::string &data, const char *path);
+void vq_subreads_line(std::string &s, uint64_t id, const VqOriginals &o);
+// constructSuperread :750-806 for one member of a super-read: its originals go into `merged` unless already there.  forward =
+// the vertex label, idx1 = index1 - startpos1 of calcSubreadInfo (the read's offset minus trim_pos), read_len = |read|
+void vq_originals_add(VqOriginals &merged, const VqOriginals &of_read, bool forward, bool first_it, long idx1, long read_len);
+// a reverse read written forward (:1204-1216): orientation flipped, index mirrored
+void vq_originals_mirror(VqOriginals &o, long read_len);
+
+// ---- cliques: vq_clique_host.cpp / vq_clique.hip (ViralQuasispecies --cliques=true, SRBuilder::cliquesToSuperreads) ---------
+// The maximal cliques of a graph.txt image (n, m, then m lines "u,v") in the order and with the vertex order quick-cliques'
+// degeneracy algorithm lists them: `text` = what `qc --algorithm=degeneracy` prints, cliques = the vertices, clique k at
+// [off[k], off[k + 1]).  Pure host code.
+struct VqCliqueList {
+    std::string text;
+    std::vector<uint32_t> members;
+    std::vector<uint64_t> off;
+};
+VqCliqueList vq_enumerate_cliques(const std::string &graph_text);
+
+namespace vqc {
+constexpr int WG = 256;
+constexpr int WAVE = 64;
+constexpr uint32_t MAX_PILE = 63;                // reads of one pile-up: 3 * min_clique_size with min_clique_size <= 21
+constexpr uint32_t MAX_MIN_CLIQUE = 21;
+// The margin of DESIGN.md 4.3f: a column whose 1 - p_incorrect lies this close to minQual, or whose p_incorrect lies this close
+// to 10^-9.3, goes back to the host; the value in front of round() gets X_SLOPE * MARGIN / p_incorrect + X_FLOOR.
+constexpr double MARGIN = 0x1p-44;
+constexpr double X_SLOPE = 4.35;                 // > 10 / ln 10
+constexpr double X_FLOOR = 0x1p-36;
+constexpr double MIN_PROB = 1e-290;              // a best base less likely than this goes back too: pow near the subnormals
+struct Pile {                                    // one clique's pile-up
+    uint32_t first, n;                           // its entries
+    uint32_t total_len, trim_pos;                // columns; the first one that is written (0 without error correction)
+    uint64_t col0;                               // its first column in the column buffers
+};
+struct Entry { uint32_t read, pos, rev; };      // read `read` (reverse-complemented when rev) from column pos on
+struct Result { uint32_t stop, empty; };         // columns [trim_pos, stop) are the consensus; empty: a column without a read
+}  // namespace vqc
+void vq_clique_opts_polyte(hlmi_vq_clique_opts *o, int error_correction);
+void vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uint64_t *n_cliques);
+void vq_cliques_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                    const hlmi_vq_clique_opts &co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst);
 
 // ---- next: vq_next.hip (SRBuilder::findNextOverlaps, FNO 1) ---------------------------------------------------------------
 namespace vqn {

@@ -26,8 +26,10 @@ using namespace vqm;
 
 constexpr double MIN_QUAL = 0.9;          // ViralQuasispecies.cpp:62 (--min_qual default) -> SRBuilder.h:89
 
-// SRBuilder::consensus_pos (:297-402) in its own expression order; n = 1 or 2 nucleotides.  -> (base << 8) | quality
-uint16_t consensus_pos(const char *nuc, const int *phred, int n) {
+}  // namespace
+
+// SRBuilder::consensus_pos (:297-402) in its own expression order.  -> (base << 8) | quality
+uint16_t vq_consensus_pos(const char *nuc, const int *phred, int n) {
     double score_A = 0, score_C = 0, score_T = 0, score_G = 0;
     for (int i = 0; i < n; ++i) {
         const double p = pow(10, -phred[i] / 10.0);                        // phred_to_prob (:289-293)
@@ -59,6 +61,9 @@ uint16_t consensus_pos(const char *nuc, const int *phred, int n) {
     else b = 'G';
     return (uint16_t)((b << 8) | (phred_out + 33));
 }
+
+namespace {
+inline uint16_t consensus_pos(const char *nuc, const int *phred, int n) { return vq_consensus_pos(nuc, phred, n); }
 
 // The tables of vq_internal.h (vqm::T_*).  Every pair of (base, quality) is evaluated; the forms by class that fit LDS are
 // kept only if the answer does not depend on which bases they are - it can, through the order of the four terms of
@@ -105,10 +110,15 @@ std::vector<uint16_t> build_consensus_tables() {
     return t;
 }
 
-const std::vector<uint16_t> &consensus_tables() {
+}  // namespace
+
+const std::vector<uint16_t> &vq_consensus_tables() {
     static const std::vector<uint16_t> tab = build_consensus_tables();     // (initialised once, also under concurrent calls)
     return tab;
 }
+
+namespace {
+inline const std::vector<uint16_t> &consensus_tables() { return vq_consensus_tables(); }
 
 void check_read(const char *seq, size_t len, const char *qual, size_t qlen, const char *what, size_t k) {
     for (size_t i = 0; i < len; ++i) {
@@ -121,56 +131,11 @@ void check_read(const char *seq, size_t len, const char *qual, size_t qlen, cons
             fail(HLMI_EINVAL, "%s %zu: quality 0x%02x at %zu is outside '!' .. '~'", what, k, (unsigned char)qual[i], i);
 }
 
-// OriginalIndex of a single-end original (Types.h): forward, index1, len1
-struct Orig { bool forward; long index; int len; };
-using Originals = std::map<uint64_t, Orig>;             // ascending original id: the order the lines are written in
-
-// buildOriginalsDict, the branch that reads subreads.txt (OverlapGraph.cpp:799-845): fields split at ':' and ','
-std::map<uint64_t, Originals> read_subreads(const char *path) {
-    std::map<uint64_t, Originals> dict;
-    const std::string data = read_file(path);
-    size_t pos = 0;
-    while (pos < data.size()) {
-        size_t e = data.find('\n', pos);
-        if (e == std::string::npos) e = data.size();
-        const std::string line = data.substr(pos, e - pos);
-        pos = e + 1;
-        if (line.empty()) continue;
-        size_t t = line.find('\t');
-        const uint64_t id = strtoul(line.substr(0, t).c_str(), nullptr, 0);
-        Originals &o = dict[id];
-        while (t != std::string::npos) {
-            const size_t b = t + 1;
-            t = line.find('\t', b);
-            const std::string info = line.substr(b, t == std::string::npos ? std::string::npos : t - b);
-            if (info.empty()) continue;
-            std::vector<std::string> f;
-            size_t s = 0;
-            for (size_t i = 0; i <= info.size(); ++i)
-                if (i == info.size() || info[i] == ':' || info[i] == ',') {
-                    if (i > s) f.push_back(info.substr(s, i - s));          // (token_compress_on)
-                    s = i + 1;
-                }
-            if (f.size() == 6) fail(HLMI_ESTATE, "vq_merge: %s holds a paired-end original (%s); HyLight builds none", path, info.c_str());
-            if (f.size() != 4) fail(HLMI_EINVAL, "vq_merge: %s: bad entry '%s'", path, info.c_str());
-            Orig oi;
-            oi.forward = f[1] == "+";
-            oi.index = strtol(f[2].c_str(), nullptr, 10);
-            oi.len = atoi(f[3].c_str());
-            o.emplace(strtoul(f[0].c_str(), nullptr, 0), oi);               // (insert: the first entry of an id stays)
-        }
-    }
-    return dict;
-}
-
-void subreads_line(std::string &s, uint64_t id, const Originals &o) {
-    s += std::to_string(id);
-    for (const auto &kv : o) {
-        s += '\t'; s += std::to_string(kv.first); s += ':'; s += kv.second.forward ? '+' : '-'; s += ':';
-        s += std::to_string(kv.second.index); s += ':'; s += std::to_string(kv.second.len);
-    }
-    s += '\n';
-}
+// the originals of subreads.txt: vq_clique_host.cpp, shared with the clique step
+using Orig = VqOrig;
+using Originals = VqOriginals;
+std::map<uint64_t, Originals> read_subreads(const char *path) { return vq_parse_subreads(read_file(path), path); }
+inline void subreads_line(std::string &s, uint64_t id, const Originals &o) { vq_subreads_line(s, id, o); }
 
 }  // namespace
 
@@ -311,16 +276,7 @@ static void merge_and_next(const char *fastq, const char *overlaps, const char *
         const uint32_t order[2] = {P.base, P.other};
         for (uint32_t v : order) {
             const long idx1 = v == P.first ? 0 : (long)P.p;
-            const bool forward = g.orient[v] != 0;
-            for (const auto &kv : originals_of(v)) {
-                if (merged.count(kv.first)) continue;
-                Orig oi = kv.second;
-                oi.forward = oi.forward == forward;
-                if (mo.first_it) oi.index = idx1;
-                else if (forward) oi.index += idx1;
-                else oi.index = (long)g.seq[v].size() + idx1 - (oi.len + oi.index);
-                merged.emplace(kv.first, oi);
-            }
+            vq_originals_add(merged, originals_of(v), g.orient[v] != 0, mo.first_it != 0, idx1, (long)g.seq[v].size());
             visited[v] = 1;
             new_id[v] = r.id;
             offset[v] = (uint32_t)idx1;
@@ -350,10 +306,7 @@ static void merge_and_next(const char *fastq, const char *overlaps, const char *
         Originals o = originals_of(v);
         if (!g.orient[v]) {                                                              // :1337-1368: a forward copy of the reverse read
             r.flags = F_REV_A;
-            for (auto &kv : o) {
-                kv.second.forward = !kv.second.forward;
-                kv.second.index = (long)len - (kv.second.index + kv.second.len);
-            }
+            vq_originals_mirror(o, (long)len);
             ++mst->trivial_reverse;
         }
         ++mst->trivial;

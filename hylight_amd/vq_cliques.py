@@ -1,0 +1,70 @@
+"""ViralQuasispecies --cliques=true for single-end reads: the overlap graph of a SAVAGE overlaps
+file, its maximal cliques and one super-read per clique, built by libhylight_mi.so (hlmi_vq_cliques) - the step POLYTE runs in
+the first iteration of every cluster.
+
+    python -m hylight_amd.vq_cliques --singles singles.fastq --overlaps overlaps.txt --out DIR [--error_correction true]
+        [--min_clique_size N] [--edge_threshold X] [--min_overlap_len N] [--keep_singletons N] [--subreads F]
+
+Writes what python -m hylight_amd.vq_graph writes, and cliques.txt (as the reference's enumerator prints it), singles.fastq,
+subreads.txt and clique_map.txt.  The defaults are what POLYTE's run_viralquasispecies passes (polyte.tune_params.py:684-738):
+with --error_correction true remove_trans 2, the back edges kept, keep_singletons 1000; without it remove_trans 1,
+remove_branches true, keep_singletons 0; tips and inclusions stay either way.  POLYTE's --min_qual=0 is not built: minQual
+stays 0.9, so a column whose best base is less than 90 % sure becomes N.  Prints {"graph": ..., "cliques": ...} as one JSON
+line.  Exit status 0 on success, 4 (EXIT_REFUSED) for what vq_graph refuses (a paired-end row among them), 2 (EXIT_INVALID)
+for a malformed input or a --min_clique_size outside 1 .. 21.
+"""
+from __future__ import annotations
+
+import json
+import sys
+
+from . import api
+from .vq_graph import EXIT_REFUSED, _bool, build_parser as graph_parser
+
+EXIT_INVALID = 2
+
+
+def build_parser():
+    p = graph_parser()
+    p.prog = "python -m hylight_amd.vq_cliques"
+    p.description = __doc__.split("\n\n")[0]
+    p.set_defaults(remove_trans=None, remove_branches=None, remove_tips=False, ignore_inclusions=False)
+    p.add_argument("--subreads", default=None, help="subreads.txt of the previous iteration (with --first_it false)")
+    p.add_argument("--first_it", type=_bool, default=True)
+    p.add_argument("--keep_singletons", type=int, default=None, help="default: 1000 with --error_correction true, else 0")
+    p.add_argument("--min_clique_size", type=int, default=2)
+    return p
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    refused = [msg for bad, msg in ((a.add_duplicates, "--add_duplicates true"),
+                                    (not a.resolve_orientations, "--resolve_orientations false"),
+                                    (a.branch_reduction, "--branch_reduction true")) if bad]
+    if refused:
+        sys.stderr.write(f"hylight_amd.vq_cliques: {', '.join(refused)} is not built\n")
+        return EXIT_REFUSED
+    ec = bool(a.error_correction)
+    polyte = api.vq_clique_opts_polyte(ec)
+    try:
+        gst, cst = api.vq_cliques(a.singles, a.overlaps, a.out, subreads_in=a.subreads, min_overlap_len=a.min_overlap_len,
+                                  min_overlap_perc=a.min_overlap_perc, min_read_len=a.min_read_len,
+                                  edge_threshold=a.edge_threshold, ov_threshold=a.ov_threshold, merge_contigs=a.merge_contigs,
+                                  mismatch=a.mismatch, max_tip_len=a.max_tip_len,
+                                  remove_trans=(2 if ec else 1) if a.remove_trans is None else a.remove_trans,
+                                  remove_branches=(not ec) if a.remove_branches is None else a.remove_branches,
+                                  remove_tips=a.remove_tips, ignore_inclusions=a.ignore_inclusions, remove_backedges=not ec,
+                                  max_overlaps=a.max_ov, error_correction=ec, first_it=a.first_it,
+                                  keep_singletons=polyte["keep_singletons"] if a.keep_singletons is None else a.keep_singletons,
+                                  min_clique_size=a.min_clique_size)
+    except api.HlmiError as e:
+        if e.code in (-6, -1):                # HLMI_ESTATE: refused; HLMI_EINVAL: malformed input, min_clique_size
+            sys.stderr.write(f"hylight_amd.vq_cliques: {e}\n")
+            return EXIT_REFUSED if e.code == -6 else EXIT_INVALID
+        raise
+    print(json.dumps({"graph": gst, "cliques": cst}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

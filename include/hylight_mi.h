@@ -154,7 +154,10 @@ int hlmi_sfo2overlaps(const char *in_sfo, const char *out_savage, int num_single
  * parser, the quality-aware overlap score, transitive edges, and the oriented, reduced overlap graph of a --graph_only run
  * (hlmi_vq_graph), and the step that reads it with --cliques=false: SRBuilder::mergeAlongEdges, the super-reads of the next
  * iteration (hlmi_vq_merge), and SRBuilder::findNextOverlaps behind it (hlmi_vq_iteration: one whole stage-b iteration; the
- * loop of pipeline_per_stage.py is hylight_amd/vq_stageb.py).  Not built: cliques, FindNextOverlaps3, BranchReduction. */
+ * loop of pipeline_per_stage.py is hylight_amd/vq_stageb.py), and the step of --cliques=true for single-end reads: the maximal
+ * cliques of graph.txt and SRBuilder::cliquesToSuperreads (hlmi_vq_cliques; cliques.txt is pinned to the reference's own
+ * enumerator).  Not built: findNextOverlaps behind the clique step (a vertex then sits in several super-reads),
+ * FindNextOverlaps3, BranchReduction. */
 typedef struct {
     uint64_t id1, id2;                 /* strtoul(..., 0) of columns 1, 2                        (Overlap.h:39-40, Types.h:99)  */
     uint32_t pos1, pos2, perc1, perc2, len1, len2;   /* atoi; pos2 = perc2 = len2 = 0 when column 4 is "-" (Overlap.h:53-57) */
@@ -316,6 +319,98 @@ typedef struct {
  * returns before this step (ViralQuasispecies.cpp:282-291): so does this call, and none of the four files is written. */
 int hlmi_vq_merge(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
                   const hlmi_vq_merge_opts *mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
+
+/* ---- SRBuilder with --cliques=true --threads 1 on single-end reads (ViralQuasispecies.cpp:397-428: quick-cliques'
+ * `qc --algorithm=degeneracy --input-file=graph.txt > cliques.txt`, then SRBuilder::cliquesToSuperreads, SRBuilder.cpp:
+ * 1031-1235): the step POLYTE runs in the first iteration of every cluster, in its branch-reduction iterations and in the
+ * diploid stage (polyte.tune_params.py:607-645).  It ends where hlmi_vq_merge ends: in front of findNextOverlaps. */
+typedef struct {
+    uint32_t min_clique_size;   /* --min_clique_size: smaller cliques give no super-read; 1 .. 21                           */
+    int error_correction;       /* --error_correction: trim to the columns with min_clique_size reads (:420-473)            */
+    int first_it;               /* as hlmi_vq_merge_opts                                                                    */
+    uint32_t keep_singletons;   /* an unvisited read shorter than this is left out (:1149)                                  */
+} hlmi_vq_clique_opts;
+/* What run_viralquasispecies passes (polyte.tune_params.py:684-738): first_it 1; keep_singletons 1000 with error correction,
+ * else 0; min_clique_size 2, as HyLight calls POLYTE (HyLight.py:228-242).  The matching graph options are the caller's to
+ * set in hlmi_vq_graph_opts: remove_trans 2 with error correction, else 1; remove_branches 1 on the --no_EC first iteration
+ * (cliques with neither error correction nor a haplotype coverage), else 0; remove_backedges 0 with error correction, else 1
+ * (ViralQuasispecies.cpp); remove_tips 0; ignore_inclusions 0; edge_threshold = POLYTE's --edge1.
+ * NOT what POLYTE passes, and not an option of this struct: run_viralquasispecies always adds --min_qual=0 (:737), so the
+ * reference never turns a column into N for disagreement.  hlmi_vq_cliques keeps minQual at SRBuilder's default 0.9: columns
+ * whose best base is less than 90 % sure become N and a super-read can fall to the N rate where POLYTE would keep it.  With
+ * these options the call reproduces ViralQuasispecies at its default --min_qual, not yet a POLYTE call. */
+void hlmi_vq_clique_opts_polyte(hlmi_vq_clique_opts *o, int error_correction);
+typedef struct {
+    uint64_t cliques_read;      /* lines of cliques.txt, its two text lines included (clique_count, :1057)                  */
+    uint64_t singletons;        /* lines with one vertex (:1075)                                                            */
+    uint64_t below_min;         /* lines with 2 .. min_clique_size - 1 vertices                                             */
+    uint64_t taken;             /* cliques of min_clique_size and more: one constructSuperread each (:1078)                 */
+    uint64_t filtered;          /* ... of more than 3 * min_clique_size vertices, cut down by filter_subreads (:721)        */
+    uint64_t superreads;        /* super-reads written                                                                      */
+    uint64_t dropped_empty;     /* cliques whose consensus is empty (:478, :498)                                            */
+    uint64_t dropped_n;         /* ... fails test_N_rate (:999)                                                             */
+    uint64_t dropped_support;   /* ... has no entry number min_clique_size (:427-432)                                       */
+    uint64_t trivial;           /* reads in no kept super-read, written as they are                                         */
+    uint64_t trivial_reverse;   /* ... of them reverse-complemented                                                         */
+    uint64_t short_reads;       /* reads left out: shorter than keep_singletons                                             */
+    uint64_t n_reads;           /* ... too many N                                                                           */
+    uint64_t columns;           /* consensus columns of the cliques whose consensus is not empty                            */
+    uint64_t columns_host;      /* ... of them redone on the host: too close to a threshold for the device's pow / log10    */
+    uint64_t bases_in;          /* bases of singles_fastq                                                                   */
+    uint64_t bytes_out;         /* bytes of the new singles.fastq                                                           */
+    double ms_cliques;          /* wall time of the step after the graph                                                    */
+} hlmi_vq_clique_stats;
+/* The maximal cliques of graph_txt - vertex count, edge-line count, then every edge as "u,v" and "v,u", as hlmi_vq_graph
+ * writes it - into cliques_out, byte for byte what `qc --algorithm=degeneracy --input-file=graph.txt` prints to stdout: its
+ * two text lines ("NOTE: Quick Cliques v2.0beta.", "Reading .edges file format. "), then one clique per line, every vertex
+ * followed by a blank.  The order of the lines and of the vertices in a line are the enumerator's (Eppstein-Loeffler-Strash
+ * over a degeneracy order, quick-cliques/src/DegeneracyAlgorithm.cpp): they decide the id of every new read.  PARITY PINNED:
+ * tests/golden/fxK_*.cliques.txt were printed by the reference's binary.  *n_cliques = the clique lines.  Host code: needs
+ * no GPU.  HLMI_EINVAL: a file that does not hold its counts and that many "u,v" lines, a vertex outside 0 .. n - 1, a loop,
+ * a vertex with n or more edge lines (the reference asserts or indexes out of bounds).  The reference picks another reader
+ * for a file name holding ".graph"; this call always reads the format of graph.txt. */
+int hlmi_vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uint64_t *n_cliques);
+/* hlmi_vq_graph (same code, same files in out_dir) and then the clique step.  subreads_in as for hlmi_vq_merge.  Written into
+ * out_dir:
+ *   cliques.txt     as hlmi_vq_cliques_of_graph writes it for out_dir's graph.txt
+ *   singles.fastq   the super-reads, ids from 0 in the order of their lines in cliques.txt (writeSinglesToFile), then the
+ *                   vertices in no KEPT super-read in ascending order (:1145-1222), reverse ones reverse-complemented
+ *   subreads.txt    as hlmi_vq_merge writes it
+ *   clique_map.txt  the project's own: per super-read "id<TAB>trim_pos" and per member, in the order of sorted_vertices,
+ *                   "<TAB>vertex:offset:+|-" - offset = index1 - startpos1 of calcSubreadInfo (negative for a read that
+ *                   starts in front of trim_pos): what findNextOverlaps reads of a super-read
+ * Rules (constructSuperread :654-870 with the 's' branch only, per line of min_clique_size vertices and more):
+ *   placement    sort_vertices (:33-286): base = the smallest vertex; for every other member in ascending order the edge is
+ *                getEdgeInfo(base, v), its offset +pos1 when the base is the edge's read 1, else -pos1; it goes in front of the
+ *                first list entry whose offset is not smaller (equal offsets: the later member first); offsets shifted to start
+ *                at 0; length = base + largest left + largest right extension; reads reverse-complemented by vertex label
+ *   filtering    more than 3 * min_clique_size members (:721-734, filter_subreads :597-636): the leftmost min_clique_size
+ *                entries, the base, then entries by descending end position until 2 * min_clique_size are chosen, where
+ *                sortVerticesByEndpos is libstdc++'s std::sort over (vertex, end) in list order, compared by end alone -
+ *                ties fall as that algorithm leaves them, and the host calls the same std::sort; the chosen keep list order;
+ *                the originals still see every member
+ *   consensus    (:406-533) read r counts in column c when pos_r <= c < pos_r + len_r.  Without error correction every
+ *                column is written and a column without a read empties the consensus.  With it trim_pos = the offset of entry
+ *                number min_clique_size; the output starts there and stops in front of the first column with fewer than
+ *                min_clique_size reads at which every read has started; the consensus is empty when a column in between has
+ *                no read or when a read that starts in front of trim_pos ends at or before it
+ *   column       consensus_pos (:297-402) as for hlmi_vq_consensus_pair, the scores summed in list order.  One or two bases:
+ *                the tables of hlmi_vq_merge.  More: the sums (of libm's log10 values, plain double adds) are the reference's
+ *                bit for bit and decide the base; the device computes pow, log10 and round itself and hands a column to
+ *                the host's libm when a comparison lies within the margin of DESIGN.md section 4.3f (columns_host), so every
+ *                byte is the reference's arithmetic.  minQual is the default 0.9 as for hlmi_vq_merge
+ *   drops        an empty consensus, test_N_rate; the members stay unvisited unless another kept super-read holds them
+ *   trivial      an unvisited read: left out when shorter than keep_singletons or failing the N rate, else written forward
+ *                or reversed with mirrored originals.  No inclusion or tip rule on this path
+ *   originals    :750-806 over the clique in ascending vertex order, the first vertex holding an original wins; first_it:
+ *                index = offset; else the forward / reverse formulas of hlmi_vq_merge.  Lines in ascending original id
+ * When the graph has no edge the call stops where hlmi_vq_graph stops.  HLMI_ESTATE: a paired-end row, as elsewhere.
+ * HLMI_EINVAL: min_clique_size 0; min_clique_size above 21 (a pile-up then never exceeds 63 reads, which one wave handles);
+ * the reads hlmi_vq_merge refuses.  remove_multi_occ, merge_self_overlap (paired only), --min_qual and threads > 1 are not
+ * options here: the contract is the sequential reference with a clique kept whole.  POLYTE passes --min_qual=0 (never an N
+ * from minQual): that needs tables of their own and is not built. */
+int hlmi_vq_cliques(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                    const hlmi_vq_clique_opts *co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst);
 
 /* ---- SRBuilder::findNextOverlaps with --FNO=1 --optimize=false --cliques=false --error_correction=false --threads 1, to the
  * end of main (FindNextOverlaps.cpp:25-327 updateOverlap, :331-347 findCliqueIndex, :351-565 computeOverlapData - the S-S

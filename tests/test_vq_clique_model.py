@@ -1,0 +1,90 @@
+"""CPU: tests/vq_clique_model.py on cases small enough to work out by hand (the expected values below were, from
+SRBuilder.cpp's text: they are not the model's own output)."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import vq_clique_cases as K  # noqa: E402
+import vq_clique_model as CM  # noqa: E402
+
+
+def _run(tmp_path, name):
+    case = K.CASES[name]()
+    sub = None
+    if "subreads" in case:
+        sub = str(tmp_path / "subreads_in.txt")
+        open(sub, "w").write(case["subreads"])
+    st = CM.superreads(K.state(case), K.clique_text(case), str(tmp_path / "out"), subreads_in=sub, **case["opts"])
+    return st, {n: open(tmp_path / "out" / n).read() for n in CM.OUTPUTS}
+
+
+def test_vote_and_equal_offsets(tmp_path):
+    """Column 2 holds A, A, C at phred 40: score A = 2 log(1 - 1e-4) + log(1e-4 / 3) = -4.4772, C = -8.9543, G = T = -13.43,
+    p_incorrect = 10^-8.9543 / 10^-4.4772 = 3.3e-5, phred 44.77 -> 45 = 'N' as a character.  Three agreeing bases give
+    p_incorrect 3 * 10^-13.43 / 1 < 10^-9.3: phred 93.  Equal offsets: each member goes in FRONT of the entries that are not
+    smaller, so the list is 2, 1, 0."""
+    st, f = _run(tmp_path, "vote")
+    assert f["singles.fastq"] == "@0\nAAAAA\n+\n~~N~~\n"
+    assert f["clique_map.txt"] == "0\t0\t2:0:+\t1:0:+\t0:0:+\n"
+    assert f["subreads.txt"] == "0\t10:+:0:5\t11:+:0:5\t12:+:0:5\n"
+    assert (st["cliques_read"], st["taken"], st["superreads"], st["columns"], st["deep"], st["trivial"]) == (3, 1, 1, 5, 5, 0)
+
+
+def test_error_correction_trims_both_ends(tmp_path):
+    """Offsets 0, 2, 4, ten bases each, min_clique_size 3: trim_pos = 4 (the third entry); columns 4 .. 9 hold three reads,
+    column 10 two while every read has started: the output is genome[4:10]; the originals' indices are offset - 4."""
+    st, f = _run(tmp_path, "ec3")
+    assert f["singles.fastq"] == f"@0\n{K.G[4:10]}\n+\n~~~~~~\n"
+    assert f["subreads.txt"] == "0\t10:+:-4:10\t11:+:-2:10\t12:+:0:10\n"
+    assert f["clique_map.txt"] == "0\t4\t0:-4:+\t1:-2:+\t2:0:+\n"
+    assert st["columns"] == 6 and st["deep"] == 6
+
+
+def test_read_that_ends_before_trim_pos_empties(tmp_path):
+    st, f = _run(tmp_path, "ends_before_trim")
+    assert (st["dropped_empty"], st["superreads"], st["trivial"]) == (1, 0, 3)
+    assert f["singles.fastq"].startswith(f"@0\n{K.G[2:12]}\n+\nIIIIIIIIII\n@1\n{K.G[0:3]}\n+\nIII\n@2\n") and f["clique_map.txt"] == ""
+
+
+def test_six_members_unfiltered_seven_filtered(tmp_path):
+    """min_clique_size 2: six members is not more than 3 * 2, all vote: column 5 holds G, G, T, T, T, G -> no base reaches
+    0.9 -> N.  Seven members are cut to four: the leftmost two (0, 1), the base (0 again), then the largest ends 6 and 5;
+    column 5 then holds G, G (0, 1) and G (5): a G."""
+    st6, f6 = _run(tmp_path / "a", "size6")
+    st7, f7 = _run(tmp_path / "b", "size7")
+    assert (st6["filtered"], st7["filtered"]) == (0, 1)
+    s6, s7 = f6["singles.fastq"].split("\n")[1], f7["singles.fastq"].split("\n")[1]
+    assert len(s6) == 29 and s6[5] == "N" and len(s7) == 30 and s7[5] == "G"          # (one N in 29: below the 5 % of test_N_rate)
+    assert f7["clique_map.txt"].count(":") == 14           # the map and the originals still see all seven
+    assert f7["subreads.txt"].count(":+:") == 7
+
+
+def test_reverse_member(tmp_path):
+    st, f = _run(tmp_path, "reverse")
+    assert f["singles.fastq"].split("\n")[1] == K.G[0:13]
+    assert f["subreads.txt"] == "0\t10:+:0:10\t11:-:3:10\n" and f["clique_map.txt"] == "0\t0\t0:0:+\t1:3:-\n"
+
+
+def test_n_rate_drop_gives_the_reads_back(tmp_path):
+    """Five of ten columns hold A against C at equal quality: N; 5 >= 0.05 * 10."""
+    st, f = _run(tmp_path, "n_rate")
+    assert (st["dropped_n"], st["superreads"], st["trivial"], st["columns"]) == (1, 0, 2, 10)
+    assert f["singles.fastq"] == "@0\nAAAAAAAAAA\n+\nIIIIIIIIII\n@1\nAAAAACCCCC\n+\nIIIIIIIIII\n"
+    assert f["subreads.txt"] == "0\t10:+:0:10\n1\t11:+:0:10\n"
+
+
+def test_not_first_iteration_forward_and_reverse(tmp_path):
+    """Read 10 (forward, offset 0) holds original 100 forward at 3: 3 + 0.  Read 11 (reverse, offset 2, ten bases) holds
+    original 101 reverse at 2 with length 4: orientation ('-' == reverse label) -> '+', index 10 + 2 - (4 + 2) = 6."""
+    st, f = _run(tmp_path, "not_first")
+    assert f["subreads.txt"] == "0\t100:+:3:5\t101:+:6:4\n"
+
+
+def test_std_sort_is_libstdcxx_on_ties():
+    """Up to 16 elements std::sort is an insertion sort (stable); above, the partition moves equal keys."""
+    a = [(k, 0) for k in range(16)]
+    CM.std_sort(a, lambda x, y: x[1] < y[1])
+    assert a == [(k, 0) for k in range(16)]
+    b = [(k, k % 3) for k in range(40)]
+    CM.std_sort(b, lambda x, y: x[1] < y[1])
+    assert [x[1] for x in b] == sorted(k % 3 for k in range(40)) and sorted(b) == [(k, k % 3) for k in range(40)]
