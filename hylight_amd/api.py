@@ -355,6 +355,19 @@ def vq_transitive_edges(n_vertices, src, dst, ovlen=None, remove_trans=1):
     return list(flags[:n]), cnt.value
 
 
+def _set_opts(caller, structs, opts):
+    """Each keyword goes into the first of the option structs that has a field of its name (a bool as an int)."""
+    for k, v in opts.items():
+        target = next((t for t in structs if k in dict(type(t)._fields_)), None)
+        if target is None:
+            raise TypeError(f"{caller}: unknown option {k!r}")
+        setattr(target, k, int(v) if isinstance(v, bool) else v)
+
+
+def _stats(st, names):
+    return {k: getattr(st, k) for k in names}
+
+
 def vq_graph_opts_stageb():
     """hlmi_vq_graph_opts_stageb: the options of HyLight's first stage-b iteration, as a dict."""
     o = VqGraphOpts()
@@ -368,14 +381,11 @@ def vq_graph(singles_fastq, overlaps, out_dir, **opts):
     stage-b values by default.  -> dict of the stats (hlmi_vq_graph_stats)."""
     o = VqGraphOpts()
     load().hlmi_vq_graph_opts_stageb(C.byref(o))
-    for k, v in opts.items():
-        if k not in dict(VqGraphOpts._fields_):
-            raise TypeError(f"vq_graph: unknown option {k!r}")
-        setattr(o, k, int(v) if isinstance(v, bool) else v)
+    _set_opts("vq_graph", (o,), opts)
     os.makedirs(out_dir, exist_ok=True)
     st = VqGraphStats()
     _check(load().hlmi_vq_graph(_b(singles_fastq), _b(overlaps), C.byref(o), _b(out_dir), C.byref(st)))
-    return {k: getattr(st, k) for k in VQ_GRAPH_STATS}
+    return _stats(st, VQ_GRAPH_STATS)
 
 
 def vq_merge_opts_stageb():
@@ -393,17 +403,12 @@ def vq_merge(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
     go, mo = VqGraphOpts(), VqMergeOpts()
     load().hlmi_vq_graph_opts_stageb(C.byref(go))
     load().hlmi_vq_merge_opts_stageb(C.byref(mo))
-    for k, v in opts.items():
-        target = go if k in dict(VqGraphOpts._fields_) else mo if k in dict(VqMergeOpts._fields_) else None
-        if target is None:
-            raise TypeError(f"vq_merge: unknown option {k!r}")
-        setattr(target, k, int(v) if isinstance(v, bool) else v)
+    _set_opts("vq_merge", (go, mo), opts)
     os.makedirs(out_dir, exist_ok=True)
     gst, mst = VqGraphStats(), VqMergeStats()
     _check(load().hlmi_vq_merge(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
                                 C.byref(go), C.byref(mo), _b(out_dir), C.byref(gst), C.byref(mst)))
-    return ({k: getattr(gst, k) for k in VQ_GRAPH_STATS},
-            {k: getattr(mst, k) for k in VQ_MERGE_STATS + VQ_MERGE_MS})
+    return _stats(gst, VQ_GRAPH_STATS), _stats(mst, VQ_MERGE_STATS + VQ_MERGE_MS)
 
 
 def vq_clique_opts_polyte(error_correction=False):
@@ -430,17 +435,12 @@ def vq_cliques(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
     go, co = VqGraphOpts(), VqCliqueOpts()
     load().hlmi_vq_graph_opts_stageb(C.byref(go))
     load().hlmi_vq_clique_opts_polyte(C.byref(co), int(bool(opts.get("error_correction", False))))
-    for k, v in opts.items():
-        target = go if k in dict(VqGraphOpts._fields_) else co if k in dict(VqCliqueOpts._fields_) else None
-        if target is None:
-            raise TypeError(f"vq_cliques: unknown option {k!r}")
-        setattr(target, k, int(v) if isinstance(v, bool) else v)
+    _set_opts("vq_cliques", (go, co), opts)
     os.makedirs(out_dir, exist_ok=True)
     gst, cst = VqGraphStats(), VqCliqueStats()
     _check(load().hlmi_vq_cliques(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
                                   C.byref(go), C.byref(co), _b(out_dir), C.byref(gst), C.byref(cst)))
-    return ({k: getattr(gst, k) for k in VQ_GRAPH_STATS},
-            {k: getattr(cst, k) for k in VQ_CLIQUE_STATS + VQ_CLIQUE_MS})
+    return _stats(gst, VQ_GRAPH_STATS), _stats(cst, VQ_CLIQUE_STATS + VQ_CLIQUE_MS)
 
 
 def vq_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
@@ -452,17 +452,12 @@ def vq_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
     load().hlmi_vq_graph_opts_stageb(C.byref(go))
     load().hlmi_vq_merge_opts_stageb(C.byref(mo))
     load().hlmi_vq_next_opts_stageb(C.byref(no))
-    for k, v in opts.items():
-        target = next((t for t in (go, mo, no) if k in dict(type(t)._fields_)), None)
-        if target is None:
-            raise TypeError(f"vq_iteration: unknown option {k!r}")
-        setattr(target, k, int(v) if isinstance(v, bool) else v)
+    _set_opts("vq_iteration", (go, mo, no), opts)
     os.makedirs(out_dir, exist_ok=True)
     gst, mst, nst = VqGraphStats(), VqMergeStats(), VqNextStats()
     _check(load().hlmi_vq_iteration(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
                                     C.byref(go), C.byref(mo), C.byref(no), _b(out_dir), C.byref(gst), C.byref(mst), C.byref(nst)))
-    return ({k: getattr(gst, k) for k in VQ_GRAPH_STATS}, {k: getattr(mst, k) for k in VQ_MERGE_STATS + VQ_MERGE_MS},
-            {k: getattr(nst, k) for k in VQ_NEXT_STATS + VQ_NEXT_MS})
+    return _stats(gst, VQ_GRAPH_STATS), _stats(mst, VQ_MERGE_STATS + VQ_MERGE_MS), _stats(nst, VQ_NEXT_STATS + VQ_NEXT_MS)
 
 
 def vq_consensus_pair(seq1, qual1, seq2, qual2, pos):

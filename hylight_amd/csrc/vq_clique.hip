@@ -7,14 +7,13 @@
 //                 pow / log10 with a margin (vqc::MARGIN) inside which the column goes back to the host.  The
 //                 end of the trimmed output - the first column with too little support once every read has started - is the
 //                 first set bit of the wave's ballot, and the tile loop ends there.
-// The host part below places the reads (sort_vertices :33-286, filter_subreads :597-636 with the same std::sort), decides
-// the drops, keeps the originals and writes the files.  Every loop on the device has an explicit bound.
+// VqMergeDev::consensus_piles checks the pile-ups' bounds and launches it; vq_cliques_run (vq_superread_run.cpp) places the
+// reads, decides the drops and writes the files.  Every loop on the device has an explicit bound.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "common.h"
-#include "paf_io.h"
 #include "vq_internal.h"
 
 namespace hlmi {
@@ -22,15 +21,9 @@ namespace vqc {
 namespace {
 
 using vqm::NQ;                                   // the consensus tables of vq_merge.hip
+using vqm::base_code; using vqm::complement;
 using vqm::T_ALL; using vqm::T_SINGLE; using vqm::T_WITH_N; using vqm::T_SAME; using vqm::T_DIFF;
 constexpr int WAVES = WG / WAVE;
-
-__device__ __forceinline__ uint32_t base_code(uint8_t c) {      // A C G T N -> 0 .. 4 (the host refuses anything else)
-    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
-}
-__device__ __forceinline__ uint8_t complement(uint8_t c) {      // Read::build_rev_comp: N stays N
-    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
-}
 
 // consensus_pos (:351-401) behind the sums, for a column of three bases and more -> (base << 8) | quality, 0: the host decides
 __device__ __forceinline__ uint32_t decide(double sA, double sC, double sG, double sT, double min_qual, double p93) {
@@ -196,242 +189,6 @@ void VqMergeDev::consensus_piles(const std::vector<Pile> &piles, const std::vect
     bases = d_b.download();
     quals = d_q.download();
     res = d_res.download();
-}
-
-void vq_clique_opts_polyte(hlmi_vq_clique_opts *o, int error_correction) {
-    *o = hlmi_vq_clique_opts{};
-    o->min_clique_size = 2;                      // HyLight.py:228-242
-    o->error_correction = error_correction != 0;
-    o->first_it = 1;
-    o->keep_singletons = error_correction ? 1000 : 0;        // polyte.tune_params.py:689-696
-}
-
-void vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uint64_t *n_cliques) {
-    const VqCliqueList list = vq_enumerate_cliques(read_file(graph_txt));
-    write_file(cliques_out, list.text.data(), list.text.size());
-    *n_cliques = list.off.size() - 1;
-}
-
-void vq_cliques_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                    const hlmi_vq_clique_opts &co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst) {
-    *cst = hlmi_vq_clique_stats{};
-    if (co.min_clique_size == 0 || co.min_clique_size > MAX_MIN_CLIQUE)
-        fail(HLMI_EINVAL, "vq_cliques: min_clique_size %u is outside 1 .. %u", co.min_clique_size, MAX_MIN_CLIQUE);
-    if (!co.first_it && !subreads_in) fail(HLMI_EINVAL, "vq_cliques: first_it is off and there is no subreads file");
-    const uint32_t mcs = co.min_clique_size;
-    VqGraphState g;
-    vq_graph_run(fastq, overlaps, go, out_dir, gst, &g, false);
-    if (!g.built) return;                        // ViralQuasispecies.cpp:282-291: nothing to be done
-    const double t0 = now_ms();
-    const uint32_t V = (uint32_t)g.seq.size();
-    for (uint32_t v = 0; v < V; ++v) cst->bases_in += g.seq[v].size();
-    std::map<uint64_t, VqOriginals> dict;
-    if (!co.first_it) dict = vq_parse_subreads(read_file(subreads_in), subreads_in);
-    auto originals_of = [&](uint32_t v) -> VqOriginals {
-        if (co.first_it) return VqOriginals{{g.id[v], VqOrig{true, 0, (int)g.seq[v].size()}}};
-        auto it = dict.find(g.id[v]);
-        if (it == dict.end() || it->second.empty())
-            fail(HLMI_EINVAL, "vq_cliques: read %llu has no line in %s", (unsigned long long)g.id[v], subreads_in);
-        return it->second;
-    };
-
-    // cliques.txt (ViralQuasispecies.cpp:400-410)
-    const VqCliqueList list = vq_enumerate_cliques(read_file(join_path(out_dir, "graph.txt").c_str()));
-    write_file(join_path(out_dir, "cliques.txt"), list.text.data(), list.text.size());
-    const double t_enumerated = now_ms();
-    const size_t n_lines = list.off.size() - 1;
-    cst->cliques_read = n_lines + 2;             // getline counts the two text lines as well (:1056-1057)
-
-    // getEdgeInfo (OverlapGraph.cpp:263-282): the first u -> v of u's list
-    auto edge_of = [&](uint32_t u, uint32_t v) -> const VqEdge * {
-        for (const VqEdge &e : g.out[u])
-            if (e.v2 == v) return &e;
-        return nullptr;
-    };
-
-    // constructSuperread per clique: the placement
-    struct Placed {
-        std::vector<uint32_t> clique;            // ascending
-        std::vector<std::pair<int64_t, uint32_t>> all;       // (offset, vertex) in list order, every member
-        uint32_t pile;                           // its pile-up
-    };
-    std::vector<Placed> placed;
-    std::vector<Pile> piles;
-    std::vector<Entry> entries;
-    uint64_t cols = 0;
-    for (size_t k = 0; k < n_lines; ++k) {
-        const size_t size = (size_t)(list.off[k + 1] - list.off[k]);
-        if (size == 1) { ++cst->singletons; continue; }
-        if (size < mcs) { ++cst->below_min; continue; }
-        ++cst->taken;
-        Placed P;
-        P.clique.assign(list.members.begin() + (ptrdiff_t)list.off[k], list.members.begin() + (ptrdiff_t)list.off[k + 1]);
-        for (uint32_t v : P.clique)
-            if (v >= V) fail(HLMI_EINVAL, "vq_cliques: clique vertex %u of %u", v, V);
-        std::sort(P.clique.begin(), P.clique.end());                       // :658
-        const uint32_t base = P.clique[0];       // single-end reads: the first one is the base (:670-679)
-        const int64_t base_len = (int64_t)g.seq[base].size();
-        int64_t l_ext = 0, r_ext = 0;
-        P.all.emplace_back(0, base);
-        for (uint32_t v : P.clique) {
-            if (v == base) continue;
-            const VqEdge *found = edge_of(base, v);
-            if (!found) found = edge_of(v, base);
-            if (!found) fail(HLMI_EINVAL, "vq_cliques: no edge between %u and %u", base, v);
-            const VqEdge &e = *found;
-            const int64_t new_pos = e.v1 == base ? (int64_t)e.pos1 : -(int64_t)e.pos1;     // :142-147
-            size_t at = 0;                       // in front of the first entry that is not smaller (:212-222)
-            while (at < P.all.size() && P.all[at].first < new_pos) ++at;
-            P.all.insert(P.all.begin() + (ptrdiff_t)at, std::make_pair(new_pos, v));
-            l_ext = std::max(l_ext, -new_pos);                             // :236-240
-            r_ext = std::max(r_ext, (int64_t)g.seq[v].size() + new_pos - base_len);
-        }
-        const int64_t total = base_len + l_ext + r_ext;
-        if (total >= (1 << 30)) fail(HLMI_EINVAL, "vq_cliques: a super-read of %lld bases", (long long)total);
-        const int64_t shift = P.all[0].first < 0 ? -P.all[0].first : 0;    // :248-252
-        for (auto &pv : P.all) pv.first += shift;
-        // filter_subreads (:597-636) when the clique is large (:721)
-        std::vector<std::pair<int64_t, uint32_t>> used = P.all;
-        if (size > 3 * (size_t)mcs) {
-            ++cst->filtered;
-            const size_t num = 2 * (size_t)mcs;
-            std::unordered_map<uint32_t, bool> sel;
-            for (size_t i = 0; i < num / 2; ++i) sel[P.all[i].second] = true;
-            sel[base] = true;
-            std::vector<std::pair<uint32_t, int>> by_end;                  // sortVerticesByEndpos (:639-652): the same std::sort
-            for (const auto &pv : P.all) by_end.emplace_back(pv.second, (int)(pv.first + (int64_t)g.seq[pv.second].size()));
-            std::sort(by_end.begin(), by_end.end(), [](const std::pair<uint32_t, int> &a, const std::pair<uint32_t, int> &b) { return a.second < b.second; });
-            for (size_t i = by_end.size(); i > 0 && sel.size() < num; --i) sel[by_end[i - 1].first] = true;
-            used.clear();
-            for (const auto &pv : P.all) if (sel.count(pv.second)) used.push_back(pv);
-        }
-        // consensus (:420-446): where the output starts; a read in front of it that ends there empties it (:478)
-        uint32_t trim = 0;
-        bool empty = false;
-        if (co.error_correction) {
-            // :427-432 drops a pile without an entry number min_clique_size.  A clique taken here has min_clique_size
-            // members and a filtered one 2 * min_clique_size, so the check never fires; it stays as the reference has it.
-            if (used.size() < mcs) { ++cst->dropped_support; continue; }
-            trim = (uint32_t)used[mcs - 1].first;
-            for (const auto &pv : used)
-                if (pv.first < (int64_t)trim && pv.first + (int64_t)g.seq[pv.second].size() <= (int64_t)trim) empty = true;
-        }
-        if (empty || trim >= total) { ++cst->dropped_empty; continue; }
-        if (used.size() > MAX_PILE) fail(HLMI_EINVAL, "vq_cliques: a pile-up of %zu reads", used.size());
-        Pile pl{};
-        pl.first = (uint32_t)entries.size(); pl.n = (uint32_t)used.size();
-        pl.total_len = (uint32_t)total; pl.trim_pos = trim; pl.col0 = cols;
-        for (const auto &pv : used) entries.push_back(Entry{pv.second, (uint32_t)pv.first, g.orient[pv.second] ? 0u : 1u});
-        cols += (uint64_t)total;
-        P.pile = (uint32_t)piles.size();
-        piles.push_back(pl);
-        placed.push_back(std::move(P));
-    }
-
-    const double t_placed = now_ms();
-    VqMergeDev dev(g.seq, g.qual, vq_consensus_tables());
-    std::vector<uint8_t> cb, cq;
-    std::vector<Result> res;
-    dev.consensus_piles(piles, entries, mcs, co.error_correction != 0, cb, cq, res);
-    const double t_device = now_ms();
-
-    // process_cliques (:998-1001), writeSinglesToFile, the originals (:750-806)
-    auto n_rate_ok = [](uint64_t n, uint64_t len) { return (double)n < 0.05 * (double)len; };       // Read.h:214-233
-    std::string fastq_text, subreads, cmap;
-    std::vector<uint8_t> visited(V, 0);
-    uint32_t count = 0;
-    std::vector<char> nuc(MAX_PILE);
-    std::vector<int> phred(MAX_PILE);
-    for (const Placed &P : placed) {
-        const Pile &pl = piles[P.pile];
-        const Result &r = res[P.pile];
-        if (r.empty || r.stop <= pl.trim_pos || r.stop > pl.total_len) {
-            if (!r.empty && r.stop > pl.total_len) fail(HLMI_EINVAL, "vq_cliques: the device ended a consensus at %u of %u", r.stop, pl.total_len);
-            ++cst->dropped_empty;
-            continue;
-        }
-        const uint32_t len = r.stop - pl.trim_pos;
-        uint8_t *b = cb.data() + pl.col0 + pl.trim_pos, *q = cq.data() + pl.col0 + pl.trim_pos;
-        uint64_t n_count = 0;
-        for (uint32_t x = 0; x < len; ++x) {
-            if (q[x] == 0) {                     // too close to a threshold for the device: the host's libm decides
-                const uint32_t c = pl.trim_pos + x;
-                int n = 0;
-                for (uint32_t k = 0; k < pl.n; ++k) {
-                    const Entry &e = entries[pl.first + k];
-                    const std::string &s = g.seq[e.read], &ql = g.qual[e.read];
-                    if (c < e.pos || c - e.pos >= s.size()) continue;
-                    const size_t i = c - e.pos;
-                    char ch = e.rev ? s[s.size() - 1 - i] : s[i];
-                    if (e.rev) ch = ch == 'A' ? 'T' : ch == 'T' ? 'A' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch;
-                    nuc[(size_t)n] = ch;
-                    phred[(size_t)n++] = (e.rev ? ql[s.size() - 1 - i] : ql[i]) - 33;
-                }
-                const uint16_t e = vq_consensus_pos(nuc.data(), phred.data(), n);
-                b[x] = (uint8_t)(e >> 8);
-                q[x] = (uint8_t)e;
-                ++cst->columns_host;
-            }
-            n_count += b[x] == 'N';
-        }
-        cst->columns += len;
-        if (!n_rate_ok(n_count, len)) { ++cst->dropped_n; continue; }
-        fastq_text += '@'; fastq_text += std::to_string(count); fastq_text += '\n';
-        fastq_text.append((const char *)b, len); fastq_text += "\n+\n";
-        fastq_text.append((const char *)q, len); fastq_text += '\n';
-        std::unordered_map<uint32_t, int64_t> offset;        // calcSubreadInfo (:536-595): index1 - startpos1 = offset - trim_pos
-        for (const auto &pv : P.all) offset.emplace(pv.second, pv.first - (int64_t)pl.trim_pos);
-        VqOriginals merged;
-        for (uint32_t v : P.clique) {
-            vq_originals_add(merged, originals_of(v), g.orient[v] != 0, co.first_it != 0, (long)offset.at(v), (long)g.seq[v].size());
-            visited[v] = 1;
-        }
-        vq_subreads_line(subreads, count, merged);
-        cmap += std::to_string(count); cmap += '\t'; cmap += std::to_string(pl.trim_pos);
-        for (const auto &pv : P.all) {
-            cmap += '\t'; cmap += std::to_string(pv.second); cmap += ':'; cmap += std::to_string(pv.first - (int64_t)pl.trim_pos);
-            cmap += ':'; cmap += g.orient[pv.second] ? '+' : '-';
-        }
-        cmap += '\n';
-        ++count;
-    }
-    cst->superreads = count;
-
-    // the reads in no kept super-read (:1145-1222)
-    const std::vector<uint32_t> read_n = dev.read_n_counts();
-    std::vector<vqm::Rec> recs;
-    for (uint32_t v = 0; v < V; ++v) {
-        if (visited[v]) continue;
-        const uint32_t len = (uint32_t)g.seq[v].size();
-        if (len < co.keep_singletons) { ++cst->short_reads; continue; }                  // :1149
-        if (!n_rate_ok(read_n[v], len)) { ++cst->n_reads; continue; }                    // :1155
-        vqm::Rec r{};
-        r.a = v; r.b = vqm::NONE; r.len = len; r.id = count;
-        VqOriginals o = originals_of(v);
-        if (!g.orient[v]) {                      // :1186-1217: a forward copy of the reverse read
-            r.flags = vqm::F_REV_A;
-            vq_originals_mirror(o, (long)len);
-            ++cst->trivial_reverse;
-        }
-        ++cst->trivial;
-        vq_subreads_line(subreads, count, o);
-        recs.push_back(r);
-        ++count;
-    }
-    std::vector<uint64_t> start;
-    fastq_text += dev.write(recs, start);
-    cst->bytes_out = fastq_text.size();
-    write_file(join_path(out_dir, "singles.fastq"), fastq_text.data(), fastq_text.size());         // (the reference removes it first, :1038)
-    write_file(join_path(out_dir, "subreads.txt"), subreads.data(), subreads.size());
-    write_file(join_path(out_dir, "clique_map.txt"), cmap.data(), cmap.size());
-    cst->ms_cliques = now_ms() - t0;
-    ktimer_flush();
-    // the phases of ms_cliques for tools/vq_cliques_time.py: enumerator, placement, device (uploads, kernel, downloads), the rest
-    stat_set("vq_clique_ms_enumerate", t_enumerated - t0);
-    stat_set("vq_clique_ms_place", t_placed - t_enumerated);
-    stat_set("vq_clique_ms_device", t_device - t_placed);
-    stat_set("vq_clique_ms_finish", t0 + cst->ms_cliques - t_device);
-    stat_set("vq_clique_piles", (double)piles.size());
 }
 
 }  // namespace hlmi

@@ -1,7 +1,7 @@
 // vq_clique_host.cpp - the order-dependent host half of ViralQuasispecies --cliques=true (tools/HaploConduct/src,
-// ViralQuasispecies.cpp:397-428): the maximal cliques of graph.txt in the order the reference's enumerator lists them, and
-// the originals bookkeeping of subreads.txt that the clique step shares with the merge step.  Pure host code: nothing here
-// touches the device, and nothing here depends on the rest of the library but common.h's fail().
+// ViralQuasispecies.cpp:397-428): the maximal cliques of graph.txt in the order the reference's enumerator lists them - the
+// reader, the listing, vq_enumerate_cliques - and nothing else.  Pure host code: nothing here touches the device, and nothing
+// here depends on the rest of the library but common.h's fail().
 //
 // Why the enumeration is not a kernel: the order of the lines of cliques.txt decides the id of every new read, and that
 // order is a product of the enumerator's data movement - a backtracking search over one array of vertices that is permuted
@@ -283,71 +283,6 @@ VqCliqueList vq_enumerate_cliques(const std::string &graph_text) {
     out.off.push_back(0);
     Lister(adj).run(out);
     return out;
-}
-
-// ---- originals ---------------------------------------------------------------------------------------------------------------
-std::map<uint64_t, VqOriginals> vq_parse_subreads(const std::string &data, const char *path) {
-    std::map<uint64_t, VqOriginals> dict;
-    size_t pos = 0;
-    while (pos < data.size()) {
-        size_t e = data.find('\n', pos);
-        if (e == std::string::npos) e = data.size();
-        const std::string line = data.substr(pos, e - pos);
-        pos = e + 1;
-        if (line.empty()) continue;
-        size_t t = line.find('\t');
-        const uint64_t id = strtoul(line.substr(0, t).c_str(), nullptr, 0);
-        VqOriginals &o = dict[id];
-        while (t != std::string::npos) {
-            const size_t b = t + 1;
-            t = line.find('\t', b);
-            const std::string info = line.substr(b, t == std::string::npos ? std::string::npos : t - b);
-            if (info.empty()) continue;
-            std::vector<std::string> f;
-            size_t s = 0;
-            for (size_t i = 0; i <= info.size(); ++i)
-                if (i == info.size() || info[i] == ':' || info[i] == ',') {
-                    if (i > s) f.push_back(info.substr(s, i - s));          // (token_compress_on)
-                    s = i + 1;
-                }
-            if (f.size() == 6) fail(HLMI_ESTATE, "vq_merge: %s holds a paired-end original (%s); HyLight builds none", path, info.c_str());
-            if (f.size() != 4) fail(HLMI_EINVAL, "vq_merge: %s: bad entry '%s'", path, info.c_str());
-            VqOrig oi;
-            oi.forward = f[1] == "+";
-            oi.index = strtol(f[2].c_str(), nullptr, 10);
-            oi.len = atoi(f[3].c_str());
-            o.emplace(strtoul(f[0].c_str(), nullptr, 0), oi);               // (insert: the first entry of an id stays)
-        }
-    }
-    return dict;
-}
-
-void vq_subreads_line(std::string &s, uint64_t id, const VqOriginals &o) {
-    s += std::to_string(id);
-    for (const auto &kv : o) {
-        s += '\t'; s += std::to_string(kv.first); s += ':'; s += kv.second.forward ? '+' : '-'; s += ':';
-        s += std::to_string(kv.second.index); s += ':'; s += std::to_string(kv.second.len);
-    }
-    s += '\n';
-}
-
-void vq_originals_add(VqOriginals &merged, const VqOriginals &of_read, bool forward, bool first_it, long idx1, long read_len) {
-    for (const auto &kv : of_read) {
-        if (merged.count(kv.first)) continue;                              // already inserted by another vertex (:762-764)
-        VqOrig oi = kv.second;
-        oi.forward = oi.forward == forward;
-        if (first_it) oi.index = idx1;
-        else if (forward) oi.index += idx1;
-        else oi.index = read_len + idx1 - (oi.len + oi.index);
-        merged.emplace(kv.first, oi);
-    }
-}
-
-void vq_originals_mirror(VqOriginals &o, long read_len) {
-    for (auto &kv : o) {
-        kv.second.forward = !kv.second.forward;
-        kv.second.index = read_len - (kv.second.index + kv.second.len);
-    }
 }
 
 }  // namespace hlmi

@@ -621,7 +621,7 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
         write_file(join_path(out_dir, "tips.txt"), s.data(), s.size());
     }
     st->edges_final = g.edge_count();
-    if (keep) {                                           // what SRBuilder reads (vq_merge_host.cpp)
+    if (keep) {                                           // what SRBuilder reads (vq_superread_run.cpp)
         sort_edges(g);                                    // ViralQuasispecies.cpp:434, in front of mergeAlongEdges
         keep->built = true;
         keep->out.resize(g.V);

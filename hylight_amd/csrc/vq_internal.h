@@ -3,7 +3,9 @@
 //   front  vq_front.hip                          the two input files (singles.fastq, the 13-column overlaps), the overlap
 //                                                score, and the rounds of findTransEdges (GraphAlgos.cpp:746-795)
 //   graph  vq_graph.hip / vq_graph_host.cpp      the oriented, reduced overlap graph (ViralQuasispecies --graph_only)
-//   merge  vq_merge.hip / vq_merge_host.cpp      super-reads along its edges (SRBuilder::mergeAlongEdges)
+//   merge  vq_merge.hip                          super-reads along its edges (SRBuilder::mergeAlongEdges)
+//   cliques  vq_clique_host.cpp / vq_clique.hip  the maximal cliques of the graph, one pile-up consensus each (--cliques=true)
+//   superread  vq_superread.cpp / .._run.cpp     what the two share through constructSuperread (pure host) / their drivers
 //   next   vq_next.hip                           the overlaps of the next iteration (SRBuilder::findNextOverlaps)
 // Everything on the device runs on the library's stream.
 #pragma once
@@ -187,7 +189,7 @@ struct VqGraphState {
 void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st,
                   VqGraphState *keep = nullptr, bool for_next = false);
 
-// ---- merge: vq_merge.hip / vq_merge_host.cpp (SRBuilder::mergeAlongEdges) -------------------------------------------------
+// ---- merge: vq_merge.hip (SRBuilder::mergeAlongEdges on the device; its driver is in vq_superread_run.cpp) -----------------
 namespace vqm {
 constexpr int WG = 256;
 constexpr int WAVE = 64;
@@ -210,10 +212,16 @@ struct Rec {                                     // one FASTQ record of the outp
     uint32_t p, len;                             // len = output bases
     uint32_t flags, id;                          // F_*; id = the number after '@'
 };
+__device__ __forceinline__ uint32_t base_code(uint8_t c) {      // A C G T N -> 0 .. 4 (the host refuses anything else)
+    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
+}
+__device__ __forceinline__ uint8_t complement(uint8_t c) {      // Read::build_rev_comp: N stays N
+    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
+}
 }  // namespace vqm
 
 namespace vqc { struct Pile; struct Entry; struct Result; }
-// The device side of a merge over resident reads: bases / quals concatenated, read r at [off[r], off[r + 1]).
+// The device side of a merge over resident reads (vq_merge.hip): bases / quals concatenated, read r at [off[r], off[r + 1]).
 class VqMergeDev {
 public:
     VqMergeDev(const std::vector<std::string> &seq, const std::vector<std::string> &qual, const std::vector<uint16_t> &tables);
@@ -234,35 +242,7 @@ private:
     size_t n_reads_;
 };
 
-// what hlmi_vq_merge refuses in a read (HLMI_EINVAL): a base outside A C G T N, a quality outside '!' .. '~', a quality line
-// of another length than the sequence
-void vq_merge_check_reads(const std::vector<std::string> &seq, const std::vector<std::string> &qual);
-// vq_merge_host.cpp: hlmi_vq_merge_opts_stageb / hlmi_vq_merge / hlmi_vq_consensus_pair (include/hylight_mi.h)
-void vq_merge_opts_stageb(hlmi_vq_merge_opts *o);
-void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                  const hlmi_vq_merge_opts &mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
-void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2, const char *qual2,
-                       uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual, uint32_t *out_len);
-
-// SRBuilder::consensus_pos (:297-402) of n >= 1 nucleotides (A C G T N) with their phreds, in the reference's expression order
-// with the host's libm -> (base << 8) | quality character
-uint16_t vq_consensus_pos(const char *nuc, const int *phred, int n);
-const std::vector<uint16_t> &vq_consensus_tables();            // the vqm::T_* tables, built once
-
-// ---- originals: vq_clique_host.cpp (what subreads.txt holds; shared by the merge and the clique step) ---------------------
-// OriginalIndex of a single-end original (Types.h): forward, index1, len1
-struct VqOrig { bool forward; long index; int len; };
-using VqOriginals = std::map<uint64_t, VqOrig>;                // ascending original id: the order the lines are written in
-// buildOriginalsDict, the branch that reads subreads.txt (OverlapGraph.cpp:799-845), over the file's text
-std::map<uint64_t, VqOriginals> vq_parse_subreads(const std::string &data, const char *path);
-void vq_subreads_line(std::string &s, uint64_t id, const VqOriginals &o);
-// constructSuperread :750-806 for one member of a super-read: its originals go into `merged` unless already there.  forward =
-// the vertex label, idx1 = index1 - startpos1 of calcSubreadInfo (the read's offset minus trim_pos), read_len = |read|
-void vq_originals_add(VqOriginals &merged, const VqOriginals &of_read, bool forward, bool first_it, long idx1, long read_len);
-// a reverse read written forward (:1204-1216): orientation flipped, index mirrored
-void vq_originals_mirror(VqOriginals &o, long read_len);
-
-// ---- cliques: vq_clique_host.cpp / vq_clique.hip (ViralQuasispecies --cliques=true, SRBuilder::cliquesToSuperreads) ---------
+// ---- cliques: vq_clique_host.cpp (the enumerator) / vq_clique.hip (the pile-up kernel; ViralQuasispecies --cliques=true) -----
 // The maximal cliques of a graph.txt image (n, m, then m lines "u,v") in the order and with the vertex order quick-cliques'
 // degeneracy algorithm lists them: `text` = what `qc --algorithm=degeneracy` prints, cliques = the vertices, clique k at
 // [off[k], off[k + 1]).  Pure host code.
@@ -292,6 +272,62 @@ struct Pile {                                    // one clique's pile-up
 struct Entry { uint32_t read, pos, rev; };      // read `read` (reverse-complemented when rev) from column pos on
 struct Result { uint32_t stop, empty; };         // columns [trim_pos, stop) are the consensus; empty: a column without a read
 }  // namespace vqc
+
+// ---- superread: vq_superread.cpp (what mergeAlongEdges and cliquesToSuperreads share; pure host, no file is touched) --------
+// refused in a read (HLMI_EINVAL): a base outside A C G T N, a quality outside '!' .. '~', a quality line of another length
+void vq_check_read(const char *seq, size_t len, const char *qual, size_t qlen, const char *what, size_t k);
+void vq_merge_check_reads(const std::vector<std::string> &seq, const std::vector<std::string> &qual);
+// SRBuilder::consensus_pos (:297-402) of n >= 1 nucleotides (A C G T N) with their phreds, in the reference's expression order
+// with the host's libm -> (base << 8) | quality character
+uint16_t vq_consensus_pos(const char *nuc, const int *phred, int n);
+const std::vector<uint16_t> &vq_consensus_tables();            // the vqm::T_* tables, built once
+
+// OriginalIndex of a single-end original (Types.h): forward, index1, len1
+struct VqOrig { bool forward; long index; int len; };
+using VqOriginals = std::map<uint64_t, VqOrig>;                // ascending original id: the order the lines are written in
+// buildOriginalsDict, the branch that reads subreads.txt (OverlapGraph.cpp:799-845), over the file's text
+std::map<uint64_t, VqOriginals> vq_parse_subreads(const std::string &data, const char *path);
+void vq_subreads_line(std::string &s, uint64_t id, const VqOriginals &o);
+// constructSuperread :750-806 for one member of a super-read: its originals go into `merged` unless already there.  forward =
+// the vertex label, idx1 = index1 - startpos1 of calcSubreadInfo (the read's offset minus trim_pos), read_len = |read|
+void vq_originals_add(VqOriginals &merged, const VqOriginals &of_read, bool forward, bool first_it, long idx1, long read_len);
+// a reverse read written forward (:1204-1216): orientation flipped, index mirrored
+void vq_originals_mirror(VqOriginals &o, long read_len);
+// original_ID_dict (buildOriginalsDict): first_it: every read is its own original at index 0, forward; else `dict` = the lines
+// of subreads_in (the driver fills it) and a read without one is refused.  `step` names the caller in messages.
+struct VqOriginalsDict {
+    VqOriginalsDict(const char *step, bool first_it, const char *subreads_in);     // refuses first_it off without a file
+    VqOriginals originals_of(const VqGraphState &g, uint32_t v) const;
+    const char *step, *subreads_in;
+    bool first_it;
+    std::map<uint64_t, VqOriginals> dict;
+};
+// getEdgeInfo(u, v) (OverlapGraph.cpp:263-282): the first u -> v of u's list, else the first v -> u of v's; NULL: neither
+const VqEdge *vq_edge_info(const VqGraphState &g, uint32_t u, uint32_t v);
+using VqPlaced = std::vector<std::pair<int64_t, uint32_t>>;    // (offset, vertex) in list order
+// sort_vertices (:33-286), single-end: `clique` ascending, its first vertex the base -> order = every member, each in front of
+// the first entry that is not smaller, shifted to start at 0; returns the total length.  Refuses a member without an edge to
+// the base and a total of 2^30 and more.
+int64_t vq_place(const VqGraphState &g, const std::vector<uint32_t> &clique, const char *step, VqPlaced &order);
+// filter_subreads (:597-636) with sortVerticesByEndpos (:639-652, std::sort on the end alone): the `num` entries that stay
+VqPlaced vq_filter_subreads(const VqGraphState &g, size_t num, uint32_t base, const VqPlaced &order);
+// consensus_pos of one pile-up column by the host's libm: the entries that cover it in list order, reversed ones complemented
+uint16_t vq_consensus_column(const VqGraphState &g, const vqc::Entry *entries, uint32_t n_entries, uint32_t column);
+bool vq_n_rate_ok(uint64_t n, uint64_t len);                   // Read::test_N_rate (Read.h:214-233)
+// The reads in no super-read (:1145-1222, :1282-1372), vertices ascending: dropped when shorter than keep_singletons or failing
+// the N rate (read_n = 'N's per read), to `diverted` when flagged in `divert` (NULL: none), else a record from id first_id on
+// - a reverse read as its forward copy with mirrored originals - and its subreads.txt line.
+struct VqLoneCounts { uint64_t short_reads = 0, n_reads = 0, trivial = 0, trivial_reverse = 0; };
+VqLoneCounts vq_lone_reads(const VqGraphState &g, const VqOriginalsDict &dict, const std::vector<uint8_t> &visited,
+                           const std::vector<uint32_t> &read_n, uint32_t keep_singletons, const std::vector<uint8_t> *divert,
+                           uint32_t first_id, std::vector<vqm::Rec> &recs, std::string &subreads, std::vector<uint32_t> *diverted);
+
+// ---- drivers: vq_superread_run.cpp (include/hylight_mi.h; vq_iteration_run is declared with `next` below) -------------------
+void vq_merge_opts_stageb(hlmi_vq_merge_opts *o);
+void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                  const hlmi_vq_merge_opts &mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
+void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2, const char *qual2,
+                       uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual, uint32_t *out_len);
 void vq_clique_opts_polyte(hlmi_vq_clique_opts *o, int error_correction);
 void vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uint64_t *n_cliques);
 void vq_cliques_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,

@@ -1,5 +1,5 @@
 // vq_merge.hip - SRBuilder::mergeAlongEdges (tools/HaploConduct/src/SRBuilder.cpp:1238-1384) on the device: the bases of the
-// super-reads and the text of singles.fastq / removed_tip_sequences.fastq.  The host (vq_merge_host.cpp) chooses the pairs
+// super-reads and the text of singles.fastq / removed_tip_sequences.fastq.  The host (vq_superread_run.cpp) chooses the pairs
 // and decides what is dropped; the kernels here read every base once per pass.
 //   read_n_kernel     one wave per read: its 'N's (Read::test_N_rate, Read.h:214-233)
 //   rec_size_kernel   per record: bases and bytes, scanned by dev_prims into starts
@@ -17,12 +17,6 @@ namespace hlmi {
 namespace vqm {
 namespace {
 
-__device__ __forceinline__ uint32_t base_code(uint8_t c) {      // A C G T N -> 0 .. 4 (the host refuses anything else)
-    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
-}
-__device__ __forceinline__ uint8_t complement(uint8_t c) {      // Read::build_rev_comp: N stays N
-    return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
-}
 __device__ __forceinline__ uint32_t dec_width(uint32_t v) {
     uint32_t w = 1;
     for (int k = 0; k < 9 && v >= 10; ++k) { v /= 10; ++w; }

@@ -19,7 +19,7 @@ import json
 import sys
 
 from . import api
-from .vq_graph import EXIT_REFUSED, _bool, build_parser as graph_parser
+from .vq_graph import EXIT_REFUSED, _bool, build_parser as graph_parser, exit_status, not_built
 
 EXIT_INVALID = 2
 
@@ -38,11 +38,7 @@ def build_parser():
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    refused = [msg for bad, msg in ((a.add_duplicates, "--add_duplicates true"),
-                                    (not a.resolve_orientations, "--resolve_orientations false"),
-                                    (a.branch_reduction, "--branch_reduction true")) if bad]
-    if refused:
-        sys.stderr.write(f"hylight_amd.vq_cliques: {', '.join(refused)} is not built\n")
+    if not_built("vq_cliques", a, tail="is not built"):
         return EXIT_REFUSED
     ec = bool(a.error_correction)
     polyte = api.vq_clique_opts_polyte(ec)
@@ -58,10 +54,7 @@ def main(argv=None):
                                   keep_singletons=polyte["keep_singletons"] if a.keep_singletons is None else a.keep_singletons,
                                   min_clique_size=a.min_clique_size)
     except api.HlmiError as e:
-        if e.code in (-6, -1):                # HLMI_ESTATE: refused; HLMI_EINVAL: malformed input, min_clique_size
-            sys.stderr.write(f"hylight_amd.vq_cliques: {e}\n")
-            return EXIT_REFUSED if e.code == -6 else EXIT_INVALID
-        raise
+        return exit_status("vq_cliques", e, invalid=EXIT_INVALID)   # HLMI_EINVAL: malformed input, min_clique_size
     print(json.dumps({"graph": gst, "cliques": cst}))
     return 0
 

@@ -56,13 +56,27 @@ def build_parser():
     return p
 
 
+def not_built(prog, a, more=(), tail="is not on HyLight's path and is not built"):
+    """Names the refused settings of the arguments `a` (`more`: a step's own (set, name) pairs) on stderr -> True if any."""
+    refused = [msg for bad, msg in ((a.add_duplicates, "--add_duplicates true"), (not a.resolve_orientations, "--resolve_orientations false"),
+                                    (a.branch_reduction, "--branch_reduction true"), *more) if bad]
+    if refused:
+        sys.stderr.write(f"hylight_amd.{prog}: {', '.join(refused)} {tail}\n")
+    return bool(refused)
+
+
+def exit_status(prog, e, invalid=None):
+    """api.HlmiError -> EXIT_REFUSED for HLMI_ESTATE (-6: not on HyLight's path), `invalid` (if given) for HLMI_EINVAL (-1),
+    with the message on stderr; anything else is raised again."""
+    if e.code != -6 and (e.code != -1 or invalid is None):
+        raise e
+    sys.stderr.write(f"hylight_amd.{prog}: {e}\n")
+    return EXIT_REFUSED if e.code == -6 else invalid
+
+
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    refused = [msg for bad, msg in ((a.add_duplicates, "--add_duplicates true"),
-                                    (not a.resolve_orientations, "--resolve_orientations false"),
-                                    (a.branch_reduction, "--branch_reduction true")) if bad]
-    if refused:
-        sys.stderr.write(f"hylight_amd.vq_graph: {', '.join(refused)} is not on HyLight's path and is not built\n")
+    if not_built("vq_graph", a):
         return EXIT_REFUSED
     try:
         st = api.vq_graph(a.singles, a.overlaps, a.out, min_overlap_len=a.min_overlap_len,
@@ -73,10 +87,7 @@ def main(argv=None):
                           ignore_inclusions=a.ignore_inclusions, remove_backedges=not a.error_correction,
                           max_overlaps=a.max_ov)
     except api.HlmiError as e:
-        if e.code == -6:                      # HLMI_ESTATE: refused, not on HyLight's path
-            sys.stderr.write(f"hylight_amd.vq_graph: {e}\n")
-            return EXIT_REFUSED
-        raise
+        return exit_status("vq_graph", e)
     print(json.dumps(st))
     return 0
 

@@ -15,7 +15,7 @@ import json
 import sys
 
 from . import api
-from .vq_graph import EXIT_REFUSED, _bool, build_parser as graph_parser
+from .vq_graph import EXIT_REFUSED, _bool, build_parser as graph_parser, exit_status, not_built
 
 
 def build_parser():
@@ -33,12 +33,7 @@ def build_parser():
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    refused = [msg for bad, msg in ((a.add_duplicates, "--add_duplicates true"),
-                                    (not a.resolve_orientations, "--resolve_orientations false"),
-                                    (a.branch_reduction, "--branch_reduction true"), (a.cliques, "--cliques true"),
-                                    (a.error_correction, "--error_correction true")) if bad]
-    if refused:
-        sys.stderr.write(f"hylight_amd.vq_merge: {', '.join(refused)} is not on HyLight's path and is not built\n")
+    if not_built("vq_merge", a, more=((a.cliques, "--cliques true"), (a.error_correction, "--error_correction true"))):
         return EXIT_REFUSED
     try:
         gst, mst = api.vq_merge(a.singles, a.overlaps, a.out, subreads_in=a.subreads, min_overlap_len=a.min_overlap_len,
@@ -50,10 +45,7 @@ def main(argv=None):
                                 max_overlaps=a.max_ov, first_it=a.first_it, keep_singletons=a.keep_singletons,
                                 store_tips_separately=a.separate_tips, min_clique_size=a.min_clique_size)
     except api.HlmiError as e:
-        if e.code == -6:                      # HLMI_ESTATE: refused, not on HyLight's path
-            sys.stderr.write(f"hylight_amd.vq_merge: {e}\n")
-            return EXIT_REFUSED
-        raise
+        return exit_status("vq_merge", e)
     print(json.dumps({"graph": gst, "merge": mst}))
     return 0
 

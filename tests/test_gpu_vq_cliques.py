@@ -69,20 +69,7 @@ def test_simulated_cluster(tmp_path, cluster, name, opts):
         assert want["deep"] < 100 and got["columns_host"] <= want["deep"]
 
 
-def _write_case(tmp_path, case):
-    fq, ov = str(tmp_path / "singles.fastq"), str(tmp_path / "overlaps.txt")
-    reads = case["reads"]
-    with open(fq, "w") as f:
-        f.write("".join(f"@{10 + k}\n{s}\n+\n{q}\n" for k, (s, q, _) in enumerate(reads)))
-    with open(ov, "w") as f:
-        for v1, v2, pos1 in case["edges"]:
-            n = min(len(reads[v1][0]) - pos1, len(reads[v2][0]))
-            f.write(f"{10 + v1}\t{10 + v2}\t{pos1}\t-\t-\t{'+' if reads[v1][2] else '-'}\t{'+' if reads[v2][2] else '-'}\t99\t-\t{n}\t-\ts\ts\n")
-    sub = None
-    if "subreads" in case:
-        sub = str(tmp_path / "subreads_in.txt")
-        open(sub, "w").write(case["subreads"])
-    return fq, ov, sub
+_write_case = K.write_files
 
 
 @pytest.mark.parametrize("name", sorted(K.CASES))
@@ -101,7 +88,7 @@ def test_hand_cases_through_the_library(tmp_path, name):
         assert lib["singles.fastq"] == open(tmp_path / "hand" / "singles.fastq", "rb").read() and want["superreads"] == 1
 
 
-_HAND = dict(min_overlap_len=1, merge_contigs=1.0, remove_trans=0, remove_branches=False, remove_tips=False, ignore_inclusions=False)
+_HAND = K.HAND_GRAPH
 # vqc::MARGIN, X_SLOPE, X_FLOOR of hylight_amd/csrc/vq_internal.h
 MARGIN, X_SLOPE, X_FLOOR = 2.0 ** -44, 4.35, 2.0 ** -36
 
@@ -149,6 +136,21 @@ def test_columns_on_a_rounding_boundary(tmp_path):
     got, want = _three_reads(tmp_path, ["A" * 60, "A" * 60, "C" * 60], ["".join(chr(33 + c[k + 1]) for c in cols) for k in range(3)])
     assert want["deep"] == 60 and got["superreads"] == 1
     assert got["columns_host"] > 0 and must <= got["columns_host"] <= may
+
+
+def test_a_pair_is_a_clique_of_two(tmp_path):
+    """The GPU half of tests/test_vq_clique_model.py::test_a_pair_is_a_clique_of_two: hlmi_vq_merge (merge_kernel) and
+    hlmi_vq_cliques (the two-base tables of pile_kernel) over the one placement, each byte for byte its model, write the same
+    records."""
+    from test_gpu_vq_merge import _compare as compare_merge
+    case = K.case_pairs()
+    fq, ov, _ = _write_case(tmp_path, case)
+    _, mst = compare_merge(tmp_path, fq, ov, "m", **_HAND, first_it=True, keep_singletons=0, store_tips_separately=False, min_clique_size=2)
+    cst, _ = _compare(tmp_path, fq, ov, "c", **_HAND, **dict(CM.CLIQUE, keep_singletons=0, **case["opts"]))
+    assert K.records(str(tmp_path / "m_lib")) == K.records(str(tmp_path / "c_lib"))
+    for k in ("dropped_empty", "dropped_n", "trivial", "trivial_reverse"):
+        assert mst[k] == cst[k], k
+    assert (mst["pairs"], mst["merged"], cst["taken"], cst["superreads"], cst["dropped_n"], cst["trivial"]) == (4, 3, 4, 3, 1, 2)
 
 
 def test_cli_and_refusals(tmp_path, cluster):

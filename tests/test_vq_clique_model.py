@@ -6,6 +6,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import vq_clique_cases as K  # noqa: E402
 import vq_clique_model as CM  # noqa: E402
+import vq_merge_model as MM  # noqa: E402
 
 
 def _run(tmp_path, name):
@@ -78,6 +79,31 @@ def test_not_first_iteration_forward_and_reverse(tmp_path):
     original 101 reverse at 2 with length 4: orientation ('-' == reverse label) -> '+', index 10 + 2 - (4 + 2) = 6."""
     st, f = _run(tmp_path, "not_first")
     assert f["subreads.txt"] == "0\t100:+:3:5\t101:+:6:4\n"
+
+
+def test_a_pair_is_a_clique_of_two(tmp_path):
+    """SRBuilder::mergeAlongEdges and cliquesToSuperreads both go through constructSuperread: on a graph of four disjoint
+    edges (K.case_pairs: an edge stored from the higher vertex, a reverse member, a pair above the N rate, a pair at pos1 0) the
+    two models write the same records - sequence, qualities, originals - under ids of their own (the merge numbers its pairs in
+    vertex order, the clique step in the enumerator's), and count the same drops and trivial reads.  The library's half is in
+    tests/test_gpu_vq_cliques.py."""
+    from hylight_amd import api              # cliques.txt: the pinned enumerator (host code)
+    case = K.case_pairs()
+    assert all(150 <= len(s) <= 200 for s, _, _ in case["reads"])
+    fq, ov, _ = K.write_files(tmp_path, case)
+    m_dir, c_dir = str(tmp_path / "merge"), str(tmp_path / "cliques")
+    _, mst = MM.merge(fq, ov, m_dir, **K.HAND_GRAPH, first_it=True, keep_singletons=0, store_tips_separately=False, min_clique_size=2)
+    _, cst = CM.cliques(fq, ov, c_dir, api.vq_cliques_of_graph, **K.HAND_GRAPH, **dict(CM.CLIQUE, keep_singletons=0, **case["opts"]))
+    smap = [line.split("\t") for line in open(os.path.join(m_dir, "superread_map.txt")).read().split("\n")[:-1]]
+    assert [r[3] for r in smap] == ["+", "+", "+", "-", "+", "+", "+", "+"]
+    assert [r[1:3] for r in smap[:2]] == [["0", "60"], ["0", "0"]] and [r[2] for r in smap[6:]] == ["0", "0"]
+    assert (mst["pairs"], mst["merged"], cst["taken"], cst["superreads"]) == (4, 3, 4, 3)
+    for k in ("dropped_empty", "dropped_n", "trivial", "trivial_reverse"):
+        assert mst[k] == cst[k], k
+    assert (cst["dropped_empty"], cst["dropped_n"], cst["trivial"], cst["trivial_reverse"]) == (0, 1, 2, 0)
+    got, want = K.records(m_dir), K.records(c_dir)
+    assert got == want and sum(got.values()) == 5
+    assert sorted(len(s) for s, _, _ in got) == [150, 160, 190, 230, 260]
 
 
 def test_std_sort_is_libstdcxx_on_ties():
