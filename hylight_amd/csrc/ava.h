@@ -52,14 +52,26 @@ struct DevReads {           // a read set resident in HBM: 1 B/base codes (0..3 
         HIP_CHECK(hipMemsetAsync(store.p, 4, PAD, stream()));
         HIP_CHECK(hipMemsetAsync(store.p + PAD + total, 4, PAD, stream()));
     }
+    // The same bases at 2 bits each for the kernels that only compare them (classify_kernel): base i in bits 2 (i & 3) of
+    // byte i >> 2, same offsets and the same PAD bases on both sides as codes().  Code 4 is stored as 0 and flagged: nflag
+    // holds one bit per granule of 32 bases (granule 0 starts at the front padding), set when any base of the granule is
+    // code 4 - the padding is.  A window whose granules are all clear holds the bases codes() holds.  pack() fills both.
+    DBuf<uint8_t> packed_store;     // (PAD + total + PAD) / 4 bytes, and 16 more that loads past the last base may touch
+    DBuf<uint32_t> nflag;           // a bit per granule, and two words more (a range's flags are read as two words)
+    const uint8_t *packed() const { return packed_store.p + PAD / 4; }
+    void pack();                    // (sketch.hip) after codes() is complete
+    static uint64_t packed_bytes(uint64_t total) {      // HBM of both buffers for a set of `total` bases
+        const uint64_t n_gran = (total + 2 * PAD + 31) / 32;
+        return (n_gran + 2) * 8 + ((n_gran + 31) / 32 + 2) * 4;
+    }
     DBuf<uint64_t> off;     // n+1 base offsets
     std::vector<uint64_t> h_off;
 };
 // reads [lo,hi) of s, in order
 void upload_reads(const SeqSet &s, size_t lo, size_t hi, DevReads &out);
 void upload_reads(const SeqSet &s, const std::vector<uint32_t> &ids, DevReads &out);
-// device-to-device subset (reads already resident in HBM)
-void subset_reads_device(const DevReads &all, const std::vector<uint32_t> &ids, DevReads &out);
+// device-to-device subset (reads already resident in HBM); pack = false: a subset that is only sketched gets no 2-bit copy
+void subset_reads_device(const DevReads &all, const std::vector<uint32_t> &ids, DevReads &out, bool pack = true);
 
 struct DevSketch {
     size_t n = 0;

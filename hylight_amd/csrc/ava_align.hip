@@ -173,6 +173,8 @@ struct AlignArgs {
     size_t n_list;
     const uint8_t *qcodes, *tcodes;
     long long q_total, t_total;   // bytes in qcodes / tcodes (4-base loads stay inside)
+    const uint8_t *qpacked, *tpacked;   // the classifier's 2-bit copies with their ambiguity flags (DevReads::packed(), nflag);
+    const uint32_t *qnflag, *tnflag;    // qpacked null: it compares the byte arrays (HLMI_CLASSIFY_BYTES)
     int match, mismatch, go, ge, ambi;
     int go2, ge2;           // second piece of the gap cost (go2 <= 0: one piece); only the 64-diagonal kernel can meet gaps long enough for it
     int end_bonus;          // ranks extension cells that reach the query end (0 in long mode)
@@ -272,8 +274,8 @@ __device__ __forceinline__ uint32_t load_window4p(const uint8_t *codes, long lon
 // exactly these runs.
 
 // stats[]: 0 bases (Lq + Lt) of all tasks, 1 of the square blocks compared here, 2 of the narrow DP tasks, 3 of the
-// wide DP tasks, 4 tasks finished on the diagonal fast path, 5 DP tasks, 6 DP rows
-enum { ST_BASES = 0, ST_BASES_SQUARE, ST_BASES_NARROW, ST_BASES_WIDE, ST_FAST, ST_DP, ST_DP_ROWS, ST_NARROW_SMALL, ST_WIDE_ONE, ST_STUB_EXT, ST_EXT_CERT, ST_EXT_DP_ROW, ST_EXT_DP_K, ST_LONG, ST_BASES_LONG, N_ALIGN_STATS };
+// wide DP tasks, 4 tasks finished on the diagonal fast path, 5 DP tasks, 6 DP rows; ST_PACKED: tasks compared from the 2-bit arrays
+enum { ST_BASES = 0, ST_BASES_SQUARE, ST_BASES_NARROW, ST_BASES_WIDE, ST_FAST, ST_DP, ST_DP_ROWS, ST_NARROW_SMALL, ST_WIDE_ONE, ST_STUB_EXT, ST_EXT_CERT, ST_EXT_DP_ROW, ST_EXT_DP_K, ST_LONG, ST_BASES_LONG, ST_PACKED, N_ALIGN_STATS };
 constexpr int NR_SMALL = 64;                    // narrow tasks with fewer rows than this run in the instance with half the plane LDS
 constexpr uint8_t CLS_LONG = 5;                 // class of the LONG tasks (align_long_kernel)
 constexpr uint8_t CLS_LONG32 = 7;               // LONG tasks in the 32-diagonal band, two to a wave (align_long32_kernel)
@@ -312,8 +314,65 @@ __device__ __forceinline__ uint64_t load_window8p(const uint8_t *codes, long lon
     return v;
 }
 
-// One lane per task: a square block is compared 8 bases at a time and given up at the third mismatch (kmax <= 3
-// would still pass with 3), so the typical task costs 8-9 iterations of two 8-byte loads; a block with m != n gets
+// ---- the same windows from the 2-bit arrays (DevReads::packed) ----
+// 32 window elements x .. x+31, element i in bits 2i, 2i+1: the nine bytes that hold them, shifted down to the first one.
+// A window read downwards is the window of its lowest base with the 2-bit groups in reverse order (a bit reversal, then the
+// two bits of every group swapped back); the complement of a code 0..3 is its inverse.  No bounds test, as load_window8p.
+__device__ __forceinline__ uint64_t load_window32p(const uint8_t *packed, long long a0, bool down, bool comp, int x) {
+    const long long s = down ? a0 - x - 31 : a0 + x;
+    const uint8_t *p = packed + (s >> 2);
+    uint64_t lo;
+    __builtin_memcpy(&lo, p, 8);
+    const int sh = 2 * (int)(s & 3);
+    uint64_t v = lo >> sh | (uint64_t)p[8] << 1 << (63 - sh);
+    if (down) {
+        v = __builtin_bitreverse64(v);
+        v = (v >> 1 & 0x5555555555555555ull) | (v & 0x5555555555555555ull) << 1;
+    }
+    return comp ? ~v : v;
+}
+// bit i = elements i of two such windows differ
+__device__ __forceinline__ uint32_t ne_bits32(uint64_t q, uint64_t t) {
+    const uint64_t d = q ^ t;
+    auto even = [](uint32_t x) {                      // bits 0, 2, .. 30 -> bits 0 .. 15
+        x = (x | x >> 1) & 0x55555555u;
+        x = (x | x >> 1) & 0x33333333u;
+        x = (x | x >> 2) & 0x0f0f0f0fu;
+        x = (x | x >> 4) & 0x00ff00ffu;
+        return (x | x >> 8) & 0xffffu;
+    };
+    return even((uint32_t)d) | even((uint32_t)(d >> 32)) << 16;
+}
+// byte y of f is 0 or 1 -> bit y (the four flags of a half gather in its top byte)
+__device__ __forceinline__ uint32_t squeeze8(uint64_t f) {
+    return (((uint32_t)f * 0x10204080u) >> 28) | (((uint32_t)(f >> 32) * 0x10204080u) >> 28) << 4;
+}
+// bit i = elements i of two 8-byte windows differ (codes are 0..4: three bits) / one of them is ambiguous
+__device__ __forceinline__ uint32_t ne_bits8(uint64_t q, uint64_t t) {
+    const uint64_t d = q ^ t;
+    return squeeze8((d | d >> 1 | d >> 2) & 0x0101010101010101ull);
+}
+__device__ __forceinline__ uint32_t amb_bits8(uint64_t q, uint64_t t) { return squeeze8((q | t) >> 2 & 0x0101010101010101ull); }
+// some base of [lo, hi] (offsets in the code array) lies in a granule flagged ambiguous: one or two words for a block
+__device__ __forceinline__ bool range_flagged(const uint32_t *nflag, long long lo, long long hi) {
+    const uint32_t g0 = (uint32_t)((lo + (long long)DevReads::PAD) >> 5), g1 = (uint32_t)((hi + (long long)DevReads::PAD) >> 5);
+    uint32_t any = 0;
+    for (uint32_t w = g0 >> 5; w <= g1 >> 5; ++w) {
+        uint32_t keep = ~0u;
+        if (w == g0 >> 5) keep &= ~0u << (g0 & 31);
+        if (w == g1 >> 5) keep &= ~0u >> (31 - (g1 & 31));
+        any |= nflag[w] & keep;
+    }
+    return any != 0;
+}
+// the same for window elements [0, len) of a task's sequence (element 0 at a0, read downwards or upwards)
+__device__ __forceinline__ bool window_flagged(const uint32_t *nflag, long long a0, bool down, int len) {
+    return down ? range_flagged(nflag, a0 - (len - 1), a0) : range_flagged(nflag, a0, a0 + (len - 1));
+}
+
+// One lane per task: a square block is compared 32 bases at a time from the 2-bit arrays (8 from the byte arrays where a
+// task touches an ambiguous base, or everywhere with HLMI_CLASSIFY_BYTES) and given up at the third mismatch (kmax <= 3
+// would still pass with 3), so the typical task costs two or three trips of two loads; a block with m != n gets
 // its common prefix / suffix measured the same way (second certificate below); the runs of the tasks that finish
 // here are allocated with one pool request per wave.
 // Two passes.  PASS 1 goes over all tasks and settles the square blocks; the blocks with m != n and the end
@@ -323,15 +382,15 @@ __device__ __forceinline__ uint64_t load_window8p(const uint8_t *codes, long lon
 template <int PASS>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 4 : 5))) void classify_kernel(AlignArgs a, uint8_t *cls, unsigned long long *stats) {
     __shared__ unsigned long long s_stat[WAVES][N_ALIGN_STATS];
-    constexpr int CMP_PIECES = PASS == 1 ? 64 * (BLOCK_MAX / 8) : 1;     // 8-base pieces of a wave's 64 square blocks
-    __shared__ uint8_t s_mm[WAVES][CMP_PIECES], s_up[WAVES][CMP_PIECES], s_dn[WAVES][CMP_PIECES];
+    constexpr int CMP_WORDS = PASS == 1 ? 64 * (BLOCK_MAX / 32) : 1;     // 32-base words of a wave's 64 square blocks
+    __shared__ uint32_t s_mm[WAVES][CMP_WORDS], s_up[WAVES][CMP_WORDS], s_dn[WAVES][CMP_WORDS];
     __shared__ uint64_t s_qa[WAVES][PASS == 1 ? 64 : 1], s_ta[WAVES][PASS == 1 ? 64 : 1];
     __shared__ uint32_t s_geo[WAVES][PASS == 1 ? 64 : 1], s_amb[WAVES][2];
     const int lane = threadIdx.x & 63;
     const size_t tid = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const size_t n_thr = (size_t)gridDim.x * blockDim.x;
     uint32_t chunk_off = 0, chunk_left = 0;
-    uint32_t st[N_ALIGN_STATS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // < 2^32 per thread by far
+    uint32_t st[N_ALIGN_STATS] = {};                                  // < 2^32 per thread by far
     const size_t n_units = PASS == 1 ? a.n_tasks : (size_t)*a.defer_count;
     const size_t rounds = (n_units + n_thr - 1) / n_thr;              // uniform trip count: the allocation is per wave
     // the reference of a task (PASS 2: its index in the list) is fetched a round ahead
@@ -387,92 +446,117 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
         int k = 0, mpos[3] = {0, 0, 0}, last_x = -1;
         bool ambig = false, shift_ok = false;
         if constexpr (PASS == 1) {
-            // The square blocks of the wave's 64 tasks are compared 8 bases per lane and step with the LANES SPREAD OVER
-            // THE 8-BASE PIECES of all of them (a lane per task would run every lane as long as the longest block of
-            // the wave, and its loads would touch 64 different lines): piece c of the wave belongs to the task whose first
-            // piece is the last one marked at or before c (a running prefix maximum over the marks), neighbouring lanes read
-            // neighbouring bytes, and each piece leaves one byte of mismatch bits in LDS for its task to read back.
+            // The square blocks of the wave's 64 tasks are compared with the LANES SPREAD OVER THE PIECES of all of them (a
+            // lane per task would run every lane as long as the longest block of the wave, and its loads would touch 64
+            // different lines): piece c of the wave belongs to the task whose first piece is the last one marked at or before
+            // c (a running prefix maximum over the marks), neighbouring lanes read neighbouring bytes, and each piece leaves
+            // its mismatch bits in LDS for its task to read back, a bit per base.  Packed form: a piece is 32 bases, one load
+            // of nine bytes per sequence from the 2-bit arrays, and leaves a 32-bit word.  Byte form: a piece is 8 bases of
+            // the code arrays and leaves a byte; a task's pieces are padded to whole words, so the words and the read-back
+            // below are the same for both.  A block that touches a granule flagged ambiguous needs the bytes (code 4 is not
+            // in the 2-bit array), and the wave then compares all its 64 blocks as bytes: blocks without a flagged granule
+            // compare alike either way.
             const int wv = threadIdx.x >> 6;
-            // (the owner marks and the mismatch bytes share an array: a piece's mark is read before its byte is written)
-            uint8_t *own = s_mm[wv], *mm = s_mm[wv], *mup = s_up[wv], *mdn = s_dn[wv];
-            const uint32_t nch = try_fast ? (uint32_t)(m + 7) >> 3 : 0u;
+            bool flagged = false;
+            if (try_fast && a.qpacked)
+                flagged = window_flagged(a.qnflag, (long long)tk.qa, (tk.kind & TASK_REV) != 0, m) || window_flagged(a.tnflag, (long long)tk.ta, false, m);
+            const bool use_packed = a.qpacked != nullptr && __ballot(flagged) == 0;
+            uint32_t *mm = s_mm[wv], *mup = s_up[wv], *mdn = s_dn[wv];
+            const uint32_t nch = try_fast ? (uint32_t)(m + 31) >> 5 : 0u;
             const uint32_t incl = wave_prefix_sum_incl_dpp(nch), tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             const uint32_t st0 = incl - nch;
-            for (uint32_t c = (uint32_t)lane; c < tot; c += 64) own[c] = 0;
             if (lane < 2) s_amb[wv][lane] = 0;
             s_qa[wv][lane] = tk.qa; s_ta[wv][lane] = tk.ta;
-            s_geo[wv][lane] = st0 | (uint32_t)m << 16 | ((tk.kind & TASK_REV) ? 0x80000000u : 0u);
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_wave_barrier();
-            if (nch) own[st0] = (uint8_t)lane;
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_wave_barrier();
-            int carry = 0;
-            constexpr int CU = 4;                                   // pieces per lane and trip: their loads are issued together
-            for (uint32_t c0 = 0; c0 < tot; c0 += 64 * CU) {
-                int ow[CU], xs[CU], left[CU];
-                bool rv[CU];
+            auto compare = [&](auto packed_form) {
+                constexpr bool PK = decltype(packed_form)::value;
+                constexpr int PB = PK ? 32 : 8, PW = 32 / PB;           // bases per piece, pieces per word
+                constexpr uint32_t FIRST = PK ? 3u : 0xffu;            // a window's first element
+                using piece_t = std::conditional_t<PK, uint32_t, uint8_t>;
+                // (the owner marks and the mismatch bits share an array: a piece's mark is read before its bits are written)
+                piece_t *own = (piece_t *)mm, *pm = (piece_t *)mm, *pup = (piece_t *)mup, *pdn = (piece_t *)mdn;
+                const uint32_t ptot = tot * PW, pst0 = st0 * PW;
+                auto window = [&](bool query, int o, bool rv, int x) {
+                    if constexpr (PK) return query ? load_window32p(a.qpacked, (long long)s_qa[wv][o], rv, rv, x) : load_window32p(a.tpacked, (long long)s_ta[wv][o], false, false, x);
+                    else return query ? load_window8p(a.qcodes, (long long)s_qa[wv][o], rv, rv, x) : load_window8p(a.tcodes, (long long)s_ta[wv][o], false, false, x);
+                };
+                for (uint32_t c = (uint32_t)lane; c < ptot; c += 64) own[c] = 0;
+                s_geo[wv][lane] = pst0 | (uint32_t)m << 16 | ((tk.kind & TASK_REV) ? 0x80000000u : 0u);
+                __builtin_amdgcn_s_waitcnt(0xc07f);
+                __builtin_amdgcn_wave_barrier();
+                if (nch) own[pst0] = (piece_t)lane;
+                __builtin_amdgcn_s_waitcnt(0xc07f);
+                __builtin_amdgcn_wave_barrier();
+                int carry = 0;
+                constexpr int CU = 4;                                   // pieces per lane and trip: their loads are issued together
+                for (uint32_t c0 = 0; c0 < ptot; c0 += 64 * CU) {
+                    int ow[CU], xs[CU], left[CU];
+                    bool rv[CU];
 #pragma unroll
-                for (int u = 0; u < CU; ++u) {
-                    const uint32_t c = c0 + 64u * u + (uint32_t)lane;
-                    int o = c < tot ? (int)own[c] : 0;
-                    o = wave_prefix_max_incl_dpp(o);
-                    o = o > carry ? o : carry;
-                    carry = __builtin_amdgcn_readlane(o, 63);
-                    const uint32_t geo = s_geo[wv][o];
-                    ow[u] = o;
-                    xs[u] = (int)(c - (geo & 0xffffu)) * 8;
-                    left[u] = c < tot ? (int)(geo >> 16 & 0x7fffu) - xs[u] : 0;      // bases of the piece inside its block (>= 1)
-                    rv[u] = (geo >> 31) != 0;
-                }
-                uint64_t q8[CU], t8[CU];
-                uint32_t q_end = 0, t_end = 0;         // lane 63: the base behind the trip's last piece (fourth certificate)
+                    for (int u = 0; u < CU; ++u) {
+                        const uint32_t c = c0 + 64u * u + (uint32_t)lane;
+                        int o = c < ptot ? (int)own[c] : 0;
+                        o = wave_prefix_max_incl_dpp(o);
+                        o = o > carry ? o : carry;
+                        carry = __builtin_amdgcn_readlane(o, 63);
+                        const uint32_t geo = s_geo[wv][o];
+                        ow[u] = o;
+                        xs[u] = (int)(c - (geo & 0xffffu)) * PB;
+                        left[u] = c < ptot ? (int)(geo >> 16 & 0x7fffu) - xs[u] : 0;     // bases of the piece inside its block (<= 0: padding)
+                        rv[u] = (geo >> 31) != 0;
+                    }
+                    uint64_t qw[CU], tw[CU];
+                    uint32_t q_end = 0, t_end = 0;         // lane 63: the base behind the trip's last piece (fourth certificate)
 #pragma unroll
-                for (int u = 0; u < CU; ++u) {
-                    q8[u] = t8[u] = 0;
-                    if (left[u] > 0) {
-                        q8[u] = load_window8p(a.qcodes, (long long)s_qa[wv][ow[u]], rv[u], rv[u], xs[u]);
-                        t8[u] = load_window8p(a.tcodes, (long long)s_ta[wv][ow[u]], false, false, xs[u]);
-                        if (u == CU - 1 && lane == 63 && a.kshift) {
-                            q_end = (uint32_t)load_window8p(a.qcodes, (long long)s_qa[wv][ow[u]], rv[u], rv[u], xs[u] + 8) & 0xffu;
-                            t_end = (uint32_t)load_window8p(a.tcodes, (long long)s_ta[wv][ow[u]], false, false, xs[u] + 8) & 0xffu;
+                    for (int u = 0; u < CU; ++u) {
+                        qw[u] = tw[u] = 0;
+                        if (left[u] > 0) {
+                            qw[u] = window(true, ow[u], rv[u], xs[u]);
+                            tw[u] = window(false, ow[u], false, xs[u]);
+                            if (u == CU - 1 && lane == 63 && a.kshift) {
+                                q_end = (uint32_t)window(true, ow[u], rv[u], xs[u] + PB) & FIRST;
+                                t_end = (uint32_t)window(false, ow[u], false, xs[u] + PB) & FIRST;
+                            }
+                        }
+                    }
+                    int nq[CU], nt[CU];
+                    if (a.kshift) {
+#pragma unroll
+                        for (int u = 0; u < CU; ++u) {
+                            const int q_after = u + 1 < CU ? __builtin_amdgcn_readlane((int)((uint32_t)qw[u + 1 < CU ? u + 1 : u] & FIRST), 0) : (int)q_end;
+                            const int t_after = u + 1 < CU ? __builtin_amdgcn_readlane((int)((uint32_t)tw[u + 1 < CU ? u + 1 : u] & FIRST), 0) : (int)t_end;
+                            nq[u] = wave_shl1((int)((uint32_t)qw[u] & FIRST), q_after);
+                            nt[u] = wave_shl1((int)((uint32_t)tw[u] & FIRST), t_after);
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < CU; ++u) {
+                        if (left[u] <= 0) continue;
+                        const uint32_t c = c0 + 64u * u + (uint32_t)lane;
+                        // the windows one base further (fourth certificate: bit i = q[i + 1] != t[i] / q[i] != t[i + 1]): the base
+                        // behind a piece is the first of the next piece (the next lane; where that is another block's, the position
+                        // lies outside [p1, pk) and is never looked at)
+                        if constexpr (PK) {
+                            pm[c] = ne_bits32(qw[u], tw[u]) & (left[u] >= 32 ? ~0u : (1u << left[u]) - 1u);
+                            if (a.kshift) {
+                                const uint64_t q9 = qw[u] >> 2 | (uint64_t)(uint32_t)nq[u] << 62, t9 = tw[u] >> 2 | (uint64_t)(uint32_t)nt[u] << 62;
+                                pup[c] = ne_bits32(q9, tw[u]);
+                                pdn[c] = ne_bits32(qw[u], t9);
+                            }
+                        } else {
+                            const uint64_t keep = left[u] >= 8 ? ~0ull : (1ull << (8 * left[u])) - 1ull;
+                            if ((qw[u] | tw[u]) & keep & 0x0404040404040404ull) atomicOr(&s_amb[wv][ow[u] >> 5], 1u << (ow[u] & 31));
+                            pm[c] = (uint8_t)ne_bits8(qw[u] & keep, tw[u] & keep);
+                            if (a.kshift) {
+                                const uint64_t q9 = qw[u] >> 8 | (uint64_t)(uint32_t)nq[u] << 56, t9 = tw[u] >> 8 | (uint64_t)(uint32_t)nt[u] << 56;
+                                pup[c] = (uint8_t)ne_bits8(q9, tw[u]);
+                                pdn[c] = (uint8_t)ne_bits8(qw[u], t9);
+                            }
                         }
                     }
                 }
-                int nq[CU], nt[CU];
-                if (a.kshift) {
-#pragma unroll
-                    for (int u = 0; u < CU; ++u) {
-                        const int q_after = u + 1 < CU ? __builtin_amdgcn_readlane((int)((uint32_t)q8[u + 1 < CU ? u + 1 : u] & 0xffu), 0) : (int)q_end;
-                        const int t_after = u + 1 < CU ? __builtin_amdgcn_readlane((int)((uint32_t)t8[u + 1 < CU ? u + 1 : u] & 0xffu), 0) : (int)t_end;
-                        nq[u] = wave_shl1((int)((uint32_t)q8[u] & 0xffu), q_after);
-                        nt[u] = wave_shl1((int)((uint32_t)t8[u] & 0xffu), t_after);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < CU; ++u) {
-                    if (left[u] <= 0) continue;
-                    const uint64_t keep = left[u] >= 8 ? ~0ull : (1ull << (8 * left[u])) - 1ull;
-                    uint64_t d = (q8[u] ^ t8[u]) & keep;
-                    if ((q8[u] | t8[u]) & keep & 0x0404040404040404ull) atomicOr(&s_amb[wv][ow[u] >> 5], 1u << (ow[u] & 31));
-                    d = (d | d >> 1 | d >> 2) & 0x0101010101010101ull;      // codes are 0..4: three bits
-                    // byte y set -> bit y: the four flags of a half gather in its top byte
-                    auto squeeze = [](uint64_t f) {
-                        return (uint8_t)((((uint32_t)f * 0x10204080u) >> 28) | (((uint32_t)(f >> 32) * 0x10204080u) >> 28) << 4);
-                    };
-                    mm[c0 + 64u * u + (uint32_t)lane] = squeeze(d);
-                    if (a.kshift) {       // fourth certificate: bit i = q[i + 1] != t[i] / q[i] != t[i + 1]
-                        // the windows one base further: the base behind a piece is the first of the next piece (the next lane;
-                        // where that is another block's, the position lies outside [p1, pk) and is never looked at)
-                        const uint64_t q9 = q8[u] >> 8 | (uint64_t)(uint32_t)nq[u] << 56, t9 = t8[u] >> 8 | (uint64_t)(uint32_t)nt[u] << 56;
-                        uint64_t du = q9 ^ t8[u], dd = q8[u] ^ t9;
-                        du = (du | du >> 1 | du >> 2) & 0x0101010101010101ull;
-                        dd = (dd | dd >> 1 | dd >> 2) & 0x0101010101010101ull;
-                        mup[c0 + 64u * u + (uint32_t)lane] = squeeze(du);
-                        mdn[c0 + 64u * u + (uint32_t)lane] = squeeze(dd);
-                    }
-                }
-            }
+            };
+            if (use_packed) { compare(std::true_type{}); if (try_fast) ++st[ST_PACKED]; }
+            else compare(std::false_type{});
             __builtin_amdgcn_s_waitcnt(0xc07f);
             __builtin_amdgcn_wave_barrier();
             if (try_fast) {
@@ -482,7 +566,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
                     while (bits) {
                         const int y = __ffs((int)bits) - 1;
                         bits &= bits - 1;
-                        if (k < 3) mpos[k] = (int)(8 * j) + y;
+                        if (k < 3) mpos[k] = (int)(32 * j) + y;
                         ++k;
                     }
                 }
@@ -497,10 +581,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
             if (try_fast && !ambig && a.kshift && k == a.kmax + 1) {
                 const int p1 = mpos[0], pk = mpos[k - 1];
                 uint32_t any_up = 0, any_dn = 0;                     // a mismatch of the shifted segment inside [p1, pk)
-                for (int j = p1 >> 3; j <= (pk - 1) >> 3; ++j) {
-                    uint32_t keepb = 0xffu;
-                    if (j == p1 >> 3) keepb &= 0xffu << (p1 & 7);
-                    if (j == (pk - 1) >> 3) keepb &= 0xffu >> (7 - ((pk - 1) & 7));
+                for (int j = p1 >> 5; j <= (pk - 1) >> 5; ++j) {
+                    uint32_t keepb = ~0u;
+                    if (j == p1 >> 5) keepb &= ~0u << (p1 & 31);
+                    if (j == (pk - 1) >> 5) keepb &= ~0u >> (31 - ((pk - 1) & 31));
                     any_up |= mup[st0 + (uint32_t)j] & keepb;
                     any_dn |= mdn[st0 + (uint32_t)j] & keepb;
                 }
@@ -509,7 +593,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
             if (try_fast && k > 0 && !ambig) {                  // last substitution of the diagonal (suffix trim below)
                 for (int j = (int)nch - 1; j >= 0; --j) {
                     const uint32_t bits = mm[st0 + (uint32_t)j];
-                    if (bits) { last_x = 8 * j + 31 - __clz((int)bits); break; }
+                    if (bits) { last_x = 32 * j + 31 - __clz((int)bits); break; }
                 }
             }
             __builtin_amdgcn_wave_barrier();                   // the next round reuses the arrays
@@ -530,6 +614,21 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
         // the bonus row could outrank it, so the certificate then needs (L, L) to lie in that row itself.
         uint32_t ext_flag = 0;
         int ext_take = -1;                   // sixth certificate: rows = columns of the cell the extension stops in
+        // The scans of the second pass compare W query elements from xq on with W target elements from xt on: bit i of `ne`
+        // = the pair differs, of `amb` = one of the two is ambiguous.  Packed form: W = 32 bases from the 2-bit arrays, for
+        // the tasks whose sequences touch no granule flagged ambiguous; byte form: W = 8.  Both leave the same positions.
+        auto pairs = [&](auto packed_form, bool q_down, bool t_down, int xq, int xt, uint32_t &ne, uint32_t &amb) {
+            const bool rev = (tk.kind & TASK_REV) != 0;
+            if constexpr (decltype(packed_form)::value) {
+                ne = ne_bits32(load_window32p(a.qpacked, (long long)tk.qa, q_down, rev, xq), load_window32p(a.tpacked, (long long)tk.ta, t_down, false, xt));
+                amb = 0;
+            } else {
+                const uint64_t q8 = load_window8p(a.qcodes, (long long)tk.qa, q_down, rev, xq), t8 = load_window8p(a.tcodes, (long long)tk.ta, t_down, false, xt);
+                ne = ne_bits8(q8, t8);
+                amb = amb_bits8(q8, t8);
+            }
+        };
+        auto low_bits = [](int n, int w) { return n >= w ? ~0u >> (32 - w) : (1u << n) - 1u; };       // the first min(n, w) elements
         if (PASS == 2 && live && c != 0 && (tk.kind & 3) != 0 && a.kmax >= 0) {
             const bool rev = (tk.kind & TASK_REV) != 0, left = (tk.kind & 3) == 1;
             const int L = m < n ? m : n;
@@ -557,31 +656,30 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
             const int k_want = bonus_row ? (L == end_row ? a.kext_bonus : 0) : a.kext_plain;
             int x1 = -1, x2 = -1;
             auto more = [&]() { return same || (!amb_ext && (k_ext <= allow || k_ext <= k_want)); };
-            auto take8 = [&](int x, uint64_t q8, uint64_t t8) {
-                const int rest = L - x;
-                const uint64_t keep = rest >= 8 ? ~0ull : (1ull << (8 * rest)) - 1ull;
-                uint64_t d = (q8 ^ t8) & keep;
-                amb_ext |= ((q8 | t8) & keep & 0x0404040404040404ull) != 0;
-                d = (d | d >> 1 | d >> 2) & 0x0101010101010101ull;
-                if (d && x2 < 0) {
-                    const int y1 = (__ffsll((long long)d) - 1) >> 3;
-                    if (x1 < 0) { x1 = x + y1; const uint64_t d2 = d & (d - 1); if (d2) x2 = x + ((__ffsll((long long)d2) - 1) >> 3); }
-                    else x2 = x + y1;
+            auto scan = [&](auto packed_form) {
+                constexpr int W = decltype(packed_form)::value ? 32 : 8;
+                auto take = [&](int x, uint32_t ne, uint32_t amb) {
+                    const uint32_t keep = low_bits(L - x, W);
+                    ne &= keep;
+                    amb_ext |= (amb & keep) != 0;
+                    if (ne && x2 < 0) {
+                        const int y1 = __ffs((int)ne) - 1;
+                        if (x1 < 0) { x1 = x + y1; const uint32_t d2 = ne & (ne - 1); if (d2) x2 = x + __ffs((int)d2) - 1; }
+                        else x2 = x + y1;
+                    }
+                    k_ext += __popc(ne);
+                    same = same && ne == 0 && !amb_ext;
+                };
+                for (int x = 0; x < L && more(); x += 2 * W) {         // two steps' loads in flight together
+                    uint32_t ne0, amb0, ne1 = 0, amb1 = 0;
+                    pairs(packed_form, left != rev, left, x, x, ne0, amb0);
+                    if (x + W < L) pairs(packed_form, left != rev, left, x + W, x + W, ne1, amb1);
+                    take(x, ne0, amb0);
+                    if (x + W < L && more()) take(x + W, ne1, amb1);
                 }
-                k_ext += __popcll(d);
-                same = same && d == 0 && !amb_ext;
             };
-            for (int x = 0; x < L && more(); x += 16) {            // two steps' loads in flight together
-                const uint64_t q8 = load_window8p(a.qcodes, (long long)tk.qa, left != rev, rev, x);
-                const uint64_t t8 = load_window8p(a.tcodes, (long long)tk.ta, left, false, x);
-                uint64_t q8b = 0, t8b = 0;
-                if (x + 8 < L) {
-                    q8b = load_window8p(a.qcodes, (long long)tk.qa, left != rev, rev, x + 8);
-                    t8b = load_window8p(a.tcodes, (long long)tk.ta, left, false, x + 8);
-                }
-                take8(x, q8, t8);
-                if (x + 8 < L && more()) take8(x + 8, q8b, t8b);
-            }
+            if (a.qpacked && !window_flagged(a.qnflag, (long long)tk.qa, left != rev, L) && !window_flagged(a.tnflag, (long long)tk.ta, left, L)) { scan(std::true_type{}); ++st[ST_PACKED]; }
+            else scan(std::false_type{});
             if (!same && !amb_ext && k_ext <= allow) { tk.kind |= TASK_ONE; ++st[ST_WIDE_ONE]; }
             if (same) {
                 runs[nr++] = (uint32_t)L << 4 | OP_EQ;
@@ -658,38 +756,43 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
             // both scans in one loop: the start diagonal forwards, the end diagonal backwards, their four loads of a trip in
             // flight together (one after the other the kernel waited 80 % of its time on a chain of dependent trips)
             const int sq = m > n ? m - n : 0, st_ = n > m ? n - m : 0;   // shift of the end diagonal in q / t
-            for (int x = 0; x < mn && (found_a < want || found_b < want); x += 8) {
-                const bool da = found_a < want, db = found_b < want;
-                const int e0 = mn - 8 - x;                                // end diagonal: elements mn-8-x .. mn-1-x
-                uint64_t q8 = 0, t8 = 0, q8e = 0, t8e = 0;
-                if (da) { q8 = load_window8p(a.qcodes, (long long)tk.qa, rev, rev, x); t8 = load_window8p(a.tcodes, (long long)tk.ta, false, false, x); }
-                if (db) { q8e = load_window8p(a.qcodes, (long long)tk.qa, rev, rev, e0 + sq); t8e = load_window8p(a.tcodes, (long long)tk.ta, false, false, e0 + st_); }
-                const int left = mn - x;
-                if (da) {
-                    const uint64_t keep = left >= 8 ? ~0ull : (1ull << (8 * left)) - 1ull;
-                    amb |= ((q8 | t8) & keep & 0x0404040404040404ull) != 0;
-                    uint64_t d = (q8 ^ t8) & keep;
-                    d = (d | d >> 1 | d >> 2) & 0x0101010101010101ull;
-                    while (d && found_a < want) {
-                        const int y = (__ffsll((long long)d) - 1) >> 3;
-                        d &= d - 1;
-                        if (found_a == 0) a1 = x + y; else if (found_a == 1) a2 = x + y; else a3 = x + y;
-                        ++found_a;
+            auto scan = [&](auto packed_form) {
+                constexpr int W = decltype(packed_form)::value ? 32 : 8;
+                for (int x = 0; x < mn && (found_a < want || found_b < want); x += W) {
+                    const bool da = found_a < want, db = found_b < want;
+                    const int e0 = mn - W - x;                                // end diagonal: elements mn-W-x .. mn-1-x
+                    uint32_t ne_a = 0, amb_a = 0, ne_b = 0, amb_b = 0;
+                    if (da) pairs(packed_form, rev, false, x, x, ne_a, amb_a);
+                    if (db) pairs(packed_form, rev, false, e0 + sq, e0 + st_, ne_b, amb_b);
+                    const int left = mn - x;
+                    if (da) {
+                        const uint32_t keep = low_bits(left, W);
+                        amb |= (amb_a & keep) != 0;
+                        uint32_t d = ne_a & keep;
+                        while (d && found_a < want) {
+                            const int y = __ffs((int)d) - 1;
+                            d &= d - 1;
+                            if (found_a == 0) a1 = x + y; else if (found_a == 1) a2 = x + y; else a3 = x + y;
+                            ++found_a;
+                        }
+                    }
+                    if (db) {
+                        const uint32_t keep = left >= W ? ~0u : low_bits(W, W) & ~low_bits(W - left, W);     // the last `left` elements
+                        amb |= (amb_b & keep) != 0;
+                        uint32_t d = ne_b & keep;
+                        while (d && found_b < want) {
+                            const int z = 31 - __clz((int)d);                  // highest set bit
+                            d &= ~(1u << z);
+                            if (found_b == 0) b1 = e0 + z; else if (found_b == 1) b2 = e0 + z; else b3 = e0 + z;
+                            ++found_b;
+                        }
                     }
                 }
-                if (db) {
-                    const uint64_t keep = left >= 8 ? ~0ull : ~0ull << (8 * (8 - left));
-                    amb |= ((q8e | t8e) & keep & 0x0404040404040404ull) != 0;
-                    uint64_t d = (q8e ^ t8e) & keep;
-                    d = (d | d >> 1 | d >> 2) & 0x0101010101010101ull;
-                    while (d && found_b < want) {
-                        const int z = 7 - (__clzll((long long)d) >> 3);      // highest set byte
-                        d &= ~(0xffull << (8 * z));
-                        if (found_b == 0) b1 = e0 + z; else if (found_b == 1) b2 = e0 + z; else b3 = e0 + z;
-                        ++found_b;
-                    }
-                }
-            }
+            };
+            // (every load of this task, the shifted scans of the seventh certificate included, stays inside the block)
+            const bool use_packed = a.qpacked && !window_flagged(a.qnflag, (long long)tk.qa, rev, m) && !window_flagged(a.tnflag, (long long)tk.ta, false, n);
+            if (use_packed) { scan(std::true_type{}); ++st[ST_PACKED]; }
+            else scan(std::false_type{});
             int p_star = -1, xpos = -1, xpos2 = -1;
             if (!amb) {
                 if (b1 < a1) p_star = b1 + 1;                                             // s* = 0
@@ -717,23 +820,25 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(PASS == 1 ? 
                 else if (a2 < mn && M2 < a3) { ps = M2 + 1; x1 = a1; x2 = a2; }
                 if (ps >= 0 && a1 < b1) {
                     // S = the shorter sequence (rows of the argument above), L = the longer one
-                    auto load_s = [&](int x) { return del ? load_window8p(a.qcodes, (long long)tk.qa, rev, rev, x) : load_window8p(a.tcodes, (long long)tk.ta, false, false, x); };
-                    auto load_l = [&](int x) { return del ? load_window8p(a.tcodes, (long long)tk.ta, false, false, x) : load_window8p(a.qcodes, (long long)tk.qa, rev, rev, x); };
                     bool far_ne = false, near_ne = false, ambx = false;
-                    for (int x = a1; x < b1 && !far_ne; x += 8) {                 // S[i] vs L[i + 2], i in [a1, b1)
-                        const uint64_t s8 = load_s(x), l8 = load_l(x + 2);
-                        const int left = b1 - x;
-                        const uint64_t keep = left >= 8 ? ~0ull : (1ull << (8 * left)) - 1ull;
-                        ambx |= ((s8 | l8) & keep & 0x0404040404040404ull) != 0;
-                        far_ne = ((s8 ^ l8) & keep) != 0;
-                    }
-                    for (int x = a1 + 1; x <= b1 && !near_ne; x += 8) {           // S[i] vs L[i - 1], i in [a1 + 1, b1]
-                        const uint64_t s8 = load_s(x), l8 = load_l(x - 1);
-                        const int left = b1 + 1 - x;
-                        const uint64_t keep = left >= 8 ? ~0ull : (1ull << (8 * left)) - 1ull;
-                        ambx |= ((s8 | l8) & keep & 0x0404040404040404ull) != 0;
-                        near_ne = ((s8 ^ l8) & keep) != 0;
-                    }
+                    auto shifted = [&](auto packed_form) {
+                        constexpr int W = decltype(packed_form)::value ? 32 : 8;
+                        uint32_t ne, ab;
+                        for (int x = a1; x < b1 && !far_ne; x += W) {                 // S[i] vs L[i + 2], i in [a1, b1)
+                            pairs(packed_form, rev, false, del ? x : x + 2, del ? x + 2 : x, ne, ab);
+                            const uint32_t keep = low_bits(b1 - x, W);
+                            ambx |= (ab & keep) != 0;
+                            far_ne = (ne & keep) != 0;
+                        }
+                        for (int x = a1 + 1; x <= b1 && !near_ne; x += W) {           // S[i] vs L[i - 1], i in [a1 + 1, b1]
+                            pairs(packed_form, rev, false, del ? x : x - 1, del ? x - 1 : x, ne, ab);
+                            const uint32_t keep = low_bits(b1 + 1 - x, W);
+                            ambx |= (ab & keep) != 0;
+                            near_ne = (ne & keep) != 0;
+                        }
+                    };
+                    if (use_packed) shifted(std::true_type{});
+                    else shifted(std::false_type{});
                     if (far_ne && near_ne && !ambx) { p_star = ps; xpos = x1; xpos2 = x2; }
                 }
             }
@@ -2766,6 +2871,11 @@ static void align_span(const AvaInput &in, const hlmi_ava_opts &o, const uint32_
         aa.geom = TaskGeom{task_ref.p, pgeom.p, ch.fps.p};
         aa.qcodes = in.Q->codes(); aa.tcodes = in.T->codes();
         aa.q_total = (long long)in.Q->total; aa.t_total = (long long)in.T->total;
+        if (!hook("HLMI_CLASSIFY_BYTES")) {
+            if (!in.Q->packed_store.p || !in.T->packed_store.p) fail(HLMI_ESTATE, "alignment of a read set without its 2-bit copy (DevReads::pack)");
+            aa.qpacked = in.Q->packed(); aa.tpacked = in.T->packed();
+            aa.qnflag = in.Q->nflag.p; aa.tnflag = in.T->nflag.p;
+        }
         aa.end_bonus = o.end_bonus;
         aa.ext_max = ext_rows(o);
         aa.ext_all_long = ext_all_long ? 1 : 0;
@@ -3140,6 +3250,7 @@ static void align_span(const AvaInput &in, const hlmi_ava_opts &o, const uint32_
     {
         std::vector<unsigned long long> h = astats.download(N_ALIGN_STATS);
         stat_add("align_tasks_fast", (double)h[ST_FAST]);
+        stat_add("align_tasks_packed", (double)h[ST_PACKED]);          // compared by the classifier from the 2-bit arrays
         stat_add("align_tasks_dp", (double)h[ST_DP]);
         stat_add("align_dp_rows", (double)h[ST_DP_ROWS]);
         stat_add("align_dp_bases", (double)h[ST_BASES]);              // Lq + Lt over all tasks

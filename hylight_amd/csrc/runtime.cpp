@@ -191,6 +191,7 @@ const char *const HOOK_NAMES[] = {
     "HLMI_SEED_GROUP", "HLMI_TEXT_GPU", "HLMI_TEXT_HOST", "HLMI_GRAPH_WINDOW_MB", "HLMI_LANES", "HLMI_SET_ASIDE_CUTS", "HLMI_SEED_NO_GUESS",
     "HLMI_CHAIN_PROF",
     "HLMI_CHAIN_UNPACKED",
+    "HLMI_CLASSIFY_BYTES",
     "HLMI_GROUP_HIST",
     "HLMI_HOST_TIMERS",
     "HLMI_LONG_SIDE_STREAM",

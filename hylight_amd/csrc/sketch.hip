@@ -190,6 +190,41 @@ __global__ void read_count_kernel(const uint32_t *midx, size_t n_mz, const uint3
 }
 }  // namespace
 
+// 2-bit copy and ambiguity flags of a read set (DevReads::pack): a thread per granule of 32 bases, padding included;
+// granules behind the array (the tail of the last flag word) count as ambiguous
+__global__ void pack_kernel(const uint8_t *store, uint64_t n_store, uint64_t *packed, uint32_t *nflag, uint64_t n_gran) {
+    const uint64_t g = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
+    uint64_t w = 0;
+    bool amb = g >= n_gran;
+    if (!amb) {
+        for (int k = 0; k < 4; ++k) {
+            const uint64_t i = 32 * g + 8 * (uint64_t)k;
+            uint64_t c8 = 0;
+            if (i + 8 <= n_store) __builtin_memcpy(&c8, store + i, 8);
+            else for (int b = 0; b < 8; ++b) c8 |= (uint64_t)(i + b < n_store ? store[i + b] : 4) << (8 * b);
+            amb |= (c8 & 0x0404040404040404ull) != 0;
+            for (int b = 0; b < 8; ++b) w |= (c8 >> (8 * b) & 3ull) << (2 * (8 * k + b));
+        }
+        packed[g] = w;
+    }
+    const uint64_t bits = __ballot(amb);
+    if ((threadIdx.x & 31) == 0 && g < n_gran) nflag[g >> 5] = (uint32_t)(bits >> (threadIdx.x & 32));
+}
+
+void DevReads::pack() {
+    const uint64_t n_store = total + 2 * PAD, n_gran = (n_store + 31) / 32, n_words = (n_gran + 31) / 32;
+    packed_store.alloc((n_gran + 2) * 8);
+    nflag.alloc(n_words + 2);
+    HIP_CHECK(hipMemsetAsync(packed_store.p + n_gran * 8, 0, 16, stream()));
+    HIP_CHECK(hipMemsetAsync(nflag.p + n_words, 0xff, 8, stream()));
+    for (uint64_t g0 = 0; g0 < n_gran; g0 += 1ull << 30) {       // (fewer than 2^32 work-items per launch, as in finish_upload)
+        const uint64_t len = std::min<uint64_t>(1ull << 30, n_gran - g0);
+        hipLaunchKernelGGL(pack_kernel, grid1(len), dim3(WG), 0, stream(), store.p + 32 * g0, n_store - 32 * g0,
+                           (uint64_t *)packed_store.p + g0, nflag.p + g0 / 32, len);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
 static void finish_upload(const char *bases, const std::vector<uint64_t> &off, DevReads &out) {
     out.n = off.size() - 1;
     out.total = off.back();
@@ -205,6 +240,7 @@ static void finish_upload(const char *bases, const std::vector<uint64_t> &off, D
         }
         HIP_CHECK(hipGetLastError());
     }
+    out.pack();
     out.off.upload(off);
     sync();
 }
@@ -232,7 +268,7 @@ __global__ void copy_reads_kernel(const uint8_t *src, const uint64_t *src_off, c
     for (uint64_t i = threadIdx.x; i < len; i += blockDim.x) dst[d0 + i] = src[s0 + i];
 }
 
-void subset_reads_device(const DevReads &all, const std::vector<uint32_t> &ids, DevReads &out) {
+void subset_reads_device(const DevReads &all, const std::vector<uint32_t> &ids, DevReads &out, bool pack) {
     std::vector<uint64_t> off(ids.size() + 1, 0);
     for (size_t i = 0; i < ids.size(); ++i) off[i + 1] = off[i] + (all.h_off[ids[i] + 1] - all.h_off[ids[i]]);
     out.n = ids.size();
@@ -246,8 +282,9 @@ void subset_reads_device(const DevReads &all, const std::vector<uint32_t> &ids, 
         hipLaunchKernelGGL(copy_reads_kernel, dim3((unsigned)ids.size()), dim3(WG), 0, stream(), all.codes(), all.off.p,
                            d_ids.p, out.off.p, out.codes());
         HIP_CHECK(hipGetLastError());
-        sync();
     }
+    if (pack) out.pack();
+    sync();
 }
 
 // shared body: returns the compacted slot indices and fills per-read counts

@@ -112,7 +112,7 @@ int64_t Job::sketch_range(int64_t lo, int64_t hi, void *dev_mz, int64_t cap, voi
         DevReads part;
         std::vector<uint32_t> ids((size_t)(b - a));
         for (size_t i = 0; i < ids.size(); ++i) ids[i] = (uint32_t)(a + (int64_t)i);
-        subset_reads_device(m.dQ, ids, part);
+        subset_reads_device(m.dQ, ids, part, false);
         total += sketch_device_into(part, m.opts.k, m.opts.w, m.opts.hpc, (uint32_t)a, (Mz *)dev_mz + total, cap - total,
                                     (uint32_t *)dev_counts + (a - lo));
         a = b;
@@ -151,7 +151,7 @@ void Job::sketch_all_queries() {
             DevReads part;
             std::vector<uint32_t> ids(b - a);
             for (size_t i = 0; i < ids.size(); ++i) ids[i] = (uint32_t)(a + i);
-            subset_reads_device(m.dQ, ids, part);
+            subset_reads_device(m.dQ, ids, part, false);
             parts.emplace_back();
             sketch_device(part, m.opts.k, m.opts.w, m.opts.hpc, (uint32_t)a, parts.back());
             first.push_back(a);
@@ -206,7 +206,9 @@ void Job::run(int rank, int world, int len_over, int mc, double iden, const char
         // scratch on divergent reads: the full C5 (265e9 left here of the card's 309e9 bytes) peaked at 298e9 with two lanes
         // against ~240e9 with one.  Lanes only where nearly the whole card is free: C2, C3, the short-read calls; not the full
         // C4 and C5, whose resident sketches and plans take 40-100 GB.
-        lanes_fit = (double)avail - plan >= 285e9;
+        // (the classifier's 2-bit copy of the reads is resident already; a sub-run's target subset brings its own)
+        const double packed_sub = (double)DevReads::packed_bytes(std::min<uint64_t>(m.T.off.empty() ? 0 : m.T.off.back(), 3ull << 30));
+        lanes_fit = (double)avail - plan - packed_sub >= 285e9;
         stat_set("lanes_fit", lanes_fit ? 1 : 0);
     }
     stat_set("subrun_out_budget_gb", SUBRUN_OUT_BYTES / 1e9);
