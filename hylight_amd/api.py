@@ -90,6 +90,13 @@ class VqNextStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in VQ_NEXT_STATS] + [(k, C.c_double) for k in VQ_NEXT_MS]
 
 
+VQ_CLIQUE_NEXT_STATS = VQ_NEXT_STATS + ("candidates", "max_list", "in_several")
+
+
+class VqCliqueNextStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in VQ_CLIQUE_NEXT_STATS] + [(k, C.c_double) for k in VQ_NEXT_MS]
+
+
 class ClusterOpts(C.Structure):
     _fields_ = [("size", C.c_int64), ("threads", C.c_int32), ("pad", C.c_int32), ("window_bytes", C.c_uint64)]
 
@@ -162,6 +169,9 @@ SYMBOLS = {
     "hlmi_vq_iteration": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqMergeOpts),
                                     C.POINTER(VqNextOpts), C.c_char_p, C.POINTER(VqGraphStats), C.POINTER(VqMergeStats),
                                     C.POINTER(VqNextStats)]),
+    "hlmi_vq_clique_iteration": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqCliqueOpts),
+                                           C.POINTER(VqNextOpts), C.c_char_p, C.POINTER(VqGraphStats), C.POINTER(VqCliqueStats),
+                                           C.POINTER(VqCliqueNextStats)]),
     "hlmi_vq_consensus_pair": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32,
                                          C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
     "hlmi_cluster_opts_default": (None, [C.POINTER(ClusterOpts)]),
@@ -458,6 +468,26 @@ def vq_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
     _check(load().hlmi_vq_iteration(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
                                     C.byref(go), C.byref(mo), C.byref(no), _b(out_dir), C.byref(gst), C.byref(mst), C.byref(nst)))
     return _stats(gst, VQ_GRAPH_STATS), _stats(mst, VQ_MERGE_STATS + VQ_MERGE_MS), _stats(nst, VQ_NEXT_STATS + VQ_NEXT_MS)
+
+
+def vq_clique_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
+    """hlmi_vq_clique_iteration: one clique iteration - the files of vq_cliques, then overlaps.txt (SRBuilder::findNextOverlaps
+    over the super-read lists of the vertices) and one line appended to stats.txt, in out_dir (created if missing).  The inputs
+    may lie in out_dir under the names written: they are read first.  Options: the fields of hlmi_vq_graph_opts,
+    hlmi_vq_clique_opts and hlmi_vq_next_opts, with the defaults of vq_cliques and vq_iteration.  -> (graph stats, clique
+    stats, next stats) as dicts; the next stats add candidates, max_list and in_several to those of vq_iteration."""
+    go, co, no = VqGraphOpts(), VqCliqueOpts(), VqNextOpts()
+    load().hlmi_vq_graph_opts_stageb(C.byref(go))
+    load().hlmi_vq_clique_opts_polyte(C.byref(co), int(bool(opts.get("error_correction", False))))
+    load().hlmi_vq_next_opts_stageb(C.byref(no))
+    _set_opts("vq_clique_iteration", (go, co, no), opts)
+    os.makedirs(out_dir, exist_ok=True)
+    gst, cst, nst = VqGraphStats(), VqCliqueStats(), VqCliqueNextStats()
+    _check(load().hlmi_vq_clique_iteration(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
+                                           C.byref(go), C.byref(co), C.byref(no), _b(out_dir), C.byref(gst), C.byref(cst),
+                                           C.byref(nst)))
+    return (_stats(gst, VQ_GRAPH_STATS), _stats(cst, VQ_CLIQUE_STATS + VQ_CLIQUE_MS),
+            _stats(nst, VQ_CLIQUE_NEXT_STATS + VQ_NEXT_MS))
 
 
 def vq_consensus_pair(seq1, qual1, seq2, qual2, pos):

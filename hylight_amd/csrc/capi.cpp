@@ -392,6 +392,18 @@ int hlmi_vq_cliques(const char *singles_fastq, const char *overlaps, const char 
     });
 }
 
+int hlmi_vq_clique_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in,
+                             const hlmi_vq_graph_opts *go, const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no,
+                             const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst,
+                             hlmi_vq_clique_next_stats *nst) {
+    return guarded([&] {
+        if (!singles_fastq || !overlaps || !go || !co || !no || !out_dir || !gst || !cst || !nst)
+            fail(HLMI_EINVAL, "hlmi_vq_clique_iteration: NULL argument");
+        require_device();
+        vq_clique_iteration_run(singles_fastq, overlaps, subreads_in, *go, *co, *no, out_dir, gst, cst, nst);
+    });
+}
+
 void hlmi_cluster_opts_default(hlmi_cluster_opts *o) {
     if (o) *o = hlmi_cluster_opts{15000, 20, 0, 0};            // HyLight.py --size, -t
 }

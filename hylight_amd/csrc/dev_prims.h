@@ -24,6 +24,7 @@ void sort_pairs_u32_u64(DBuf<uint32_t> &keys, DBuf<uint64_t> &vals, size_t n, in
 // out[i] = sum_{j<i} in[j]; returns nothing, total = out[n-1] + in[n-1] (use scan_total)
 void exclusive_scan_u32(const uint32_t *in, uint32_t *out, size_t n);
 void exclusive_scan_u32_to_u64(const uint32_t *in, uint64_t *out, size_t n);
+void exclusive_scan_u64(const uint64_t *in, uint64_t *out, size_t n);
 // writes the indices i with flags[i] != 0 (ascending) to out_idx; returns their count (the only call here that waits
 // for the device: the count goes back to the host)
 size_t select_flagged_indices(const uint8_t *flags, uint32_t *out_idx, size_t n);

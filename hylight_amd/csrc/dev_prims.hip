@@ -165,6 +165,14 @@ void exclusive_scan_u32_to_u64(const uint32_t *in, uint64_t *out, size_t n) {
     HIP_CHECK(rocprim::exclusive_scan(tmp.p, tmp_bytes, in64, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), stream()));
 }
 
+void exclusive_scan_u64(const uint64_t *in, uint64_t *out, size_t n) {
+    if (!n) return;
+    size_t tmp_bytes = 0;
+    HIP_CHECK(rocprim::exclusive_scan(nullptr, tmp_bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), stream()));
+    DBuf<char> tmp(tmp_bytes ? tmp_bytes : 1);
+    HIP_CHECK(rocprim::exclusive_scan(tmp.p, tmp_bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), stream()));
+}
+
 // Three small launches instead of rocprim::select: set bits per 64 flags (ballot), their exclusive scan, scatter by
 // ballot rank.  The flags are read twice (1 B each); on the 5e7-element head arrays of the anchor batches this is
 // several times quicker than the look-back partition, and most calls of a step are such selections.

@@ -622,11 +622,17 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
     }
     st->edges_final = g.edge_count();
     if (keep) {                                           // what SRBuilder reads (vq_superread_run.cpp)
+        const auto unsorted = g.out;                      // what the --cliques=true branch walks: it never runs the sort below
         sort_edges(g);                                    // ViralQuasispecies.cpp:434, in front of mergeAlongEdges
         keep->built = true;
         keep->out.resize(g.V);
         for (uint32_t u = 0; u < g.V; ++u)
             for (uint32_t e : g.out[u]) keep->out[u].push_back(g.pool[e]);
+        if (for_next && unsorted != g.out) {              // a tie moved: only findNextOverlaps behind the cliques reads this
+            keep->out_unsorted.resize(g.V);
+            for (uint32_t u = 0; u < g.V; ++u)
+                for (uint32_t e : unsorted[u]) keep->out_unsorted[u].push_back(g.pool[e]);
+        }
         keep->orient = lab.orient;
         keep->incl = incl;
         keep->tip = tip;

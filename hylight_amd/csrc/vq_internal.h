@@ -6,7 +6,7 @@
 //   merge  vq_merge.hip                          super-reads along its edges (SRBuilder::mergeAlongEdges)
 //   cliques  vq_clique_host.cpp / vq_clique.hip  the maximal cliques of the graph, one pile-up consensus each (--cliques=true)
 //   superread  vq_superread.cpp / .._run.cpp     what the two share through constructSuperread (pure host) / their drivers
-//   next   vq_next.hip                           the overlaps of the next iteration (SRBuilder::findNextOverlaps)
+//   next   vq_next.hip                           the overlaps of the next iteration (SRBuilder::findNextOverlaps), behind either
 // Everything on the device runs on the library's stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -184,7 +184,12 @@ struct VqGraphState {
     // [incl_off[l], incl_off[l + 1])
     std::vector<VqSrcEdge> branching, nonedge, incl_edges;
     std::vector<uint32_t> incl_off;
+    // for_next: the out-lists as the cycle removal left them, kept only where the sortEdges of :434 moved an edge.  The
+    // --cliques=true branch never runs that sort (ViralQuasispecies.cpp:417-428), so this is the adj_out its findNextOverlaps
+    // walks; std::sort may move the ties of a list of more than 16 edges that was sorted before
+    std::vector<std::vector<VqEdge>> out_unsorted;
 };
+inline const std::vector<std::vector<VqEdge>> &vq_cliques_out(const VqGraphState &g) { return g.out_unsorted.empty() ? g.out : g.out_unsorted; }
 // for_next: also keep what findNextOverlaps reads, and refuse a paired-end non-edge row before a file is written
 void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st,
                   VqGraphState *keep = nullptr, bool for_next = false);
@@ -340,19 +345,32 @@ constexpr uint32_t NONE = 0xffffffffu;
 constexpr uint32_t LINE_WIDTH = 64;              // lines up to this many bytes are ordered on the device (8 words of 8 bytes)
 constexpr int SEARCH_STEPS = 33;                 // a binary search over fewer than 2^32 entries ends within this many steps
 }  // namespace vqn
-// What the merge leaves per vertex (the columns of superread_map.txt and the new reads' lengths)
+// What SRBuilder leaves per vertex for updateOverlap: nodes_to_SR as a CSR over the vertices, one (new id, findCliqueIndex)
+// per entry in ascending id, and the new reads' lengths.  An unvisited vertex that was copied is a list of one entry, its new
+// id at index 0, and flagged; a visited vertex in no super-read (too short, N rate, diverted) is an empty list.
 struct VqNextTables {
-    std::vector<uint32_t> ent;                   // new id of the read or of its super-read; NONE: visited without a super-read
-    std::vector<uint8_t> in_sr;                  // 1: ent is a super-read
-    std::vector<uint32_t> off;                   // offset of the read in it (0 for a copied read)
-    std::vector<uint32_t> len;                   // length of the new read `ent`
+    std::vector<uint32_t> start;                 // list of vertex v: entries [start[v], start[v + 1])
+    std::vector<uint32_t> id;                    // new id of the super-read (of the copied read)
+    std::vector<int32_t> idx;                    // index1 - startpos1 of the vertex in it: SIGNED (negative in front of trim_pos)
+    std::vector<uint8_t> copied;                 // per vertex
+    std::vector<uint32_t> len;                   // per new id: the read's length
 };
+struct VqMember { uint32_t vertex, id; int32_t idx; };          // one member of kept super-read `id`
+// vq_superread.cpp (pure host): members = those of the kept super-reads 0 .. n_superreads - 1 in ascending id, lone = the records
+// vq_lone_reads made (ids from n_superreads on)
+VqNextTables vq_next_tables(uint32_t n_vertices, const std::vector<VqMember> &members, size_t n_superreads,
+                            const std::vector<uint32_t> &superread_len, const std::vector<vqm::Rec> &lone);
+void vq_next_tables_check(const VqNextTables &t, uint32_t n_vertices);      // HLMI_EINVAL: an index the device would follow out of bounds
 void vq_next_opts_stageb(hlmi_vq_next_opts *o);
-// -> the image of overlaps.txt
-std::string vq_next_run(const VqGraphState &g, const VqNextTables &t, double edge_threshold, const hlmi_vq_next_opts &no,
-                        hlmi_vq_next_stats *st);
+// -> the image of overlaps.txt.  out = the out-lists that are source group 1 and that checkEdge walks: g.out behind a merge,
+// vq_cliques_out(g) behind the cliques.  HLMI_EINVAL: 2^32 - 1 candidates and more.
+std::string vq_next_run(const VqGraphState &g, const std::vector<std::vector<VqEdge>> &out, const VqNextTables &t,
+                        double edge_threshold, const hlmi_vq_next_opts &no, hlmi_vq_clique_next_stats *st);
 void vq_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
                       const hlmi_vq_merge_opts &mo, const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst,
                       hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst);
+void vq_clique_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                             const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst,
+                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst);
 
 }  // namespace hlmi

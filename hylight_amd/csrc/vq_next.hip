@@ -1,14 +1,19 @@
-// vq_next.hip - SRBuilder::findNextOverlaps with --FNO=1 --optimize=false --cliques=false --error_correction=false
-// --threads 1 (tools/HaploConduct/src, FindNextOverlaps.cpp:25-327 updateOverlap, :331-347 findCliqueIndex, :351-385 the S-S
-// branch of computeOverlapData, :605-631, :635-697, :816-887, :890-958; ViralQuasispecies.cpp:449-479): the overlaps of the
-// next stage-b iteration.  The reference pushes every source edge through updateOverlap and inserts each line as text into a
-// std::set<std::string>; here a thread per source edge works out case and claim key, a stable radix sort of (key, sequence
-// number) and its run heads decide the claims, a thread per line writes the text, and LSD radix passes over the lines'
-// 8-byte big-endian words order them.  The rules are in include/hylight_mi.h.
+// vq_next.hip - SRBuilder::findNextOverlaps with --FNO=1 --optimize=false --threads 1, behind mergeAlongEdges and behind
+// cliquesToSuperreads (tools/HaploConduct/src, FindNextOverlaps.cpp:25-327 updateOverlap, :331-347 findCliqueIndex, :351-385
+// the S-S branch of computeOverlapData, :605-631, :635-697, :816-887, :890-958; ViralQuasispecies.cpp:449-479): the overlaps
+// of the next iteration.  The reference pushes every source edge through updateOverlap, which loops over the super-reads of
+// u, of v or over their product (nodes_to_SR, :896-913), and inserts each line as text into a std::set<std::string>; here a
+// thread per source edge counts its loop turns, one scan numbers them - the number IS the reference's loop order -, a thread
+// per turn (a candidate) works out case, ids and claim key, a stable radix sort of (key, candidate number) and its run heads
+// decide the claims, a thread per line writes the text, and LSD radix passes over the lines' 8-byte big-endian words order
+// them.  After a merge every list has one entry at the most and a candidate is a source edge: case_kernel makes the candidate
+// records directly, as it did before the lists (count, scan and search cost the merge iteration 0.4 of its 2.1 ms, DESIGN.md
+// 4.3d); everything behind the records is one code for both callers.  The rules are in include/hylight_mi.h.
 // PARITY UNPINNED: the reference needs Boost and cannot be built here; tests/vq_next_model.py restates it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <string_view>
 #include <vector>
@@ -27,8 +32,15 @@ constexpr uint64_t NO_KEY = ~0ull;
 enum { C_COPIED = 0, C_U2SR, C_V2SR, C_SR2SR, C_FAILED, C_MAXLEN, C_COUNT };
 
 struct Tab {                                     // VqNextTables and the vertex labels, on the device
-    const uint32_t *ent, *off, *len;
-    const uint8_t *in_sr, *orient;
+    const uint32_t *start, *id, *len;            // list of vertex v: entries [start[v], start[v + 1]); len per NEW read id
+    const int32_t *idx;                          // findCliqueIndex per entry: signed
+    const uint8_t *copied, *orient;              // per vertex
+};
+struct Cand {                                    // one turn of updateOverlap's loops (a copied edge: its one turn)
+    uint32_t edge;                               // its source edge
+    uint32_t id1, id2;                           // the new reads standing for u and for v
+    int32_t idx1, idx2;                          // where u lies in id1, v in id2
+    uint32_t kase;                               // 0 nothing (:255), 1 copied (:47), 2 u not in a super-read (:73), 3 v not (:151), 4 both (:229)
 };
 struct Graph {                                   // the final graph's edges as sorted (source << 32 | target) keys
     const uint64_t *key;                         // ascending; equal keys in list order (stable sort)
@@ -119,32 +131,93 @@ __global__ void count_flags_kernel(const uint8_t *flag, uint32_t first, uint32_t
     if (threadIdx.x == 0 && c) atomicAdd(out, c);
 }
 
-// updateOverlap's case per source edge: 0 nothing, 1 copied (:47), 2 u not in a super-read (:73), 3 v not (:151), 4 both in
-// one (:229); key = the pair it claims in overlaps_found, NO_KEY without a claim
-__global__ void case_kernel(const VqSrcEdge *rec, const uint8_t *valid, uint32_t n, Tab t, uint8_t *kase, uint64_t *key,
-                            uint32_t *seq) {
+// loop turns of updateOverlap per source edge: |list(u)| * |list(v)| - an unvisited vertex is a list of one, its copied read;
+// a visited vertex in no super-read is an empty list (nodes_to_SR.at() holds nothing) - and 0 for an edge that is left out.
+// cnt has n + 1 entries, the last one 0: their exclusive scan ends in the total.  A product is capped at 2^32, which the
+// total then reaches: the caller refuses it, and n < 2^32 such terms cannot wrap 64 bits.
+__global__ void count_kernel(const VqSrcEdge *rec, const uint8_t *valid, uint32_t n, Tab t, uint64_t *cnt) {
     const uint32_t i = blockIdx.x * WG + threadIdx.x;
-    if (i >= n) return;
-    uint8_t k = 0;
-    uint64_t claim = NO_KEY;
-    if (valid[i]) {
+    if (i > n) return;
+    uint64_t c = 0;
+    if (i < n && valid[i]) {
         const VqSrcEdge e = rec[i];
-        const uint32_t a = t.ent[e.v1], b = t.ent[e.v2];
-        if (a != NONE && b != NONE) {                        // a visited vertex without a super-read: nodes_to_SR is empty
-            const bool su = t.in_sr[e.v1], sv = t.in_sr[e.v2];
-            if (!su && !sv) k = 1;
-            else if (!(su && sv && a == b)) {                // :255 id1 == id2 is skipped before the claim
-                k = !su ? 2 : !sv ? 3 : 4;
-                claim = (uint64_t)min(a, b) << 32 | max(a, b);
-            }
-        }
+        c = (uint64_t)(t.start[e.v1 + 1] - t.start[e.v1]) * (t.start[e.v2 + 1] - t.start[e.v2]);
+        if (c > (1ull << 32)) c = 1ull << 32;
     }
-    kase[i] = k;
-    key[i] = claim;
-    seq[i] = i;
+    cnt[i] = c;
 }
 
-// the first source edge of a key owns it (:84-97)
+// One turn of updateOverlap for source edge `edge` = e: entry i of u's list against entry j of v's -> its record and the pair
+// it claims in overlaps_found (NO_KEY without a claim); true when the turn counts as a candidate (a claim is made)
+__device__ inline bool make_cand(const Tab &t, const VqSrcEdge &e, uint32_t edge, uint32_t i, uint32_t j, Cand &k, uint64_t &claim) {
+    const bool cu = t.copied[e.v1], cv = t.copied[e.v2];
+    k.edge = edge;
+    k.id1 = t.id[i]; k.id2 = t.id[j];
+    k.idx1 = t.idx[i]; k.idx2 = t.idx[j];
+    k.kase = 0;
+    claim = NO_KEY;
+    if (cu && cv) { k.kase = 1; return false; }
+    if (!cu && !cv && k.id1 == k.id2) return false;              // :255 id1 == id2 is skipped before the claim
+    k.kase = cu ? 2 : cv ? 3 : 4;
+    claim = (uint64_t)min(k.id1, k.id2) << 32 | max(k.id1, k.id2);
+    return true;
+}
+
+// Every list holds one entry at the most (always so behind a merge): a source edge has one turn or none and is its own
+// candidate.  One thread per source edge, as before the lists; no count, no scan, no search.
+__global__ void case_kernel(const VqSrcEdge *rec, const uint8_t *valid, uint32_t n, Tab t, Cand *cand, uint64_t *key,
+                            uint32_t *seq, uint32_t *turns) {
+    __shared__ uint32_t c_turns;
+    if (threadIdx.x == 0) c_turns = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * WG + threadIdx.x;
+    if (i < n) {
+        Cand k{};
+        uint64_t claim = NO_KEY;
+        k.edge = i;
+        if (valid[i]) {
+            const VqSrcEdge e = rec[i];
+            const uint32_t su = t.start[e.v1], sv = t.start[e.v2];
+            if (t.start[e.v1 + 1] > su && t.start[e.v2 + 1] > sv && make_cand(t, e, i, su, sv, k, claim)) atomicAdd(&c_turns, 1u);
+        }
+        cand[i] = k;
+        key[i] = claim;
+        seq[i] = i;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && c_turns) atomicAdd(turns, c_turns);
+}
+
+// Lists of several entries: one thread per candidate c.  Its source edge is the one with cstart[edge] <= c < cstart[edge + 1]
+// (cstart[n] = n_cand), the rest splits into (i, j) = (entry of u's list, entry of v's list), u's list outer as in :233-253;
+// seq = c, the reference's loop order
+__global__ void expand_kernel(const VqSrcEdge *rec, const uint64_t *cstart, uint32_t n, uint32_t n_cand, Tab t, Cand *cand,
+                              uint64_t *key, uint32_t *seq, uint32_t *turns) {
+    __shared__ uint32_t c_turns;
+    if (threadIdx.x == 0) c_turns = 0;
+    __syncthreads();
+    const uint32_t c = blockIdx.x * WG + threadIdx.x;
+    if (c < n_cand) {
+        uint32_t lo = 0, hi = n;                                 // cstart[lo] <= c < cstart[hi]
+        for (int it = 0; it < SEARCH_STEPS && hi - lo > 1; ++it) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (cstart[mid] <= c) lo = mid; else hi = mid;
+        }
+        const VqSrcEdge e = rec[lo];
+        const uint32_t su = t.start[e.v1], sv = t.start[e.v2], nu = t.start[e.v1 + 1] - su, nv = t.start[e.v2 + 1] - sv;
+        const uint32_t r = (uint32_t)(c - cstart[lo]);
+        Cand k{};
+        uint64_t claim = NO_KEY;
+        if (nv && r / nv < nu && make_cand(t, e, lo, su + r / nv, sv + r % nv, k, claim)) atomicAdd(&c_turns, 1u);   // (r < nu * nv)
+        cand[c] = k;
+        key[c] = claim;
+        seq[c] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && c_turns) atomicAdd(turns, c_turns);
+}
+
+// the first candidate of a key owns it (:84-97, :162-175, :261-273)
 __global__ void owner_kernel(const uint64_t *key, const uint32_t *seq, const uint32_t *heads, uint32_t runs, uint8_t *owner) {
     const uint32_t r = blockIdx.x * WG + threadIdx.x;
     if (r >= runs) return;
@@ -163,18 +236,19 @@ __device__ inline uint32_t line_len(const Line &l) {
            digits_i(l.len2) + 6 + 12;                        // ord, ori1, ori2, "0", "s", "s"; 12 tabs
 }
 
-// one thread per source edge: the copied edges and the owners of a key produce their line's numbers (computeOverlapData)
-__global__ void eval_kernel(const VqSrcEdge *rec, const uint8_t *kase, const uint8_t *owner, uint32_t n, Tab t, int no_incl,
+// one thread per candidate: the copied edges and the owners of a key produce their line's numbers (computeOverlapData)
+__global__ void eval_kernel(const VqSrcEdge *rec, const Cand *cand, const uint8_t *owner, uint32_t n, Tab t, int no_incl,
                             Line *line, uint32_t *llen, uint8_t *has, uint32_t *counters) {
     __shared__ uint32_t c[C_COUNT];
     if (threadIdx.x < C_COUNT) c[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t i = blockIdx.x * WG + threadIdx.x;
     if (i < n) {
-        const uint8_t k = kase[i];
+        const Cand cd = cand[i];
+        const uint32_t k = cd.kase;
         Line l{};
         if (k == 1 || (k >= 2 && owner[i])) {
-            const VqSrcEdge e = rec[i];
+            const VqSrcEdge e = rec[cd.edge];
             l.o1 = l.o2 = '+';
             if (e.score0) {                                  // :34-37
                 l.o1 = e.ori1 == t.orient[e.v1] ? '+' : '-';
@@ -182,13 +256,12 @@ __global__ void eval_kernel(const VqSrcEdge *rec, const uint8_t *kase, const uin
             }
             bool ok = true;
             if (k == 1) {                                    // :49-67
-                l.a = t.ent[e.v1]; l.b = t.ent[e.v2];
+                l.a = cd.id1; l.b = cd.id2;
                 l.pos1 = e.pos1; l.pos2 = e.pos2; l.ord = e.ord;
                 l.perc = e.perc; l.len1 = e.len1; l.len2 = e.len2;
-            } else {                                         // :357-385
-                const int64_t idx1 = t.in_sr[e.v1] ? t.off[e.v1] : 0, idx2 = t.in_sr[e.v2] ? t.off[e.v2] : 0;
-                const int64_t len1 = t.len[e.v1], len2 = t.len[e.v2];
-                int64_t np = ((int64_t)e.pos1 + idx1) - idx2, len;
+            } else {                                         // :357-385; a copied read lies at 0 in itself
+                const int64_t len1 = t.len[cd.id1], len2 = t.len[cd.id2];
+                int64_t np = ((int64_t)e.pos1 + cd.idx1) - cd.idx2, len;
                 bool first = true;
                 if (np < 0) { first = false; np = -np; len = len2; } else len = len1;
                 int64_t ol = len - np;                             // std::min({len - new_pos1, len1, len2})
@@ -200,14 +273,14 @@ __global__ void eval_kernel(const VqSrcEdge *rec, const uint8_t *kase, const uin
                 } else {
                     const float f = fmaxf(__fdiv_rn((float)ol, (float)len1), __fdiv_rn((float)ol, (float)len2));
                     l.perc = (int32_t)floorf(__fmul_rn(f, 100.0f));
-                    l.a = first ? t.ent[e.v1] : t.ent[e.v2];
-                    l.b = first ? t.ent[e.v2] : t.ent[e.v1];
+                    l.a = first ? cd.id1 : cd.id2;
+                    l.b = first ? cd.id2 : cd.id1;
                     l.pos1 = (int32_t)np; l.pos2 = 0; l.ord = '-';
                     l.len1 = (int32_t)ol; l.len2 = 0;
                 }
             }
             if (ok && !(no_incl && l.perc == 100)) {         // :68, :145, :223, :320
-                l.kind = k;
+                l.kind = (uint8_t)k;
                 atomicAdd(&c[k - 1], 1u);
             }
         }
@@ -307,16 +380,17 @@ __global__ void gather_kernel(const uint8_t *text, const uint64_t *start, const 
 
 }  // namespace
 
-std::string vq_next_run(const VqGraphState &g, const VqNextTables &t, double edge_threshold, const hlmi_vq_next_opts &no,
-                        hlmi_vq_next_stats *st) {
+std::string vq_next_run(const VqGraphState &g, const std::vector<std::vector<VqEdge>> &out, const VqNextTables &t,
+                        double edge_threshold, const hlmi_vq_next_opts &no, hlmi_vq_clique_next_stats *st) {
     const uint32_t V = (uint32_t)g.seq.size();
     // the final graph, flattened in list order: source edges 1, and the keys of the existence test
     std::vector<VqSrcEdge> recs;
     std::vector<uint32_t> src, dst, rlen(V);
     std::vector<uint8_t> positive;
+    if (out.size() != V) fail(HLMI_EINVAL, "vq_next: %zu out-lists for %u vertices", out.size(), V);
     for (uint32_t u = 0; u < V; ++u) {
         rlen[u] = (uint32_t)g.seq[u].size();
-        for (const VqEdge &e : g.out[u]) {
+        for (const VqEdge &e : out[u]) {
             recs.push_back(vq_src_edge(e));
             src.push_back(u); dst.push_back(e.v2); positive.push_back(e.score > 0);
         }
@@ -338,18 +412,29 @@ std::string vq_next_run(const VqGraphState &g, const VqNextTables &t, double edg
         if (e.v1 >= V || e.v2 >= V) fail(HLMI_EINVAL, "vq_next: a source edge names vertex %u / %u of %u", e.v1, e.v2, V);
     for (const VqSrcEdge &e : g.incl_edges)
         if (e.v1 >= V || e.v2 >= V) fail(HLMI_EINVAL, "vq_next: an inclusion edge names vertex %u / %u of %u", e.v1, e.v2, V);
-    if (t.ent.size() != V || t.in_sr.size() != V || t.off.size() != V || t.len.size() != V || g.orient.size() != V)
-        fail(HLMI_EINVAL, "vq_next: the merge's tables do not cover the %u vertices", V);
+    vq_next_tables_check(t, V);
+    if (g.orient.size() != V) fail(HLMI_EINVAL, "vq_next: the labels do not cover the %u vertices", V);
     st->src_graph = n_g;
     st->src_branching = n_b;
+    uint32_t max_entries = 0;
+    for (uint32_t v = 0; v < V; ++v) {
+        const uint32_t l = t.start[v + 1] - t.start[v];
+        max_entries = std::max(max_entries, l);
+        if (!t.copied[v]) {
+            st->max_list = std::max<uint64_t>(st->max_list, l);
+            st->in_several += l >= 2;
+        }
+    }
     if (!n) return std::string();
 
-    DBuf<uint32_t> d_ent, d_off, d_len, d_rlen, d_src, d_dst, d_gval(n_g ? n_g : 1);
-    DBuf<uint8_t> d_in_sr, d_orient, d_positive;
+    DBuf<uint32_t> d_start, d_id, d_len, d_rlen, d_src, d_dst, d_gval(n_g ? n_g : 1);
+    DBuf<int32_t> d_idx;
+    DBuf<uint8_t> d_copied, d_orient, d_positive;
     DBuf<uint64_t> d_gkey(n_g ? n_g : 1);
-    d_ent.upload(t.ent); d_off.upload(t.off); d_len.upload(t.len); d_in_sr.upload(t.in_sr); d_orient.upload(g.orient);
+    d_start.upload(t.start); d_id.upload(t.id); d_idx.upload(t.idx); d_len.upload(t.len); d_copied.upload(t.copied);
+    d_orient.upload(g.orient);
     d_rlen.upload(rlen);
-    const Tab tab{d_ent.p, d_off.p, d_len.p, d_in_sr.p, d_orient.p};
+    const Tab tab{d_start.p, d_id.p, d_len.p, d_idx.p, d_copied.p, d_orient.p};
     if (n_g) {
         d_src.upload(src); d_dst.upload(dst); d_positive.upload(positive);
         hipLaunchKernelGGL(vqk::edge_keys_kernel, grid1(n_g), dim3(WG), 0, stream(), d_src.p, d_dst.p, (const uint32_t *)nullptr, n_g,
@@ -360,7 +445,7 @@ std::string vq_next_run(const VqGraphState &g, const VqNextTables &t, double edg
 
     DBuf<VqSrcEdge> d_rec(n);
     DBuf<uint8_t> valid(n);
-    DBuf<uint32_t> d_cnt(C_COUNT + 2);
+    DBuf<uint32_t> d_cnt(C_COUNT + 3);
     d_cnt.zero();
     if (!recs.empty()) HIP_CHECK(hipMemcpyAsync(d_rec.p, recs.data(), recs.size() * sizeof(VqSrcEdge), hipMemcpyHostToDevice, stream()));
     HIP_CHECK(hipMemsetAsync(valid.p, 1, n, stream()));
@@ -380,43 +465,84 @@ std::string vq_next_run(const VqGraphState &g, const VqNextTables &t, double edg
     }
     HIP_CHECK(hipGetLastError());
 
-    // case and key, then the claims: the first source edge of a key owns it
-    DBuf<uint8_t> kase(n), owner(n), has(n);
-    DBuf<uint64_t> key(n);
-    DBuf<uint32_t> seq(n), heads(n);
+    auto counters = [&] {
+        const std::vector<uint32_t> cnt = d_cnt.download(C_COUNT + 3);
+        st->copied = cnt[C_COPIED]; st->u2sr = cnt[C_U2SR]; st->v2sr = cnt[C_V2SR]; st->sr2sr = cnt[C_SR2SR];
+        st->claims_failed = cnt[C_FAILED];
+        st->src_nonedge = cnt[C_COUNT];
+        st->nonedge_skipped = n_ne - cnt[C_COUNT];
+        st->src_induced = cnt[C_COUNT + 1];
+        st->candidates = cnt[C_COUNT + 2];
+        return cnt[C_MAXLEN];
+    };
+    // Case, ids and key per candidate.  Lists of one entry at the most (behind a merge: always): a candidate is a source edge
+    // and case_kernel does what it did before the lists.  Otherwise the loop turns of every source edge are counted and
+    // numbered in the reference's order, and a thread per turn works them out.  The timers run on the second path only: the
+    // merge path is held to its time before the lists.
+    const bool lists = max_entries > 1;
+    auto timer = [&](const char *name) { return std::unique_ptr<KTimer>(lists ? new KTimer(name) : nullptr); };
+    uint32_t nc = n;
+    DBuf<uint64_t> cstart;
+    if (lists) {
+        DBuf<uint64_t> ccnt((size_t)n + 1);
+        cstart.alloc((size_t)n + 1);
+        {
+            auto kt = timer("vq_next_count");
+            hipLaunchKernelGGL(count_kernel, grid1((size_t)n + 1), dim3(WG), 0, stream(), d_rec.p, valid.p, n, tab, ccnt.p);
+            exclusive_scan_u64(ccnt.p, cstart.p, (size_t)n + 1);
+        }
+        HIP_CHECK(hipGetLastError());
+        const uint64_t n_cand64 = download_one(cstart.p + n);
+        if (n_cand64 >= (1ull << 32) - 1)
+            fail(HLMI_EINVAL, "vq_next: %llu and more candidates (2^32 - 1 and more)", (unsigned long long)n_cand64);
+        nc = (uint32_t)n_cand64;
+        if (!nc) { counters(); return std::string(); }
+    }
+    DBuf<Cand> cand(nc);
+    DBuf<uint8_t> owner(nc), has(nc);
+    DBuf<uint64_t> key(nc);
+    DBuf<uint32_t> seq(nc), heads(nc);
     owner.zero();
-    hipLaunchKernelGGL(case_kernel, grid1(n), dim3(WG), 0, stream(), d_rec.p, valid.p, n, tab, kase.p, key.p, seq.p);
-    sort_pairs_u64_u32(key.p, seq.p, n, 0, 64);                  // stable: a key's claimants stay in source order
-    const size_t runs = select_run_heads_u64(key.p, n, 0, heads.p);
-    hipLaunchKernelGGL(owner_kernel, grid1(runs), dim3(WG), 0, stream(), key.p, seq.p, heads.p, (uint32_t)runs, owner.p);
+    if (lists) {
+        auto kt = timer("vq_next_expand");
+        hipLaunchKernelGGL(expand_kernel, grid1(nc), dim3(WG), 0, stream(), d_rec.p, cstart.p, n, nc, tab, cand.p, key.p, seq.p,
+                           d_cnt.p + C_COUNT + 2);
+    } else {
+        hipLaunchKernelGGL(case_kernel, grid1(n), dim3(WG), 0, stream(), d_rec.p, valid.p, n, tab, cand.p, key.p, seq.p,
+                           d_cnt.p + C_COUNT + 2);
+    }
+    {                                                            // the claims: the first candidate of a key owns it
+        auto kt = timer("vq_next_claim_sort");
+        sort_pairs_u64_u32(key.p, seq.p, nc, 0, 64);             // stable: a key's claimants stay in loop order
+        const size_t runs = select_run_heads_u64(key.p, nc, 0, heads.p);
+        hipLaunchKernelGGL(owner_kernel, grid1(runs), dim3(WG), 0, stream(), key.p, seq.p, heads.p, (uint32_t)runs, owner.p);
+    }
 
-    DBuf<Line> line(n);
-    DBuf<uint32_t> llen((size_t)n + 1);
-    DBuf<uint64_t> start((size_t)n + 1);
+    DBuf<Line> line(nc);
+    DBuf<uint32_t> llen((size_t)nc + 1);
+    DBuf<uint64_t> start((size_t)nc + 1);
     llen.zero();
-    hipLaunchKernelGGL(eval_kernel, grid1(n), dim3(WG), 0, stream(), d_rec.p, kase.p, owner.p, n, tab, no.no_inclusion_overlaps ? 1 : 0,
-                       line.p, llen.p, has.p, d_cnt.p);
+    {
+        auto kt = timer("vq_next_eval");
+        hipLaunchKernelGGL(eval_kernel, grid1(nc), dim3(WG), 0, stream(), d_rec.p, cand.p, owner.p, nc, tab,
+                           no.no_inclusion_overlaps ? 1 : 0, line.p, llen.p, has.p, d_cnt.p);
+    }
     HIP_CHECK(hipGetLastError());
-    exclusive_scan_u32_to_u64(llen.p, start.p, (size_t)n + 1);
-    const std::vector<uint32_t> cnt = d_cnt.download(C_COUNT + 2);
-    st->copied = cnt[C_COPIED]; st->u2sr = cnt[C_U2SR]; st->v2sr = cnt[C_V2SR]; st->sr2sr = cnt[C_SR2SR];
-    st->claims_failed = cnt[C_FAILED];
-    st->src_nonedge = cnt[C_COUNT];
-    st->nonedge_skipped = n_ne - cnt[C_COUNT];
-    st->src_induced = cnt[C_COUNT + 1];
-    const uint32_t max_len = cnt[C_MAXLEN];
-    const uint64_t text_bytes = download_one(start.p + n);
+    exclusive_scan_u32_to_u64(llen.p, start.p, (size_t)nc + 1);
+    const uint32_t max_len = counters();
+    const uint64_t text_bytes = download_one(start.p + nc);
     if (!text_bytes) return std::string();
 
+    auto kt_order = timer("vq_next_order");
     DBuf<uint8_t> text(text_bytes);
-    hipLaunchKernelGGL(text_kernel, grid1(n), dim3(WG), 0, stream(), line.p, llen.p, start.p, n, text.p);
-    DBuf<uint32_t> perm(n);
-    const size_t n_l = select_flagged_indices(has.p, perm.p, n);
+    hipLaunchKernelGGL(text_kernel, grid1(nc), dim3(WG), 0, stream(), line.p, llen.p, start.p, nc, text.p);
+    DBuf<uint32_t> perm(nc);
+    const size_t n_l = select_flagged_indices(has.p, perm.p, nc);
 
     if (max_len > LINE_WIDTH) {                                  // a line wider than the device's order reads: the host's
         const std::vector<uint8_t> h_text = text.download(text_bytes);
-        const std::vector<uint64_t> h_start = start.download(n);
-        const std::vector<uint32_t> h_len = llen.download(n), h_idx = perm.download(n_l);
+        const std::vector<uint64_t> h_start = start.download(nc);
+        const std::vector<uint32_t> h_len = llen.download(nc), h_idx = perm.download(n_l);
         std::vector<std::string_view> lines;
         lines.reserve(n_l);
         for (uint32_t r : h_idx) lines.emplace_back((const char *)h_text.data() + h_start[r], h_len[r]);

@@ -286,4 +286,45 @@ VqLoneCounts vq_lone_reads(const VqGraphState &g, const VqOriginalsDict &dict, c
     return c;
 }
 
+// nodes_to_SR, nodes_to_new_IDs and findCliqueIndex as tables (FindNextOverlaps.cpp:896-913, :331-347, SRBuilder.cpp:1219): one
+// counting pass over the members, which come super-read after super-read in ascending id, so every list is ascending too
+VqNextTables vq_next_tables(uint32_t n_vertices, const std::vector<VqMember> &members, size_t n_superreads,
+                            const std::vector<uint32_t> &superread_len, const std::vector<vqm::Rec> &lone) {
+    if (superread_len.size() != n_superreads) fail(HLMI_EINVAL, "vq_next: %zu lengths for %zu super-reads", superread_len.size(), n_superreads);
+    VqNextTables t;
+    t.start.assign((size_t)n_vertices + 1, 0);
+    t.copied.assign(n_vertices, 0);
+    t.len = superread_len;
+    t.len.resize(n_superreads + lone.size(), 0);
+    for (const VqMember &m : members) {
+        if (m.vertex >= n_vertices || m.id >= n_superreads)
+            fail(HLMI_EINVAL, "vq_next: member %u of super-read %u (%u vertices, %zu super-reads)", m.vertex, m.id, n_vertices, n_superreads);
+        ++t.start[m.vertex + 1];
+    }
+    for (const vqm::Rec &r : lone) {             // an unvisited read that was copied: a list of one, itself at 0
+        if (r.a >= n_vertices || r.id < n_superreads || r.id >= t.len.size() || t.start[r.a + 1] || t.len[r.id])
+            fail(HLMI_EINVAL, "vq_next: copied read %u as new read %u", r.a, r.id);
+        t.start[r.a + 1] = 1;
+        t.copied[r.a] = 1;
+        t.len[r.id] = r.len;
+    }
+    for (uint32_t v = 0; v < n_vertices; ++v) t.start[v + 1] += t.start[v];
+    t.id.assign(t.start[n_vertices], 0);
+    t.idx.assign(t.start[n_vertices], 0);
+    std::vector<uint32_t> fill(t.start.begin(), t.start.end() - 1);
+    for (const VqMember &m : members) { t.id[fill[m.vertex]] = m.id; t.idx[fill[m.vertex]++] = m.idx; }
+    for (const vqm::Rec &r : lone) t.id[fill[r.a]] = r.id;
+    return t;
+}
+
+void vq_next_tables_check(const VqNextTables &t, uint32_t n_vertices) {
+    bool ok = t.start.size() == (size_t)n_vertices + 1 && t.copied.size() == n_vertices && t.start[0] == 0 && t.id.size() == t.idx.size() &&
+              t.id.size() < (1ull << 32);
+    for (uint32_t v = 0; ok && v < n_vertices; ++v)
+        ok = t.start[v] <= t.start[v + 1] && (!t.copied[v] || t.start[v + 1] - t.start[v] == 1);
+    ok = ok && t.start[n_vertices] == t.id.size();
+    for (size_t k = 0; ok && k < t.id.size(); ++k) ok = t.id[k] < t.len.size();
+    if (!ok) fail(HLMI_EINVAL, "vq_next: the tables do not cover the %u vertices", n_vertices);
+}
+
 }  // namespace hlmi

@@ -2,8 +2,10 @@
 //   merge_and_next   --cliques=false --error_correction=false --threads 1 (ViralQuasispecies.cpp:413-447, mergeAlongEdges,
 //                    SRBuilder.cpp:1238-1384) behind hlmi_vq_merge / hlmi_vq_iteration: the greedy merge list, each pair placed as
 //                    a clique of two, the drops, the text files; vq_merge.hip reads, combines and lays out the bases
-//   vq_cliques_run   --cliques=true, single-end (cliquesToSuperreads, :1031-1235): the cliques of vq_clique_host.cpp placed, one
-//                    pile-up consensus each in vq_clique.hip, the drops, the text files; vq_cliques_of_graph: the enumerator alone
+//   cliques_and_next --cliques=true, single-end (cliquesToSuperreads, :1031-1235) behind hlmi_vq_cliques / hlmi_vq_clique_iteration:
+//                    the cliques of vq_clique_host.cpp placed, one pile-up consensus each in vq_clique.hip, the drops, the text
+//                    files; vq_cliques_of_graph: the enumerator alone
+// Both end, when asked, in findNextOverlaps (vq_next.hip) over the lists vq_next_tables builds of what they placed.
 // and hlmi_vq_consensus_pair with the three option defaults.  PARITY UNPINNED, as vq_superread.cpp says.
 #include <algorithm>
 #include <cstring>
@@ -61,6 +63,17 @@ void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint3
 // original_ID_dict of a run that is not the first iteration: the lines of its subreads file
 static void read_originals(VqOriginalsDict &d) {
     if (!d.first_it) d.dict = vq_parse_subreads(read_file(d.subreads_in), d.subreads_in);
+}
+
+// ViralQuasispecies.cpp:449-479 behind either builder: overlaps.txt and the line of stats.txt
+static void next_and_stats(const VqGraphState &g, const std::vector<std::vector<VqEdge>> &out, const VqNextTables &t,
+                           const hlmi_vq_graph_opts &go, const hlmi_vq_next_opts &no, const char *out_dir, const hlmi_vq_graph_stats *gst,
+                           hlmi_vq_clique_next_stats *nst) {
+    const std::string image = vq_next_run(g, out, t, go.edge_threshold, no, nst);
+    write_file(join_path(out_dir, "overlaps.txt"), image.data(), image.size());
+    const std::string line = std::to_string(gst->vertices) + "\t" + std::to_string(gst->edges_final) + "\t" +
+                             std::to_string(nst->lines) + "\n";
+    write_file(join_path(out_dir, "stats.txt"), line.data(), line.size(), "ab");
 }
 
 // hlmi_vq_merge (no == NULL) and hlmi_vq_iteration: one path.  With `no` the call goes on to findNextOverlaps, and reads
@@ -122,6 +135,8 @@ static void merge_and_next(const char *fastq, const char *overlaps, const char *
     std::vector<uint8_t> visited(V, 0);
     std::vector<int64_t> new_id(V, -1);
     std::vector<uint32_t> offset(V, 0);
+    std::vector<VqMember> sr_members;            // of the kept super-reads: what findNextOverlaps reads of them
+    std::vector<uint32_t> sr_len;
     std::string subreads;
     size_t ci = 0;
     for (Rec r : placed) {
@@ -138,7 +153,9 @@ static void merge_and_next(const char *fastq, const char *overlaps, const char *
             visited[v] = 1;
             new_id[v] = r.id;
             offset[v] = (uint32_t)idx1;
+            sr_members.push_back(VqMember{v, r.id, (int32_t)idx1});
         }
+        sr_len.push_back(r.len);
         vq_subreads_line(subreads, r.id, merged);
         recs.push_back(r);
     }
@@ -176,17 +193,14 @@ static void merge_and_next(const char *fastq, const char *overlaps, const char *
     mst->ms_merge = now_ms() - t0;
     if (no) {                                                    // ViralQuasispecies.cpp:449-479
         const double t1 = now_ms();
-        VqNextTables t;
-        t.ent.resize(V); t.in_sr = visited; t.off = offset; t.len.assign(V, 0);
-        for (uint32_t v = 0; v < V; ++v) {
-            t.ent[v] = new_id[v] < 0 ? vqn::NONE : (uint32_t)new_id[v];
-            if (new_id[v] >= 0) t.len[v] = recs[(size_t)new_id[v]].len;
-        }
-        const std::string image = vq_next_run(g, t, go.edge_threshold, *no, nst);
-        write_file(join_path(out_dir, "overlaps.txt"), image.data(), image.size());
-        const std::string line = std::to_string(gst->vertices) + "\t" + std::to_string(gst->edges_final) + "\t" +
-                                 std::to_string(nst->lines) + "\n";
-        write_file(join_path(out_dir, "stats.txt"), line.data(), line.size(), "ab");
+        // a merged vertex is a list of one super-read, a copied one a list of itself: the lists of at most one entry
+        const std::vector<Rec> lone(recs.begin() + (ptrdiff_t)mst->merged, recs.begin() + (ptrdiff_t)n_singles);
+        hlmi_vq_clique_next_stats x{};
+        next_and_stats(g, g.out, vq_next_tables(V, sr_members, mst->merged, sr_len, lone), go, *no, out_dir, gst, &x);
+        nst->src_graph = x.src_graph; nst->src_branching = x.src_branching; nst->src_nonedge = x.src_nonedge;
+        nst->nonedge_skipped = x.nonedge_skipped; nst->src_induced = x.src_induced;
+        nst->copied = x.copied; nst->u2sr = x.u2sr; nst->v2sr = x.v2sr; nst->sr2sr = x.sr2sr;
+        nst->claims_failed = x.claims_failed; nst->lines = x.lines;
         nst->ms_next = now_ms() - t1;
     }
     ktimer_flush();
@@ -209,21 +223,25 @@ void vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uint64_
     *n_cliques = list.off.size() - 1;
 }
 
-void vq_cliques_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                    const hlmi_vq_clique_opts &co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst) {
+// hlmi_vq_cliques (no == NULL) and hlmi_vq_clique_iteration: one path, as merge_and_next is
+static void cliques_and_next(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                             const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
+                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst) {
     using namespace vqc;
     *cst = hlmi_vq_clique_stats{};
+    if (nst) *nst = hlmi_vq_clique_next_stats{};
     if (co.min_clique_size == 0 || co.min_clique_size > MAX_MIN_CLIQUE)
         fail(HLMI_EINVAL, "vq_cliques: min_clique_size %u is outside 1 .. %u", co.min_clique_size, MAX_MIN_CLIQUE);
     VqOriginalsDict dict("vq_cliques", co.first_it != 0, subreads_in);
     const uint32_t mcs = co.min_clique_size;
+    if (no) read_originals(dict);                // in place: subreads_in may be the subreads.txt written below
     VqGraphState g;
-    vq_graph_run(fastq, overlaps, go, out_dir, gst, &g, false);
+    vq_graph_run(fastq, overlaps, go, out_dir, gst, &g, no != nullptr);
     if (!g.built) return;                        // ViralQuasispecies.cpp:282-291: nothing to be done
     const double t0 = now_ms();
     const uint32_t V = (uint32_t)g.seq.size();
     for (uint32_t v = 0; v < V; ++v) cst->bases_in += g.seq[v].size();
-    read_originals(dict);
+    if (!no) read_originals(dict);
 
     // cliques.txt (ViralQuasispecies.cpp:400-410)
     const VqCliqueList list = vq_enumerate_cliques(read_file(join_path(out_dir, "graph.txt").c_str()));
@@ -292,6 +310,8 @@ void vq_cliques_run(const char *fastq, const char *overlaps, const char *subread
     // process_cliques (:998-1001), writeSinglesToFile, the originals (:750-806)
     std::string fastq_text, subreads, cmap;
     std::vector<uint8_t> visited(V, 0);
+    std::vector<VqMember> sr_members;            // of the kept super-reads: what findNextOverlaps reads of them
+    std::vector<uint32_t> sr_len;
     uint32_t count = 0;
     for (const Placed &P : placed) {
         const Pile &pl = piles[P.pile];
@@ -330,8 +350,10 @@ void vq_cliques_run(const char *fastq, const char *overlaps, const char *subread
         for (const auto &pv : P.all) {
             cmap += '\t'; cmap += std::to_string(pv.second); cmap += ':'; cmap += std::to_string(pv.first - (int64_t)pl.trim_pos);
             cmap += ':'; cmap += g.orient[pv.second] ? '+' : '-';
+            if (no) sr_members.push_back(VqMember{pv.second, count, (int32_t)(pv.first - (int64_t)pl.trim_pos)});
         }
         cmap += '\n';
+        sr_len.push_back(len);
         ++count;
     }
     cst->superreads = count;
@@ -355,6 +377,23 @@ void vq_cliques_run(const char *fastq, const char *overlaps, const char *subread
     stat_set("vq_clique_ms_device", t_device - t_placed);
     stat_set("vq_clique_ms_finish", t0 + cst->ms_cliques - t_device);
     stat_set("vq_clique_piles", (double)piles.size());
+    if (no) {                                    // ViralQuasispecies.cpp:449-479
+        const double t1 = now_ms();
+        next_and_stats(g, vq_cliques_out(g), vq_next_tables(V, sr_members, count, sr_len, recs), go, *no, out_dir, gst, nst);
+        nst->ms_next = now_ms() - t1;
+        ktimer_flush();
+    }
+}
+
+void vq_cliques_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                    const hlmi_vq_clique_opts &co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst) {
+    cliques_and_next(fastq, overlaps, subreads_in, go, co, nullptr, out_dir, gst, cst, nullptr);
+}
+
+void vq_clique_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
+                             const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst,
+                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst) {
+    cliques_and_next(fastq, overlaps, subreads_in, go, co, &no, out_dir, gst, cst, nst);
 }
 
 }  // namespace hlmi

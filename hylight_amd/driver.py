@@ -18,9 +18,10 @@ The short-read branch (HyLight.py:211-275) is opt-in: `--stop_after clusters` ru
 (hlmi_cluster_short: readnames.txt, the grouped JSON and fq_<size>/ in tmp/) and exits 0; `--polyte_cmd PREFIX`, without
 `--short_contigs`, also runs POLYTE per cluster through PREFIX (the reference's polyte.tune_params.py, external), collects
 tmp/all.contigs_<size>.fasta, extends it into short_stageb.fa (with `--stageb_cmd`) and builds all_contigs.fa from it and
-long_con_polished.fa.  Without these flags the run is the same as before.  POLYTE's clique step exists natively
-(python -m hylight_amd.vq_cliques); `--polyte_cmd` is not rewired to it: a clique-aware findNextOverlaps, BranchReduction
-and POLYTE's --min_qual=0 (the native step keeps minQual 0.9) are still missing.
+long_con_polished.fa.  Without these flags the run is the same as before.  POLYTE's clique iteration exists natively and now
+ends in overlaps.txt (python -m hylight_amd.vq_cliques --iteration: hlmi_vq_clique_iteration, findNextOverlaps over the
+super-read lists); `--polyte_cmd` stays external and is not rewired to it: BranchReduction, paired-end reads and POLYTE's
+--min_qual=0 (the native step keeps minQual 0.9) are still missing.
 
 `--gpus N` (extension): every split_reads2 call is sharded over N GPUs of the node, chunk i -> rank i % N, the way the
 reference fans its chunks out with `xargs -P` (script/utils.py:44-69).  The process starts N - 1 further copies of

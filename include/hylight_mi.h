@@ -456,14 +456,71 @@ typedef struct {
  * :261-273): the first source edge in the order above owns the pair, later ones are dropped, and when the owner's
  * computeOverlapData fails the pair gets no line.  Copied edges never consult the table.  ori1 / ori2: for a score-0 edge
  * '+' where the edge's orientation equals the vertex label, else '-' (:34-37); '+' for every other edge.
- * Device: one thread per source edge for case and key, a stable radix sort of (key, sequence number) and its run heads for
- * the claims, one thread per line for the text, LSD radix passes over the lines' 8-byte big-endian words for the order (a
+ * Device: one thread per source edge for case and key (a candidate in the words of hlmi_vq_clique_iteration, whose lists make
+ * several of one edge), a stable radix sort of (key, sequence number) and its run heads for the claims, one thread per line for the text, LSD radix passes over the lines' 8-byte big-endian words for the order (a
  * line padded with zero bytes orders as the string does) - lines longer than 64 bytes make the call order on the host.
  * Refused with HLMI_ESTATE before anything is written: a paired-end row ('p') among the candidates or the non-edge rows.
- * add_duplicates and resolve_orientations = false are not options; FindNextOverlaps3 and cliques are not built. */
+ * add_duplicates and resolve_orientations = false are not options; FindNextOverlaps3 is not built; behind the cliques:
+ * hlmi_vq_clique_iteration. */
 int hlmi_vq_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
                       const hlmi_vq_merge_opts *mo, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
                       hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst);
+
+/* ---- findNextOverlaps behind the cliques: ViralQuasispecies --cliques=true --FNO=1 --optimize=false --threads 1 on
+ * single-end reads to the end of main - what POLYTE runs in the first iteration of every cluster and in every
+ * branch-reduction iteration (polyte.tune_params.py:607-645, --FNO=1 at :698). */
+typedef struct {
+    uint64_t src_graph, src_branching, src_nonedge, nonedge_skipped, src_induced;   /* as hlmi_vq_next_stats               */
+    uint64_t copied, u2sr, v2sr, sr2sr;
+    uint64_t claims_failed;
+    uint64_t lines;
+    uint64_t candidates;        /* turns of updateOverlap's three loops (:78, :156, :233-253) after the id1 == id2 skip of  */
+                                /* :255; a copied edge (:47-72) runs no loop and is not counted                             */
+    uint64_t max_list;          /* the longest super-read list of a vertex (nodes_to_SR, :896-913)                          */
+    uint64_t in_several;        /* vertices in two or more kept super-reads                                                 */
+    double ms_next;             /* wall time of the step after the clique step                                              */
+} hlmi_vq_clique_next_stats;
+/* One clique iteration: hlmi_vq_cliques (same code, same files in out_dir), then overlaps.txt and one line APPENDED to
+ * stats.txt, both exactly as hlmi_vq_iteration documents them.  All inputs are read before any output is written, so
+ * singles_fastq, overlaps and subreads_in may lie in out_dir under the names written here.  When the graph has no edge the
+ * call stops where hlmi_vq_cliques stops: no overlaps.txt, no stats.txt line.
+ * What differs from hlmi_vq_iteration is one fact: behind mergeAlongEdges a vertex lies in one super-read at the most, behind
+ * cliquesToSuperreads in a LIST of them, and updateOverlap loops over the list of u, of v, or over their product.
+ *   the list      (FindNextOverlaps.cpp:896-913) of vertex v: the KEPT super-reads whose sorted_clique(0) holds v - every
+ *                 member of the clique, those filter_subreads left out of the pile-up included (SRBuilder.cpp:864) - in
+ *                 ascending super-read id (single_SR_vec order, :900-906).  A dropped clique (empty consensus, N rate, no
+ *                 support) adds nothing
+ *   visited       (SRBuilder.cpp:1125-1160) the members of kept super-reads; an unvisited vertex that is shorter than
+ *                 keep_singletons or fails the N rate is marked visited with an EMPTY list - every source edge at it gives
+ *                 nothing -; every other unvisited vertex is copied under a new id (nodes_to_new_IDs, :1219)
+ *   index         findCliqueIndex (:331-347) = index1 - startpos1 of calcSubreadInfo (SRBuilder.cpp:536-595) = the offset
+ *                 column of clique_map.txt: NEGATIVE for a read that starts in front of trim_pos under error correction.
+ *                 new_pos1 = pos1 + idx(u) - idx(v) (:360) is signed arithmetic throughout
+ *   loop order    per source edge u -> v (:47, :73, :151, :229): both unvisited: copied; u unvisited: the list of v (:78); v
+ *                 unvisited: the list of u (:156); both visited: the list of u outer, the list of v inner (:233, :253), and
+ *                 id1 == id2 is skipped BEFORE the claim (:255).  Every turn claims (min id, max id) in overlaps_found before
+ *                 computeOverlapData runs (:84-97, :162-175, :261-273): the first turn in source-edge order, then loop order,
+ *                 owns the pair, and an owner that fails (new_pos1 >= len, :378-384) leaves the pair without a line though a
+ *                 later turn might have succeeded
+ *   source edges  the four groups of hlmi_vq_iteration in its order, with one difference in group 1: the --cliques=true branch
+ *                 never runs the sortEdges of ViralQuasispecies.cpp:434 (:417-428), so reconsiderEdgeOverlaps (:612) and
+ *                 checkEdge walk each out-list as cycleRemovalHeuristic left it: the order of the sortEdges of :359 without
+ *                 the back edges that were removed.  The two orders differ only where std::sort moves tying keys of a sorted
+ *                 list (more than 16 edges, two of one length to one target); this call carries the unsorted lists then.
+ *                 What hlmi_vq_cliques writes does not depend on it and is unchanged
+ * Device: one thread per source edge counts its turns (|list(u)| * |list(v)|, 64 bits), one exclusive scan numbers them, one
+ * thread per turn finds its edge by binary search and works out case, ids, indices and claim key; the turn's number is the
+ * reference's loop order and the sequence number of the stable claim sort.  No thread or wave loops over a list: a vertex in
+ * hundreds of super-reads costs as many threads as it has turns.  Everything behind that - claims, computeOverlapData, text,
+ * order - is hlmi_vq_iteration's code; there, and wherever no list holds more than one entry, a source edge is its own turn
+ * and needs no count, scan or search.
+ * HLMI_EINVAL: 2^32 - 1 turns and more in one call (the limit of the sequence numbers); what hlmi_vq_cliques refuses.
+ * HLMI_ESTATE: a paired-end row among the candidates or the non-edge rows.  Paired-end reads, add_duplicates,
+ * FindNextOverlaps3 (--FNO=3), BranchReduction and --min_qual=0 are not built, as for hlmi_vq_cliques. */
+int hlmi_vq_clique_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in,
+                             const hlmi_vq_graph_opts *go, const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no,
+                             const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst,
+                             hlmi_vq_clique_next_stats *nst);
 
 /* ---- short-read clustering (HyLight.py:215-226: get_readnames.py, bin_pointer_limited_filechunks_shortpath2.py,
  * getclusters.py, get_fq_cluster.py with cwd = tmp/ and run id HiStrain).  Parity pinned: tests/golden/fxH_cluster_*.json
