@@ -97,6 +97,19 @@ class VqCliqueNextStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in VQ_CLIQUE_NEXT_STATS] + [(k, C.c_double) for k in VQ_NEXT_MS]
 
 
+class VqBranchOpts(C.Structure):
+    _fields_ = [("se_count", C.c_uint32), ("pe_count", C.c_uint32), ("careful", C.c_int)]
+
+
+VQ_BRANCH_STATS = ("in_branches", "out_branches", "pairs", "diff_positions", "work_items", "evidence_ids", "missing_edges",
+                   "false_branches", "inclusion_pairs", "components", "components_kept", "dist_too_large", "scheduled", "edges_removed")
+VQ_BRANCH_MS = ("ms_diff", "ms_evidence", "ms_branch")
+
+
+class VqBranchStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in VQ_BRANCH_STATS] + [(k, C.c_double) for k in VQ_BRANCH_MS]
+
+
 class ClusterOpts(C.Structure):
     _fields_ = [("size", C.c_int64), ("threads", C.c_int32), ("pad", C.c_int32), ("window_bytes", C.c_uint64)]
 
@@ -171,6 +184,13 @@ SYMBOLS = {
                                     C.POINTER(VqNextStats)]),
     "hlmi_vq_clique_iteration": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqCliqueOpts),
                                            C.POINTER(VqNextOpts), C.c_char_p, C.POINTER(VqGraphStats), C.POINTER(VqCliqueStats),
+                                           C.POINTER(VqCliqueNextStats)]),
+    "hlmi_vq_branch_opts_polyte": (None, [C.POINTER(VqBranchOpts)]),
+    "hlmi_vq_branch_graph": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts),
+                                       C.POINTER(VqBranchOpts), C.c_char_p, C.POINTER(VqGraphStats), C.POINTER(VqBranchStats)]),
+    "hlmi_vq_branch_iteration": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts),
+                                           C.POINTER(VqBranchOpts), C.POINTER(VqCliqueOpts), C.POINTER(VqNextOpts), C.c_char_p,
+                                           C.POINTER(VqGraphStats), C.POINTER(VqBranchStats), C.POINTER(VqCliqueStats),
                                            C.POINTER(VqCliqueNextStats)]),
     "hlmi_vq_consensus_pair": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32,
                                          C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
@@ -487,6 +507,51 @@ def vq_clique_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **op
                                            C.byref(go), C.byref(co), C.byref(no), _b(out_dir), C.byref(gst), C.byref(cst),
                                            C.byref(nst)))
     return (_stats(gst, VQ_GRAPH_STATS), _stats(cst, VQ_CLIQUE_STATS + VQ_CLIQUE_MS),
+            _stats(nst, VQ_CLIQUE_NEXT_STATS + VQ_NEXT_MS))
+
+
+def vq_branch_opts_polyte():
+    """hlmi_vq_branch_opts_polyte: careful on, the counts 0, as a dict."""
+    o = VqBranchOpts()
+    load().hlmi_vq_branch_opts_polyte(C.byref(o))
+    return {k: getattr(o, k) for k, _ in VqBranchOpts._fields_}
+
+
+def _branch_graph_opts(caller, structs, opts):
+    """The graph options of a branch-reduction run: the stage-b values with remove_branches off (the reduction takes its place)."""
+    load().hlmi_vq_graph_opts_stageb(C.byref(structs[0]))
+    structs[0].remove_branches = 0
+    load().hlmi_vq_branch_opts_polyte(C.byref(structs[1]))
+    _set_opts(caller, structs, opts)
+
+
+def vq_branch_graph(singles_fastq, overlaps, original_fastq, threshold_table, out_dir, subreads_in=None, **opts):
+    """hlmi_vq_branch_graph: ViralQuasispecies --graph_only with --branch_reduction=true - the files of vq_graph plus
+    branch_components.txt in out_dir (created if missing).  Options: the fields of hlmi_vq_graph_opts (stage-b values,
+    remove_branches off) and of hlmi_vq_branch_opts (se_count, pe_count, careful).  subreads_in None: every read is its own
+    original.  -> (graph stats, branch stats) as dicts."""
+    go, bo = VqGraphOpts(), VqBranchOpts()
+    _branch_graph_opts("vq_branch_graph", (go, bo), opts)
+    os.makedirs(out_dir, exist_ok=True)
+    gst, bst = VqGraphStats(), VqBranchStats()
+    _check(load().hlmi_vq_branch_graph(_b(singles_fastq), _b(overlaps), _b(subreads_in), _b(original_fastq), _b(threshold_table),
+                                       C.byref(go), C.byref(bo), _b(out_dir), C.byref(gst), C.byref(bst)))
+    return _stats(gst, VQ_GRAPH_STATS), _stats(bst, VQ_BRANCH_STATS + VQ_BRANCH_MS)
+
+
+def vq_branch_iteration(singles_fastq, overlaps, original_fastq, threshold_table, out_dir, subreads_in=None, **opts):
+    """hlmi_vq_branch_iteration: the graph of vq_branch_graph, then everything vq_clique_iteration does behind its graph.
+    Options: those of vq_branch_graph and of vq_clique_iteration.  -> (graph, branch, clique, next stats) as dicts."""
+    go, bo, co, no = VqGraphOpts(), VqBranchOpts(), VqCliqueOpts(), VqNextOpts()
+    load().hlmi_vq_clique_opts_polyte(C.byref(co), int(bool(opts.get("error_correction", False))))
+    load().hlmi_vq_next_opts_stageb(C.byref(no))
+    _branch_graph_opts("vq_branch_iteration", (go, bo, co, no), opts)
+    os.makedirs(out_dir, exist_ok=True)
+    gst, bst, cst, nst = VqGraphStats(), VqBranchStats(), VqCliqueStats(), VqCliqueNextStats()
+    _check(load().hlmi_vq_branch_iteration(_b(singles_fastq), _b(overlaps), _b(subreads_in), _b(original_fastq), _b(threshold_table),
+                                           C.byref(go), C.byref(bo), C.byref(co), C.byref(no), _b(out_dir), C.byref(gst),
+                                           C.byref(bst), C.byref(cst), C.byref(nst)))
+    return (_stats(gst, VQ_GRAPH_STATS), _stats(bst, VQ_BRANCH_STATS + VQ_BRANCH_MS), _stats(cst, VQ_CLIQUE_STATS + VQ_CLIQUE_MS),
             _stats(nst, VQ_CLIQUE_NEXT_STATS + VQ_NEXT_MS))
 
 

@@ -404,6 +404,36 @@ int hlmi_vq_clique_iteration(const char *singles_fastq, const char *overlaps, co
     });
 }
 
+void hlmi_vq_branch_opts_polyte(hlmi_vq_branch_opts *o) {
+    if (o) vq_branch_opts_polyte(o);
+}
+
+int hlmi_vq_branch_graph(const char *singles_fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
+                         const char *threshold_table, const hlmi_vq_graph_opts *go, const hlmi_vq_branch_opts *bo,
+                         const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst) {
+    return guarded([&] {
+        if (!singles_fastq || !overlaps || !original_fastq || !threshold_table || !go || !bo || !out_dir || !gst || !bst)
+            fail(HLMI_EINVAL, "hlmi_vq_branch_graph: NULL argument");
+        require_device();
+        vq_branch_graph_run(singles_fastq, overlaps, subreads_in, original_fastq, threshold_table, *go, *bo, out_dir, gst, bst);
+    });
+}
+
+int hlmi_vq_branch_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
+                             const char *threshold_table, const hlmi_vq_graph_opts *go, const hlmi_vq_branch_opts *bo,
+                             const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no, const char *out_dir,
+                             hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst, hlmi_vq_clique_stats *cst,
+                             hlmi_vq_clique_next_stats *nst) {
+    return guarded([&] {
+        if (!singles_fastq || !overlaps || !original_fastq || !threshold_table || !go || !bo || !co || !no || !out_dir || !gst || !bst ||
+            !cst || !nst)
+            fail(HLMI_EINVAL, "hlmi_vq_branch_iteration: NULL argument");
+        require_device();
+        vq_branch_iteration_run(singles_fastq, overlaps, subreads_in, original_fastq, threshold_table, *go, *bo, *co, *no, out_dir, gst,
+                                bst, cst, nst);
+    });
+}
+
 void hlmi_cluster_opts_default(hlmi_cluster_opts *o) {
     if (o) *o = hlmi_cluster_opts{15000, 20, 0, 0};            // HyLight.py --size, -t
 }

@@ -428,7 +428,7 @@ void vq_graph_opts_stageb(hlmi_vq_graph_opts *o) {
 }
 
 void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st,
-                  VqGraphState *keep, bool for_next) {
+                  VqGraphState *keep, bool for_next, VqBranchRun *branch) {
     if (o.remove_trans > 3) fail(HLMI_EINVAL, "vq_graph: remove_trans must be 0 .. 3");
     if (o.remove_branches && o.remove_trans != 1)
         fail(HLMI_ESTATE, "vq_graph: remove_branches needs remove_trans 1 (findBranchfreeGraph asserts it, GraphAlgos.cpp:716)");
@@ -440,6 +440,7 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
         vq_merge_check_reads(reads.seq, reads.qual);      // refused inputs are refused before a file is written
     }
     if (reads.seq.size() >= (1u << 31)) fail(HLMI_EINVAL, "vq_graph: more than 2^31 reads");
+    if (branch) branch->prepare(o, reads);               // --branch_reduction=true: its refusals come before the first write
     Graph g;
     g.V = (uint32_t)reads.seq.size();
     g.out.resize(g.V);
@@ -536,7 +537,31 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
         std::fill(incl.begin(), incl.end(), 0);
     }
 
-    if (o.remove_trans) {                                 // removeTransitiveEdges (GraphAlgos.cpp:938-1077)
+    if (branch) {                                         // removeTransitiveEdges with edges_to_be_deleted (:967-993)
+        sort_adj_out(g);
+        g.flatten(off, src, dst, eid);
+        std::vector<uint32_t> ovlen(eid.size());
+        for (size_t p = 0; p < eid.size(); ++p) ovlen[p] = (uint32_t)g.pool[eid[p]].len;
+        std::vector<uint8_t> flags(eid.size(), 0);
+        uint64_t n_trans = 0;
+        vq_transitive_edges(g.V, eid.size(), src.data(), dst.data(), ovlen.data(), 1, flags.data(), &n_trans);
+        st->transitive = n_trans;
+        std::set<std::pair<uint32_t, uint32_t>> scheduled;
+        for (size_t p = 0; p < eid.size(); ++p) if (flags[p] & 2) scheduled.insert(std::make_pair(src[p], dst[p]));
+        branch->st->scheduled = scheduled.size();
+        gone.assign(eid.size(), 0);
+        for (size_t p = 0; p < eid.size(); ++p) gone[p] = flags[p] & 1;
+        if (1.0 * (double)n_trans > 0.5 * (double)eid.size()) {
+            // :995-1061, the rebuild: a transitive edge is skipped, and so is EVERY other edge whose (source, target) is scheduled
+            for (size_t p = 0; p < eid.size(); ++p) if (scheduled.count(std::make_pair(src[p], dst[p]))) gone[p] = 1;
+            g.drop(gone, src, eid);
+        } else {
+            // :1063-1076, one by one: the transitive edges, then per scheduled pair in std::set order the FIRST edge still there.
+            // The two branches differ only where a list holds two edges to one target, one of them scheduled and not transitive
+            g.drop(gone, src, eid);
+            for (const auto &pr : scheduled) g.erase_first(pr.first, pr.second, -1);
+        }
+    } else if (o.remove_trans) {                          // removeTransitiveEdges (GraphAlgos.cpp:938-1077)
         sort_adj_out(g);
         g.flatten(off, src, dst, eid);
         st->transitive = vq_trans_flags(g.V, src, dst, (int)o.remove_trans, gone);
@@ -572,7 +597,25 @@ void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_o
     }
     for (uint8_t t : tip) st->tip_reads += t;
 
-    if (o.remove_branches) {                              // removeBranches
+    if (branch) {                                         // readBasedBranchReduction in removeBranches' place (:326-347)
+        sort_adj_out(g);                                  // sortAdjOut sorts adj_out itself (BranchReduction.cpp:48)
+        std::vector<std::vector<VqEdge>> lists(g.V);
+        for (uint32_t u = 0; u < g.V; ++u)
+            for (uint32_t e : g.out[u]) lists[u].push_back(g.pool[e]);
+        std::vector<VqEdge> missing;
+        std::vector<std::pair<uint32_t, uint32_t>> removed;
+        std::string report;
+        branch->reduce(o, reads.seq, reads.id, lists, lab.orient, missing, removed, report);
+        // branching_edges: the missing edges (:83-85), then each removed edge as it stood (:217-225)
+        if (for_next) for (const VqEdge &e : missing) keep->branching.push_back(vq_src_edge(e));
+        for (const auto &pr : removed) {
+            if (for_next)
+                for (uint32_t e : g.out[pr.first])
+                    if (g.pool[e].v2 == pr.second) { keep->branching.push_back(vq_src_edge(g.pool[e])); break; }
+            if (!g.erase_first(pr.first, pr.second, -1)) fail(HLMI_EINVAL, "vq_branch: edge %u -> %u not found", pr.first, pr.second);
+        }
+        write_file(join_path(out_dir, "branch_components.txt"), report.data(), report.size());
+    } else if (o.remove_branches) {                       // removeBranches
         sort_adj_out(g);
         g.flatten(off, src, dst, eid);
         std::vector<uint32_t> comp;

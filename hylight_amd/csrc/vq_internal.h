@@ -190,9 +190,12 @@ struct VqGraphState {
     std::vector<std::vector<VqEdge>> out_unsorted;
 };
 inline const std::vector<std::vector<VqEdge>> &vq_cliques_out(const VqGraphState &g) { return g.out_unsorted.empty() ? g.out : g.out_unsorted; }
-// for_next: also keep what findNextOverlaps reads, and refuse a paired-end non-edge row before a file is written
+struct VqBranchRun;
+// for_next: also keep what findNextOverlaps reads, and refuse a paired-end non-edge row before a file is written.  branch:
+// --branch_reduction=true (vq_branch_host.cpp): the 3-clique rule in removeTransitiveEdges and readBasedBranchReduction where
+// removeBranches would run; without it nothing changes
 void vq_graph_run(const char *fastq, const char *overlaps, const hlmi_vq_graph_opts &o, const char *out_dir, hlmi_vq_graph_stats *st,
-                  VqGraphState *keep = nullptr, bool for_next = false);
+                  VqGraphState *keep = nullptr, bool for_next = false, VqBranchRun *branch = nullptr);
 
 // ---- merge: vq_merge.hip (SRBuilder::mergeAlongEdges on the device; its driver is in vq_superread_run.cpp) -----------------
 namespace vqm {
@@ -326,6 +329,66 @@ struct VqLoneCounts { uint64_t short_reads = 0, n_reads = 0, trivial = 0, trivia
 VqLoneCounts vq_lone_reads(const VqGraphState &g, const VqOriginalsDict &dict, const std::vector<uint8_t> &visited,
                            const std::vector<uint32_t> &read_n, uint32_t keep_singletons, const std::vector<uint8_t> *divert,
                            uint32_t first_id, std::vector<vqm::Rec> &recs, std::string &subreads, std::vector<uint32_t> *diverted);
+
+// ---- branch: vq_branch_host.cpp / vq_branch.hip (BranchReduction::readBasedBranchReduction, --branch_reduction=true) --------
+namespace vqb {
+constexpr int WG = 256;
+constexpr int WAVE = 64;
+constexpr uint32_t MAX_DIFF = 100;               // findDiffPos keeps the first 100 positions of a pair (:703)
+constexpr uint32_t NONE = 0xffffffffu;
+constexpr int SEARCH_STEPS = 33;                 // a binary search over fewer than 2^32 entries ends within this many steps
+struct Pair {                                    // one compared neighbour pair: sequence a from `rel` on against b from 0
+    uint32_t a, b;                               // vertices
+    uint32_t rel, len;                           // len >= 1 common bases
+    uint32_t flags;                              // 1: both reverse-complemented (the branching vertex's label), 2: compared reversed
+};
+struct Slot {                                    // one (branch, neighbour)
+    uint32_t node, nb;                           // the branching vertex, the neighbour (the contig)
+    int32_t startpos;
+    uint32_t rc;                                 // the contig is reverse-complemented
+    uint32_t diff0, diff1;                       // the branch's sorted, uniqued difference list: diff[diff0, diff1)
+};
+// The device side: reads and original reads resident, bases concatenated, read r at [off[r], off[r + 1]) (VqMergeDev's layout)
+class Dev {
+public:
+    Dev(const std::vector<std::string> &reads, const std::vector<std::string> &originals);
+    // cnt[p] = mismatches found (at most MAX_DIFF), pos[p * MAX_DIFF + k] = the k-th one's position in compare order
+    void diff_positions(const std::vector<Pair> &pairs, std::vector<uint32_t> &cnt, std::vector<uint32_t> &pos);
+    // Originals of the vertices as a CSR (vertex v: [ooff[v], ooff[v + 1]), ascending id): id, row in the original FASTQ,
+    // forward, index1.  Item t of slot s (items [item0[s], item0[s + 1])) is original t - item0[s] of slots[s].nb.
+    // -> ev[2 * t], ev[2 * t + 1] = the subread's id / the joint id where checkReadEvidence holds, else NONE
+    void evidence(const std::vector<Slot> &slots, const std::vector<uint32_t> &item0, const std::vector<int32_t> &diff,
+                  const std::vector<uint32_t> &ooff, const std::vector<uint32_t> &oid, const std::vector<uint32_t> &orow,
+                  const std::vector<uint8_t> &ofwd, const std::vector<int32_t> &oidx, uint32_t se_count, uint32_t pe_count,
+                  std::vector<uint32_t> &ev);
+private:
+    DBuf<uint8_t> d_reads_, d_orig_;
+    DBuf<uint64_t> d_roff_, d_ooff_;
+};
+}  // namespace vqb
+// What vq_graph_run needs for --branch_reduction=true.  prepare() runs in front of the graph's first write and refuses what
+// hlmi_vq_branch_graph documents; reduce() is readBasedBranchReduction over the graph as removeTips left it (out-lists already
+// through sortAdjOut): the missing edges and the (source, target) pairs to remove, both in the reference's push order.
+struct VqBranchRun {
+    hlmi_vq_branch_opts bo{};
+    const char *original_fastq = nullptr, *table_path = nullptr;
+    const VqOriginalsDict *dict = nullptr;
+    hlmi_vq_branch_stats *st = nullptr;
+    Singles originals;
+    std::map<int, int> table;
+    void prepare(const hlmi_vq_graph_opts &o, const Singles &reads);
+    void reduce(const hlmi_vq_graph_opts &o, const std::vector<std::string> &seq, const std::vector<uint64_t> &id,
+                const std::vector<std::vector<VqEdge>> &out, const std::vector<uint8_t> &orient, std::vector<VqEdge> &missing,
+                std::vector<std::pair<uint32_t, uint32_t>> &removed, std::string &report);
+};
+void vq_branch_opts_polyte(hlmi_vq_branch_opts *o);
+void vq_branch_graph_run(const char *fastq, const char *overlaps, const char *subreads_in, const char *original_fastq, const char *table,
+                         const hlmi_vq_graph_opts &go, const hlmi_vq_branch_opts &bo, const char *out_dir, hlmi_vq_graph_stats *gst,
+                         hlmi_vq_branch_stats *bst);
+void vq_branch_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
+                             const char *table, const hlmi_vq_graph_opts &go, const hlmi_vq_branch_opts &bo, const hlmi_vq_clique_opts &co,
+                             const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst,
+                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst);
 
 // ---- drivers: vq_superread_run.cpp (include/hylight_mi.h; vq_iteration_run is declared with `next` below) -------------------
 void vq_merge_opts_stageb(hlmi_vq_merge_opts *o);

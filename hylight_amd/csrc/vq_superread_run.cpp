@@ -226,7 +226,7 @@ void vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uint64_
 // hlmi_vq_cliques (no == NULL) and hlmi_vq_clique_iteration: one path, as merge_and_next is
 static void cliques_and_next(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
                              const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
-                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst) {
+                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst, VqBranchRun *branch = nullptr) {
     using namespace vqc;
     *cst = hlmi_vq_clique_stats{};
     if (nst) *nst = hlmi_vq_clique_next_stats{};
@@ -236,7 +236,8 @@ static void cliques_and_next(const char *fastq, const char *overlaps, const char
     const uint32_t mcs = co.min_clique_size;
     if (no) read_originals(dict);                // in place: subreads_in may be the subreads.txt written below
     VqGraphState g;
-    vq_graph_run(fastq, overlaps, go, out_dir, gst, &g, no != nullptr);
+    if (branch) branch->dict = &dict;            // --branch_reduction=true reads the same original_ID_dict
+    vq_graph_run(fastq, overlaps, go, out_dir, gst, &g, no != nullptr, branch);
     if (!g.built) return;                        // ViralQuasispecies.cpp:282-291: nothing to be done
     const double t0 = now_ms();
     const uint32_t V = (uint32_t)g.seq.size();
@@ -394,6 +395,17 @@ void vq_clique_iteration_run(const char *fastq, const char *overlaps, const char
                              const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst,
                              hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst) {
     cliques_and_next(fastq, overlaps, subreads_in, go, co, &no, out_dir, gst, cst, nst);
+}
+
+// hlmi_vq_branch_iteration: hlmi_vq_clique_iteration's path with the branch reduction inside its graph
+void vq_branch_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
+                             const char *table, const hlmi_vq_graph_opts &go, const hlmi_vq_branch_opts &bo, const hlmi_vq_clique_opts &co,
+                             const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst,
+                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst) {
+    *bst = hlmi_vq_branch_stats{};
+    VqBranchRun br;
+    br.bo = bo; br.original_fastq = original_fastq; br.table_path = table; br.st = bst;
+    cliques_and_next(fastq, overlaps, subreads_in, go, co, &no, out_dir, gst, cst, nst, &br);
 }
 
 }  // namespace hlmi

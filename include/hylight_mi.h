@@ -156,8 +156,9 @@ int hlmi_sfo2overlaps(const char *in_sfo, const char *out_savage, int num_single
  * iteration (hlmi_vq_merge), and SRBuilder::findNextOverlaps behind it (hlmi_vq_iteration: one whole stage-b iteration; the
  * loop of pipeline_per_stage.py is hylight_amd/vq_stageb.py), and the step of --cliques=true for single-end reads: the maximal
  * cliques of graph.txt and SRBuilder::cliquesToSuperreads (hlmi_vq_cliques; cliques.txt is pinned to the reference's own
- * enumerator).  Not built: findNextOverlaps behind the clique step (a vertex then sits in several super-reads),
- * FindNextOverlaps3, BranchReduction. */
+ * enumerator), findNextOverlaps behind the clique step (hlmi_vq_clique_iteration), and the read-evidence branch reduction of
+ * --branch_reduction=true (hlmi_vq_branch_graph, hlmi_vq_branch_iteration).  Not built: FindNextOverlaps3, the diploid
+ * resolution of BranchReduction, paired-end vertices, --min_qual=0. */
 typedef struct {
     uint64_t id1, id2;                 /* strtoul(..., 0) of columns 1, 2                        (Overlap.h:39-40, Types.h:99)  */
     uint32_t pos1, pos2, perc1, perc2, len1, len2;   /* atoi; pos2 = perc2 = len2 = 0 when column 4 is "-" (Overlap.h:53-57) */
@@ -233,9 +234,9 @@ typedef struct {
  * critical sections run (EdgeCalculator.cpp:395-419), so the first candidate of a (pair, orientation class) - the only
  * one that can mark an inclusion - may differ between its multi-thread runs.
  * Refused with HLMI_ESTATE (not on HyLight's path): an edge candidate of type 'p' (HyLight runs --num_pairs 0),
- * remove_branches with remove_trans != 1 (the reference asserts).  add_duplicates, resolve_orientations = false and
- * branch_reduction are not options here: this call always resolves orientations by labelling and never reduces branches
- * by read evidence.  remove_trans > 3 is HLMI_EINVAL. */
+ * remove_branches with remove_trans != 1 (the reference asserts).  add_duplicates and resolve_orientations = false are not
+ * options here: this call always resolves orientations by labelling.  branch_reduction is hlmi_vq_branch_graph, below; this
+ * call never reduces branches by read evidence.  remove_trans > 3 is HLMI_EINVAL. */
 int hlmi_vq_graph(const char *singles_fastq, const char *overlaps, const hlmi_vq_graph_opts *o, const char *out_dir,
                   hlmi_vq_graph_stats *st);
 
@@ -516,10 +517,68 @@ typedef struct {
  * and needs no count, scan or search.
  * HLMI_EINVAL: 2^32 - 1 turns and more in one call (the limit of the sequence numbers); what hlmi_vq_cliques refuses.
  * HLMI_ESTATE: a paired-end row among the candidates or the non-edge rows.  Paired-end reads, add_duplicates,
- * FindNextOverlaps3 (--FNO=3), BranchReduction and --min_qual=0 are not built, as for hlmi_vq_cliques. */
+ * FindNextOverlaps3 (--FNO=3) and --min_qual=0 are not built, as for hlmi_vq_cliques; BranchReduction is
+ * hlmi_vq_branch_iteration, below. */
 int hlmi_vq_clique_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in,
                              const hlmi_vq_graph_opts *go, const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no,
                              const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst,
+                             hlmi_vq_clique_next_stats *nst);
+
+/* ---- read-evidence branch reduction: ViralQuasispecies --branch_reduction=true --remove_branches=false --remove_trans=1
+ * --threads 1 on single-end reads, diploid off (BranchReduction::readBasedBranchReduction, BranchReduction.cpp; the
+ * edges_to_be_deleted rule of removeTransitiveEdges, GraphAlgos.cpp:967-1077) - the iteration POLYTE runs after every merge
+ * round (polyte.tune_params.py:641-645).  PARITY UNPINNED; tests/vq_branch_model.py restates the reference. */
+typedef struct {
+    uint32_t se_count, pe_count;   /* --branch_SE_c / --branch_PE_c: the original reads are numbered singles, /1 mates, /2
+                                      mates; se_count + 2 * pe_count must be the number of reads of original_fastq, and is
+                                      what this call takes for --original_readcount                                         */
+    int careful;                   /* --careful_diploid: a component next to a kept one is removed (default true, :97)      */
+} hlmi_vq_branch_opts;
+void hlmi_vq_branch_opts_polyte(hlmi_vq_branch_opts *o);       /* careful 1, the counts 0 */
+typedef struct {
+    uint64_t in_branches, out_branches;   /* vertices with more than one in- / out-edge (findBranchfreeGraph)              */
+    uint64_t pairs;                /* neighbour pairs compared on the device (inclusion pairs are not)                      */
+    uint64_t diff_positions;       /* first-difference positions they gave, at most 100 each                                */
+    uint64_t work_items;           /* (branch, neighbour, original of the neighbour) triples of the evidence kernel         */
+    uint64_t evidence_ids;         /* evidence ids over all (branch, neighbour) lists, sorted and uniqued                   */
+    uint64_t missing_edges;        /* identical overlaps: edges pushed to branching_edges for the next iteration            */
+    uint64_t false_branches;       /* branching vertices with one                                                           */
+    uint64_t inclusion_pairs;      /* pairs of an out-branch decided by the lengths (:449, :461)                            */
+    uint64_t components;           /* branching components without a false branch                                           */
+    uint64_t components_kept;      /* ... with an edge of enough unique evidence                                            */
+    uint64_t dist_too_large;       /* ... whose distance the table does not hold                                            */
+    uint64_t scheduled;            /* edges_to_be_deleted of removeTransitiveEdges (the 3-clique rule)                      */
+    uint64_t edges_removed;        /* edges_to_remove after sort and unique                                                 */
+    double ms_diff, ms_evidence;   /* wall time of the two device steps (upload, kernel, download)                          */
+    double ms_branch;              /* wall time of the whole reduction                                                      */
+} hlmi_vq_branch_stats;
+/* hlmi_vq_graph (same code, same files) with the reduction where removeBranches would run (ViralQuasispecies.cpp:326-351) and
+ * the 3-clique rule in removeTransitiveEdges, plus the project's own branch_components.txt: one line per component of
+ * branching_components in the reference's order, "dist<TAB>threshold (-1: not in the table)<TAB>kept 0|1" and per edge
+ * "<TAB>u>v:unique evidence count" (-1 where countUniqueEvidence never ran: no threshold, or next to a kept component).
+ * subreads_in: the previous iteration's subreads.txt (NULL: every read is its own original, --first_it);  original_fastq: the
+ * reads the originals name, looked up by id;  threshold_table: the reference's evidence_threshold_table.tsv ('#' and empty
+ * lines skipped, column 1 = distance, column 3 = minimum evidence, std::stoi each).
+ * Device: one wave per neighbour pair of a branch walks the common stretch 64 bases a step (reversed for in-branches) and
+ * appends the first 100 mismatch positions by ballot and popcount; one thread per (branch, neighbour, original) looks the id
+ * and its mate up in the branching vertex's id-sorted originals and tests the original read against the neighbour at the
+ * branch's difference list.  Components, unique evidence, thresholds and removals run on the host.
+ * Refused before anything is written: remove_trans != 1, remove_branches set, se_count + 2 * pe_count != reads of
+ * original_fastq, a table that cannot be opened or holds a line std::stoi rejects, an original id that original_fastq does not
+ * hold, read ids that are not the file positions (HLMI_EINVAL); a paired-end row (HLMI_ESTATE).  Refused during the reduction
+ * (HLMI_EINVAL): an in-branch pair the reference's assertion of :605 rejects.  The table is read as the reference reads it,
+ * through one stringstream: what a line holds behind its third column goes in front of the next line's first column.
+ * Not built: --min_qual=0, diploid (the typical-double-branch resolution), paired-end vertices, the POLYTE loop with its
+ * threshold table (min_ev_table.py). */
+int hlmi_vq_branch_graph(const char *singles_fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
+                         const char *threshold_table, const hlmi_vq_graph_opts *go, const hlmi_vq_branch_opts *bo,
+                         const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst);
+/* The same graph, then everything hlmi_vq_clique_iteration does behind its graph (same code): one branch-reduction iteration of
+ * POLYTE.  co->first_it decides the originals as there (subreads_in NULL only with first_it). */
+int hlmi_vq_branch_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
+                             const char *threshold_table, const hlmi_vq_graph_opts *go, const hlmi_vq_branch_opts *bo,
+                             const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no, const char *out_dir,
+                             hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst, hlmi_vq_clique_stats *cst,
                              hlmi_vq_clique_next_stats *nst);
 
 /* ---- short-read clustering (HyLight.py:215-226: get_readnames.py, bin_pointer_limited_filechunks_shortpath2.py,
