@@ -194,6 +194,23 @@ SYMBOLS = {
                                            C.POINTER(VqCliqueNextStats)]),
     "hlmi_vq_consensus_pair": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32,
                                          C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
+    # the same calls with --min_qual: the sibling's signature with one double in front of out_dir (consensus_pair: of out_seq)
+    "hlmi_vq_consensus_pair_mq": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_double, C.c_char_p, C.c_char_p, C.POINTER(C.c_uint32)]),
+    "hlmi_vq_merge_mq": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqMergeOpts), C.c_double,
+                                   C.c_char_p, C.POINTER(VqGraphStats), C.POINTER(VqMergeStats)]),
+    "hlmi_vq_cliques_mq": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqCliqueOpts), C.c_double,
+                                     C.c_char_p, C.POINTER(VqGraphStats), C.POINTER(VqCliqueStats)]),
+    "hlmi_vq_iteration_mq": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqMergeOpts),
+                                       C.POINTER(VqNextOpts), C.c_double, C.c_char_p, C.POINTER(VqGraphStats),
+                                       C.POINTER(VqMergeStats), C.POINTER(VqNextStats)]),
+    "hlmi_vq_clique_iteration_mq": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts), C.POINTER(VqCliqueOpts),
+                                              C.POINTER(VqNextOpts), C.c_double, C.c_char_p, C.POINTER(VqGraphStats),
+                                              C.POINTER(VqCliqueStats), C.POINTER(VqCliqueNextStats)]),
+    "hlmi_vq_branch_iteration_mq": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VqGraphOpts),
+                                              C.POINTER(VqBranchOpts), C.POINTER(VqCliqueOpts), C.POINTER(VqNextOpts), C.c_double,
+                                              C.c_char_p, C.POINTER(VqGraphStats), C.POINTER(VqBranchStats),
+                                              C.POINTER(VqCliqueStats), C.POINTER(VqCliqueNextStats)]),
     "hlmi_cluster_opts_default": (None, [C.POINTER(ClusterOpts)]),
     "hlmi_cluster_short": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(ClusterOpts), C.c_char_p, C.POINTER(ClusterStats)]),
     "hlmi_polish_opts_default": (None, [C.POINTER(PolishOpts)]),
@@ -398,6 +415,13 @@ def _stats(st, names):
     return {k: getattr(st, k) for k in names}
 
 
+def _mq(name, min_qual, head, tail):
+    """The call `name` over head + tail; with a min_qual its `_mq` sibling, the value between the two."""
+    if min_qual is None:
+        return getattr(load(), name)(*head, *tail)
+    return getattr(load(), name + "_mq")(*head, float(min_qual), *tail)
+
+
 def vq_graph_opts_stageb():
     """hlmi_vq_graph_opts_stageb: the options of HyLight's first stage-b iteration, as a dict."""
     o = VqGraphOpts()
@@ -425,25 +449,27 @@ def vq_merge_opts_stageb():
     return {k: getattr(o, k) for k, _ in VqMergeOpts._fields_}
 
 
-def vq_merge(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
+def vq_merge(singles_fastq, overlaps, out_dir, subreads_in=None, min_qual=None, **opts):
     """hlmi_vq_merge: the graph of vq_graph (same files) and then SRBuilder::mergeAlongEdges - singles.fastq, subreads.txt,
     removed_tip_sequences.fastq (appended to) and superread_map.txt in out_dir (created if missing).  Options: the fields
     of hlmi_vq_graph_opts and of hlmi_vq_merge_opts, the stage-b values by default; subreads_in: the previous iteration's
-    subreads.txt when first_it is off.  -> (graph stats, merge stats) as dicts."""
+    subreads.txt when first_it is off; min_qual: --min_qual, 0 .. 1 (None: SRBuilder's default 0.9 through hlmi_vq_merge itself,
+    a number: hlmi_vq_merge_mq).  -> (graph stats, merge stats) as dicts."""
     go, mo = VqGraphOpts(), VqMergeOpts()
     load().hlmi_vq_graph_opts_stageb(C.byref(go))
     load().hlmi_vq_merge_opts_stageb(C.byref(mo))
     _set_opts("vq_merge", (go, mo), opts)
     os.makedirs(out_dir, exist_ok=True)
     gst, mst = VqGraphStats(), VqMergeStats()
-    _check(load().hlmi_vq_merge(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
-                                C.byref(go), C.byref(mo), _b(out_dir), C.byref(gst), C.byref(mst)))
+    _check(_mq("hlmi_vq_merge", min_qual, (_b(singles_fastq), _b(overlaps), _b(subreads_in), C.byref(go), C.byref(mo)),
+               (_b(out_dir), C.byref(gst), C.byref(mst))))
     return _stats(gst, VQ_GRAPH_STATS), _stats(mst, VQ_MERGE_STATS + VQ_MERGE_MS)
 
 
 def vq_clique_opts_polyte(error_correction=False):
     """hlmi_vq_clique_opts_polyte: the SRBuilder options POLYTE passes with --cliques=true, as a dict.  POLYTE also passes
-    --min_qual=0, which is not built: hlmi_vq_cliques keeps minQual 0.9, so disagreeing columns become N (see the header)."""
+    --min_qual=0, which is no field of the struct: give min_qual=0 to vq_cliques / vq_clique_iteration / vq_branch_iteration.
+    Without it they keep minQual 0.9, so disagreeing columns become N (see the header)."""
     o = VqCliqueOpts()
     load().hlmi_vq_clique_opts_polyte(C.byref(o), int(bool(error_correction)))
     return {k: getattr(o, k) for k, _ in VqCliqueOpts._fields_}
@@ -457,27 +483,28 @@ def vq_cliques_of_graph(graph_txt, cliques_out):
     return n.value
 
 
-def vq_cliques(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
+def vq_cliques(singles_fastq, overlaps, out_dir, subreads_in=None, min_qual=None, **opts):
     """hlmi_vq_cliques: the graph of vq_graph (same files) and then ViralQuasispecies' --cliques=true step for single-end reads -
     cliques.txt, singles.fastq, subreads.txt and clique_map.txt in out_dir (created if missing).  Options: the fields of
     hlmi_vq_graph_opts (the stage-b values by default; what POLYTE passes beside them is written down in the header) and of
-    hlmi_vq_clique_opts (hlmi_vq_clique_opts_polyte for the error_correction given).  -> (graph stats, clique stats)."""
+    hlmi_vq_clique_opts (hlmi_vq_clique_opts_polyte for the error_correction given); min_qual as for vq_merge (POLYTE: 0).
+    -> (graph stats, clique stats)."""
     go, co = VqGraphOpts(), VqCliqueOpts()
     load().hlmi_vq_graph_opts_stageb(C.byref(go))
     load().hlmi_vq_clique_opts_polyte(C.byref(co), int(bool(opts.get("error_correction", False))))
     _set_opts("vq_cliques", (go, co), opts)
     os.makedirs(out_dir, exist_ok=True)
     gst, cst = VqGraphStats(), VqCliqueStats()
-    _check(load().hlmi_vq_cliques(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
-                                  C.byref(go), C.byref(co), _b(out_dir), C.byref(gst), C.byref(cst)))
+    _check(_mq("hlmi_vq_cliques", min_qual, (_b(singles_fastq), _b(overlaps), _b(subreads_in), C.byref(go), C.byref(co)),
+               (_b(out_dir), C.byref(gst), C.byref(cst))))
     return _stats(gst, VQ_GRAPH_STATS), _stats(cst, VQ_CLIQUE_STATS + VQ_CLIQUE_MS)
 
 
-def vq_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
+def vq_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, min_qual=None, **opts):
     """hlmi_vq_iteration: one stage-b iteration - the files of vq_merge, then overlaps.txt (SRBuilder::findNextOverlaps) and one
     line appended to stats.txt, in out_dir (created if missing).  The inputs may lie in out_dir under the names written: they
     are read first.  Options: the fields of hlmi_vq_graph_opts, hlmi_vq_merge_opts and hlmi_vq_next_opts, the stage-b values
-    by default.  -> (graph stats, merge stats, next stats) as dicts."""
+    by default; min_qual as for vq_merge.  -> (graph stats, merge stats, next stats) as dicts."""
     go, mo, no = VqGraphOpts(), VqMergeOpts(), VqNextOpts()
     load().hlmi_vq_graph_opts_stageb(C.byref(go))
     load().hlmi_vq_merge_opts_stageb(C.byref(mo))
@@ -485,16 +512,16 @@ def vq_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
     _set_opts("vq_iteration", (go, mo, no), opts)
     os.makedirs(out_dir, exist_ok=True)
     gst, mst, nst = VqGraphStats(), VqMergeStats(), VqNextStats()
-    _check(load().hlmi_vq_iteration(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
-                                    C.byref(go), C.byref(mo), C.byref(no), _b(out_dir), C.byref(gst), C.byref(mst), C.byref(nst)))
+    _check(_mq("hlmi_vq_iteration", min_qual, (_b(singles_fastq), _b(overlaps), _b(subreads_in), C.byref(go), C.byref(mo), C.byref(no)),
+               (_b(out_dir), C.byref(gst), C.byref(mst), C.byref(nst))))
     return _stats(gst, VQ_GRAPH_STATS), _stats(mst, VQ_MERGE_STATS + VQ_MERGE_MS), _stats(nst, VQ_NEXT_STATS + VQ_NEXT_MS)
 
 
-def vq_clique_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **opts):
+def vq_clique_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, min_qual=None, **opts):
     """hlmi_vq_clique_iteration: one clique iteration - the files of vq_cliques, then overlaps.txt (SRBuilder::findNextOverlaps
     over the super-read lists of the vertices) and one line appended to stats.txt, in out_dir (created if missing).  The inputs
     may lie in out_dir under the names written: they are read first.  Options: the fields of hlmi_vq_graph_opts,
-    hlmi_vq_clique_opts and hlmi_vq_next_opts, with the defaults of vq_cliques and vq_iteration.  -> (graph stats, clique
+    hlmi_vq_clique_opts and hlmi_vq_next_opts, with the defaults of vq_cliques and vq_iteration; min_qual as there.  -> (graph stats, clique
     stats, next stats) as dicts; the next stats add candidates, max_list and in_several to those of vq_iteration."""
     go, co, no = VqGraphOpts(), VqCliqueOpts(), VqNextOpts()
     load().hlmi_vq_graph_opts_stageb(C.byref(go))
@@ -503,9 +530,9 @@ def vq_clique_iteration(singles_fastq, overlaps, out_dir, subreads_in=None, **op
     _set_opts("vq_clique_iteration", (go, co, no), opts)
     os.makedirs(out_dir, exist_ok=True)
     gst, cst, nst = VqGraphStats(), VqCliqueStats(), VqCliqueNextStats()
-    _check(load().hlmi_vq_clique_iteration(_b(singles_fastq), _b(overlaps), _b(subreads_in) if subreads_in is not None else None,
-                                           C.byref(go), C.byref(co), C.byref(no), _b(out_dir), C.byref(gst), C.byref(cst),
-                                           C.byref(nst)))
+    _check(_mq("hlmi_vq_clique_iteration", min_qual,
+               (_b(singles_fastq), _b(overlaps), _b(subreads_in), C.byref(go), C.byref(co), C.byref(no)),
+               (_b(out_dir), C.byref(gst), C.byref(cst), C.byref(nst))))
     return (_stats(gst, VQ_GRAPH_STATS), _stats(cst, VQ_CLIQUE_STATS + VQ_CLIQUE_MS),
             _stats(nst, VQ_CLIQUE_NEXT_STATS + VQ_NEXT_MS))
 
@@ -539,32 +566,34 @@ def vq_branch_graph(singles_fastq, overlaps, original_fastq, threshold_table, ou
     return _stats(gst, VQ_GRAPH_STATS), _stats(bst, VQ_BRANCH_STATS + VQ_BRANCH_MS)
 
 
-def vq_branch_iteration(singles_fastq, overlaps, original_fastq, threshold_table, out_dir, subreads_in=None, **opts):
+def vq_branch_iteration(singles_fastq, overlaps, original_fastq, threshold_table, out_dir, subreads_in=None, min_qual=None, **opts):
     """hlmi_vq_branch_iteration: the graph of vq_branch_graph, then everything vq_clique_iteration does behind its graph.
-    Options: those of vq_branch_graph and of vq_clique_iteration.  -> (graph, branch, clique, next stats) as dicts."""
+    Options: those of vq_branch_graph and of vq_clique_iteration, its min_qual among them.  -> (graph, branch, clique, next stats)
+    as dicts."""
     go, bo, co, no = VqGraphOpts(), VqBranchOpts(), VqCliqueOpts(), VqNextOpts()
     load().hlmi_vq_clique_opts_polyte(C.byref(co), int(bool(opts.get("error_correction", False))))
     load().hlmi_vq_next_opts_stageb(C.byref(no))
     _branch_graph_opts("vq_branch_iteration", (go, bo, co, no), opts)
     os.makedirs(out_dir, exist_ok=True)
     gst, bst, cst, nst = VqGraphStats(), VqBranchStats(), VqCliqueStats(), VqCliqueNextStats()
-    _check(load().hlmi_vq_branch_iteration(_b(singles_fastq), _b(overlaps), _b(subreads_in), _b(original_fastq), _b(threshold_table),
-                                           C.byref(go), C.byref(bo), C.byref(co), C.byref(no), _b(out_dir), C.byref(gst),
-                                           C.byref(bst), C.byref(cst), C.byref(nst)))
+    _check(_mq("hlmi_vq_branch_iteration", min_qual,
+               (_b(singles_fastq), _b(overlaps), _b(subreads_in), _b(original_fastq), _b(threshold_table), C.byref(go), C.byref(bo),
+                C.byref(co), C.byref(no)), (_b(out_dir), C.byref(gst), C.byref(bst), C.byref(cst), C.byref(nst))))
     return (_stats(gst, VQ_GRAPH_STATS), _stats(bst, VQ_BRANCH_STATS + VQ_BRANCH_MS), _stats(cst, VQ_CLIQUE_STATS + VQ_CLIQUE_MS),
             _stats(nst, VQ_CLIQUE_NEXT_STATS + VQ_NEXT_MS))
 
 
-def vq_consensus_pair(seq1, qual1, seq2, qual2, pos):
+def vq_consensus_pair(seq1, qual1, seq2, qual2, pos, min_qual=None):
     """hlmi_vq_consensus_pair: SRBuilder::consensus of two oriented sequences (str or bytes), the second `pos` bases behind
-    the first -> (sequence, qualities) as str; ("", "") where the reference returns an empty consensus."""
+    the first -> (sequence, qualities) as str; ("", "") where the reference returns an empty consensus.  min_qual as for
+    vq_merge (a number: hlmi_vq_consensus_pair_mq)."""
     if pos < 0 or pos >= 1 << 30:
         raise ValueError(f"vq_consensus_pair: pos {pos} is outside 0 .. 2^30")
     s1, q1, s2, q2 = (x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in (seq1, qual1, seq2, qual2))
     cap = max(len(s1), pos + len(s2), 1)
     out_s, out_q = C.create_string_buffer(cap), C.create_string_buffer(cap)
     n = C.c_uint32(0)
-    _check(load().hlmi_vq_consensus_pair(s1, q1, len(s1), len(q1), s2, q2, len(s2), len(q2), pos, out_s, out_q, C.byref(n)))
+    _check(_mq("hlmi_vq_consensus_pair", min_qual, (s1, q1, len(s1), len(q1), s2, q2, len(s2), len(q2), pos), (out_s, out_q, C.byref(n))))
     return out_s.raw[:n.value].decode("latin-1"), out_q.raw[:n.value].decode("latin-1")
 
 

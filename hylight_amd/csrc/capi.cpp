@@ -337,39 +337,57 @@ void hlmi_vq_merge_opts_stageb(hlmi_vq_merge_opts *o) {
     if (o) vq_merge_opts_stageb(o);
 }
 
-int hlmi_vq_merge(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
-                  const hlmi_vq_merge_opts *mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst) {
+int hlmi_vq_merge_mq(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                     const hlmi_vq_merge_opts *mo, double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst,
+                     hlmi_vq_merge_stats *mst) {
     return guarded([&] {
         if (!singles_fastq || !overlaps || !go || !mo || !out_dir || !gst || !mst) fail(HLMI_EINVAL, "hlmi_vq_merge: NULL argument");
         require_device();
-        vq_merge_run(singles_fastq, overlaps, subreads_in, *go, *mo, out_dir, gst, mst);
+        vq_merge_run(singles_fastq, overlaps, subreads_in, *go, *mo, min_qual, out_dir, gst, mst);
     });
+}
+
+int hlmi_vq_merge(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                  const hlmi_vq_merge_opts *mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst) {
+    return hlmi_vq_merge_mq(singles_fastq, overlaps, subreads_in, go, mo, VQ_MIN_QUAL, out_dir, gst, mst);
 }
 
 void hlmi_vq_next_opts_stageb(hlmi_vq_next_opts *o) {
     if (o) vq_next_opts_stageb(o);
 }
 
-int hlmi_vq_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
-                      const hlmi_vq_merge_opts *mo, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
-                      hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst) {
+int hlmi_vq_iteration_mq(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                         const hlmi_vq_merge_opts *mo, const hlmi_vq_next_opts *no, double min_qual, const char *out_dir,
+                         hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst) {
     return guarded([&] {
         if (!singles_fastq || !overlaps || !go || !mo || !no || !out_dir || !gst || !mst || !nst)
             fail(HLMI_EINVAL, "hlmi_vq_iteration: NULL argument");
         require_device();
-        vq_iteration_run(singles_fastq, overlaps, subreads_in, *go, *mo, *no, out_dir, gst, mst, nst);
+        vq_iteration_run(singles_fastq, overlaps, subreads_in, *go, *mo, *no, min_qual, out_dir, gst, mst, nst);
+    });
+}
+
+int hlmi_vq_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                      const hlmi_vq_merge_opts *mo, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
+                      hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst) {
+    return hlmi_vq_iteration_mq(singles_fastq, overlaps, subreads_in, go, mo, no, VQ_MIN_QUAL, out_dir, gst, mst, nst);
+}
+
+int hlmi_vq_consensus_pair_mq(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2,
+                              const char *qual2, uint32_t len2, uint32_t qlen2, uint32_t pos, double min_qual, char *out_seq,
+                              char *out_qual, uint32_t *out_len) {
+    return guarded([&] {
+        if (!out_len || (len1 && !seq1) || (qlen1 && !qual1) || (len2 && !seq2) || (qlen2 && !qual2) || !out_seq || !out_qual)
+            fail(HLMI_EINVAL, "hlmi_vq_consensus_pair: NULL argument");
+        require_device();
+        vq_consensus_pair(seq1, qual1, len1, qlen1, seq2, qual2, len2, qlen2, pos, min_qual, out_seq, out_qual, out_len);
     });
 }
 
 int hlmi_vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2,
                            const char *qual2, uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual,
                            uint32_t *out_len) {
-    return guarded([&] {
-        if (!out_len || (len1 && !seq1) || (qlen1 && !qual1) || (len2 && !seq2) || (qlen2 && !qual2) || !out_seq || !out_qual)
-            fail(HLMI_EINVAL, "hlmi_vq_consensus_pair: NULL argument");
-        require_device();
-        vq_consensus_pair(seq1, qual1, len1, qlen1, seq2, qual2, len2, qlen2, pos, out_seq, out_qual, out_len);
-    });
+    return hlmi_vq_consensus_pair_mq(seq1, qual1, len1, qlen1, seq2, qual2, len2, qlen2, pos, VQ_MIN_QUAL, out_seq, out_qual, out_len);
 }
 
 void hlmi_vq_clique_opts_polyte(hlmi_vq_clique_opts *o, int error_correction) {
@@ -383,12 +401,30 @@ int hlmi_vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uin
     });
 }
 
-int hlmi_vq_cliques(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
-                    const hlmi_vq_clique_opts *co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst) {
+int hlmi_vq_cliques_mq(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                       const hlmi_vq_clique_opts *co, double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst,
+                       hlmi_vq_clique_stats *cst) {
     return guarded([&] {
         if (!singles_fastq || !overlaps || !go || !co || !out_dir || !gst || !cst) fail(HLMI_EINVAL, "hlmi_vq_cliques: NULL argument");
         require_device();
-        vq_cliques_run(singles_fastq, overlaps, subreads_in, *go, *co, out_dir, gst, cst);
+        vq_cliques_run(singles_fastq, overlaps, subreads_in, *go, *co, min_qual, out_dir, gst, cst);
+    });
+}
+
+int hlmi_vq_cliques(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                    const hlmi_vq_clique_opts *co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst) {
+    return hlmi_vq_cliques_mq(singles_fastq, overlaps, subreads_in, go, co, VQ_MIN_QUAL, out_dir, gst, cst);
+}
+
+int hlmi_vq_clique_iteration_mq(const char *singles_fastq, const char *overlaps, const char *subreads_in,
+                                const hlmi_vq_graph_opts *go, const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no,
+                                double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst,
+                                hlmi_vq_clique_next_stats *nst) {
+    return guarded([&] {
+        if (!singles_fastq || !overlaps || !go || !co || !no || !out_dir || !gst || !cst || !nst)
+            fail(HLMI_EINVAL, "hlmi_vq_clique_iteration: NULL argument");
+        require_device();
+        vq_clique_iteration_run(singles_fastq, overlaps, subreads_in, *go, *co, *no, min_qual, out_dir, gst, cst, nst);
     });
 }
 
@@ -396,12 +432,7 @@ int hlmi_vq_clique_iteration(const char *singles_fastq, const char *overlaps, co
                              const hlmi_vq_graph_opts *go, const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no,
                              const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst,
                              hlmi_vq_clique_next_stats *nst) {
-    return guarded([&] {
-        if (!singles_fastq || !overlaps || !go || !co || !no || !out_dir || !gst || !cst || !nst)
-            fail(HLMI_EINVAL, "hlmi_vq_clique_iteration: NULL argument");
-        require_device();
-        vq_clique_iteration_run(singles_fastq, overlaps, subreads_in, *go, *co, *no, out_dir, gst, cst, nst);
-    });
+    return hlmi_vq_clique_iteration_mq(singles_fastq, overlaps, subreads_in, go, co, no, VQ_MIN_QUAL, out_dir, gst, cst, nst);
 }
 
 void hlmi_vq_branch_opts_polyte(hlmi_vq_branch_opts *o) {
@@ -419,19 +450,28 @@ int hlmi_vq_branch_graph(const char *singles_fastq, const char *overlaps, const 
     });
 }
 
-int hlmi_vq_branch_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
-                             const char *threshold_table, const hlmi_vq_graph_opts *go, const hlmi_vq_branch_opts *bo,
-                             const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no, const char *out_dir,
-                             hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst, hlmi_vq_clique_stats *cst,
-                             hlmi_vq_clique_next_stats *nst) {
+int hlmi_vq_branch_iteration_mq(const char *singles_fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
+                                const char *threshold_table, const hlmi_vq_graph_opts *go, const hlmi_vq_branch_opts *bo,
+                                const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no, double min_qual, const char *out_dir,
+                                hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst, hlmi_vq_clique_stats *cst,
+                                hlmi_vq_clique_next_stats *nst) {
     return guarded([&] {
         if (!singles_fastq || !overlaps || !original_fastq || !threshold_table || !go || !bo || !co || !no || !out_dir || !gst || !bst ||
             !cst || !nst)
             fail(HLMI_EINVAL, "hlmi_vq_branch_iteration: NULL argument");
         require_device();
-        vq_branch_iteration_run(singles_fastq, overlaps, subreads_in, original_fastq, threshold_table, *go, *bo, *co, *no, out_dir, gst,
-                                bst, cst, nst);
+        vq_branch_iteration_run(singles_fastq, overlaps, subreads_in, original_fastq, threshold_table, *go, *bo, *co, *no, min_qual,
+                                out_dir, gst, bst, cst, nst);
     });
+}
+
+int hlmi_vq_branch_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
+                             const char *threshold_table, const hlmi_vq_graph_opts *go, const hlmi_vq_branch_opts *bo,
+                             const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no, const char *out_dir,
+                             hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst, hlmi_vq_clique_stats *cst,
+                             hlmi_vq_clique_next_stats *nst) {
+    return hlmi_vq_branch_iteration_mq(singles_fastq, overlaps, subreads_in, original_fastq, threshold_table, go, bo, co, no, VQ_MIN_QUAL,
+                                       out_dir, gst, bst, cst, nst);
 }
 
 void hlmi_cluster_opts_default(hlmi_cluster_opts *o) {

@@ -21,7 +21,7 @@ namespace vqc {
 namespace {
 
 using vqm::NQ;                                   // the consensus tables of vq_merge.hip
-using vqm::base_code; using vqm::complement;
+using vqm::base_code; using vqm::complement; using vqm::pair_base;
 using vqm::T_ALL; using vqm::T_SINGLE; using vqm::T_WITH_N; using vqm::T_SAME; using vqm::T_DIFF;
 constexpr int WAVES = WG / WAVE;
 
@@ -117,8 +117,7 @@ __global__ __launch_bounds__(WG) void pile_kernel(const Pile *piles, uint32_t n_
                         else if (c1 == 4 || c2 == 4) e = c1 == 4 ? lds_tab[T_WITH_N + c2 * NQ + i2] : lds_tab[T_WITH_N + c1 * NQ + i1];
                         else {
                             const uint32_t t = lds_tab[(c1 == c2 ? T_SAME : T_DIFF) + i1 * NQ + i2];
-                            const uint32_t act = t >> 8;
-                            e = ((uint32_t)(act == 0 ? 'N' : act == 2 ? b2 : b1) << 8) | (t & 0xffu);
+                            e = ((uint32_t)pair_base(t >> 8, b1, b2, c1, c2) << 8) | (t & 0xffu);
                         }
                     } else {
                         e = decide(sA, sC, sG, sT, min_qual, p93);
@@ -140,10 +139,11 @@ __global__ __launch_bounds__(WG) void pile_kernel(const Pile *piles, uint32_t n_
 using namespace vqc;
 
 void VqMergeDev::consensus_piles(const std::vector<Pile> &piles, const std::vector<Entry> &entries, uint32_t min_support,
-                                 bool error_correction, std::vector<uint8_t> &bases, std::vector<uint8_t> &quals,
+                                 bool error_correction, double min_qual, std::vector<uint8_t> &bases, std::vector<uint8_t> &quals,
                                  std::vector<Result> &res) {
     bases.clear(); quals.clear(); res.clear();
     if (piles.empty()) return;
+    vq_check_min_qual(min_qual, "vq_cliques");
     if (piles.size() >= (1ull << 31) || entries.size() >= (1ull << 32)) fail(HLMI_EINVAL, "vq_cliques: %zu pile-ups", piles.size());
     const std::vector<uint64_t> off = d_off_.download();
     uint64_t cols = 0;
@@ -182,7 +182,7 @@ void VqMergeDev::consensus_piles(const std::vector<Pile> &piles, const std::vect
     {
         KTimer t("vq_clique_piles");
         hipLaunchKernelGGL(pile_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(vqc::WG), 0, stream(), d_piles.p,
-                           (uint32_t)piles.size(), d_entries.p, d_bases_.p, d_quals_.p, d_off_.p, d_tab_.p, d_logs.p, 0.9,
+                           (uint32_t)piles.size(), d_entries.p, d_bases_.p, d_quals_.p, d_off_.p, d_tab_.p, d_logs.p, min_qual,
                            pow(10.0, -9.3), min_support, error_correction ? 1 : 0, d_b.p, d_q.p, d_res.p);
         HIP_CHECK(hipGetLastError());
     }

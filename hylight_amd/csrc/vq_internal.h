@@ -208,10 +208,13 @@ constexpr uint32_t NONE = 0xffffffffu;
 // The answers of SRBuilder::consensus_pos as 16-bit entries, low byte = quality character.
 //   single[c][q]      one base c (A C G T N = 0 .. 4): high byte = the base written
 //   with_n[c][q]      base c (0 .. 3) against an N of any quality: high byte = the base written
-//   same[q1][q2]      twice one base: high byte 1 = that base, 0 = N
-//   diff[q1][q2]      two different bases: 0 = N, 1 = the first, 2 = the second
-// The host evaluates every (base, quality) pair and builds same / diff only if the answer is the same whichever bases they
-// are (it depends on them through the order of the four terms of total_prob alone); otherwise the call fails.
+//   same[q1][q2]      twice one base: high byte 1 = that base, 0 = N, 4 = the first of A, T, C, G that is another base
+//   diff[q1][q2]      two different bases: 0 = N, 1 = the first, 2 = the second, 3 = the one of the two that comes first in
+//                     A, T, C, G, 4 = the first of A, T, C, G that is neither
+// The host evaluates every (base, quality) pair for the call's minQual and builds same / diff only if the answer is the same
+// whichever bases they are (it depends on them through the order of the four terms of total_prob) or is the tie rule of
+// consensus_pos (:390-393) in every pair: 3 for two different bases of equal score, 4 where both bases are Q0 / Q1 and the
+// bases that were not read score best - columns a minQual of 1/2 and more turns into N.  Otherwise the call fails.
 constexpr int T_SINGLE = 0, T_WITH_N = T_SINGLE + 5 * NQ, T_SAME = T_WITH_N + 4 * NQ, T_DIFF = T_SAME + NQ * NQ,
               T_ALL = T_DIFF + NQ * NQ;
 constexpr uint32_t F_REV_A = 1, F_REV_B = 2, F_CONS = 4;
@@ -226,6 +229,13 @@ __device__ __forceinline__ uint32_t base_code(uint8_t c) {      // A C G T N -> 
 __device__ __forceinline__ uint8_t complement(uint8_t c) {      // Read::build_rev_comp: N stays N
     return c == 'A' ? 'T' : c == 'T' ? 'A' : c == 'C' ? 'G' : c == 'G' ? 'C' : c;
 }
+// the base a two-base cell of same / diff stands for: b1 / b2 with base codes c1 / c2 (0 .. 3), act = the cell's high byte
+__device__ __forceinline__ uint8_t pair_base(uint32_t act, uint8_t b1, uint8_t b2, uint32_t c1, uint32_t c2) {
+    const uint32_t first2 = ((0x1320u >> (4 * c2)) & 3u) < ((0x1320u >> (4 * c1)) & 3u);      // rank in A, T, C, G per nibble
+    const uint32_t read = (1u << c1) | (1u << c2);                        // bit per base code: A C G T
+    const uint8_t other = !(read & 1u) ? 'A' : !(read & 8u) ? 'T' : !(read & 2u) ? 'C' : 'G';
+    return act == 0 ? (uint8_t)'N' : act == 4 ? other : (act == 2) | ((act == 3) & first2) ? b2 : b1;
+}
 }  // namespace vqm
 
 namespace vqc { struct Pile; struct Entry; struct Result; }
@@ -239,8 +249,9 @@ public:
     std::string write(const std::vector<vqm::Rec> &recs, std::vector<uint64_t> &start);
     // vq_clique.hip: SRBuilder::consensus of every pile-up, one wave each.  bases / quals receive the piles' columns (pile k
     // at col0), a quality byte of 0 marks a column the host has to redo (vqc::MARGIN); res[k] as vqc::Result says
+    // min_qual: the value the tables handed to the constructor were built for
     void consensus_piles(const std::vector<vqc::Pile> &piles, const std::vector<vqc::Entry> &entries, uint32_t min_support,
-                         bool error_correction, std::vector<uint8_t> &bases, std::vector<uint8_t> &quals,
+                         bool error_correction, double min_qual, std::vector<uint8_t> &bases, std::vector<uint8_t> &quals,
                          std::vector<vqc::Result> &res);
 private:
     void layout(const std::vector<vqm::Rec> &recs, DBuf<vqm::Rec> &d_rec, DBuf<uint64_t> &pos0, DBuf<uint64_t> &byte0);
@@ -285,10 +296,13 @@ struct Result { uint32_t stop, empty; };         // columns [trim_pos, stop) are
 // refused in a read (HLMI_EINVAL): a base outside A C G T N, a quality outside '!' .. '~', a quality line of another length
 void vq_check_read(const char *seq, size_t len, const char *qual, size_t qlen, const char *what, size_t k);
 void vq_merge_check_reads(const std::vector<std::string> &seq, const std::vector<std::string> &qual);
+constexpr double VQ_MIN_QUAL = 0.9;                           // ViralQuasispecies.cpp:62 (--min_qual default) -> SRBuilder.h:89
+void vq_check_min_qual(double min_qual, const char *step);     // HLMI_EINVAL outside [0, 1], a NaN included
 // SRBuilder::consensus_pos (:297-402) of n >= 1 nucleotides (A C G T N) with their phreds, in the reference's expression order
-// with the host's libm -> (base << 8) | quality character
-uint16_t vq_consensus_pos(const char *nuc, const int *phred, int n);
-const std::vector<uint16_t> &vq_consensus_tables();            // the vqm::T_* tables, built once
+// with the host's libm -> (base << 8) | quality character.  The one evaluation: tables and column redo both come from it
+uint16_t vq_consensus_pos(const char *nuc, const int *phred, int n, double min_qual = VQ_MIN_QUAL);
+// the vqm::T_* tables of one minQual, built once per distinct value; refuses a value vq_check_min_qual refuses
+const std::vector<uint16_t> &vq_consensus_tables(double min_qual);
 
 // OriginalIndex of a single-end original (Types.h): forward, index1, len1
 struct VqOrig { bool forward; long index; int len; };
@@ -320,7 +334,8 @@ int64_t vq_place(const VqGraphState &g, const std::vector<uint32_t> &clique, con
 // filter_subreads (:597-636) with sortVerticesByEndpos (:639-652, std::sort on the end alone): the `num` entries that stay
 VqPlaced vq_filter_subreads(const VqGraphState &g, size_t num, uint32_t base, const VqPlaced &order);
 // consensus_pos of one pile-up column by the host's libm: the entries that cover it in list order, reversed ones complemented
-uint16_t vq_consensus_column(const VqGraphState &g, const vqc::Entry *entries, uint32_t n_entries, uint32_t column);
+uint16_t vq_consensus_column(const VqGraphState &g, const vqc::Entry *entries, uint32_t n_entries, uint32_t column,
+                             double min_qual = VQ_MIN_QUAL);
 bool vq_n_rate_ok(uint64_t n, uint64_t len);                   // Read::test_N_rate (Read.h:214-233)
 // The reads in no super-read (:1145-1222, :1282-1372), vertices ascending: dropped when shorter than keep_singletons or failing
 // the N rate (read_n = 'N's per read), to `diverted` when flagged in `divert` (NULL: none), else a record from id first_id on
@@ -387,19 +402,21 @@ void vq_branch_graph_run(const char *fastq, const char *overlaps, const char *su
                          hlmi_vq_branch_stats *bst);
 void vq_branch_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
                              const char *table, const hlmi_vq_graph_opts &go, const hlmi_vq_branch_opts &bo, const hlmi_vq_clique_opts &co,
-                             const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst,
-                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst);
+                             const hlmi_vq_next_opts &no, double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst,
+                             hlmi_vq_branch_stats *bst, hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst);
 
-// ---- drivers: vq_superread_run.cpp (include/hylight_mi.h; vq_iteration_run is declared with `next` below) -------------------
+// ---- drivers: vq_superread_run.cpp (include/hylight_mi.h; vq_iteration_run is declared with `next` below).  min_qual is
+// --min_qual: it reaches the tables, the pile-up kernel and the host's column redo, and is checked before a file is written ----
 void vq_merge_opts_stageb(hlmi_vq_merge_opts *o);
 void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                  const hlmi_vq_merge_opts &mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
+                  const hlmi_vq_merge_opts &mo, double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
 void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2, const char *qual2,
-                       uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual, uint32_t *out_len);
+                       uint32_t len2, uint32_t qlen2, uint32_t pos, double min_qual, char *out_seq, char *out_qual, uint32_t *out_len);
 void vq_clique_opts_polyte(hlmi_vq_clique_opts *o, int error_correction);
 void vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uint64_t *n_cliques);
 void vq_cliques_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                    const hlmi_vq_clique_opts &co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst);
+                    const hlmi_vq_clique_opts &co, double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst,
+                    hlmi_vq_clique_stats *cst);
 
 // ---- next: vq_next.hip (SRBuilder::findNextOverlaps, FNO 1) ---------------------------------------------------------------
 namespace vqn {
@@ -430,10 +447,10 @@ void vq_next_opts_stageb(hlmi_vq_next_opts *o);
 std::string vq_next_run(const VqGraphState &g, const std::vector<std::vector<VqEdge>> &out, const VqNextTables &t,
                         double edge_threshold, const hlmi_vq_next_opts &no, hlmi_vq_clique_next_stats *st);
 void vq_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                      const hlmi_vq_merge_opts &mo, const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst,
-                      hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst);
+                      const hlmi_vq_merge_opts &mo, const hlmi_vq_next_opts &no, double min_qual, const char *out_dir,
+                      hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst);
 void vq_clique_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                             const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst,
-                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst);
+                             const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts &no, double min_qual, const char *out_dir,
+                             hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst);
 
 }  // namespace hlmi

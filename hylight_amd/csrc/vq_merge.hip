@@ -106,9 +106,8 @@ __global__ __launch_bounds__(WG) void merge_kernel(const Rec *rec, const uint64_
                     ob = (uint8_t)(e >> 8); oq = (uint8_t)e;
                 } else {
                     const uint16_t e = lds_tab[(c1 == c2 ? T_SAME : T_DIFF) + i1 * NQ + i2];
-                    const uint32_t act = e >> 8;
                     oq = (uint8_t)e;
-                    ob = act == 0 ? 'N' : act == 2 ? b2 : b1;
+                    ob = pair_base(e >> 8, b1, b2, c1, c2);
                 }
             }
             if (WRITE) {

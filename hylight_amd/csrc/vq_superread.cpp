@@ -6,16 +6,22 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
+#include <mutex>
 
 #include "vq_internal.h"
 
 namespace hlmi {
 
 using namespace vqm;
-static constexpr double MIN_QUAL = 0.9;   // ViralQuasispecies.cpp:62 (--min_qual default) -> SRBuilder.h:89
+
+// --min_qual (ViralQuasispecies.cpp:62 -> SRBuilder.h:89) lies in [0, 1]: 0 never writes an N for disagreement, 1 nearly always
+void vq_check_min_qual(double min_qual, const char *step) {
+    if (!(min_qual >= 0.0 && min_qual <= 1.0)) fail(HLMI_EINVAL, "%s: min_qual %g is outside 0 .. 1", step, min_qual);
+}
 
 // SRBuilder::consensus_pos (:297-402) in its own expression order.  -> (base << 8) | quality
-uint16_t vq_consensus_pos(const char *nuc, const int *phred, int n) {
+uint16_t vq_consensus_pos(const char *nuc, const int *phred, int n, double min_qual) {
     double score_A = 0, score_C = 0, score_T = 0, score_G = 0;
     for (int i = 0; i < n; ++i) {
         const double p = pow(10, -phred[i] / 10.0);                        // phred_to_prob (:289-293)
@@ -33,7 +39,7 @@ uint16_t vq_consensus_pos(const char *nuc, const int *phred, int n) {
     const uint16_t n_out = (uint16_t)(('N' << 8) | '$');
     if (max_score == 0 || total_prob == 0.0) return n_out;                 // :354-359
     const double p_incorrect = 1 - (max_prob / total_prob);
-    if (n > 1 && (1 - p_incorrect) < MIN_QUAL) return n_out;               // :362-368
+    if (n > 1 && (1 - p_incorrect) < min_qual) return n_out;               // :362-368
     if (p_incorrect != p_incorrect) fail(HLMI_EINVAL, "vq_merge: consensus table entry is not a number");   // (:369-372: never)
     int phred_out;
     if (p_incorrect < std::pow(10.0, -9.3)) phred_out = 93;
@@ -48,18 +54,29 @@ uint16_t vq_consensus_pos(const char *nuc, const int *phred, int n) {
     return (uint16_t)((b << 8) | (phred_out + 33));
 }
 
-// The tables of vq_internal.h (vqm::T_*).  Every pair of (base, quality) is evaluated; the forms by class that fit LDS are
-// kept only if the answer does not depend on which bases they are - it can, through the order of the four terms of
-// total_prob - and the build fails otherwise (with glibc's libm it does not).
-static std::vector<uint16_t> build_consensus_tables() {
+// The tables of vq_internal.h (vqm::T_*) for one minQual.  Every pair of (base, quality) is evaluated; the forms by class that
+// fit LDS are kept only if the answer does not depend on which bases they are - it can, through the order of the four terms of
+// total_prob - and the build fails otherwise (with glibc's libm it does not).  Two dependences are part of the reference and
+// have codes of their own, both through the chain of :390-393 once minQual no longer turns the column into N:
+//   3  two different bases whose scores are EQUAL (a + b == b + a: equal qualities): the one that comes first in A, T, C, G
+//   4  neither of the two wins: a base of Q0 or Q1 is more likely wrong than right (p > 3/4, so p / 3 > 1 - p), and when that
+//      holds for both the bases that were NOT read tie for the best score: the first of them in A, T, C, G
+static int atcg_rank(int c) { return c == 0 ? 0 : c == 3 ? 1 : c == 1 ? 2 : 3; }      // c: A C G T = 0 .. 3
+static char first_other(int c1, int c2) {
+    for (int c : {0, 3, 1, 2})
+        if (c != c1 && c != c2) return "ACGT"[c];
+    return 0;
+}
+
+static std::vector<uint16_t> build_consensus_tables(double min_qual) {
     std::vector<uint16_t> t((size_t)T_ALL);
     const char B[6] = "ACGTN";
     for (int c = 0; c < 5; ++c)
-        for (int q = 0; q < NQ; ++q) t[T_SINGLE + c * NQ + q] = vq_consensus_pos(&B[c], &q, 1);
+        for (int q = 0; q < NQ; ++q) t[T_SINGLE + c * NQ + q] = vq_consensus_pos(&B[c], &q, 1, min_qual);
     auto pair = [&](int c1, int c2, int q1, int q2) {
         const char nuc[2] = {B[c1], B[c2]};
         const int ph[2] = {q1, q2};
-        return vq_consensus_pos(nuc, ph, 2);
+        return vq_consensus_pos(nuc, ph, 2, min_qual);
     };
     for (int c = 0; c < 4; ++c)
         for (int q = 0; q < NQ; ++q) {
@@ -71,31 +88,41 @@ static std::vector<uint16_t> build_consensus_tables() {
     for (int q1 = 0; q1 < NQ; ++q1)
         for (int q2 = 0; q2 < NQ; ++q2) {
             if (pair(4, 4, q1, q2) != (uint16_t)(('N' << 8) | '$')) fail(HLMI_EINVAL, "vq_merge: N against N is not N");
-            uint16_t same = 0, diff = 0;
-            bool first_same = true, first_diff = true;
+            // per class: the quality byte (one for all pairs), whether every pair gives one act of 0 / 1 / 2, whether every pair
+            // gives the earlier base of the chain
+            int same_act = -1, diff_act = -1, same_q = -1, diff_q = -1;
+            bool same_one = true, diff_one = true, diff_chain = true;
             for (int c1 = 0; c1 < 4; ++c1)
                 for (int c2 = 0; c2 < 4; ++c2) {
                     const uint16_t f = pair(c1, c2, q1, q2);
                     const char b = (char)(f >> 8);
-                    const int act = b == 'N' ? 0 : b == B[c1] ? 1 : (c1 != c2 && b == B[c2]) ? 2 : -1;
-                    const uint16_t cur = (uint16_t)((act << 8) | (f & 0xff));
-                    uint16_t &slot = c1 == c2 ? same : diff;
-                    bool &first = c1 == c2 ? first_same : first_diff;
-                    if (act < 0 || (!first && cur != slot))
+                    const int act = b == 'N' ? 0 : b == B[c1] ? 1 : (c1 != c2 && b == B[c2]) ? 2 : b == first_other(c1, c2) ? 4 : -1;
+                    int &cls_act = c1 == c2 ? same_act : diff_act, &cls_q = c1 == c2 ? same_q : diff_q;
+                    if (cls_q < 0) { cls_act = act; cls_q = f & 0xff; }
+                    if (act != cls_act) (c1 == c2 ? same_one : diff_one) = false;
+                    if (c1 != c2 && act != (atcg_rank(c1) < atcg_rank(c2) ? 1 : 2)) diff_chain = false;
+                    if (act < 0 || (f & 0xff) != cls_q || !same_one || (!diff_one && !diff_chain))
                         fail(HLMI_EINVAL, "vq_merge: the consensus of %c/Q%d and %c/Q%d depends on the bases' identity: the tables "
                                           "by class do not hold on this libm", B[c1], q1, B[c2], q2);
-                    slot = cur;
-                    first = false;
                 }
-            t[T_SAME + q1 * NQ + q2] = same;
-            t[T_DIFF + q1 * NQ + q2] = diff;
+            t[T_SAME + q1 * NQ + q2] = (uint16_t)((same_act << 8) | same_q);
+            t[T_DIFF + q1 * NQ + q2] = (uint16_t)(((diff_one ? diff_act : 3) << 8) | diff_q);
         }
     return t;
 }
 
-const std::vector<uint16_t> &vq_consensus_tables() {
-    static const std::vector<uint16_t> tab = build_consensus_tables();     // (initialised once, also under concurrent calls)
-    return tab;
+// built once per distinct value (the bit pattern of the double is the key) and kept: a run uses one value, a process a few
+const std::vector<uint16_t> &vq_consensus_tables(double min_qual) {
+    vq_check_min_qual(min_qual, "vq_merge");
+    if (min_qual == 0.0) min_qual = 0.0;                                   // (-0.0 compares like 0.0 everywhere: one entry)
+    uint64_t key;
+    memcpy(&key, &min_qual, sizeof key);
+    static std::mutex lock;
+    static std::map<uint64_t, std::vector<uint16_t>> built;                // (a map: an entry never moves once it is there)
+    std::lock_guard<std::mutex> hold(lock);
+    auto it = built.find(key);
+    if (it == built.end()) it = built.emplace(key, build_consensus_tables(min_qual)).first;
+    return it->second;
 }
 
 void vq_check_read(const char *seq, size_t len, const char *qual, size_t qlen, const char *what, size_t k) {
@@ -240,7 +267,7 @@ VqPlaced vq_filter_subreads(const VqGraphState &g, size_t num, uint32_t base, co
     return used;
 }
 
-uint16_t vq_consensus_column(const VqGraphState &g, const vqc::Entry *entries, uint32_t n_entries, uint32_t column) {
+uint16_t vq_consensus_column(const VqGraphState &g, const vqc::Entry *entries, uint32_t n_entries, uint32_t column, double min_qual) {
     std::vector<char> nuc(n_entries);
     std::vector<int> phred(n_entries);
     int n = 0;
@@ -254,7 +281,7 @@ uint16_t vq_consensus_column(const VqGraphState &g, const vqc::Entry *entries, u
         nuc[n] = ch;
         phred[n++] = (e.rev ? ql[s.size() - 1 - i] : ql[i]) - 33;
     }
-    return vq_consensus_pos(nuc.data(), phred.data(), n);
+    return vq_consensus_pos(nuc.data(), phred.data(), n, min_qual);
 }
 
 bool vq_n_rate_ok(uint64_t n, uint64_t len) { return (double)n < 0.05 * (double)len; }

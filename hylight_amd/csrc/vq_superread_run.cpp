@@ -36,8 +36,9 @@ void vq_clique_opts_polyte(hlmi_vq_clique_opts *o, int error_correction) {
 void vq_next_opts_stageb(hlmi_vq_next_opts *o) { *o = hlmi_vq_next_opts{}; }
 
 void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2, const char *qual2,
-                       uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual, uint32_t *out_len) {
+                       uint32_t len2, uint32_t qlen2, uint32_t pos, double min_qual, char *out_seq, char *out_qual, uint32_t *out_len) {
     *out_len = 0;
+    const std::vector<uint16_t> &tables = vq_consensus_tables(min_qual);
     vq_check_read(seq1, len1, qual1, qlen1, "hlmi_vq_consensus_pair: sequence", 1);
     vq_check_read(seq2, len2, qual2, qlen2, "hlmi_vq_consensus_pair: sequence", 2);
     const uint64_t total = std::max<uint64_t>(len1, (uint64_t)pos + len2);   // base + left + right extension (:224-252)
@@ -52,7 +53,7 @@ void vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint3
     std::vector<std::string> seq{std::string(seq1, len1), std::string(seq2, len2)}, qual{std::string(qual1, len1), std::string(qual2, len2)};
     Rec r{};
     r.a = 0; r.b = len2 ? 1u : NONE; r.p = pos; r.len = (uint32_t)total; r.flags = F_CONS; r.id = 0;
-    VqMergeDev dev(seq, qual, vq_consensus_tables());
+    VqMergeDev dev(seq, qual, tables);
     std::vector<uint64_t> start;
     const std::string text = dev.write(std::vector<Rec>{r}, start);
     memcpy(out_seq, text.data() + 3, total);                                // "@0\n"
@@ -78,11 +79,13 @@ static void next_and_stats(const VqGraphState &g, const std::vector<std::vector<
 
 // hlmi_vq_merge (no == NULL) and hlmi_vq_iteration: one path.  With `no` the call goes on to findNextOverlaps, and reads
 // subreads_in in front of the graph's first write: the iteration loop runs in place, its inputs under the names written here.
+// min_qual reaches the tables the two passes of merge_kernel read, and through the 'N's they count, test_N_rate.
 static void merge_and_next(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                           const hlmi_vq_merge_opts &mo, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
-                           hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst) {
+                           const hlmi_vq_merge_opts &mo, const hlmi_vq_next_opts *no, double min_qual, const char *out_dir,
+                           hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst) {
     *mst = hlmi_vq_merge_stats{};
     if (nst) *nst = hlmi_vq_next_stats{};
+    const std::vector<uint16_t> &tables = vq_consensus_tables(min_qual);     // refuses a bad min_qual in front of the first write
     VqOriginalsDict dict("vq_merge", mo.first_it != 0, subreads_in);
     if (no) read_originals(dict);
     VqGraphState g;
@@ -93,7 +96,7 @@ static void merge_and_next(const char *fastq, const char *overlaps, const char *
     for (uint32_t v = 0; v < V; ++v) mst->bases_in += g.seq[v].size();       // (checked by vq_graph_run: vq_merge_check_reads)
     if (!no) read_originals(dict);
 
-    VqMergeDev dev(g.seq, g.qual, vq_consensus_tables());
+    VqMergeDev dev(g.seq, g.qual, tables);
 
     // getEdgesForMerging (GraphAlgos.cpp:112-148): vertices ascending; each free one takes its first free out-neighbour
     std::vector<uint8_t> taken(V, 0);
@@ -207,14 +210,14 @@ static void merge_and_next(const char *fastq, const char *overlaps, const char *
 }
 
 void vq_merge_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                  const hlmi_vq_merge_opts &mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst) {
-    merge_and_next(fastq, overlaps, subreads_in, go, mo, nullptr, out_dir, gst, mst, nullptr);
+                  const hlmi_vq_merge_opts &mo, double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst) {
+    merge_and_next(fastq, overlaps, subreads_in, go, mo, nullptr, min_qual, out_dir, gst, mst, nullptr);
 }
 
 void vq_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                      const hlmi_vq_merge_opts &mo, const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst,
-                      hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst) {
-    merge_and_next(fastq, overlaps, subreads_in, go, mo, &no, out_dir, gst, mst, nst);
+                      const hlmi_vq_merge_opts &mo, const hlmi_vq_next_opts &no, double min_qual, const char *out_dir,
+                      hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst) {
+    merge_and_next(fastq, overlaps, subreads_in, go, mo, &no, min_qual, out_dir, gst, mst, nst);
 }
 
 void vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uint64_t *n_cliques) {
@@ -223,13 +226,16 @@ void vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uint64_
     *n_cliques = list.off.size() - 1;
 }
 
-// hlmi_vq_cliques (no == NULL) and hlmi_vq_clique_iteration: one path, as merge_and_next is
+// hlmi_vq_cliques (no == NULL) and hlmi_vq_clique_iteration: one path, as merge_and_next is.  min_qual reaches the tables, the
+// pile-up kernel and the host's redo of a marked column: the three places a column is decided
 static void cliques_and_next(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                             const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
-                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst, VqBranchRun *branch = nullptr) {
+                             const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts *no, double min_qual, const char *out_dir,
+                             hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst,
+                             VqBranchRun *branch = nullptr) {
     using namespace vqc;
     *cst = hlmi_vq_clique_stats{};
     if (nst) *nst = hlmi_vq_clique_next_stats{};
+    const std::vector<uint16_t> &tables = vq_consensus_tables(min_qual);     // refuses a bad min_qual in front of the first write
     if (co.min_clique_size == 0 || co.min_clique_size > MAX_MIN_CLIQUE)
         fail(HLMI_EINVAL, "vq_cliques: min_clique_size %u is outside 1 .. %u", co.min_clique_size, MAX_MIN_CLIQUE);
     VqOriginalsDict dict("vq_cliques", co.first_it != 0, subreads_in);
@@ -302,10 +308,10 @@ static void cliques_and_next(const char *fastq, const char *overlaps, const char
     }
 
     const double t_placed = now_ms();
-    VqMergeDev dev(g.seq, g.qual, vq_consensus_tables());
+    VqMergeDev dev(g.seq, g.qual, tables);
     std::vector<uint8_t> cb, cq;
     std::vector<Result> res;
-    dev.consensus_piles(piles, entries, mcs, co.error_correction != 0, cb, cq, res);
+    dev.consensus_piles(piles, entries, mcs, co.error_correction != 0, min_qual, cb, cq, res);
     const double t_device = now_ms();
 
     // process_cliques (:998-1001), writeSinglesToFile, the originals (:750-806)
@@ -327,7 +333,7 @@ static void cliques_and_next(const char *fastq, const char *overlaps, const char
         uint64_t n_count = 0;
         for (uint32_t x = 0; x < len; ++x) {
             if (q[x] == 0) {                     // too close to a threshold for the device: the host's libm decides
-                const uint16_t e = vq_consensus_column(g, &entries[pl.first], pl.n, pl.trim_pos + x);
+                const uint16_t e = vq_consensus_column(g, &entries[pl.first], pl.n, pl.trim_pos + x, min_qual);
                 b[x] = (uint8_t)(e >> 8);
                 q[x] = (uint8_t)e;
                 ++cst->columns_host;
@@ -387,25 +393,26 @@ static void cliques_and_next(const char *fastq, const char *overlaps, const char
 }
 
 void vq_cliques_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                    const hlmi_vq_clique_opts &co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst) {
-    cliques_and_next(fastq, overlaps, subreads_in, go, co, nullptr, out_dir, gst, cst, nullptr);
+                    const hlmi_vq_clique_opts &co, double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst,
+                    hlmi_vq_clique_stats *cst) {
+    cliques_and_next(fastq, overlaps, subreads_in, go, co, nullptr, min_qual, out_dir, gst, cst, nullptr);
 }
 
 void vq_clique_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts &go,
-                             const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst,
-                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst) {
-    cliques_and_next(fastq, overlaps, subreads_in, go, co, &no, out_dir, gst, cst, nst);
+                             const hlmi_vq_clique_opts &co, const hlmi_vq_next_opts &no, double min_qual, const char *out_dir,
+                             hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst) {
+    cliques_and_next(fastq, overlaps, subreads_in, go, co, &no, min_qual, out_dir, gst, cst, nst);
 }
 
 // hlmi_vq_branch_iteration: hlmi_vq_clique_iteration's path with the branch reduction inside its graph
 void vq_branch_iteration_run(const char *fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
                              const char *table, const hlmi_vq_graph_opts &go, const hlmi_vq_branch_opts &bo, const hlmi_vq_clique_opts &co,
-                             const hlmi_vq_next_opts &no, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst,
-                             hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst) {
+                             const hlmi_vq_next_opts &no, double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst,
+                             hlmi_vq_branch_stats *bst, hlmi_vq_clique_stats *cst, hlmi_vq_clique_next_stats *nst) {
     *bst = hlmi_vq_branch_stats{};
     VqBranchRun br;
     br.bo = bo; br.original_fastq = original_fastq; br.table_path = table; br.st = bst;
-    cliques_and_next(fastq, overlaps, subreads_in, go, co, &no, out_dir, gst, cst, nst, &br);
+    cliques_and_next(fastq, overlaps, subreads_in, go, co, &no, min_qual, out_dir, gst, cst, nst, &br);
 }
 
 }  // namespace hlmi

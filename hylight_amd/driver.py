@@ -20,8 +20,9 @@ The short-read branch (HyLight.py:211-275) is opt-in: `--stop_after clusters` ru
 tmp/all.contigs_<size>.fasta, extends it into short_stageb.fa (with `--stageb_cmd`) and builds all_contigs.fa from it and
 long_con_polished.fa.  Without these flags the run is the same as before.  POLYTE's clique iteration exists natively and now
 ends in overlaps.txt (python -m hylight_amd.vq_cliques --iteration: hlmi_vq_clique_iteration, findNextOverlaps over the
-super-read lists); `--polyte_cmd` stays external and is not rewired to it: BranchReduction, paired-end reads and POLYTE's
---min_qual=0 (the native step keeps minQual 0.9) are still missing.
+super-read lists), with POLYTE's --min_qual=0 as `--min_qual 0`; `--polyte_cmd` stays external and is not rewired to it: the
+loop of polyte.tune_params.py with its threshold table and paired-end reads are still missing.  `--stageb_native` keeps minQual
+0.9: pipeline_per_stage.py does not pass the flag.
 
 `--gpus N` (extension): every split_reads2 call is sharded over N GPUs of the node, chunk i -> rank i % N, the way the
 reference fans its chunks out with `xargs -P` (script/utils.py:44-69).  The process starts N - 1 further copies of

@@ -4,13 +4,13 @@ file with its branches reduced by read evidence (BranchReduction::readBasedBranc
 
     python -m hylight_amd.vq_branches --singles singles.fastq --overlaps overlaps.txt --out DIR --branch_reduction true
         --original_fastq original.fastq --branch_SE_c N --branch_PE_c M --thresholds evidence_threshold_table.tsv
-        [--careful_diploid true] [--subreads subreads.txt --first_it false] [--iteration [clique options]]
+        [--careful_diploid true] [--subreads subreads.txt --first_it false] [--iteration [clique options, --min_qual X]]
 
 Writes what python -m hylight_amd.vq_graph writes, and branch_components.txt.  The flags carry the reference's names;
 --thresholds names the table the reference reads from its working directory.  The defaults are POLYTE's for this iteration:
 remove_trans 1, remove_branches false, tips and inclusions kept, the cliques without error correction.  With --iteration the run
-goes on through the clique step to the end of ViralQuasispecies' main (hlmi_vq_branch_iteration).  Not built, and said so:
---min_qual=0, --diploid (the typical-double-branch resolution), paired-end vertices, POLYTE's loop and its threshold table
+goes on through the clique step to the end of ViralQuasispecies' main (hlmi_vq_branch_iteration); --min_qual 0 there is what
+POLYTE passes (not passed by default: minQual 0.9).  Not built, and said so: --diploid (the typical-double-branch resolution), paired-end vertices, POLYTE's loop and its threshold table
 (min_ev_table.py).  Prints {"graph": ..., "branches": ...} - with --iteration also "cliques" and "next" - as one JSON line.
 Exit status 0 on success, 4 (EXIT_REFUSED) for what is refused as not built (a paired-end row, --remove_trans other than 1,
 --remove_branches true, --branch_reduction false, --diploid true), 2 (EXIT_INVALID) for a malformed input: counts that do not
@@ -60,6 +60,9 @@ def main(argv=None):
                 remove_trans=1, remove_branches=False, remove_tips=a.remove_tips, ignore_inclusions=a.ignore_inclusions,
                 remove_backedges=not ec, max_overlaps=a.max_ov, se_count=a.branch_SE_c, pe_count=a.branch_PE_c,
                 careful=a.careful_diploid)
+    if a.min_qual is not None and not a.iteration:
+        sys.stderr.write("hylight_amd.vq_branches: --min_qual belongs to the clique step: it needs --iteration\n")
+        return EXIT_INVALID
     if not a.first_it and a.subreads is None:
         sys.stderr.write("hylight_amd.vq_branches: --first_it false needs --subreads\n")
         return EXIT_INVALID
@@ -68,7 +71,8 @@ def main(argv=None):
             gst, bst, cst, nst = api.vq_branch_iteration(
                 a.singles, a.overlaps, a.original_fastq, a.thresholds, a.out, no_inclusion_overlaps=a.no_inclusion_overlaps,
                 error_correction=ec, first_it=a.first_it, min_clique_size=a.min_clique_size,
-                keep_singletons=polyte["keep_singletons"] if a.keep_singletons is None else a.keep_singletons, **opts)
+                keep_singletons=polyte["keep_singletons"] if a.keep_singletons is None else a.keep_singletons,
+                min_qual=a.min_qual, **opts)
             result = {"graph": gst, "branches": bst, "cliques": cst, "next": nst}
         else:
             gst, bst = api.vq_branch_graph(a.singles, a.overlaps, a.original_fastq, a.thresholds, a.out, **opts)

@@ -4,13 +4,15 @@ the first iteration of every cluster.
 
     python -m hylight_amd.vq_cliques --singles singles.fastq --overlaps overlaps.txt --out DIR [--error_correction true]
         [--min_clique_size N] [--edge_threshold X] [--min_overlap_len N] [--keep_singletons N] [--subreads F]
-        [--iteration [--no_inclusion_overlaps true]]
+        [--min_qual X] [--iteration [--no_inclusion_overlaps true]]
 
 Writes what python -m hylight_amd.vq_graph writes, and cliques.txt (as the reference's enumerator prints it), singles.fastq,
 subreads.txt and clique_map.txt.  The defaults are what POLYTE's run_viralquasispecies passes (polyte.tune_params.py:684-738):
 with --error_correction true remove_trans 2, the back edges kept, keep_singletons 1000; without it remove_trans 1,
-remove_branches true, keep_singletons 0; tips and inclusions stay either way.  POLYTE's --min_qual=0 is not built: minQual
-stays 0.9, so a column whose best base is less than 90 % sure becomes N.  With --iteration the run goes on to the end of
+remove_branches true, keep_singletons 0; tips and inclusions stay either way.  One of its options is not a default here:
+--min_qual 0 ("never insert N's", :737).  Without the flag minQual stays at ViralQuasispecies' own default 0.9, and a column
+whose best base is less than 90 % sure becomes N; with `--min_qual 0 --iteration` the run is a POLYTE first-iteration call.  The
+loop around such calls and its threshold table are not built.  With --iteration the run goes on to the end of
 ViralQuasispecies' main (hlmi_vq_clique_iteration, --FNO=1): overlaps.txt and one line appended to stats.txt, so that another
 iteration can follow; the inputs may then lie in DIR under the names written.  Prints {"graph": ..., "cliques": ...} - with
 --iteration also "next": ... - as one JSON line.  Exit status 0 on success, 4 (EXIT_REFUSED) for what vq_graph refuses (a
@@ -36,6 +38,7 @@ def build_parser():
     p.add_argument("--first_it", type=_bool, default=True)
     p.add_argument("--keep_singletons", type=int, default=None, help="default: 1000 with --error_correction true, else 0")
     p.add_argument("--min_clique_size", type=int, default=2)
+    p.add_argument("--min_qual", type=float, default=None, help="0 .. 1; POLYTE passes 0 (default: not passed, minQual 0.9)")
     p.add_argument("--iteration", action="store_true", help="go on to findNextOverlaps: overlaps.txt and the stats.txt line")
     p.add_argument("--no_inclusion_overlaps", type=_bool, default=False, help="with --iteration: leave out the lines with percentage 100")
     return p
@@ -56,7 +59,7 @@ def main(argv=None):
                 remove_tips=a.remove_tips, ignore_inclusions=a.ignore_inclusions, remove_backedges=not ec,
                 max_overlaps=a.max_ov, error_correction=ec, first_it=a.first_it,
                 keep_singletons=polyte["keep_singletons"] if a.keep_singletons is None else a.keep_singletons,
-                min_clique_size=a.min_clique_size)
+                min_clique_size=a.min_clique_size, min_qual=a.min_qual)
     try:
         if a.iteration:
             gst, cst, nst = api.vq_clique_iteration(a.singles, a.overlaps, a.out, no_inclusion_overlaps=a.no_inclusion_overlaps, **opts)

@@ -55,14 +55,16 @@ def loop(step):
 
 
 def run(fastq_dir, overlaps, out_dir, edge_threshold=1.0, min_overlap_perc=0, min_overlap_len=300, merge_contigs=0.0,
-        min_read_len=0, max_tip_len=1000, verbose=False):
-    """-> dict(iterations, reads, overlaps, edges): the counts pipeline_per_stage.py prints, `overlaps` led by the input's."""
+        min_read_len=0, max_tip_len=1000, verbose=False, min_qual=None):
+    """-> dict(iterations, reads, overlaps, edges): the counts pipeline_per_stage.py prints, `overlaps` led by the input's.
+    min_qual: --min_qual for every iteration (None, as pipeline_per_stage.py leaves it: minQual 0.9)."""
     os.makedirs(out_dir, exist_ok=True)
     p = lambda name: os.path.join(out_dir, name)
     for name in ("stats.txt", "removed_tip_sequences.fastq"):                  # :127-132
         open(p(name), "w").close()
     common = dict(edge_threshold=edge_threshold, min_overlap_perc=min_overlap_perc, min_overlap_len=min_overlap_len,
-                  keep_singletons=max(min_overlap_len, min_read_len), min_read_len=min_read_len, max_tip_len=max_tip_len)
+                  keep_singletons=max(min_overlap_len, min_read_len), min_read_len=min_read_len, max_tip_len=max_tip_len,
+                  min_qual=min_qual)
 
     def step(k):
         if k == 0:
@@ -102,6 +104,7 @@ def build_parser():
     p.add_argument("--merge_contigs", type=float, default=0.0)
     p.add_argument("--min_read_len", type=int, default=0)
     p.add_argument("--max_tip_len", type=int, default=1000)
+    p.add_argument("--min_qual", type=float, default=None, help="0 .. 1, passed to every iteration (default: not passed, minQual 0.9)")
     p.add_argument("--verbose", action="store_true")
     return p
 
@@ -110,7 +113,7 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     try:
         r = run(a.fastq, a.overlaps, a.out, a.edge_threshold, a.min_overlap_perc, a.min_overlap_len, a.merge_contigs, a.min_read_len,
-                a.max_tip_len, a.verbose)
+                a.max_tip_len, a.verbose, a.min_qual)
     except api.HlmiError as e:
         sys.stderr.write(f"hylight_amd.vq_stageb: {e}\n")
         return 1

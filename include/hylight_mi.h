@@ -34,10 +34,11 @@ extern "C" {
 /* Select the HIP device used by this process (one process per GPU).  device < 0 keeps the
  * current device.  host_threads bounds host-side helper threads (text formatting, sorting,
  * the output writer); <= 0: the CPUs this process may run on, 16 at most. */
-/* ABI version: bumped whenever a public struct grows or an entry point changes (5: hlmi_ava_opts ends in zdrop; 6:
- * hlmi_vq_merge, hlmi_vq_consensus_pair).  A caller
- * compares hlmi_abi_version() with the HLMI_ABI_VERSION of the header it was built against BEFORE passing structs: a caller of
- * an older header would hand over a shorter hlmi_ava_opts than the library reads. */
+/* ABI version: bumped whenever a public struct grows or an EXISTING entry point changes its signature (5: hlmi_ava_opts ends
+ * in zdrop; 6: hlmi_vq_merge, hlmi_vq_consensus_pair).  It guards struct layouts and the signatures of existing symbols.  A
+ * caller compares hlmi_abi_version() with the HLMI_ABI_VERSION of the header it was built against BEFORE passing structs: a
+ * caller of an older header would hand over a shorter hlmi_ava_opts than the library reads.  A NEW symbol beside the old ones
+ * (the hlmi_vq_*_mq calls) leaves the version alone: it is found, or not found, when the library is loaded. */
 #define HLMI_ABI_VERSION 7
 int         hlmi_abi_version(void);
 int         hlmi_init(int device, int host_threads);
@@ -251,7 +252,7 @@ int hlmi_vq_graph(const char *singles_fastq, const char *overlaps, const hlmi_vq
  * quality string while it is active (:478: an empty sequence, a quality string shorter than its sequence).  pos == len1
  * is NOT empty: read 1 goes inactive at its last base (:487-492) and read 2 becomes active at position pos (:455-459).
  * minQual is the reference's default 0.9 (ViralQuasispecies.cpp:62 -> SRBuilder.h:89; HyLight's path does not pass
- * --min_qual).  Per position (:297-402): log10 / pow / round are the host's libm in the reference's expression order, kept
+ * --min_qual); hlmi_vq_consensus_pair_mq, below, takes another.  Per position (:297-402): log10 / pow / round are the host's libm in the reference's expression order, kept
  * in tables by (bases, qualities) - the device only looks up.  A position with ONE active base goes through consensus_pos
  * too: the base comes back with its quality except that Q0 and Q1 give another base (the three others score higher: an A
  * becomes T, a T, C or G becomes A; quality '#' for Q0, '"' for Q1), and an N comes back as N with quality '$' (:354-357).
@@ -259,6 +260,22 @@ int hlmi_vq_graph(const char *singles_fastq, const char *overlaps, const hlmi_vq
 int hlmi_vq_consensus_pair(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2,
                            const char *qual2, uint32_t len2, uint32_t qlen2, uint32_t pos, char *out_seq, char *out_qual,
                            uint32_t *out_len);
+/* ---- --min_qual.  Every hlmi_vq_*_mq call is its sibling with ViralQuasispecies' --min_qual as one more argument, in front of
+ * out_dir (here: of out_seq); the sibling is the same call at 0.9.  A column of two bases and more whose best base is less than
+ * min_qual sure is N (SRBuilder.cpp:362-368); 0 never writes such an N, which is what POLYTE passes ("never insert N's",
+ * polyte.tune_params.py:737).  The value reaches the three places a column is decided: the tables of one and two bases, the
+ * pile-up kernel's comparison, and the host's redo of a column the kernel hands back; through the 'N's, test_N_rate.  What
+ * changes below 1/2: two different bases of equal quality score exactly alike and consensus_pos picks by its chain A, T, C, G
+ * (:390-393): A beats everything, T beats C, G loses to all; A/Q40 against G/Q40 at min_qual 0 is A with quality '$'
+ * (p_incorrect 0.500017).  And where both bases are Q0 or Q1 - each more likely wrong than right - the best score belongs to
+ * the bases that were NOT read, and the first of those in the chain is written (A/Q0 against C/Q0: T).
+ * HLMI_EINVAL, before any file is written: min_qual outside [0, 1], a NaN included; and a min_qual at which the reference's
+ * answer for two bases depends on the order it sums four probabilities in, so that no table by quality holds it.  With glibc
+ * that is 1 alone (1 - p_incorrect < 1 is decided by the last bit of a quotient: twice C at Q61 / Q93 is N, twice A is A);
+ * every other value tried, 0.999999 among them, builds. */
+int hlmi_vq_consensus_pair_mq(const char *seq1, const char *qual1, uint32_t len1, uint32_t qlen1, const char *seq2,
+                              const char *qual2, uint32_t len2, uint32_t qlen2, uint32_t pos, double min_qual, char *out_seq,
+                              char *out_qual, uint32_t *out_len);
 typedef struct {
     int first_it;               /* --first_it: every read is its own original (OverlapGraph::buildOriginalsDict, :772-798) */
     uint32_t keep_singletons;   /* --keep_singletons: an unmerged read shorter than this is not kept (:1286)               */
@@ -320,6 +337,10 @@ typedef struct {
  * returns before this step (ViralQuasispecies.cpp:282-291): so does this call, and none of the four files is written. */
 int hlmi_vq_merge(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
                   const hlmi_vq_merge_opts *mo, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst);
+/* hlmi_vq_merge with --min_qual (see hlmi_vq_consensus_pair_mq); hlmi_vq_merge is this call at 0.9 */
+int hlmi_vq_merge_mq(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                     const hlmi_vq_merge_opts *mo, double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst,
+                     hlmi_vq_merge_stats *mst);
 
 /* ---- SRBuilder with --cliques=true --threads 1 on single-end reads (ViralQuasispecies.cpp:397-428: quick-cliques'
  * `qc --algorithm=degeneracy --input-file=graph.txt > cliques.txt`, then SRBuilder::cliquesToSuperreads, SRBuilder.cpp:
@@ -336,10 +357,12 @@ typedef struct {
  * set in hlmi_vq_graph_opts: remove_trans 2 with error correction, else 1; remove_branches 1 on the --no_EC first iteration
  * (cliques with neither error correction nor a haplotype coverage), else 0; remove_backedges 0 with error correction, else 1
  * (ViralQuasispecies.cpp); remove_tips 0; ignore_inclusions 0; edge_threshold = POLYTE's --edge1.
- * NOT what POLYTE passes, and not an option of this struct: run_viralquasispecies always adds --min_qual=0 (:737), so the
- * reference never turns a column into N for disagreement.  hlmi_vq_cliques keeps minQual at SRBuilder's default 0.9: columns
- * whose best base is less than 90 % sure become N and a super-read can fall to the N rate where POLYTE would keep it.  With
- * these options the call reproduces ViralQuasispecies at its default --min_qual, not yet a POLYTE call. */
+ * Not an option of this struct: run_viralquasispecies always adds --min_qual=0 (:737), so the reference never turns a column
+ * into N for disagreement.  That is the min_qual argument of hlmi_vq_cliques_mq, hlmi_vq_clique_iteration_mq and
+ * hlmi_vq_branch_iteration_mq: with these options and min_qual 0 the call is POLYTE's call of ViralQuasispecies.  hlmi_vq_cliques
+ * itself keeps minQual at SRBuilder's default 0.9 - columns whose best base is less than 90 % sure become N, and a super-read
+ * can fall to the N rate where POLYTE keeps it - and reproduces ViralQuasispecies at its default --min_qual.  The loop POLYTE
+ * runs around these calls (polyte.tune_params.py:583-682) and its threshold table are not built. */
 void hlmi_vq_clique_opts_polyte(hlmi_vq_clique_opts *o, int error_correction);
 typedef struct {
     uint64_t cliques_read;      /* lines of cliques.txt, its two text lines included (clique_count, :1057)                  */
@@ -399,7 +422,8 @@ int hlmi_vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uin
  *                the tables of hlmi_vq_merge.  More: the sums (of libm's log10 values, plain double adds) are the reference's
  *                bit for bit and decide the base; the device computes pow, log10 and round itself and hands a column to
  *                the host's libm when a comparison lies within the margin of DESIGN.md section 4.3f (columns_host), so every
- *                byte is the reference's arithmetic.  minQual is the default 0.9 as for hlmi_vq_merge
+ *                byte is the reference's arithmetic.  minQual is the default 0.9 as for hlmi_vq_merge; hlmi_vq_cliques_mq
+ *                takes another
  *   drops        an empty consensus, test_N_rate; the members stay unvisited unless another kept super-read holds them
  *   trivial      an unvisited read: left out when shorter than keep_singletons or failing the N rate, else written forward
  *                or reversed with mirrored originals.  No inclusion or tip rule on this path
@@ -407,11 +431,16 @@ int hlmi_vq_cliques_of_graph(const char *graph_txt, const char *cliques_out, uin
  *                index = offset; else the forward / reverse formulas of hlmi_vq_merge.  Lines in ascending original id
  * When the graph has no edge the call stops where hlmi_vq_graph stops.  HLMI_ESTATE: a paired-end row, as elsewhere.
  * HLMI_EINVAL: min_clique_size 0; min_clique_size above 21 (a pile-up then never exceeds 63 reads, which one wave handles);
- * the reads hlmi_vq_merge refuses.  remove_multi_occ, merge_self_overlap (paired only), --min_qual and threads > 1 are not
- * options here: the contract is the sequential reference with a clique kept whole.  POLYTE passes --min_qual=0 (never an N
- * from minQual): that needs tables of their own and is not built. */
+ * the reads hlmi_vq_merge refuses.  remove_multi_occ, merge_self_overlap (paired only) and threads > 1 are not options here:
+ * the contract is the sequential reference with a clique kept whole.  --min_qual is hlmi_vq_cliques_mq. */
 int hlmi_vq_cliques(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
                     const hlmi_vq_clique_opts *co, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst);
+/* hlmi_vq_cliques with --min_qual (see hlmi_vq_consensus_pair_mq; POLYTE: 0); hlmi_vq_cliques is this call at 0.9.  Towards
+ * min_qual 1 more columns of three bases and more lie within the device's margin of the threshold and are redone on the host
+ * (columns_host): the output is the same, the call slower.  At 0 none does: the best of four is at least 1/4 sure. */
+int hlmi_vq_cliques_mq(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                       const hlmi_vq_clique_opts *co, double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst,
+                       hlmi_vq_clique_stats *cst);
 
 /* ---- SRBuilder::findNextOverlaps with --FNO=1 --optimize=false --cliques=false --error_correction=false --threads 1, to the
  * end of main (FindNextOverlaps.cpp:25-327 updateOverlap, :331-347 findCliqueIndex, :351-565 computeOverlapData - the S-S
@@ -466,6 +495,10 @@ typedef struct {
 int hlmi_vq_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
                       const hlmi_vq_merge_opts *mo, const hlmi_vq_next_opts *no, const char *out_dir, hlmi_vq_graph_stats *gst,
                       hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst);
+/* hlmi_vq_iteration with --min_qual (see hlmi_vq_consensus_pair_mq); hlmi_vq_iteration is this call at 0.9 */
+int hlmi_vq_iteration_mq(const char *singles_fastq, const char *overlaps, const char *subreads_in, const hlmi_vq_graph_opts *go,
+                         const hlmi_vq_merge_opts *mo, const hlmi_vq_next_opts *no, double min_qual, const char *out_dir,
+                         hlmi_vq_graph_stats *gst, hlmi_vq_merge_stats *mst, hlmi_vq_next_stats *nst);
 
 /* ---- findNextOverlaps behind the cliques: ViralQuasispecies --cliques=true --FNO=1 --optimize=false --threads 1 on
  * single-end reads to the end of main - what POLYTE runs in the first iteration of every cluster and in every
@@ -516,13 +549,19 @@ typedef struct {
  * order - is hlmi_vq_iteration's code; there, and wherever no list holds more than one entry, a source edge is its own turn
  * and needs no count, scan or search.
  * HLMI_EINVAL: 2^32 - 1 turns and more in one call (the limit of the sequence numbers); what hlmi_vq_cliques refuses.
- * HLMI_ESTATE: a paired-end row among the candidates or the non-edge rows.  Paired-end reads, add_duplicates,
- * FindNextOverlaps3 (--FNO=3) and --min_qual=0 are not built, as for hlmi_vq_cliques; BranchReduction is
- * hlmi_vq_branch_iteration, below. */
+ * HLMI_ESTATE: a paired-end row among the candidates or the non-edge rows.  Paired-end reads, add_duplicates and
+ * FindNextOverlaps3 (--FNO=3) are not built, as for hlmi_vq_cliques; --min_qual is hlmi_vq_clique_iteration_mq; BranchReduction
+ * is hlmi_vq_branch_iteration, below. */
 int hlmi_vq_clique_iteration(const char *singles_fastq, const char *overlaps, const char *subreads_in,
                              const hlmi_vq_graph_opts *go, const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no,
                              const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst,
                              hlmi_vq_clique_next_stats *nst);
+/* hlmi_vq_clique_iteration with --min_qual (see hlmi_vq_cliques_mq): with hlmi_vq_clique_opts_polyte, its graph options and
+ * min_qual 0, a POLYTE first-iteration call.  hlmi_vq_clique_iteration is this call at 0.9 */
+int hlmi_vq_clique_iteration_mq(const char *singles_fastq, const char *overlaps, const char *subreads_in,
+                                const hlmi_vq_graph_opts *go, const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no,
+                                double min_qual, const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_clique_stats *cst,
+                                hlmi_vq_clique_next_stats *nst);
 
 /* ---- read-evidence branch reduction: ViralQuasispecies --branch_reduction=true --remove_branches=false --remove_trans=1
  * --threads 1 on single-end reads, diploid off (BranchReduction::readBasedBranchReduction, BranchReduction.cpp; the
@@ -568,8 +607,8 @@ typedef struct {
  * hold, read ids that are not the file positions (HLMI_EINVAL); a paired-end row (HLMI_ESTATE).  Refused during the reduction
  * (HLMI_EINVAL): an in-branch pair the reference's assertion of :605 rejects.  The table is read as the reference reads it,
  * through one stringstream: what a line holds behind its third column goes in front of the next line's first column.
- * Not built: --min_qual=0, diploid (the typical-double-branch resolution), paired-end vertices, the POLYTE loop with its
- * threshold table (min_ev_table.py). */
+ * Not built: diploid (the typical-double-branch resolution), paired-end vertices, the POLYTE loop with its threshold table
+ * (min_ev_table.py).  The graph has no consensus in it: --min_qual belongs to hlmi_vq_branch_iteration_mq. */
 int hlmi_vq_branch_graph(const char *singles_fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
                          const char *threshold_table, const hlmi_vq_graph_opts *go, const hlmi_vq_branch_opts *bo,
                          const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst);
@@ -580,6 +619,13 @@ int hlmi_vq_branch_iteration(const char *singles_fastq, const char *overlaps, co
                              const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no, const char *out_dir,
                              hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst, hlmi_vq_clique_stats *cst,
                              hlmi_vq_clique_next_stats *nst);
+/* hlmi_vq_branch_iteration with --min_qual for its clique step (see hlmi_vq_cliques_mq; POLYTE: 0); hlmi_vq_branch_iteration
+ * is this call at 0.9 */
+int hlmi_vq_branch_iteration_mq(const char *singles_fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
+                                const char *threshold_table, const hlmi_vq_graph_opts *go, const hlmi_vq_branch_opts *bo,
+                                const hlmi_vq_clique_opts *co, const hlmi_vq_next_opts *no, double min_qual, const char *out_dir,
+                                hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst, hlmi_vq_clique_stats *cst,
+                                hlmi_vq_clique_next_stats *nst);
 
 /* ---- short-read clustering (HyLight.py:215-226: get_readnames.py, bin_pointer_limited_filechunks_shortpath2.py,
  * getclusters.py, get_fq_cluster.py with cwd = tmp/ and run id HiStrain).  Parity pinned: tests/golden/fxH_cluster_*.json

@@ -1,12 +1,13 @@
 """Time hlmi_vq_cliques after the graph on a simulated cluster set (not part of the test suite).
 
-    python tools/vq_cliques_time.py [--clusters 250] [--reads 400] [--min_clique_size 3] [--no_ec] [--iteration] [--out DIR]
+    python tools/vq_cliques_time.py [--clusters 250] [--reads 400] [--min_clique_size 3] [--no_ec] [--min_qual X] [--iteration] [--out DIR]
 
 Makes `--clusters` clusters of the kind tests/test_gpu_vq_cliques.py uses - 3 haplotypes of 2 kb at 1 % divergence, `--reads`
 reads of 150 bases with 1 % substitutions and qualities that know about them - into one singles.fastq, with the overlaps
 the coordinates give inside every cluster; runs the command line (hylight_amd.vq_cliques.main) once and prints one JSON
 line: the stats, ms_cliques and its phases (enumerator, placement, device with its copies, the rest), the kernel's time
 from the library's own timer and the share of columns the host redid.  250 x 400 is the 1e5-read set of DESIGN.md 4.3f.
+--min_qual X is passed on as it stands (POLYTE: 0); without it the run is the one at minQual 0.9.
 With --iteration the run goes on to findNextOverlaps (hlmi_vq_clique_iteration) and the line also holds "next": ms_next,
 candidates, max_list and the rest of its stats, and "next_kernel_ms": the library's timers of the count, expand, claim sort,
 eval and order passes.  No reference time exists beside any of these: ViralQuasispecies needs Boost and is not built here.
@@ -62,6 +63,7 @@ def main():
     p.add_argument("--reads", type=int, default=400)
     p.add_argument("--min_clique_size", type=int, default=3)
     p.add_argument("--no_ec", action="store_true")
+    p.add_argument("--min_qual", type=float, default=None, help="--min_qual of the run (default: not passed, minQual 0.9)")
     p.add_argument("--iteration", action="store_true", help="go on to findNextOverlaps and report its stats and kernel timers")
     p.add_argument("--out", default=None)
     a = p.parse_args()
@@ -71,6 +73,8 @@ def main():
     argv = ["--singles", fq, "--overlaps", ov, "--out", os.path.join(d, "out"), "--min_overlap_len", str(MIN_OVL),
             "--edge_threshold", "0.97", "--min_clique_size", str(a.min_clique_size),
             "--error_correction", "false" if a.no_ec else "true"] + (["--iteration"] if a.iteration else [])
+    if a.min_qual is not None:
+        argv += ["--min_qual", repr(a.min_qual)]
     text = io.StringIO()
     with contextlib.redirect_stdout(text):
         rc = vq_cliques.main(argv)
@@ -79,7 +83,7 @@ def main():
     st = json.loads(text.getvalue().strip().split("\n")[-1])
     stats = api.last_stats()
     cst = st["cliques"]
-    out = {"version": api.version(), "reads": a.clusters * a.reads, "overlap_rows": rows, "graph": st["graph"], "cliques": cst,
+    out = {"version": api.version(), "min_qual": a.min_qual, "reads": a.clusters * a.reads, "overlap_rows": rows, "graph": st["graph"], "cliques": cst,
            "phases_ms": {k[len("vq_clique_ms_"):]: round(v, 2) for k, v in stats.items() if k.startswith("vq_clique_ms_")},
            "piles": int(stats.get("vq_clique_piles", 0)),
            "kernel_ms": stats.get("kernel_ms.vq_clique_piles"),
