@@ -163,6 +163,7 @@ SYMBOLS = {
     "hlmi_ava": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.c_char_p]),
     "hlmi_miniasm": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]),
     "hlmi_sfo2overlaps": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
+    "hlmi_sr_overlaps": (C.c_int, [C.c_char_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_char_p, C.POINTER(C.c_uint64)]),
     "hlmi_vq_parse_overlaps": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.POINTER(VqOverlap),
                                          C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "hlmi_vq_transitive_edges": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
@@ -357,6 +358,15 @@ def miniasm(paf, reads_fa, out_path, bub_dist=10000, n_rounds_arg=1, max_ext=1, 
 
 def sfo2overlaps(in_sfo, out_savage, num_singles, num_pairs=0):
     _check(load().hlmi_sfo2overlaps(_b(in_sfo), _b(out_savage), num_singles, num_pairs))
+
+
+def sr_overlaps(reads, out_overlaps, min_ovlp_len, min_identity=0.98, o=1, r=0.8):
+    """hlmi_sr_overlaps: the self-overlaps of `reads` (FASTQ / FASTA, names 0, 1, 2, ..) as a SAVAGE overlaps file - POLYTE's
+    run_sfo chain (ava with driver.contig_ava_opts() -> filter_ovlp_inline -> minimap22sfo(0, 0) -> sfo2overlaps) in one call,
+    no intermediate files.  -> the number of lines written."""
+    n = C.c_uint64(0)
+    _check(load().hlmi_sr_overlaps(_b(reads), min_ovlp_len, min_identity, o, r, _b(out_overlaps), C.byref(n)))
+    return n.value
 
 
 def vq_parse_overlaps(savage_path, min_len=150, min_perc=0, relax_pe=False, max_overlaps=100000000):

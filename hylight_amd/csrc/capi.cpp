@@ -16,6 +16,8 @@ void init_device(int device, int threads);
 void cluster_run(const char *paf, const char *fastq, const hlmi_cluster_opts &o, const char *out_dir, hlmi_cluster_stats *st);
 void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
                 hlmi_polish_stats *st);
+void sr_overlaps_run(const char *reads, int min_ovlp_len, double min_identity, int o, double r, const char *out_overlaps,
+                     uint64_t *n_lines);
 void shutdown_device();
 const std::string &last_error();
 }  // namespace hlmi
@@ -290,6 +292,15 @@ int hlmi_sfo2overlaps(const char *in_sfo, const char *out_savage, int num_single
     return guarded([&] {
         if (!in_sfo || !out_savage) fail(HLMI_EINVAL, "hlmi_sfo2overlaps: NULL path");
         sfo2overlaps_run(in_sfo, out_savage, num_singles, num_pairs);
+    });
+}
+
+int hlmi_sr_overlaps(const char *reads, int min_ovlp_len, double min_identity, int o, double r, const char *out_overlaps,
+                     uint64_t *n_lines) {
+    return guarded([&] {
+        if (!reads || !out_overlaps || !n_lines) fail(HLMI_EINVAL, "hlmi_sr_overlaps: NULL argument");
+        require_device();
+        sr_overlaps_run(reads, min_ovlp_len, min_identity, o, r, out_overlaps, n_lines);
     });
 }
 

@@ -1,6 +1,7 @@
 // sfo.cpp - a18: sfo2overlaps.py as HyLight calls it (`--num_pairs 0`, script/HyLight.py:315-318): SFO rows with the
 // smaller id first, `sort -k1,1n -k2,2n -k3,3n -k4,4n | uniq`, single-end SAVAGE rows (script/sfo2overlaps.py:31-200).
-// Contig-scale text (10^3 - 10^5 rows): host.
+// Contig-scale text (10^3 - 10^5 rows): host.  Read-scale input (POLYTE's clusters, millions of rows) goes through
+// hlmi_sr_overlaps (sr_overlaps.hip), which restates this file's arithmetic per row on the device.
 #include <array>
 #include <cctype>
 #include <cmath>

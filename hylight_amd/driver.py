@@ -8,8 +8,7 @@ external (`--polish_native` replaces racon with the library's own pile-up consen
 failing tool stops the run with a message.  The two short-read overlap calls of the path (HyLight.py:200,207)
 run in the library's short mode.  `extend_con` (HyLight.py:282-326) is wired up to the SAVAGE overlap file: contigs ->
 contigs_b.fastq -> self-overlaps (the `minimap2 --sr -X ... -r 0` call as hlmi_ava) -> v3 window filter with -sfo ->
-sfo2overlaps; the consumers of that file - short-read clustering, POLYTE and the stage-b contig merge
-(pipeline_per_stage.py / ViralQuasispecies) - are outside this implementation (SURVEY.md sections 2 and 8f): without
+sfo2overlaps; the stage-b contig merge (pipeline_per_stage.py / ViralQuasispecies) that reads that file is opt-in (`--stageb_native`): without
 `--stageb_cmd` the run says so on stderr and, because the contractual output final_contigs.fa was not written, exits
 with EXIT_NO_FINAL (3) and everything up to tmp/stageb/sfoverlap.out.savage in place (`--stop_after savage` declares
 that partial run and exits 0).  The text passes (filter_non_atcg, gfa2fa, pick_up) are the library's native ones.
@@ -18,11 +17,11 @@ The short-read branch (HyLight.py:211-275) is opt-in: `--stop_after clusters` ru
 (hlmi_cluster_short: readnames.txt, the grouped JSON and fq_<size>/ in tmp/) and exits 0; `--polyte_cmd PREFIX`, without
 `--short_contigs`, also runs POLYTE per cluster through PREFIX (the reference's polyte.tune_params.py, external), collects
 tmp/all.contigs_<size>.fasta, extends it into short_stageb.fa (with `--stageb_cmd`) and builds all_contigs.fa from it and
-long_con_polished.fa.  Without these flags the run is the same as before.  POLYTE's clique iteration exists natively and now
-ends in overlaps.txt (python -m hylight_amd.vq_cliques --iteration: hlmi_vq_clique_iteration, findNextOverlaps over the
-super-read lists), with POLYTE's --min_qual=0 as `--min_qual 0`; `--polyte_cmd` stays external and is not rewired to it: the
-loop of polyte.tune_params.py with its threshold table and paired-end reads are still missing.  `--stageb_native` keeps minQual
-0.9: pipeline_per_stage.py does not pass the flag.
+long_con_polished.fa.  Without these flags the run is the same as before.  `--polyte_native` takes the place of `--polyte_cmd`
+with the library's own POLYTE (hylight_amd.polyte: the loop of polyte.tune_params.py, its threshold table, every iteration and
+every overlap computation a library call; HyLight's copy of the script treats the mates as single reads, so no paired-end
+vertices are needed), one cluster after the other in this process; `--polyte_cmd` itself is untouched, and both together are an
+error.  `--stageb_native` keeps minQual 0.9: pipeline_per_stage.py does not pass the flag.
 
 `--gpus N` (extension): every split_reads2 call is sharded over N GPUs of the node, chunk i -> rank i % N, the way the
 reference fans its chunks out with `xargs -P` (script/utils.py:44-69).  The process starts N - 1 further copies of
@@ -212,6 +211,10 @@ def build_parser():
     p.add_argument("--polyte_cmd", default=None,
                    help="(extension) command prefix of the reference's polyte.tune_params.py, if installed: without "
                         "--short_contigs, cluster the short reads and run it per cluster (HyLight.py:215-275)")
+    p.add_argument("--polyte_native", action="store_true",
+                   help="(extension) the same with the library's own POLYTE (hylight_amd.polyte: the clique, merge and branch "
+                        "iterations and the overlaps between them on the GPU), cluster after cluster in this process; not "
+                        "together with --polyte_cmd")
     p.add_argument("--stageb_cmd", default=None,
                    help="(extension) command prefix of the reference's pipeline_per_stage.py, if installed")
     p.add_argument("--stageb_native", action="store_true",
@@ -236,17 +239,48 @@ def polyte_lines(tmp, size, polyte_cmd, insert_size, average_read_len):
     return lines
 
 
+def polyte_native(tmp, size, insert_size, average_read_len):
+    """HyLight.py:228-242 with the library's own POLYTE (`--polyte_native`): hylight_amd.polyte.run in every cluster directory
+    of tmp/fq_<size>/, one after the other in this process, with the options of polyte_lines; each cluster's output goes to its
+    log.txt.  A cluster that fails leaves no contigs.fasta and is named by the caller's warning, as in the reference."""
+    import contextlib
+    from . import polyte
+    outdir2 = os.path.abspath(os.path.join(tmp, f"fq_{size}"))
+    cwd = os.getcwd()
+    for i in sorted(os.listdir(outdir2)):
+        folder = f"{outdir2}/{i}"
+        try:
+            os.chdir(folder)
+            with open("log.txt", "w") as log, contextlib.redirect_stdout(log):
+                try:
+                    polyte.run(f"{folder}/{i}.1.fq", f"{folder}/{i}.2.fq", min_overlap_len=50, min_overlap_len_EC=60, hap_cov=10,
+                               insert_size=insert_size, stddev=27, average_read_len=average_read_len, min_clique_size=2,
+                               edge1=0.93, edge2=1.0)
+                except (api.HlmiError, ValueError) as e:
+                    if isinstance(e, api.HlmiError) and e.code not in (-1, -6):    # only what the cluster's own data causes
+                        raise                                                      # (HLMI_EINVAL, HLMI_ESTATE) is the cluster's
+                    log.write(f"hylight_amd.polyte: {e}\n")
+                    if os.path.exists("contigs.fasta"):
+                        os.remove("contigs.fasta")
+        finally:
+            os.chdir(cwd)
+
+
 def _short_branch(args, tmp, outdir, long_con3):
-    """HyLight.py:228-275 after the clustering: POLYTE per cluster (external, `--polyte_cmd`), the cluster contigs, their
-    stage-b extension (short_stageb.fa) and all_contigs.fa; then the final extend_con as on the other path."""
+    """HyLight.py:228-275 after the clustering: POLYTE per cluster (external with `--polyte_cmd`, the library's with
+    `--polyte_native`), the cluster contigs, their stage-b extension (short_stageb.fa) and all_contigs.fa; then the final
+    extend_con as on the other path."""
     from concurrent.futures import ThreadPoolExecutor
 
     size = args.size
-    lines = polyte_lines(tmp, size, args.polyte_cmd, args.insert_size, args.average_read_len)
-    with open(os.path.join(tmp, "cmd_polyte.sh"), "w") as f:
-        f.writelines(line + "\n" for line in lines)
-    with ThreadPoolExecutor(max_workers=max(1, args.threads)) as ex:    # `xargs -i -P threads bash -c "{}"`
-        list(ex.map(lambda line: subprocess.run(["bash", "-c", line]), lines))
+    if args.polyte_native:
+        polyte_native(tmp, size, args.insert_size, args.average_read_len)
+    else:
+        lines = polyte_lines(tmp, size, args.polyte_cmd, args.insert_size, args.average_read_len)
+        with open(os.path.join(tmp, "cmd_polyte.sh"), "w") as f:
+            f.writelines(line + "\n" for line in lines)
+        with ThreadPoolExecutor(max_workers=max(1, args.threads)) as ex:    # `xargs -i -P threads bash -c "{}"`
+            list(ex.map(lambda line: subprocess.run(["bash", "-c", line]), lines))
     outdir2 = os.path.join(tmp, f"fq_{size}")
     ids = sorted(os.listdir(outdir2))
     for i in ids:                                               # HyLight.py:248-256
@@ -292,6 +326,8 @@ def _init_rank(args, world, local):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = build_parser().parse_args(argv)
+    if args.polyte_native and args.polyte_cmd:
+        raise SystemExit("--polyte_native and --polyte_cmd are two ways to run the same step: give one of them")
     if args.gpus > 1 and not launch.launched():
         # one process per GPU, started before this one has made any GPU call; this process only waits for them
         return launch.spawn_ranks(args.gpus, [sys.executable, "-m", "hylight_amd.driver", *argv])
@@ -406,7 +442,7 @@ def _pipeline(args, pool):
     shortr2 = os.devnull                                       # no reads remain: the clustering sees no rows
     if os.path.exists(remain_short) and os.path.getsize(remain_short):
         shortr2 = stage(short_reads, remain_short, nsplit, tmp + "shortr2.paf", 70, 3, iden, long=False)
-    if args.stop_after == "clusters" or (args.polyte_cmd and not args.short_contigs):
+    if args.stop_after == "clusters" or ((args.polyte_cmd or args.polyte_native) and not args.short_contigs):
         st = api.cluster_short(shortr2, short_reads, tmp, size=args.size, threads=args.threads)    # HyLight.py:215-226
         sys.stderr.write(f"hylight-mi: {st['files'] // 2} short-read clusters in tmp/fq_{args.size}/\n")
         if args.stop_after == "clusters":

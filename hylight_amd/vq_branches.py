@@ -10,8 +10,8 @@ Writes what python -m hylight_amd.vq_graph writes, and branch_components.txt.  T
 --thresholds names the table the reference reads from its working directory.  The defaults are POLYTE's for this iteration:
 remove_trans 1, remove_branches false, tips and inclusions kept, the cliques without error correction.  With --iteration the run
 goes on through the clique step to the end of ViralQuasispecies' main (hlmi_vq_branch_iteration); --min_qual 0 there is what
-POLYTE passes (not passed by default: minQual 0.9).  Not built, and said so: --diploid (the typical-double-branch resolution), paired-end vertices, POLYTE's loop and its threshold table
-(min_ev_table.py).  Prints {"graph": ..., "branches": ...} - with --iteration also "cliques" and "next" - as one JSON line.
+POLYTE passes (not passed by default: minQual 0.9).  Not built, and said so: --diploid (the typical-double-branch resolution), paired-end vertices.  POLYTE's loop is
+python -m hylight_amd.polyte, its threshold table hylight_amd/min_ev.py.  Prints {"graph": ..., "branches": ...} - with --iteration also "cliques" and "next" - as one JSON line.
 Exit status 0 on success, 4 (EXIT_REFUSED) for what is refused as not built (a paired-end row, --remove_trans other than 1,
 --remove_branches true, --branch_reduction false, --diploid true), 2 (EXIT_INVALID) for a malformed input: counts that do not
 match --original_fastq, a table that cannot be read, an original the FASTQ does not hold.

@@ -12,7 +12,7 @@ with --error_correction true remove_trans 2, the back edges kept, keep_singleton
 remove_branches true, keep_singletons 0; tips and inclusions stay either way.  One of its options is not a default here:
 --min_qual 0 ("never insert N's", :737).  Without the flag minQual stays at ViralQuasispecies' own default 0.9, and a column
 whose best base is less than 90 % sure becomes N; with `--min_qual 0 --iteration` the run is a POLYTE first-iteration call.  The
-loop around such calls and its threshold table are not built.  With --iteration the run goes on to the end of
+loop around such calls is python -m hylight_amd.polyte.  With --iteration the run goes on to the end of
 ViralQuasispecies' main (hlmi_vq_clique_iteration, --FNO=1): overlaps.txt and one line appended to stats.txt, so that another
 iteration can follow; the inputs may then lie in DIR under the names written.  Prints {"graph": ..., "cliques": ...} - with
 --iteration also "next": ... - as one JSON line.  Exit status 0 on success, 4 (EXIT_REFUSED) for what vq_graph refuses (a

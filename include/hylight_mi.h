@@ -149,6 +149,19 @@ int hlmi_miniasm(const char *paf, const char *reads_fa, int bub_dist, int n_roun
 /* ---- a18: sfo2overlaps.py (--num_pairs 0 branch, HyLight.py:315-318) --------------------- */
 int hlmi_sfo2overlaps(const char *in_sfo, const char *out_savage, int num_singles, int num_pairs);
 
+/* ---- POLYTE's run_sfo chain in one call (polyte.tune_params.py:488-529, :534-579) ---------------------------------------
+ * The self-overlaps of a read set as a SAVAGE overlaps file: byte for byte what
+ *   hlmi_ava(reads, reads, <-X -r 0 short-read options>) -> hlmi_filter_ovlp_inline(min_ovlp_len, min_identity, o, r) ->
+ *   hlmi_minimap22sfo(0, 0.0) -> hlmi_sfo2overlaps(num_singles = reads, num_pairs = 0)
+ * write when chained on the reads as FASTA, without the three text files in between: the overlapper's rows stay on the device,
+ * the inline filter reads them there in the overlapper's order, and the SFO / SAVAGE conversion, the sort | uniq and the text
+ * are kernels (csrc/sr_overlaps.hip).  `reads`: FASTQ or FASTA whose names are non-negative decimal integers below 10^18 (the
+ * files POLYTE renumbers, singles.fastq).  *n_lines: lines written.  An input without overlaps leaves an empty file and 0.
+ * HLMI_EINVAL before anything is written: a NULL argument, a name that is no decimal integer, two reads of one name (or of one
+ * number: 7 and 007). */
+int hlmi_sr_overlaps(const char *reads, int min_ovlp_len, double min_identity, int o, double r, const char *out_overlaps,
+                     uint64_t *n_lines);
+
 /* ---- f3 (STARTED): front end of the SAVAGE overlap-graph assembler ------ */
 /* tools/HaploConduct/src (ViralQuasispecies) needs Boost and cannot be built here: the entry points below restate its
  * text of record and are checked against oracle/vq.py and tests/vq_graph_model.py only (parity unpinned).  Built: the
@@ -362,7 +375,7 @@ typedef struct {
  * hlmi_vq_branch_iteration_mq: with these options and min_qual 0 the call is POLYTE's call of ViralQuasispecies.  hlmi_vq_cliques
  * itself keeps minQual at SRBuilder's default 0.9 - columns whose best base is less than 90 % sure become N, and a super-read
  * can fall to the N rate where POLYTE keeps it - and reproduces ViralQuasispecies at its default --min_qual.  The loop POLYTE
- * runs around these calls (polyte.tune_params.py:583-682) and its threshold table are not built. */
+ * runs around these calls (polyte.tune_params.py:583-682) is hylight_amd/polyte.py, its threshold table hylight_amd/min_ev.py. */
 void hlmi_vq_clique_opts_polyte(hlmi_vq_clique_opts *o, int error_correction);
 typedef struct {
     uint64_t cliques_read;      /* lines of cliques.txt, its two text lines included (clique_count, :1057)                  */
@@ -607,8 +620,8 @@ typedef struct {
  * hold, read ids that are not the file positions (HLMI_EINVAL); a paired-end row (HLMI_ESTATE).  Refused during the reduction
  * (HLMI_EINVAL): an in-branch pair the reference's assertion of :605 rejects.  The table is read as the reference reads it,
  * through one stringstream: what a line holds behind its third column goes in front of the next line's first column.
- * Not built: diploid (the typical-double-branch resolution), paired-end vertices, the POLYTE loop with its threshold table
- * (min_ev_table.py).  The graph has no consensus in it: --min_qual belongs to hlmi_vq_branch_iteration_mq. */
+ * Not built: diploid (the typical-double-branch resolution), paired-end vertices (POLYTE as HyLight runs it needs neither; its
+ * loop is hylight_amd/polyte.py, its threshold table hylight_amd/min_ev.py).  The graph has no consensus in it: --min_qual belongs to hlmi_vq_branch_iteration_mq. */
 int hlmi_vq_branch_graph(const char *singles_fastq, const char *overlaps, const char *subreads_in, const char *original_fastq,
                          const char *threshold_table, const hlmi_vq_graph_opts *go, const hlmi_vq_branch_opts *bo,
                          const char *out_dir, hlmi_vq_graph_stats *gst, hlmi_vq_branch_stats *bst);
