@@ -216,6 +216,8 @@ SYMBOLS = {
     "hlmi_cluster_short": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(ClusterOpts), C.c_char_p, C.POINTER(ClusterStats)]),
     "hlmi_polish_opts_default": (None, [C.POINTER(PolishOpts)]),
     "hlmi_polish": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PolishOpts), C.c_char_p, C.POINTER(PolishStats)]),
+    "hlmi_polish_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PolishOpts), C.c_char_p,
+                                    C.POINTER(PolishStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -630,14 +632,31 @@ def polish(contigs, reads, paf, out_fa, **opts):
     api.ava writes them) of `reads`, written to out_fa - the native stand-in for `racon --no-trimming -u` (a function of
     this project's own: include/hylight_mi.h states it, tests/polish_model.py is its contract).  Options: the fields of
     hlmi_polish_opts (min_len 0, min_iden 0.0, min_cov 3, include_unpolished 1).  -> dict of the stats (hlmi_polish_stats)."""
+    o = _polish_opts("polish", opts)
+    st = PolishStats()
+    _check(load().hlmi_polish(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(out_fa), C.byref(st)))
+    return {k: getattr(st, k) for k in POLISH_STATS + POLISH_MS}
+
+
+def _polish_opts(who, opts):
     o = PolishOpts()
     load().hlmi_polish_opts_default(C.byref(o))
     for k, v in opts.items():
         if k not in dict(PolishOpts._fields_):
-            raise TypeError(f"polish: unknown option {k!r}")
+            raise TypeError(f"{who}: unknown option {k!r}")
         setattr(o, k, int(v) if isinstance(v, bool) else v)
+    return o
+
+
+def polish_reads(contigs, reads, out_fa, ava_opts=None, **polish_opts):
+    """hlmi_polish_reads: `ava(contigs, reads, P, ava_opts)` and `polish(contigs, reads, P, out_fa, **polish_opts)` in one
+    call without the PAF P - the same file and the same integer stats, the overlapper's rows never leaving the device.
+    ava_opts None: the long constants.  Refused (HlmiError, code -1) besides what polish refuses: a name twice among the reads
+    or among the contigs, ava_opts.stub_oh >= 0.  -> dict of the stats (hlmi_polish_stats)."""
+    o = _polish_opts("polish_reads", polish_opts)
     st = PolishStats()
-    _check(load().hlmi_polish(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(out_fa), C.byref(st)))
+    _check(load().hlmi_polish_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
+                                    _b(out_fa), C.byref(st)))
     return {k: getattr(st, k) for k in POLISH_STATS + POLISH_MS}
 
 

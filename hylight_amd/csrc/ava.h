@@ -124,6 +124,21 @@ struct AvaRows {            // overlapper output in stream order (chunk, query, 
 };
 void ava_device(const AvaInput &in, const hlmi_ava_opts &o, AvaRows &out);
 
+// One target set against one query set, the targets as one chunk: what ava_device needs for such a call, resident in HBM -
+// both sets uploaded, the strcmp ranks of their names over the union, the query sketch.  `in` points into this object.
+struct AvaPairCall {
+    std::vector<uint32_t> rt, rq;              // name rank of every target / query record
+    std::vector<std::string> name_of_rank;
+    DevReads dT, dQ;
+    DBuf<uint32_t> d_rt, d_rq, d_chunk;
+    DevSketch qsk;
+    AvaInput in;
+    AvaPairCall() = default;
+    AvaPairCall(const AvaPairCall &) = delete;
+    AvaPairCall &operator=(const AvaPairCall &) = delete;
+    void setup(const SeqSet &T, const SeqSet &Q, const hlmi_ava_opts &o);
+};
+
 // one target file vs one query file, PAF text out (the minimap2 call of filter_overlap_slr2.py:51)
 void ava_files(const char *target_fa, const char *query_fa, const hlmi_ava_opts &o, const char *out_paf);
 

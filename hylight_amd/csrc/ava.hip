@@ -451,34 +451,36 @@ void format_ava_row(const PafRec &r, const uint32_t *ops, const std::string &qna
     if (!r.cig_n) out.push_back('*');          // the bare row of a stub candidate (hlmi_ava_opts::stub_oh)
 }
 
-void ava_files(const char *target_fa, const char *query_fa, const hlmi_ava_opts &o, const char *out_paf) {
-    stat_reset();
-    SeqSet T, Q;
-    read_seqs(target_fa, T);
-    read_seqs(query_fa, Q);
-    std::vector<uint32_t> rt, rq;
-    std::vector<std::string> name_of_rank;
+void AvaPairCall::setup(const SeqSet &T, const SeqSet &Q, const hlmi_ava_opts &o) {
     name_ranks(T.names, Q.names, rt, rq, name_of_rank);
-    DevReads dT, dQ;
     upload_reads(T, 0, T.size(), dT);
     upload_reads(Q, 0, Q.size(), dQ);
-    DBuf<uint32_t> d_rt, d_rq, d_chunk(T.size() ? T.size() : 1);
+    d_chunk.alloc(T.size() ? T.size() : 1);
     d_rt.upload(rt);
     d_rq.upload(rq);
     if (rt.empty()) d_rt.alloc(1);
     if (rq.empty()) d_rq.alloc(1);
     d_chunk.zero();
-    DevSketch qsk;
     sketch_device(dQ, o.k, o.w, o.hpc, 0, qsk);
     std::vector<uint32_t> qc = qsk.counts.download(Q.size());
-    AvaInput in;
+    in = AvaInput();
     in.T = &dT; in.Q = &dQ; in.d_rank_t = d_rt.p; in.d_rank_q = d_rq.p; in.d_chunk_of_t = d_chunk.p; in.n_chunks = 1;
     in.n_ranks = name_of_rank.size();
     in.d_qmz = qsk.mz.p;
     in.qmz_off.assign(Q.size() + 1, 0);
     for (size_t i = 0; i < Q.size(); ++i) in.qmz_off[i + 1] = in.qmz_off[i] + qc[i];
+}
+
+void ava_files(const char *target_fa, const char *query_fa, const hlmi_ava_opts &o, const char *out_paf) {
+    stat_reset();
+    SeqSet T, Q;
+    read_seqs(target_fa, T);
+    read_seqs(query_fa, Q);
+    AvaPairCall call;
+    call.setup(T, Q, o);
+    const std::vector<std::string> &name_of_rank = call.name_of_rank;
     AvaRows rows;
-    ava_device(in, o, rows);
+    ava_device(call.in, o, rows);
     ktimer_flush();
     std::vector<PafRec> hr = rows.recs.download(rows.n_rows);
     // the parts of the CIGAR array, on the host one after the other: a row's offset from ops_base -> its place there

@@ -16,6 +16,8 @@ void init_device(int device, int threads);
 void cluster_run(const char *paf, const char *fastq, const hlmi_cluster_opts &o, const char *out_dir, hlmi_cluster_stats *st);
 void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
                 hlmi_polish_stats *st);
+void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
+                      const char *out_fa, hlmi_polish_stats *st);
 void sr_overlaps_run(const char *reads, int min_ovlp_len, double min_identity, int o, double r, const char *out_overlaps,
                      uint64_t *n_lines);
 void shutdown_device();
@@ -508,6 +510,15 @@ int hlmi_polish(const char *contigs, const char *reads, const char *paf, const h
         if (!contigs || !reads || !paf || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish: NULL argument");
         require_device();
         polish_run(contigs, reads, paf, *o, out_fa, st);
+    });
+}
+
+int hlmi_polish_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_opts *po,
+                      const char *out_fa, hlmi_polish_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !po || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish_reads: NULL argument");
+        require_device();
+        polish_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), *po, out_fa, st);
     });
 }
 

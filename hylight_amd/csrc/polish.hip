@@ -9,6 +9,8 @@
 //                length counters of each opened slot, then, the lengths decided, into the 16 x 4 base counters
 //   write        a thread per position: output length, a device scan for the offsets, one kernel for the bytes
 // Every counter is 32 bits wide: coverage needs no overflow path.  Every loop is bounded by a count known at its head.
+// polish_device uploads what polish_host.cpp built and runs polish_core; hlmi_polish_reads (polish_rows.hip) runs polish_core
+// over rows, CIGARs and reads that are in device memory already - its reads as the overlapper's codes (column_symbol).
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -25,11 +27,21 @@ constexpr int C_OTHER = 5, C_START = 6, C_INS = 7, POLISH_CNT = 8;     // counte
 constexpr uint32_t SHORT_RUN = 16;         // a lane votes a run of up to this many columns itself; longer ones take the wave
 constexpr uint32_t NO_SLOT = 0xffffffffu;
 
-// symbol of alignment column `col` of row r: 0..3, or C_OTHER for anything that is not A C G T
+// symbol of alignment column `col` of row r: 0..3, or C_OTHER for anything that is not A C G T.
+// ENC = READS_ASCII: `reads` holds the file's bytes, folded to upper case here.  ENC = READS_CODES: it holds the overlapper's
+// resident codes (DevReads::codes(): 0..3 = A C G T of either case, 4 = anything else).  Code 4 is exactly the set of bytes the
+// ASCII form refuses to count after `& 0xdf` - with one exception the encoder makes for the aligner, U / u -> 3: the caller
+// (polish_rows.hip) sets those bases to 4 once the alignment is done, so that both forms count the same columns.
+template <int ENC>
 __device__ __forceinline__ uint32_t column_symbol(const PolRow &r, const uint8_t *__restrict__ reads, uint32_t col) {
     if (col >= r.qn) return C_OTHER;                                   // (validated on the host: never)
-    const uint8_t c = reads[r.read_off + (r.rev ? r.qn - 1 - col : col)] & 0xdfu;      // upper case
-    const uint32_t k = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : (uint32_t)C_OTHER;
+    uint8_t c = reads[r.read_off + (r.rev ? r.qn - 1 - col : col)];
+    uint32_t k;
+    if (ENC == READS_CODES) k = c < 4 ? (uint32_t)c : (uint32_t)C_OTHER;
+    else {
+        c &= 0xdfu;                                                    // upper case
+        k = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : (uint32_t)C_OTHER;
+    }
     return r.rev && k < 4 ? 3u - k : k;
 }
 
@@ -51,6 +63,7 @@ __device__ __forceinline__ void walk_row(const PolRow &r, const uint32_t *__rest
     }
 }
 
+template <int ENC>
 __global__ __launch_bounds__(POLISH_WG) void polish_count_kernel(const PolRow *__restrict__ rows, const uint32_t *__restrict__ ops,
                                                                  const uint8_t *__restrict__ reads, const uint8_t *__restrict__ contig,
                                                                  const PolTile *__restrict__ tiles, int min_cov,
@@ -66,7 +79,7 @@ __global__ __launch_bounds__(POLISH_WG) void polish_count_kernel(const PolRow *_
         if (r.te <= t.t0 || r.ts >= t_end) continue;
         if (lane == 0 && r.ts >= t.t0) atomicAdd(&s_cnt[C_START][r.ts - t.t0], 1u);
         auto vote = [&](uint32_t p, uint32_t code, uint32_t tp0, uint32_t qc0) {
-            const uint32_t s = code == OP_D ? (uint32_t)SYM_DEL : column_symbol(r, reads, qc0 + (p - tp0));
+            const uint32_t s = code == OP_D ? (uint32_t)SYM_DEL : column_symbol<ENC>(r, reads, qc0 + (p - tp0));
             atomicAdd(&s_cnt[s][p - t.t0], 1u);
         };
         walk_row(r, ops, lane, t_end, [&](uint32_t code, uint32_t len, uint32_t tp0, uint32_t qc0) {
@@ -118,7 +131,7 @@ __global__ void slot_index_kernel(const uint32_t *__restrict__ open_pos, uint32_
 }
 
 // MODE 0: the length every inserting row votes for at its opened slots; MODE 1: its bases, where its length won
-template <int MODE>
+template <int MODE, int ENC>
 __global__ __launch_bounds__(POLISH_WG) void polish_slot_kernel(const PolRow *__restrict__ rows, uint32_t n_rows,
                                                                 const uint32_t *__restrict__ ops, const uint8_t *__restrict__ reads,
                                                                 const uint32_t *__restrict__ slot_of, const uint8_t *__restrict__ win_len,
@@ -134,7 +147,7 @@ __global__ __launch_bounds__(POLISH_WG) void polish_slot_kernel(const PolRow *__
         if (MODE == 0) atomicAdd(&len_cnt[(size_t)s * POLISH_INS_CAP + len - 1], 1u);
         else if (win_len[s] == len)
             for (uint32_t j = 0; j < len; ++j) {
-                const uint32_t k = column_symbol(r, reads, qc0 + j);
+                const uint32_t k = column_symbol<ENC>(r, reads, qc0 + j);
                 if (k < 4) atomicAdd(&base_cnt[((size_t)s * POLISH_INS_CAP + j) * 4 + k], 1u);
             }
     });
@@ -192,30 +205,55 @@ __global__ void gather_off_kernel(const uint64_t *__restrict__ off, const uint32
     if (i < n) out[i] = off[at[i]];
 }
 
+template <int ENC>
+void launch_count(const PolCoreIn &in, uint8_t *d_sym, uint8_t *d_open) {
+    hipLaunchKernelGGL(polish_count_kernel<ENC>, dim3((unsigned)in.n_tiles), dim3(POLISH_WG), 0, stream(), in.rows, in.ops, in.reads,
+                       in.contig, in.tiles, in.min_cov, d_sym, d_open);
+}
+template <int MODE, int ENC>
+void launch_slot(const PolCoreIn &in, const uint32_t *d_slot_of, const uint8_t *d_win_len, uint32_t *d_len_cnt, uint32_t *d_base_cnt) {
+    hipLaunchKernelGGL((polish_slot_kernel<MODE, ENC>), dim3(cdiv(in.n_rows, POLISH_WAVES)), dim3(POLISH_WG), 0, stream(), in.rows,
+                       in.n_rows, in.ops, in.reads, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+}
+
 }  // namespace
 
 void polish_device(const PolDevIn &in, PolDevOut &out) {
-    const size_t G = in.contigs.size();
-    out = PolDevOut{};
-    out.start.assign(in.cbase.size(), 0);
-    if (!G) return;
-    constexpr int B = 256;
-    DBuf<uint8_t> d_contig, d_reads, d_sym(G), d_open(G);
+    DBuf<uint8_t> d_contig, d_reads;
     DBuf<PolRow> d_rows;
     DBuf<uint32_t> d_ops, d_cbase;
     DBuf<PolTile> d_tiles;
-    d_contig.upload((const uint8_t *)in.contigs.data(), G);
+    d_contig.upload((const uint8_t *)in.contigs.data(), in.contigs.size());
     d_reads.upload((const uint8_t *)in.reads.data(), in.reads.size());
     d_rows.upload(in.rows);
     d_ops.upload(in.ops);
     d_tiles.upload(in.tiles);
     d_cbase.upload(in.cbase);
+    PolCoreIn c;
+    c.rows = d_rows.p; c.n_rows = (uint32_t)in.rows.size();
+    c.ops = d_ops.p;
+    c.reads = d_reads.p; c.enc = READS_ASCII;
+    c.contig = d_contig.p; c.n_contig = in.contigs.size();
+    c.tiles = d_tiles.p; c.n_tiles = in.tiles.size();
+    c.cbase = d_cbase.p; c.n_cbase = in.cbase.size();
+    c.min_cov = in.min_cov;
+    polish_core(c, out);
+}
+
+void polish_core(const PolCoreIn &in, PolDevOut &out) {
+    const size_t G = in.n_contig;
+    const bool codes = in.enc == READS_CODES;
+    out = PolDevOut{};
+    out.start.assign(in.n_cbase, 0);
+    if (!G) return;
+    constexpr int B = 256;
+    DBuf<uint8_t> d_sym(G), d_open(G);
     HIP_CHECK(hipMemsetAsync(d_sym.p, SYM_KEEP, G, stream()));
     d_open.zero();
-    if (!in.tiles.empty()) {
+    if (in.n_tiles) {
         KTimer kt("polish_count");
-        hipLaunchKernelGGL(polish_count_kernel, dim3((unsigned)in.tiles.size()), dim3(POLISH_WG), 0, stream(), d_rows.p, d_ops.p,
-                           d_reads.p, d_contig.p, d_tiles.p, in.min_cov, d_sym.p, d_open.p);
+        if (codes) launch_count<READS_CODES>(in, d_sym.p, d_open.p);
+        else launch_count<READS_ASCII>(in, d_sym.p, d_open.p);
         HIP_CHECK(hipGetLastError());
     }
     DBuf<uint32_t> d_open_pos(G), d_slot_of(G);
@@ -225,19 +263,18 @@ void polish_device(const PolDevIn &in, PolDevOut &out) {
     DBuf<uint8_t> d_win_len(std::max<size_t>(n_open, 1));
     if (n_open) {
         KTimer kt("polish_slots");
-        const uint32_t n_rows = (uint32_t)in.rows.size();
         d_len_cnt.zero();
         d_base_cnt.zero();
         hipLaunchKernelGGL(slot_index_kernel, dim3(cdiv(n_open, B)), dim3(B), 0, stream(), d_open_pos.p, (uint32_t)n_open, d_slot_of.p);
-        hipLaunchKernelGGL(polish_slot_kernel<0>, dim3(cdiv(n_rows, POLISH_WAVES)), dim3(POLISH_WG), 0, stream(), d_rows.p, n_rows,
-                           d_ops.p, d_reads.p, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
+        if (codes) launch_slot<0, READS_CODES>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
+        else launch_slot<0, READS_ASCII>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
         hipLaunchKernelGGL(slot_len_kernel, dim3(cdiv(n_open, B)), dim3(B), 0, stream(), d_len_cnt.p, (uint32_t)n_open, d_win_len.p);
-        hipLaunchKernelGGL(polish_slot_kernel<1>, dim3(cdiv(n_rows, POLISH_WAVES)), dim3(POLISH_WG), 0, stream(), d_rows.p, n_rows,
-                           d_ops.p, d_reads.p, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
+        if (codes) launch_slot<1, READS_CODES>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
+        else launch_slot<1, READS_ASCII>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
         HIP_CHECK(hipGetLastError());
     }
     DBuf<uint32_t> d_out_len(G + 1);
-    DBuf<uint64_t> d_off(G + 1), d_start(in.cbase.size());
+    DBuf<uint64_t> d_off(G + 1), d_start(in.n_cbase);
     hipLaunchKernelGGL(out_len_kernel, dim3(cdiv(G + 1, B)), dim3(B), 0, stream(), d_sym.p, d_slot_of.p, d_win_len.p, G, d_out_len.p);
     exclusive_scan_u32_to_u64(d_out_len.p, d_off.p, G + 1);
     const uint64_t total = download_one(d_off.p + G);
@@ -245,9 +282,9 @@ void polish_device(const PolDevIn &in, PolDevOut &out) {
     {
         KTimer kt("polish_write");
         hipLaunchKernelGGL(write_kernel, dim3(cdiv(G, B)), dim3(B), 0, stream(), d_sym.p, d_slot_of.p, d_win_len.p, d_base_cnt.p,
-                           d_contig.p, d_off.p, G, d_out.p);
-        hipLaunchKernelGGL(gather_off_kernel, dim3(cdiv(in.cbase.size(), B)), dim3(B), 0, stream(), d_off.p, d_cbase.p,
-                           (uint32_t)in.cbase.size(), d_start.p);
+                           in.contig, d_off.p, G, d_out.p);
+        hipLaunchKernelGGL(gather_off_kernel, dim3(cdiv(in.n_cbase, B)), dim3(B), 0, stream(), d_off.p, in.cbase,
+                           (uint32_t)in.n_cbase, d_start.p);
         HIP_CHECK(hipGetLastError());
     }
     out.start = d_start.download();

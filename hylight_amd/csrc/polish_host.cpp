@@ -1,6 +1,7 @@
 // polish_host.cpp - the host part of hlmi_polish (include/hylight_mi.h): reading, the refusals, row selection, the rows and
 // tiles the device works on (sorted by contig and start), the statistics, the headers and the file.  The votes, the
-// decisions and the bases are polish.hip's.
+// decisions and the bases are polish.hip's.  The layout (contigs side by side, tiles) and the output (statistics, headers,
+// file) are functions of their own: hlmi_polish_reads (polish_rows.hip) selects its rows on the device and shares them.
 // PARITY UNPINNED: racon is not part of the reference tree; tests/polish_model.py is the contract.
 #include <algorithm>
 #include <cstdio>
@@ -12,6 +13,7 @@
 #include "common.h"
 #include "paf_io.h"
 #include "polish_internal.h"
+#include "polish_rows.h"
 
 namespace hlmi {
 
@@ -113,21 +115,13 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
     st->rows_selected = sel.size();
 
     // the device's input: polished contigs side by side, the aligned stretch of every read, compact CIGARs, tiles
+    std::vector<PolSpan> spans;
+    spans.reserve(sel.size());
+    for (const Sel &s : sel) spans.push_back(PolSpan{s.contig, pt.recs[s.line].ts, pt.recs[s.line].te});
+    PolLayout L;
+    polish_layout(cs, spans, "hlmi_polish", L, st);
     PolDevIn in;
     in.min_cov = o.min_cov;
-    std::vector<uint32_t> rc(cs.size(), 0), slot_of_contig(cs.size(), 0);
-    for (const Sel &s : sel) ++rc[s.contig];
-    std::vector<uint32_t> polished;
-    for (uint32_t c = 0; c < cs.size(); ++c)
-        if (rc[c]) {
-            slot_of_contig[c] = (uint32_t)polished.size();
-            polished.push_back(c);
-            if (in.contigs.size() + cs.len(c) >= (1ull << 31)) fail(HLMI_EINVAL, "hlmi_polish: 2^31 contig bases or more to polish in one call");
-            in.cbase.push_back((uint32_t)in.contigs.size());
-            in.contigs.append(cs.bases, cs.off[c], cs.len(c));
-        }
-    in.cbase.push_back((uint32_t)in.contigs.size());
-    st->contigs_polished = polished.size();
     in.rows.reserve(sel.size());
     for (const Sel &s : sel) {
         const PafRec &r = pt.recs[s.line];
@@ -137,79 +131,96 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
         row.cig_off = in.ops.size();
         row.ts = r.ts; row.te = r.te; row.qn = r.qe - r.qs;
         row.rev = (r.flags & PF_REV) ? 1u : 0u;
-        row.cbase = in.cbase[slot_of_contig[s.contig]];
+        row.cbase = L.cbase[L.slot_of_contig[s.contig]];
         in.reads.append(rs.bases, rs.off[s.read] + r.qs, row.qn);
-        uint32_t p = r.ts;
-        for (uint32_t k = 0; k < r.cig_n; ++k) {
-            const uint32_t len = op[k] >> 4, code = op[k] & 15u;
-            if (!len) continue;
-            if (code == OP_I) {
-                if (p == r.ts || p == r.te) ++st->ins_edge;
-                if (in.ops.size() > row.cig_off && (in.ops.back() & 15u) == OP_I) {       // the same slot: one op
-                    in.ops.back() += len << 4;
-                    continue;
-                }
-            } else p += len;
-            in.ops.push_back(op[k]);
-        }
-        row.cig_n = (uint32_t)(in.ops.size() - row.cig_off);
-        p = r.ts;
-        for (uint32_t k = 0; k < row.cig_n; ++k) {
-            const uint32_t w = in.ops[row.cig_off + k];
-            if ((w & 15u) != OP_I) p += w >> 4;
-            else if (p != r.ts && p != r.te && (w >> 4) > (uint32_t)POLISH_INS_CAP) ++st->ins_long;
-        }
+        RowWalk w;                                           // polish_rows.h: drop, merge, ins_edge, ins_long
+        RowOp done;
+        row_walk_begin(w, r.ts, r.te);
+        for (uint32_t k = 0; k < r.cig_n; ++k)
+            if (row_walk_op(w, op[k], &done)) in.ops.push_back(done.word);
+        if (row_walk_end(w, &done)) in.ops.push_back(done.word);
+        st->ins_edge += w.ins_edge;
+        st->ins_long += w.ins_long;
+        row.cig_n = w.n_out;
         in.rows.push_back(row);
     }
-    for (size_t r0 = 0; r0 < in.rows.size();) {
-        size_t r1 = r0;
-        while (r1 < in.rows.size() && in.rows[r1].cbase == in.rows[r0].cbase) ++r1;
-        const uint32_t cbase = in.rows[r0].cbase;
-        const uint32_t len = *std::upper_bound(in.cbase.begin(), in.cbase.end(), cbase) - cbase;
-        size_t lo = r0, hi = r0;
-        for (uint32_t t0 = 0; t0 < len; t0 += POLISH_TILE) {
-            const uint32_t n_pos = std::min<uint32_t>(POLISH_TILE, len - t0);
-            while (hi < r1 && in.rows[hi].ts < t0 + n_pos) ++hi;
-            while (lo < hi && in.rows[lo].te <= t0) ++lo;        // (rows behind lo that ended too are passed over by the kernel)
-            if (lo < hi) in.tiles.push_back(PolTile{t0, n_pos, (uint32_t)lo, (uint32_t)hi, cbase});
-        }
-        r0 = r1;
-    }
+    in.contigs = std::move(L.contigs);
+    in.cbase = L.cbase;
+    in.tiles = std::move(L.tiles);
 
     const double t_dev = now_ms();
     PolDevOut out;
     polish_device(in, out);
     st->ms_device = now_ms() - t_dev;
+    L.contigs = std::move(in.contigs);
+    polish_emit(cs, L, out, o, out_fa, st);
+    st->ms_total = now_ms() - t_begin;
+}
 
+namespace pol {
+
+void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, hlmi_polish_stats *st) {
+    L = PolLayout{};
+    L.rc.assign(cs.size(), 0);
+    L.slot_of_contig.assign(cs.size(), 0);
+    for (const PolSpan &s : sel) ++L.rc[s.contig];
+    uint32_t n_polished = 0;
+    for (uint32_t c = 0; c < cs.size(); ++c)
+        if (L.rc[c]) {
+            L.slot_of_contig[c] = n_polished++;
+            if (L.contigs.size() + cs.len(c) >= (1ull << 31)) fail(HLMI_EINVAL, "%s: 2^31 contig bases or more to polish in one call", who);
+            L.cbase.push_back((uint32_t)L.contigs.size());
+            L.contigs.append(cs.bases, cs.off[c], cs.len(c));
+        }
+    L.cbase.push_back((uint32_t)L.contigs.size());
+    st->contigs_polished = n_polished;
+    for (size_t r0 = 0; r0 < sel.size();) {
+        size_t r1 = r0;
+        while (r1 < sel.size() && sel[r1].contig == sel[r0].contig) ++r1;
+        const uint32_t cbase = L.cbase[L.slot_of_contig[sel[r0].contig]], len = cs.len(sel[r0].contig);
+        size_t lo = r0, hi = r0;
+        for (uint32_t t0 = 0; t0 < len; t0 += POLISH_TILE) {
+            const uint32_t n_pos = std::min<uint32_t>(POLISH_TILE, len - t0);
+            while (hi < r1 && sel[hi].ts < t0 + n_pos) ++hi;
+            while (lo < hi && sel[lo].te <= t0) ++lo;            // (rows behind lo that ended too are passed over by the kernel)
+            if (lo < hi) L.tiles.push_back(PolTile{t0, n_pos, (uint32_t)lo, (uint32_t)hi, cbase});
+        }
+        r0 = r1;
+    }
+}
+
+void polish_emit(const SeqSet &cs, const PolLayout &L, const PolDevOut &out, const hlmi_polish_opts &o, const char *out_fa,
+                 hlmi_polish_stats *st) {
     st->slots_opened = out.open_pos.size();
     for (uint8_t l : out.open_len) st->inserted_bases += l;
     std::vector<std::string> lines;
     for (uint32_t c = 0; c < cs.size(); ++c) {
-        if (!rc[c]) {
+        if (!L.rc[c]) {
             if (o.include_unpolished && cs.len(c)) {
                 lines.push_back(">" + cs.names[c]);
                 lines.push_back(cs.bases.substr(cs.off[c], cs.len(c)));
             }
             continue;
         }
-        const uint32_t j = slot_of_contig[c], b = in.cbase[j], L = cs.len(c);
+        const uint32_t j = L.slot_of_contig[c], b = L.cbase[j], len = cs.len(c);
         uint64_t covered = 0;
-        for (uint32_t p = 0; p < L; ++p) {
+        for (uint32_t p = 0; p < len; ++p) {
             const uint8_t d = out.sym[b + p];
             if (d == SYM_KEEP) continue;
             ++covered;
             if (d == SYM_DEL) ++st->deleted;
-            else if ("ACGT"[d] != (char)((unsigned char)in.contigs[b + p] & 0xdfu)) ++st->substituted;
+            else if ("ACGT"[d] != (char)((unsigned char)L.contigs[b + p] & 0xdfu)) ++st->substituted;
         }
         const uint64_t new_len = out.start[j + 1] - out.start[j];
         if (!new_len) continue;
         char head[96];
-        snprintf(head, sizeof head, " LN:i:%llu RC:i:%u XC:f:%.6f", (unsigned long long)new_len, rc[c], (double)covered / (double)L);
+        snprintf(head, sizeof head, " LN:i:%llu RC:i:%u XC:f:%.6f", (unsigned long long)new_len, L.rc[c], (double)covered / (double)len);
         lines.push_back(">" + cs.names[c] + head);
         lines.push_back(out.bases.substr(out.start[j], new_len));
     }
     write_lines(out_fa, lines);
-    st->ms_total = now_ms() - t_begin;
 }
+
+}  // namespace pol
 
 }  // namespace hlmi

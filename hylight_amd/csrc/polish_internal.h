@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.h"
+#include "paf_io.h"
 
 namespace hlmi {
 namespace pol {
@@ -44,11 +45,51 @@ struct PolDevOut {
     std::vector<uint32_t> open_pos;     // opened slots, ascending, and the length each one got
     std::vector<uint8_t> open_len;
 };
-void polish_device(const PolDevIn &in, PolDevOut &out);
+void polish_device(const PolDevIn &in, PolDevOut &out);        // uploads `in`, then polish_core
+
+// The device part over what is already in HBM: hlmi_polish reaches it through polish_device, hlmi_polish_reads (polish_rows.hip)
+// with the rows, compact CIGARs and reads where its own kernels and the overlapper left them.
+enum ReadEnc : int { READS_ASCII = 0, READS_CODES = 1 };       // PolRow::read_off counts bytes of ASCII, or of DevReads::codes()
+struct PolCoreIn {
+    const PolRow *rows = nullptr;
+    uint32_t n_rows = 0;
+    const uint32_t *ops = nullptr;
+    const uint8_t *reads = nullptr;
+    ReadEnc enc = READS_ASCII;
+    const uint8_t *contig = nullptr;    // the polished contigs side by side, ASCII as in the file (their case reaches the output)
+    size_t n_contig = 0;
+    const PolTile *tiles = nullptr;
+    size_t n_tiles = 0;
+    const uint32_t *cbase = nullptr;    // PolDevIn::cbase
+    size_t n_cbase = 0;
+    int min_cov = 3;
+};
+void polish_core(const PolCoreIn &in, PolDevOut &out);
+
+// ---- what both entry points do on the host around the device part (polish_host.cpp) ----------------------------------------
+// a selected row as the layout sees it: contig record, [ts, te); in the order (contig, ts, line)
+struct PolSpan {
+    uint32_t contig, ts, te;
+};
+struct PolLayout {
+    std::vector<uint32_t> rc;               // selected rows per contig record (RC:i:)
+    std::vector<uint32_t> slot_of_contig;   // contig record -> its place among the polished ones
+    std::vector<uint32_t> cbase;            // PolDevIn::cbase
+    std::string contigs;                    // PolDevIn::contigs
+    std::vector<PolTile> tiles;
+};
+// who: the entry point's name for the refusal of 2^31 contig bases; sets contigs_polished
+void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, hlmi_polish_stats *st);
+// slots_opened, inserted_bases, substituted, deleted, the headers and the file
+void polish_emit(const SeqSet &cs, const PolLayout &L, const PolDevOut &out, const hlmi_polish_opts &o, const char *out_fa,
+                 hlmi_polish_stats *st);
 
 }  // namespace pol
 
 void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
                 hlmi_polish_stats *st);
+// hlmi_polish_reads (polish_rows.hip): the overlapper's rows selected, ordered and compacted where they are
+void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
+                      const char *out_fa, hlmi_polish_stats *st);
 
 }  // namespace hlmi

@@ -1,0 +1,259 @@
+// polish_rows.hip - hlmi_polish_reads (include/hylight_mi.h): hlmi_ava and hlmi_polish in one call, without the PAF between
+// them.  The overlapper's rows stay in HBM (ava_device: AvaRows, in the order of the lines hlmi_ava writes - a row's index IS its
+// PAF line), and what polish_host.cpp does with the parsed text happens where the rows are:
+//   pr_facts_kernel    a wave per row: n_eq and n_all over the row's ops, the selection rules in polish_host.cpp's order, and a
+//                      surviving row claims its read with one 64-bit atomicMax on span << 32 | ~row (largest span, earliest line)
+//   pr_winner_kernel   a thread per row: is it the one its read kept?  (flag-select: the winners, ascending by line)
+//   pr_key_kernel      a thread per winner: contig record << 28 | ts; a stable radix sort gives the order (contig, ts, line)
+//   pr_count_kernel    a thread per winner walks its CIGAR with the rule of polish_rows.h: ops of the compact CIGAR, ins_edge,
+//                      ins_long, and the (contig, ts, te) the host lays the tiles out from - all that comes back of the rows
+//   pr_write_kernel    the same walk once more behind a scan: the compact ops and the PolRow table
+// The reads are voted from the overlapper's resident codes (PolRow::read_off points into DevReads::codes()); the votes, the
+// decisions and the bases are polish.hip's (polish_core), headers and file polish_host.cpp's (polish_layout, polish_emit).
+//
+// Why a wave per row in the first kernel and a thread per row in the last two: the first reads the ops of EVERY row (all of
+// the CIGAR traffic of this file), needs two sums and nothing else of them, so 64 consecutive words per load and a DPP sum fit;
+// the walk of polish_rows.h is sequential by nature (an op's fate depends on the op before it), runs over the winners only (one
+// row per read at most) and shares its code with the host - a thread reads its row's words one behind the other, 16 to a
+// cache line.  Every loop is bounded by a count known at its head.
+#include <hip/hip_runtime.h>
+
+#include "ava.h"
+#include "common.h"
+#include "dev_prims.h"
+#include "paf_io.h"
+#include "polish_internal.h"
+#include "polish_rows.h"
+#include "wave_ops.h"
+
+namespace hlmi {
+
+using namespace pol;
+
+namespace {
+
+static_assert(ROW_OP_I == OP_I && ROW_INS_CAP == (uint32_t)POLISH_INS_CAP, "polish_rows.h restates two constants");
+
+constexpr int WG = 256, WAVES = WG / 64;
+constexpr unsigned MAX_GRID = 1u << 16;         // blocks of a strided launch
+constexpr uint32_t NO_REC = 0xffffffffu;
+inline dim3 grid1(size_t n) { return dim3((unsigned)std::min<size_t>(cdiv(n ? n : 1, WG), MAX_GRID)); }
+
+__global__ __launch_bounds__(WG) void pr_facts_kernel(const PafRec *__restrict__ recs, size_t n_rows, const uint32_t *__restrict__ ops_base,
+                                                      int min_len, double min_iden, unsigned long long *__restrict__ best) {
+    const int lane = threadIdx.x & 63;
+    const size_t n_waves = (size_t)gridDim.x * WAVES;
+    for (size_t i = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); i < n_rows; i += n_waves) {
+        const PafRec r = recs[i];
+        const uint32_t span = r.te - r.ts;
+        if (r.qid == r.tid || span == 0 || (int64_t)span < (int64_t)min_len) continue;          // (the same in every lane)
+        const uint32_t *o = ops_base + r.cig_off;
+        uint32_t eq = 0, all = 0;               // a row's op lengths add up to less than 2^29 (two sequences below 2^28)
+        for (uint32_t k0 = 0; k0 < r.cig_n; k0 += 64) {
+            const uint32_t k = k0 + (uint32_t)lane;
+            const uint32_t w = k < r.cig_n ? o[k] : 0u;
+            all += w >> 4;
+            eq += (w & 15u) == OP_EQ ? w >> 4 : 0u;
+        }
+        const uint32_t n_eq = (uint32_t)__builtin_amdgcn_readlane((int)wave_prefix_sum_incl_dpp(eq), 63);
+        const uint32_t n_all = (uint32_t)__builtin_amdgcn_readlane((int)wave_prefix_sum_incl_dpp(all), 63);
+        if ((double)n_eq / (double)n_all < min_iden) continue;                                  // one IEEE division, as on the host
+        if (lane == 0) atomicMax(&best[r.qid], (unsigned long long)span << 32 | (uint32_t)~(uint32_t)i);
+    }
+}
+
+// A row that did not survive never claimed; a read nobody claimed holds 0, whose low word no row's ~index equals (fewer than
+// 2^32 rows).
+__global__ __launch_bounds__(WG) void pr_winner_kernel(const PafRec *__restrict__ recs, size_t n_rows,
+                                                       const unsigned long long *__restrict__ best, uint8_t *__restrict__ flag) {
+    const size_t step = (size_t)gridDim.x * WG;
+    for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n_rows; i += step)
+        flag[i] = (uint32_t)best[recs[i].qid] == (uint32_t)~(uint32_t)i;
+}
+
+__global__ __launch_bounds__(WG) void pr_key_kernel(const PafRec *__restrict__ recs, const uint32_t *__restrict__ idx, size_t n_sel,
+                                                    const uint32_t *__restrict__ crec_of_rank, uint64_t *__restrict__ key) {
+    const size_t step = (size_t)gridDim.x * WG;
+    for (size_t j = (size_t)blockIdx.x * WG + threadIdx.x; j < n_sel; j += step) {
+        const PafRec r = recs[idx[j]];
+        key[j] = (uint64_t)crec_of_rank[r.tid] << 28 | r.ts;                    // ts < 2^28
+    }
+}
+
+// totals[0] += ins_edge, totals[1] += ins_long
+__global__ __launch_bounds__(WG) void pr_count_kernel(const PafRec *__restrict__ recs, const uint32_t *__restrict__ idx, size_t n_sel,
+                                                      const uint32_t *__restrict__ ops_base, const uint32_t *__restrict__ crec_of_rank,
+                                                      uint32_t *__restrict__ cig_n, PolSpan *__restrict__ span,
+                                                      unsigned long long *__restrict__ totals) {
+    const size_t step = (size_t)gridDim.x * WG;
+    for (size_t j = (size_t)blockIdx.x * WG + threadIdx.x; j < n_sel; j += step) {
+        const PafRec r = recs[idx[j]];
+        const uint32_t *o = ops_base + r.cig_off;
+        RowWalk w;
+        RowOp done;
+        row_walk_begin(w, r.ts, r.te);
+        for (uint32_t k = 0; k < r.cig_n; ++k) row_walk_op(w, o[k], &done);
+        row_walk_end(w, &done);
+        cig_n[j] = w.n_out;
+        span[j] = PolSpan{crec_of_rank[r.tid], r.ts, r.te};
+        if (w.ins_edge) atomicAdd(&totals[0], (unsigned long long)w.ins_edge);
+        if (w.ins_long) atomicAdd(&totals[1], (unsigned long long)w.ins_long);
+    }
+}
+
+__global__ __launch_bounds__(WG) void pr_write_kernel(const PafRec *__restrict__ recs, const uint32_t *__restrict__ idx, size_t n_sel,
+                                                      const uint32_t *__restrict__ ops_base, const uint32_t *__restrict__ crec_of_rank,
+                                                      const uint32_t *__restrict__ qrec_of_rank, const uint64_t *__restrict__ q_off,
+                                                      const uint32_t *__restrict__ cbase_of_crec, uint32_t n_crec,
+                                                      const uint64_t *__restrict__ cig_off, const uint32_t *__restrict__ cig_n,
+                                                      PolRow *__restrict__ rows, uint32_t *__restrict__ ops_out) {
+    const size_t step = (size_t)gridDim.x * WG;
+    for (size_t j = (size_t)blockIdx.x * WG + threadIdx.x; j < n_sel; j += step) {
+        const PafRec r = recs[idx[j]];
+        const uint32_t *o = ops_base + r.cig_off;
+        const uint64_t off = cig_off[j];
+        const uint32_t n = cig_n[j];            // what the count pass found: no op is written behind it
+        RowWalk w;
+        RowOp done;
+        row_walk_begin(w, r.ts, r.te);
+        for (uint32_t k = 0; k < r.cig_n; ++k)
+            if (row_walk_op(w, o[k], &done) && w.n_out <= n) ops_out[off + w.n_out - 1] = done.word;
+        if (row_walk_end(w, &done) && w.n_out <= n) ops_out[off + w.n_out - 1] = done.word;
+        const uint32_t crec = crec_of_rank[r.tid];
+        PolRow row;
+        row.read_off = q_off[qrec_of_rank[r.qid]] + r.qs;
+        row.cig_off = off;
+        row.cig_n = n;
+        row.ts = r.ts; row.te = r.te; row.qn = r.qe - r.qs;
+        row.rev = (r.flags & PF_REV) ? 1u : 0u;
+        row.cbase = crec < n_crec ? cbase_of_crec[crec] : 0u;
+        rows[j] = row;
+    }
+}
+
+// the bases the encoder folded into T for the aligner and the ASCII vote does not count (U, u): code 4 from here on
+__global__ __launch_bounds__(WG) void pr_unvote_kernel(uint8_t *__restrict__ codes, const uint64_t *__restrict__ at, size_t n) {
+    const size_t step = (size_t)gridDim.x * WG;
+    for (size_t i = (size_t)blockIdx.x * WG + threadIdx.x; i < n; i += step) codes[at[i]] = 4;
+}
+
+// the refusals that need the sequences only: 2^28 bases, a name twice in one file; -> name rank -> record (NO_REC: none)
+std::vector<uint32_t> record_of_rank(const SeqSet &s, const std::vector<uint32_t> &rank, size_t n_ranks, const char *path) {
+    std::vector<uint32_t> rec(n_ranks, NO_REC);
+    for (size_t i = 0; i < s.size(); ++i) {
+        if (s.len(i) >= MAX_SEQ) fail(HLMI_EINVAL, "hlmi_polish_reads: %s: %s has 2^28 bases or more", path, s.names[i].c_str());
+        if (rec[rank[i]] != NO_REC) fail(HLMI_EINVAL, "hlmi_polish_reads: %s: two records are named %s", path, s.names[i].c_str());
+        rec[rank[i]] = (uint32_t)i;
+    }
+    return rec;
+}
+
+}  // namespace
+
+void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
+                      const char *out_fa, hlmi_polish_stats *st) {
+    const double t_begin = now_ms();
+    *st = hlmi_polish_stats{};
+    stat_reset();
+    if (po.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish_reads: min_cov %d (< 1)", po.min_cov);
+    if (ao.stub_oh >= 0) fail(HLMI_EINVAL, "hlmi_polish_reads: stub_oh %d: the bare rows of stub candidates have no CIGAR", ao.stub_oh);
+    SeqSet cs, rs;
+    read_seqs(contigs, cs);
+    read_seqs(reads, rs);
+    const double t_dev = now_ms();
+    AvaPairCall call;
+    call.setup(cs, rs, ao);
+    const size_t n_ranks = call.name_of_rank.size();
+    const std::vector<uint32_t> crec_of_rank = record_of_rank(cs, call.rt, n_ranks, contigs),      // (refusals: before the overlapper runs)
+                                qrec_of_rank = record_of_rank(rs, call.rq, n_ranks, reads);
+    AvaRows rows;
+    ava_device(call.in, ao, rows);
+    const size_t R = rows.n_rows;
+    if (R >= (1ull << 32)) fail(HLMI_EINVAL, "hlmi_polish_reads: %zu overlapper rows (2^32 and more)", R);
+    st->rows = R;
+    st->contigs = cs.size();
+
+    // ---- selection and order ----------------------------------------------------------------------------------------------------
+    size_t S = 0;
+    DBuf<uint32_t> idx(std::max<size_t>(R, 1)), d_crec_of_rank, d_qrec_of_rank;
+    if (R) {
+        KTimer kt("polish_rows");
+        DBuf<unsigned long long> best(n_ranks);
+        DBuf<uint8_t> flag(R);
+        best.zero();
+        hipLaunchKernelGGL(pr_facts_kernel, dim3((unsigned)std::min<size_t>(cdiv(R, WAVES), MAX_GRID)), dim3(WG), 0, stream(), rows.recs.p,
+                           R, rows.ops_base, po.min_len, po.min_iden, best.p);
+        hipLaunchKernelGGL(pr_winner_kernel, grid1(R), dim3(WG), 0, stream(), rows.recs.p, R, best.p, flag.p);
+        HIP_CHECK(hipGetLastError());
+        S = select_flagged_indices(flag.p, idx.p, R);
+    }
+    st->rows_selected = S;
+    std::vector<PolSpan> spans;
+    DBuf<uint32_t> cig_n(std::max<size_t>(S, 1));
+    DBuf<uint64_t> cig_off(std::max<size_t>(S, 1));
+    uint64_t n_ops = 0;
+    if (S) {
+        KTimer kt("polish_rows");
+        d_crec_of_rank.upload(crec_of_rank);
+        d_qrec_of_rank.upload(qrec_of_rank);
+        DBuf<uint64_t> key(S);
+        hipLaunchKernelGGL(pr_key_kernel, grid1(S), dim3(WG), 0, stream(), rows.recs.p, idx.p, S, d_crec_of_rank.p, key.p);
+        sort_pairs_u64_u32(key.p, idx.p, S, 0, 28 + bits_for(cs.size() - 1));
+        DBuf<PolSpan> d_span(S);
+        DBuf<unsigned long long> totals(2);
+        totals.zero();
+        hipLaunchKernelGGL(pr_count_kernel, grid1(S), dim3(WG), 0, stream(), rows.recs.p, idx.p, S, rows.ops_base, d_crec_of_rank.p,
+                           cig_n.p, d_span.p, totals.p);
+        HIP_CHECK(hipGetLastError());
+        exclusive_scan_u32_to_u64(cig_n.p, cig_off.p, S);
+        n_ops = download_one(cig_off.p + (S - 1)) + download_one(cig_n.p + (S - 1));
+        const std::vector<unsigned long long> t = totals.download(2);
+        st->ins_edge = t[0];
+        st->ins_long = t[1];
+        spans = d_span.download(S);
+        for (const PolSpan &s : spans)
+            if (s.contig >= cs.size()) fail(HLMI_EINVAL, "hlmi_polish_reads: a row names a target that is no contig");    // (never)
+    }
+    PolLayout L;
+    polish_layout(cs, spans, "hlmi_polish_reads", L, st);
+
+    // ---- CIGARs and rows, then the votes ----------------------------------------------------------------------------------------
+    DBuf<PolRow> d_rows(std::max<size_t>(S, 1));
+    DBuf<uint32_t> d_ops(std::max<uint64_t>(n_ops, 1)), d_cbase, d_cbase_of_crec;
+    DBuf<PolTile> d_tiles;
+    DBuf<uint8_t> d_contig;
+    if (S) {
+        std::vector<uint32_t> cbase_of_crec(cs.size(), 0);
+        for (size_t c = 0; c < cs.size(); ++c)
+            if (L.rc[c]) cbase_of_crec[c] = L.cbase[L.slot_of_contig[c]];
+        d_cbase_of_crec.upload(cbase_of_crec);
+        std::vector<uint64_t> u_at;             // U / u in the reads (see pr_unvote_kernel)
+        for (size_t p = rs.bases.find_first_of("Uu"); p != std::string::npos; p = rs.bases.find_first_of("Uu", p + 1)) u_at.push_back(p);
+        DBuf<uint64_t> d_u_at;
+        d_u_at.upload(u_at);
+        KTimer kt("polish_rows");
+        if (!u_at.empty())
+            hipLaunchKernelGGL(pr_unvote_kernel, grid1(u_at.size()), dim3(WG), 0, stream(), call.dQ.codes(), d_u_at.p, u_at.size());
+        hipLaunchKernelGGL(pr_write_kernel, grid1(S), dim3(WG), 0, stream(), rows.recs.p, idx.p, S, rows.ops_base, d_crec_of_rank.p,
+                           d_qrec_of_rank.p, call.dQ.off.p, d_cbase_of_crec.p, (uint32_t)cs.size(), cig_off.p, cig_n.p, d_rows.p, d_ops.p);
+        HIP_CHECK(hipGetLastError());
+    }
+    d_contig.upload((const uint8_t *)L.contigs.data(), L.contigs.size());
+    d_cbase.upload(L.cbase);
+    d_tiles.upload(L.tiles);
+    PolCoreIn c;
+    c.rows = d_rows.p; c.n_rows = (uint32_t)S;
+    c.ops = d_ops.p;
+    c.reads = call.dQ.codes(); c.enc = READS_CODES;
+    c.contig = d_contig.p; c.n_contig = L.contigs.size();
+    c.tiles = d_tiles.p; c.n_tiles = L.tiles.size();
+    c.cbase = d_cbase.p; c.n_cbase = L.cbase.size();
+    c.min_cov = po.min_cov;
+    PolDevOut out;
+    polish_core(c, out);
+    st->ms_device = now_ms() - t_dev;
+    polish_emit(cs, L, out, po, out_fa, st);
+    st->ms_total = now_ms() - t_begin;
+}
+
+}  // namespace hlmi

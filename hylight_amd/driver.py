@@ -4,7 +4,8 @@ Keeps script/HyLight.py's CLI flags and defaults (HyLight.py:25-52), stage order
 (OUT/1.split_fastx/s1.fa, OUT/2.overlap/s1_s1.paf, OUT/tmp/contigs1.{gfa,fa}, OUT/tmp/ov_long_ref.paf,
 ...), and calls libhylight_mi.so at the two boundaries the path owns: B1 = split_reads2 and
 B3 = miniasm.  External tools the reference shells out to (bfc, ropebwt2, fmlrc2, racon) are still
-external (`--polish_native` replaces racon with the library's own pile-up consensus, hlmi_polish); unlike the reference (whose `execute()` swallows most failures) a missing or
+external (`--polish_native` replaces racon with the library's own pile-up consensus, hlmi_polish, and `--polish_direct` does
+the same without the PAF between overlapper and polisher, hlmi_polish_reads); unlike the reference (whose `execute()` swallows most failures) a missing or
 failing tool stops the run with a message.  The two short-read overlap calls of the path (HyLight.py:200,207)
 run in the library's short mode.  `extend_con` (HyLight.py:282-326) is wired up to the SAVAGE overlap file: contigs ->
 contigs_b.fastq -> self-overlaps (the `minimap2 --sr -X ... -r 0` call as hlmi_ava) -> v3 window filter with -sfo ->
@@ -159,16 +160,20 @@ def extend_con(input_con, outdir1, out_file, threads=30, len_c=50000000, stageb_
     return n
 
 
-def polish_native(k, reads, contigs, out_fa, tmp, min_len, iden, short=False, append=False):
+def polish_native(k, reads, contigs, out_fa, tmp, min_len, iden, short=False, append=False, direct=False):
     """One racon site with the library's own polisher (`--polish_native`): the reads are aligned to the contigs once more
     (hlmi_ava, every pair: the stage's scored PAF carries no CIGAR) into tmp/polish_<k>.paf, and hlmi_polish votes over those
-    rows.  `append`: out_fa grows, as the `>>` of HyLight.py:182 does."""
-    paf = os.path.join(tmp, f"polish_{k}.paf")
+    rows.  `direct` (`--polish_direct`): both in one call (hlmi_polish_reads) with the same options - the same file, and no
+    tmp/polish_<k>.paf.  `append`: out_fa grows, as the `>>` of HyLight.py:182 does."""
     o = api.ava_opts_short() if short else api.ava_opts_long()
     o.pair_once = 0
-    api.ava(contigs, reads, paf, o)
     part = out_fa + ".part" if append else out_fa
-    st = api.polish(contigs, reads, paf, part, min_len=min_len, min_iden=iden)
+    if direct:
+        st = api.polish_reads(contigs, reads, part, o, min_len=min_len, min_iden=iden)
+    else:
+        paf = os.path.join(tmp, f"polish_{k}.paf")
+        api.ava(contigs, reads, paf, o)
+        st = api.polish(contigs, reads, paf, part, min_len=min_len, min_iden=iden)
     if append:
         with open(part, "rb") as f, open(out_fa, "ab") as w:
             shutil.copyfileobj(f, w)
@@ -223,6 +228,9 @@ def build_parser():
     p.add_argument("--polish_native", action="store_true",
                    help="(extension) polish with the library (hlmi_polish: a pile-up consensus over the overlapper's own CIGARs, "
                         "tmp/polish_<k>.paf) in place of the three racon calls; racon is then not needed")
+    p.add_argument("--polish_direct", action="store_true",
+                   help="(extension) the same polisher with the alignment inside the call (hlmi_polish_reads): the same contigs, "
+                        "no tmp/polish_<k>.paf; not together with --polish_native")
     return p
 
 
@@ -328,6 +336,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.polyte_native and args.polyte_cmd:
         raise SystemExit("--polyte_native and --polyte_cmd are two ways to run the same step: give one of them")
+    if args.polish_native and args.polish_direct:
+        raise SystemExit("--polish_native and --polish_direct are two ways to run the same step: give one of them")
     if args.gpus > 1 and not launch.launched():
         # one process per GPU, started before this one has made any GPU call; this process only waits for them
         return launch.spawn_ranks(args.gpus, [sys.executable, "-m", "hylight_amd.driver", *argv])
@@ -390,10 +400,11 @@ def _pipeline(args, pool):
         return 0
 
     ov_long_ref = stage(infile, long_con, nsplit, tmp + "ov_long_ref.paf", len_over, 2, iden)   # HyLight.py:149
-    racon = None if args.polish_native else _tool("racon")
+    native = args.polish_native or args.polish_direct
+    racon = None if native else _tool("racon")
     p1, p2 = tmp + "polish1.fa", tmp + "polish2.fa"
-    if args.polish_native:
-        polish_native(1, infile, long_con, p1, tmp, len_over, iden)
+    if native:
+        polish_native(1, infile, long_con, p1, tmp, len_over, iden, direct=args.polish_direct)
     else:
         _run(f"{racon} --no-trimming -u -t 30 {infile} {ov_long_ref} {long_con} > {p1}", cwd=tmp)
     ti = 0
@@ -409,8 +420,8 @@ def _pipeline(args, pool):
         remain_con = tmp + "remain_con.fa"
         gfa2fa(remain_gfa, remain_con)
         ov2 = stage(infile, remain_con, nsplit, tmp + "ov_long_ref2.paf", len_over, 2, iden)
-        if args.polish_native:
-            polish_native(2 if ti == 0 else f"2_{ti}", infile, remain_con, p2, tmp, len_over, iden, append=True)
+        if native:
+            polish_native(2 if ti == 0 else f"2_{ti}", infile, remain_con, p2, tmp, len_over, iden, append=True, direct=args.polish_direct)
             with open(ov2, "rb") as f, open(ov_long_ref, "ab") as w:
                 shutil.copyfileobj(f, w)
         else:
@@ -434,8 +445,8 @@ def _pipeline(args, pool):
     # the two short-read calls of the same path (HyLight.py:200,207: len_over 70, mc 3, short mode)
     ov_short = stage(short_reads, long_con2, nsplit, tmp + "shortr1.paf", 70, 3, iden, long=False)
     long_con3 = os.path.join(outdir, "long_con_polished.fa")
-    if args.polish_native:
-        polish_native(3, short_reads, long_con2, long_con3, tmp, 70, iden, short=True)
+    if native:
+        polish_native(3, short_reads, long_con2, long_con3, tmp, 70, iden, short=True, direct=args.polish_direct)
     else:
         _run(f"{racon} --no-trimming -u -t 30 {short_reads} {ov_short} {long_con2} > {long_con3}", cwd=outdir)
     remain_short = pick_up(ov_short, tmp, short_reads)

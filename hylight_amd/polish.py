@@ -3,9 +3,12 @@ calls of HyLight.py:152,182,203.  Not racon's function - a column vote over the 
 (include/hylight_mi.h states the rules, tests/polish_model.py is their contract).
 
     python -m hylight_amd.polish --contigs contigs.fa --reads reads.fa --paf rows.paf --out polished.fa [options]
+    python -m hylight_amd.polish --contigs contigs.fa --reads reads.fa --out polished.fa [--short] [options]
 
 --paf holds rows with a cg:Z: CIGAR in = X I D as the last field, reads against contigs, as `api.ava(contigs, reads, paf)`
-writes them.  Prints the stats as one JSON line.  Exit status 0 on success.
+writes them.  Without --paf the reads are aligned to the contigs in the same call (hlmi_polish_reads: the overlapper's long
+constants, --short: its short-read ones; every pair, pair_once = 0, as the driver's polishing sites do) and no PAF exists.
+Prints the stats as one JSON line.  Exit status 0 on success.
 """
 from __future__ import annotations
 
@@ -21,7 +24,9 @@ def build_parser():
                                 formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--contigs", required=True, help="FASTA / FASTQ of the contigs to polish")
     p.add_argument("--reads", required=True, help="FASTA / FASTQ of the reads the rows name")
-    p.add_argument("--paf", required=True, help="rows of reads (query) against contigs (target) with cg:Z: CIGARs")
+    p.add_argument("--paf", default=None,
+                   help="rows of reads (query) against contigs (target) with cg:Z: CIGARs; not given: align here, write none")
+    p.add_argument("--short", action="store_true", help="without --paf: the overlapper's short-read constants")
     p.add_argument("--out", required=True, help="polished contigs (FASTA, two lines per record)")
     p.add_argument("--min_len", type=int, default=0, help="drop rows that cover fewer contig bases")
     p.add_argument("--min_iden", type=float, default=0.0, help="drop rows with a smaller share of '=' columns")
@@ -30,10 +35,23 @@ def build_parser():
     return p
 
 
+def read_ava_opts(short=False):
+    """The overlapper's options of a polishing site: long or short constants, every pair (driver.polish_native)."""
+    o = api.ava_opts_short() if short else api.ava_opts_long()
+    o.pair_once = 0
+    return o
+
+
 def main(argv=None):
-    a = build_parser().parse_args(argv)
-    st = api.polish(a.contigs, a.reads, a.paf, a.out, min_len=a.min_len, min_iden=a.min_iden, min_cov=a.min_cov,
-                    include_unpolished=not a.drop_unpolished)
+    parser = build_parser()
+    a = parser.parse_args(argv)
+    opts = dict(min_len=a.min_len, min_iden=a.min_iden, min_cov=a.min_cov, include_unpolished=not a.drop_unpolished)
+    if a.paf is not None:
+        if a.short:
+            parser.error("--short chooses the alignment of a call without --paf")
+        st = api.polish(a.contigs, a.reads, a.paf, a.out, **opts)
+    else:
+        st = api.polish_reads(a.contigs, a.reads, a.out, read_ava_opts(a.short), **opts)
     print(json.dumps(st))
     return 0
 

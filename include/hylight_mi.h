@@ -737,6 +737,19 @@ typedef struct {
  * Device: every counter is 32 bits wide, so coverage has no limit below 2^32 rows. */
 int hlmi_polish(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts *o, const char *out_fa,
                 hlmi_polish_stats *st);
+/* The two calls hlmi_ava(contigs, reads, ao, P) and hlmi_polish(contigs, reads, P, po, out_fa, st) in one, without the PAF P:
+ * out_fa and every integer field of *st are byte for byte what that chain gives (ao NULL: hlmi_ava's default, the long
+ * constants).  No PAF is written and no row or CIGAR op travels to the host: the overlapper's rows are selected, ordered and
+ * compacted in device memory (csrc/polish_rows.hip; a row's index there is its line in P) and the reads are voted from the
+ * overlapper's resident copy.  Three differences from the chain:
+ *  - two records of one name in `reads`, or in `contigs`, are HLMI_EINVAL before anything is written (the chain aligns the
+ *    second record and then votes with the first record's bases);
+ *  - ao->stub_oh >= 0 is HLMI_EINVAL: the bare rows of stub candidates have no CIGAR (the chain refuses those rows too);
+ *  - 2^32 overlapper rows or more are HLMI_EINVAL.
+ * hlmi_polish's own refusals that can still occur are kept: min_cov < 1, a sequence of 2^28 bases or more, 2^31 contig
+ * bases to polish in one call.  What hlmi_polish checks only because a PAF is foreign text does not arise here. */
+int hlmi_polish_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_opts *po,
+                      const char *out_fa, hlmi_polish_stats *st);
 
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
