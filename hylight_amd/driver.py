@@ -22,7 +22,10 @@ long_con_polished.fa.  Without these flags the run is the same as before.  `--po
 with the library's own POLYTE (hylight_amd.polyte: the loop of polyte.tune_params.py, its threshold table, every iteration and
 every overlap computation a library call; HyLight's copy of the script treats the mates as single reads, so no paired-end
 vertices are needed), one cluster after the other in this process; `--polyte_cmd` itself is untouched, and both together are an
-error.  `--stageb_native` keeps minQual 0.9: pipeline_per_stage.py does not pass the flag.
+error.  `--polyte_workers W` (extension) deals the clusters out, largest first, to W processes per GPU (this one and W - 1 fresh
+interpreters, hylight_amd/polyte_pool.py) and, under `--gpus N`, to the N ranks as well (StagePool.polyte): the reference's
+`xargs -i -P threads` over cmd_polyte.sh (HyLight.py:245).  A cluster's files do not depend on who ran it.
+`--stageb_native` keeps minQual 0.9: pipeline_per_stage.py does not pass the flag.
 
 `--gpus N` (extension): every split_reads2 call is sharded over N GPUs of the node, chunk i -> rank i % N, the way the
 reference fans its chunks out with `xargs -P` (script/utils.py:44-69).  The process starts N - 1 further copies of
@@ -43,6 +46,7 @@ from . import api, launch
 from .stage import StagePool
 
 __version__ = "1.0.1-mi355x"
+MAX_GPU_PROCESSES = 16   # --gpus x --polyte_workers: shared machines allow this many processes with a GPU open
 EXIT_NO_FINAL = 3        # everything this implementation covers ran, but final_contigs.fa (the stage-b merge) was not written
 
 
@@ -218,8 +222,11 @@ def build_parser():
                         "--short_contigs, cluster the short reads and run it per cluster (HyLight.py:215-275)")
     p.add_argument("--polyte_native", action="store_true",
                    help="(extension) the same with the library's own POLYTE (hylight_amd.polyte: the clique, merge and branch "
-                        "iterations and the overlaps between them on the GPU), cluster after cluster in this process; not "
-                        "together with --polyte_cmd")
+                        "iterations and the overlaps between them on the GPU), cluster after cluster in this process "
+                        "(--polyte_workers: in several); not together with --polyte_cmd")
+    p.add_argument("--polyte_workers", type=int, default=1,
+                   help="(extension) processes per GPU during the --polyte_native step: the clusters are dealt out to them by "
+                        "size, every cluster's files are the same whichever process ran it; --gpus times this is at most 16")
     p.add_argument("--stageb_cmd", default=None,
                    help="(extension) command prefix of the reference's pipeline_per_stage.py, if installed")
     p.add_argument("--stageb_native", action="store_true",
@@ -247,34 +254,21 @@ def polyte_lines(tmp, size, polyte_cmd, insert_size, average_read_len):
     return lines
 
 
-def polyte_native(tmp, size, insert_size, average_read_len):
+def polyte_native(tmp, size, insert_size, average_read_len, workers=1, device=0, host_threads=20, pool=None):
     """HyLight.py:228-242 with the library's own POLYTE (`--polyte_native`): hylight_amd.polyte.run in every cluster directory
-    of tmp/fq_<size>/, one after the other in this process, with the options of polyte_lines; each cluster's output goes to its
-    log.txt.  A cluster that fails leaves no contigs.fasta and is named by the caller's warning, as in the reference."""
-    import contextlib
-    from . import polyte
-    outdir2 = os.path.abspath(os.path.join(tmp, f"fq_{size}"))
-    cwd = os.getcwd()
-    for i in sorted(os.listdir(outdir2)):
-        folder = f"{outdir2}/{i}"
-        try:
-            os.chdir(folder)
-            with open("log.txt", "w") as log, contextlib.redirect_stdout(log):
-                try:
-                    polyte.run(f"{folder}/{i}.1.fq", f"{folder}/{i}.2.fq", min_overlap_len=50, min_overlap_len_EC=60, hap_cov=10,
-                               insert_size=insert_size, stddev=27, average_read_len=average_read_len, min_clique_size=2,
-                               edge1=0.93, edge2=1.0)
-                except (api.HlmiError, ValueError) as e:
-                    if isinstance(e, api.HlmiError) and e.code not in (-1, -6):    # only what the cluster's own data causes
-                        raise                                                      # (HLMI_EINVAL, HLMI_ESTATE) is the cluster's
-                    log.write(f"hylight_amd.polyte: {e}\n")
-                    if os.path.exists("contigs.fasta"):
-                        os.remove("contigs.fasta")
-        finally:
-            os.chdir(cwd)
+    of tmp/fq_<size>/ with the options of polyte_lines; each cluster's output goes to its log.txt.  A cluster that fails leaves
+    no contigs.fasta and is named by the caller's warning, as in the reference.  With one worker and no pool of ranks: one
+    cluster after the other in this process.  `workers` > 1 (`--polyte_workers`): that many processes on GPU `device`, this one
+    among them, with `host_threads` shared out (polyte_pool.run); `pool`: the StagePool of the run, which knows its own device
+    and threads - under `--gpus N` every rank takes its share of the clusters with `workers` processes on its own GPU.  The
+    files are the same in every case."""
+    from . import polyte_pool
+    if pool is not None:
+        return pool.polyte(tmp, size, insert_size, average_read_len, workers)
+    polyte_pool.run(polyte_pool.cluster_folders(tmp, size), workers, device, host_threads, insert_size, average_read_len)
 
 
-def _short_branch(args, tmp, outdir, long_con3):
+def _short_branch(args, tmp, outdir, long_con3, pool=None):
     """HyLight.py:228-275 after the clustering: POLYTE per cluster (external with `--polyte_cmd`, the library's with
     `--polyte_native`), the cluster contigs, their stage-b extension (short_stageb.fa) and all_contigs.fa; then the final
     extend_con as on the other path."""
@@ -282,7 +276,8 @@ def _short_branch(args, tmp, outdir, long_con3):
 
     size = args.size
     if args.polyte_native:
-        polyte_native(tmp, size, args.insert_size, args.average_read_len)
+        polyte_native(tmp, size, args.insert_size, args.average_read_len, workers=args.polyte_workers, device=args.device,
+                      host_threads=args.threads, pool=pool)
     else:
         lines = polyte_lines(tmp, size, args.polyte_cmd, args.insert_size, args.average_read_len)
         with open(os.path.join(tmp, "cmd_polyte.sh"), "w") as f:
@@ -321,14 +316,33 @@ def _short_branch(args, tmp, outdir, long_con3):
     return 0
 
 
+def _rank_device(args, world, local):
+    """The index of this rank's GPU."""
+    import torch
+    n_dev = torch.cuda.device_count()                         # (counting devices does not initialise the GPU)
+    return args.device if world == 1 else local % max(n_dev, 1)
+
+
 def _init_rank(args, world, local):
     """This rank's GPU, the library on it, the process group of the run (RCCL)."""
     import torch
-    n_dev = torch.cuda.device_count()                         # (counting devices does not initialise the GPU)
-    dev = args.device if world == 1 else local % max(n_dev, 1)
+    dev = _rank_device(args, world, local)
     torch.cuda.set_device(dev)
     api.init(dev, args.threads)
     launch.init_process_group(dev)
+
+
+def refuse_polyte_workers(args):
+    """`--polyte_workers` against the flags it goes with; before anything is created."""
+    w = args.polyte_workers
+    if w < 1:
+        raise SystemExit(f"--polyte_workers {w}: at least one process runs the POLYTE step")
+    if w > 1 and not args.polyte_native:
+        raise SystemExit("--polyte_workers is about the library's own POLYTE: give --polyte_native with it (--polyte_cmd runs "
+                         "its lines with -t workers)")
+    if args.gpus * w > MAX_GPU_PROCESSES:
+        raise SystemExit(f"--gpus {args.gpus} with --polyte_workers {w} is {args.gpus * w} processes with a GPU open; shared "
+                         f"machines allow {MAX_GPU_PROCESSES} at a time")
 
 
 def main(argv=None):
@@ -338,6 +352,7 @@ def main(argv=None):
         raise SystemExit("--polyte_native and --polyte_cmd are two ways to run the same step: give one of them")
     if args.polish_native and args.polish_direct:
         raise SystemExit("--polish_native and --polish_direct are two ways to run the same step: give one of them")
+    refuse_polyte_workers(args)
     if args.gpus > 1 and not launch.launched():
         # one process per GPU, started before this one has made any GPU call; this process only waits for them
         return launch.spawn_ranks(args.gpus, [sys.executable, "-m", "hylight_amd.driver", *argv])
@@ -345,7 +360,7 @@ def main(argv=None):
     if launch.launched() and args.gpus not in (1, world):
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     _init_rank(args, world, local)
-    pool = StagePool(rank, world)
+    pool = StagePool(rank, world, device_index=_rank_device(args, world, local), host_threads=args.threads)
     try:
         if rank != 0:
             pool.serve()
@@ -458,7 +473,7 @@ def _pipeline(args, pool):
         sys.stderr.write(f"hylight-mi: {st['files'] // 2} short-read clusters in tmp/fq_{args.size}/\n")
         if args.stop_after == "clusters":
             return 0
-        return _short_branch(args, tmp, outdir, long_con3)
+        return _short_branch(args, tmp, outdir, long_con3, pool)
     # HyLight.py:211-262 (read clustering, POLYTE per cluster) is the short-read branch: not part of this path.  Its
     # contigs can be handed in; the contig-overlap half of extend_con runs either way (HyLight.py:264-280).
     sys.stderr.write("hylight-mi: short-read clustering and POLYTE (HyLight.py:211-262) are outside this implementation"

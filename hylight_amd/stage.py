@@ -137,10 +137,12 @@ class StagePool:
     """Every split_reads2 call of a run on the N ranks of a node (the reference: `xargs -i -P threads` per call,
     script/utils.py:65).  Rank 0 drives the pipeline and calls `stage()`; the other ranks sit in `serve()` and take part
     in every stage call they are told about (the call's arguments are broadcast): each rank opens the same files, sketches
-    its slice of the reads, runs its chunks (chunk i -> rank i % N), rank 0 merges.  With one rank this is a plain call."""
+    its slice of the reads, runs its chunks (chunk i -> rank i % N), rank 0 merges.  With one rank this is a plain call.  `polyte()` is the other call the
+    ranks share: the short-read clusters of the native POLYTE step, dealt out over ranks x workers (polyte_pool.py)."""
 
-    def __init__(self, rank=0, world=1, group=None):
+    def __init__(self, rank=0, world=1, group=None, device_index=0, host_threads=20):
         self.rank, self.world, self.group = rank, world, group
+        self.device_index, self.host_threads = device_index, host_threads      # this rank's GPU and -t: the POLYTE step's workers
         self.calls = 0
         self.broken = False          # a stage call failed on this rank: the other ranks are inside collectives, not in serve()
 
@@ -179,7 +181,46 @@ class StagePool:
             msg = self._tell(None)
             if msg[0] == "exit":
                 return self.calls
-            self._run(*msg[1:])
+            if msg[0] == "polyte":
+                self._polyte(*msg[1:])
+            else:
+                self._run(*msg[1:])
+
+    def _polyte(self, tmp, size, insert_size, average_read_len, workers):
+        """This rank's share of the POLYTE step.  Every rank lists the same tmp/fq_<size>/ and makes the same plan over
+        world * workers bins; rank r runs bins r*workers .. r*workers + workers - 1 on its own GPU.  The ranks then exchange
+        how it went: a failure anywhere raises on every rank (and marks the pool broken), naming the first rank that failed."""
+        import torch.distributed as dist
+        from . import polyte_pool
+        err = None
+        try:
+            folders = polyte_pool.cluster_folders(tmp, size)
+            bins = polyte_pool.plan(polyte_pool.cluster_sizes(folders), self.world * workers)
+            lo = self.rank * workers
+            polyte_pool.run(folders, workers, self.device_index, self.host_threads, insert_size, average_read_len,
+                            bins=bins[lo:lo + workers], first_bin=lo, share_dir=tmp)
+        except Exception as e:
+            err = f"{type(e).__name__}: {e}"
+        status = [None] * self.world
+        dist.all_gather_object(status, err, group=self.group)
+        bad = [(r, s) for r, s in enumerate(status) if s is not None]
+        if bad:
+            self.broken = True
+            raise RuntimeError(f"POLYTE step failed on rank {bad[0][0]}: {bad[0][1]}")
+        self.calls += 1
+
+    def polyte(self, tmp, size, insert_size, average_read_len, workers=1):
+        """The native POLYTE step (driver.polyte_native) on all ranks, `workers` processes per GPU; called on rank 0 only.
+        With one rank this is a plain call of polyte_pool.run."""
+        if self.rank != 0:
+            raise RuntimeError("StagePool.polyte is called on rank 0; the other ranks run serve()")
+        args = (os.path.abspath(os.fspath(tmp)), int(size), insert_size, average_read_len, int(workers))
+        if self.world == 1:
+            from . import polyte_pool
+            return polyte_pool.run(polyte_pool.cluster_folders(*args[:2]), args[4], self.device_index, self.host_threads,
+                                   args[2], args[3])
+        self._tell(("polyte",) + args)
+        self._polyte(*args)
 
     def shutdown(self):
         """Rank 0, at the end of the run: releases the other ranks.  After a failed stage call nothing is sent (the
