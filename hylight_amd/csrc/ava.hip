@@ -18,7 +18,7 @@ namespace hlmi {
 
 namespace {
 constexpr int WG = 256;
-inline dim3 grid1(size_t n) { return dim3(cdiv(n ? n : 1, WG)); }
+inline dim3 grid1(size_t n) { return grid_for(n, WG); }
 constexpr size_t ANCHOR_BATCH = 384u << 20;  // anchors per query batch: ~80 B of buffers each (anchor x2 for the sort, chain scratch, fixed
                                              // points, pieces) = 30 GB of the 288; on C3 128 M costs 8 % more per step (per-batch fixed
                                              // costs: scans, fills, list selections), 512 M outgrows the buffer pool's cap

@@ -34,7 +34,7 @@ constexpr int NR_SHORT = 128;                   // rows of an align_narrow_kerne
                                                 // blocks (3-4 % of them) run in the <BLOCK_MAX> instance with twice the LDS
 constexpr int WIDE_SHORT = 128;                 // rows of an align_kernel<WIDE_SHORT> task (most extensions are short): half the
                                                 // plane LDS of the <EXT_MAX> instance, twice the resident waves
-inline dim3 grid1(size_t n) { return dim3(cdiv(n ? n : 1, WG)); }
+inline dim3 grid1(size_t n) { return grid_for(n, WG); }
 
 struct Task {               // 32 B, self-contained: the kernels reach the bases without touching Piece / offset tables
     uint32_t piece;

@@ -21,6 +21,7 @@
 
 #include "ava_internal.h"
 #include "dev_prims.h"
+#include "dev_search.h"
 #include "wave_ops.h"
 
 namespace hlmi {
@@ -39,16 +40,8 @@ constexpr bool INSTR = false;
 #endif
 constexpr int QL_BITS = 16, T_BITS_MAX = 21, TPOS_BITS_MAX = 29;     // target positions: 29 bits (contigs as targets, HyLight.py:149,180); chain scores are
                                                                       // bounded by the QUERY length (22 bits in the packed DP, else 26: 6 tie-break bits in 32)
-inline dim3 grid1(size_t n) { return dim3(cdiv(n ? n : 1, WG)); }
+inline dim3 grid1(size_t n) { return grid_for(n, WG); }
 
-__device__ __forceinline__ size_t lower_bound_u64(const uint64_t *a, size_t n, uint64_t v) {
-    size_t lo = 0, hi = n;
-    while (lo < hi) {
-        size_t m = (lo + hi) >> 1;
-        if (a[m] < v) lo = m + 1; else hi = m;
-    }
-    return lo;
-}
 __device__ __forceinline__ size_t upper_bound_u32(const uint32_t *a, size_t n, uint32_t v) {
     size_t lo = 0, hi = n;
     while (lo < hi) {

@@ -21,7 +21,7 @@ namespace hlmi {
 
 namespace {
 constexpr int WG = 256;
-inline dim3 grid1(size_t n) { return dim3(cdiv(n ? n : 1, WG)); }
+inline dim3 grid1(size_t n) { return grid_for(n, WG); }
 constexpr size_t SLAB = size_t(1) << 31;          // line-start selections per slab (32-bit indices)
 
 enum : uint32_t {

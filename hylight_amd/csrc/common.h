@@ -180,6 +180,8 @@ inline unsigned cdiv(size_t a, size_t b) {
     if (n * b >= (1ull << 32) && b > 1) fail(HLMI_EINVAL, "kernel grid of %zu x %zu work-items (2^32 and more wrap)", n, b);
     return (unsigned)n;
 }
+// the grid of a kernel with one work-item per item in workgroups of wg; no item: one workgroup that finds nothing to do
+inline dim3 grid_for(size_t n, int wg) { return dim3(cdiv(n ? n : 1, (size_t)wg)); }
 
 // ------------------------------------------------------------------------------------------
 // PAF row as the kernels see it (one 64-byte record; rows keep stream order by index)

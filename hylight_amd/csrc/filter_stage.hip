@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "dev_prims.h"
+#include "dev_search.h"
 #include "wave_ops.h"
 
 namespace hlmi {
@@ -187,7 +188,7 @@ __global__ void head_flags_kernel(const uint32_t *chunk, const uint64_t *key, ui
     if (i < n) head[i] = (i == 0 || chunk[i] != chunk[i - 1] || key[i] != key[i - 1]) ? 1 : 0;
 }
 
-inline dim3 grid1(size_t n) { return dim3(cdiv(n ? n : 1, WG)); }
+inline dim3 grid1(size_t n) { return grid_for(n, WG); }
 
 // order (chunk[i], key[i]) lexicographically: returns the permutation and the sorted copies
 struct SortedCK {
@@ -442,11 +443,6 @@ __global__ __launch_bounds__(WG) void snp_fill_kernel(const PafRec *recs, const 
 // further spanning reads) and writes the verdict over the key's event range; (2) one thread per EVENT of a
 // supported key bumps the counter of its row's pair group (recorded with the event).  (A key on a deeply covered read has
 // hundreds of events; a single thread walking them all was the long pole of the filter stage.)
-__device__ __forceinline__ size_t lower_bound_u64(const uint64_t *v, size_t n, uint64_t k) {
-    size_t lo = 0, hi = n;
-    while (lo < hi) { const size_t mid = (lo + hi) >> 1; if (v[mid] < k) lo = mid + 1; else hi = mid; }
-    return lo;
-}
 __global__ void snp_support_kernel(const uint64_t *ev_ck, const uint32_t *kseg_start, size_t n_kseg, size_t n_ev,
                                    const uint64_t *ivs_ck, const uint64_t *ive_ck, size_t n_iv, int lb, int mc,
                                    uint8_t *ev_supported) {

@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "dev_prims.h"
+#include "dev_search.h"
 #include "graph.h"
 #include "paf_io.h"
 #include "text_dev.h"
@@ -35,7 +36,7 @@ __global__ void line_start_kernel(const uint8_t *txt, size_t base, size_t n, uin
 
 namespace {
 constexpr int WG = 256;
-inline dim3 grid1(size_t n) { return dim3(cdiv(n ? n : 1, WG)); }
+inline dim3 grid1(size_t n) { return grid_for(n, WG); }
 
 // ---------------------------------------------------------------------------------------------
 // a9: text -> rows
@@ -214,14 +215,6 @@ __global__ void win_ends_kernel(const Ovl *ovl, size_t n, float min_iden, uint64
     const bool skip = h.t == h.q || (float)ml < (float)bl * min_iden || !(h.qe > h.qs);
     ends[2 * i] = skip ? NO_END : (uint64_t)h.q << 32 | (uint32_t)(h.qs << 1);
     ends[2 * i + 1] = skip ? NO_END : (uint64_t)h.q << 32 | (uint32_t)(h.qe << 1 | 1u);
-}
-__device__ __forceinline__ size_t lower_bound_u64(const uint64_t *a, size_t n, uint64_t v) {
-    size_t lo = 0, hi = n;
-    while (lo < hi) {
-        const size_t m = (lo + hi) >> 1;
-        if (a[m] < v) lo = m + 1; else hi = m;
-    }
-    return lo;
 }
 __device__ __forceinline__ int wave_incl_sum_i32(int v, int lane) {
 #pragma unroll

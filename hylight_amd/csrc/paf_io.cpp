@@ -341,41 +341,12 @@ void read_seqs_subset(const char *path, const std::function<bool(std::string_vie
 // final rows
 // ------------------------------------------------------------------------------------------
 // "%.4f" of v into dst (at least 64 bytes), the bytes printf writes.  A finite v in [0, 2^40) - every score of a row - is
-// converted exactly in integers: v = m x 2^e, so v x 10^4 = (m x 10^4) >> -e, rounded to nearest, ties to even (the
-// rounding glibc's printf applies to the exact binary value in the default rounding mode); three conversions per row were
-// most of the stage's text time with printf and still a third of it with std::to_chars.  Anything else goes through
-// std::to_chars / printf.
+// converted exactly in integers (dec_text.h: fixed4_q, the source the kernels of row_text.hip compile too); three conversions
+// per row were most of the stage's text time with printf and still a third of it with std::to_chars.  Anything else goes
+// through std::to_chars / printf.
 size_t format_fixed4(double v, char *dst) {
-    uint64_t bits;
-    memcpy(&bits, &v, 8);
-    const int be = (int)((bits >> 52) & 0x7ff);
-    if (!(bits >> 63) && be != 0x7ff && v < 1099511627776.0) {
-        uint64_t m = bits & ((1ull << 52) - 1);
-        int e = be - 1075;                                   // v = m x 2^e
-        if (be) m |= 1ull << 52; else e = -1074;
-        uint64_t q;
-        if (e >= 0) q = (m << e) * 10000ull;                 // (an integer below 2^40)
-        else {
-            const unsigned __int128 N = (unsigned __int128)m * 10000u;      // < 2^67
-            const int sh = -e;
-            if (sh > 68) q = 0;                              // below a half: rounds to zero
-            else {
-                q = (uint64_t)(N >> sh);
-                const unsigned __int128 rem = N & (((unsigned __int128)1 << sh) - 1), half = (unsigned __int128)1 << (sh - 1);
-                if (rem > half || (rem == half && (q & 1))) ++q;
-            }
-        }
-        const uint64_t ip = q / 10000u;
-        uint32_t fp = (uint32_t)(q % 10000u);
-        auto res = std::to_chars(dst, dst + 24, ip);
-        char *p = res.ptr;
-        *p++ = '.';
-        p[3] = (char)('0' + fp % 10); fp /= 10;
-        p[2] = (char)('0' + fp % 10); fp /= 10;
-        p[1] = (char)('0' + fp % 10); fp /= 10;
-        p[0] = (char)('0' + fp);
-        return (size_t)(p + 4 - dst);
-    }
+    uint64_t q;
+    if (fixed4_q(v, q)) return (size_t)(put_fixed4(dst, q) - dst);
     if (std::isfinite(v)) {
         auto res = std::to_chars(dst, dst + 48, v, std::chars_format::fixed, 4);
         if (res.ec == std::errc()) return (size_t)(res.ptr - dst);
@@ -385,19 +356,28 @@ size_t format_fixed4(double v, char *dst) {
 
 bool format_scored_row(const PafRec &r, const std::string &qname, const std::string &tname,
                        uint32_t x_digit_sum, double iden, std::string &out, uint32_t *sort_key) {
-    // filter_overlap_slr2.py:113,138-146 - plain IEEE doubles in the reference's evaluation order
-    double mc = (double)r.nmatch, ln = (double)r.blen;
-    double mlen = (double)((uint64_t)r.qlen + r.tlen) / 2.0;
-    double t1 = mc / mlen, t2 = mc / ln;
-    double a = 0.4 * t1, b = 0.6 * t2;
-    double score = a + b;
-    double mis = (double)x_digit_sum / mc;
-    double score2 = 1.0 - mis;
-    // "%.4f" (format_fixed4).  float("0.9876") is the correctly rounded 9876 / 10^4, which is what the division below gives.
-    auto f4 = [](double v, char *dst) -> size_t { return format_fixed4(v, dst); };
+    // filter_overlap_slr2.py:113,138-146: the scores as the integers their "%.4f" shows (row_score.h, the source the kernels
+    // of row_text.hip compile too); the identity test and the sort key come with them
+    RowScore rs;
+    const int st = row_score(r.nmatch, r.blen, r.qlen, r.tlen, x_digit_sum, iden, rs);
+    if (st == SCORE_DROPPED) return false;
     char s1[64], s2[64], s3[64];
-    const size_t n1 = f4(score, s1), n2 = f4(score2, s2), n3 = f4(t2, s3);
-    {
+    size_t n1, n2, n3;
+    uint32_t key;
+    if (st == SCORE_KEPT) {
+        n1 = (size_t)(put_fixed4(s1, rs.q1) - s1); n2 = (size_t)(put_fixed4(s2, rs.q2) - s2); n3 = (size_t)(put_fixed4(s3, rs.q3) - s3);
+        key = rs.key;
+    } else {
+        // a score that is negative or not finite (no matches, no length, more X digits than matches): plain IEEE doubles in the
+        // reference's evaluation order, printed, and the test and the key read back from the text as float() and `sort -n` do
+        double mc = (double)r.nmatch, ln = (double)r.blen;
+        double mlen = (double)((uint64_t)r.qlen + r.tlen) / 2.0;
+        double t1 = mc / mlen, t2 = mc / ln;
+        double a = 0.4 * t1, b = 0.6 * t2;
+        double score = a + b;
+        double mis = (double)x_digit_sum / mc;
+        double score2 = 1.0 - mis;
+        n1 = format_fixed4(score, s1); n2 = format_fixed4(score2, s2); n3 = format_fixed4(t2, s3);
         double shown;
         const char *p = s2;
         const bool neg = *p == '-';
@@ -413,6 +393,16 @@ bool format_scored_row(const PafRec &r, const std::string &qname, const std::str
         if (plain && digits < (1ull << 53)) { shown = (double)digits / 10000.0; if (neg) shown = -shown; }
         else { s2[n2] = 0; shown = strtod(s2, nullptr); }
         if (shown < iden) return false;
+        uint64_t v = 0;                          // column 12 as sort_scored_lines reads it: value x 10^4 when it is plain digits
+        size_t frac = 0;
+        bool dot = false;
+        plain = n1 > 0;
+        for (size_t i = 0; plain && i < n1; ++i) {
+            if (s1[i] == '.' && !dot) dot = true;
+            else if (s1[i] >= '0' && s1[i] <= '9' && v < (1ull << 40)) { v = v * 10 + (uint64_t)(s1[i] - '0'); frac += dot ? 1 : 0; }
+            else plain = false;
+        }
+        key = plain && dot && frac == 4 && v < SCORE_KEY_LIMIT ? (uint32_t)v : 0xffffffffu;
     }
     auto put_u32 = [&](uint32_t v) {
         char b[16];
@@ -434,17 +424,7 @@ bool format_scored_row(const PafRec &r, const std::string &qname, const std::str
     out.push_back('\t'); out.append(s2, n2);
     out.push_back('\t'); out.append(s3, n3);
     out.push_back('\t');
-    if (sort_key) {                              // column 12 as sort_scored_lines reads it: value x 10^4 when it is plain digits
-        uint64_t v = 0;
-        size_t frac = 0;
-        bool plain = n1 > 0, dot = false;
-        for (size_t i = 0; plain && i < n1; ++i) {
-            if (s1[i] == '.' && !dot) dot = true;
-            else if (s1[i] >= '0' && s1[i] <= '9' && v < (1ull << 40)) { v = v * 10 + (uint64_t)(s1[i] - '0'); frac += dot ? 1 : 0; }
-            else plain = false;
-        }
-        *sort_key = plain && dot && frac == 4 && v < SCORE_KEY_LIMIT ? (uint32_t)v : 0xffffffffu;
-    }
+    if (sort_key) *sort_key = key;
     return true;
 }
 

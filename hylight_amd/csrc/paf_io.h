@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.h"
+#include "row_score.h"
 
 namespace hlmi {
 
@@ -53,8 +54,8 @@ void read_seqs_subset(const char *path, const std::function<bool(std::string_vie
 // false when the row is dropped by the identity test `float(score2) < iden` (slr2:146).
 // "%.4f" of v, the bytes printf writes, into dst (>= 64 bytes); returns the length (tests/capi/fixed4_check.cpp)
 size_t format_fixed4(double v, char *dst);
-// sort_key (optional): column 12 as an integer (value x 10^4) for sort_scored_lines, 0xffffffff when it is not plain digits.
-constexpr uint32_t SCORE_KEY_LIMIT = 1u << 22;                // 419.4304
+// sort_key (optional): column 12 as an integer (value x 10^4) for sort_scored_lines, 0xffffffff when it is not plain digits
+// below SCORE_KEY_LIMIT (row_score.h).
 bool format_scored_row(const PafRec &r, const std::string &qname, const std::string &tname,
                        uint32_t x_digit_sum, double iden, std::string &out, uint32_t *sort_key = nullptr);
 

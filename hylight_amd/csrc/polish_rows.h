@@ -6,11 +6,7 @@
 #pragma once
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define HLMI_HD __host__ __device__
-#else
-#define HLMI_HD
-#endif
+#include "hd.h"
 
 namespace hlmi {
 namespace pol {
@@ -35,13 +31,13 @@ struct RowWalk {
     uint32_t ins_long;      // finished I ops inside (ts, te) of more than ROW_INS_CAP bases
 };
 
-HLMI_HD inline void row_walk_begin(RowWalk &w, uint32_t ts, uint32_t te) {
+HLMI_HD void row_walk_begin(RowWalk &w, uint32_t ts, uint32_t te) {
     w.ts = ts; w.te = te; w.p = ts;
     w.pend = 0; w.n_out = 0; w.ins_edge = 0; w.ins_long = 0;
 }
 
 // the waiting op leaves: true when there was one (then *out holds it and it is op number n_out - 1)
-HLMI_HD inline bool row_walk_flush(RowWalk &w, RowOp *out) {
+HLMI_HD bool row_walk_flush(RowWalk &w, RowOp *out) {
     if (!w.pend) return false;
     out->word = w.pend;
     out->slot = ROW_NO_SLOT;
@@ -55,7 +51,7 @@ HLMI_HD inline bool row_walk_flush(RowWalk &w, RowOp *out) {
 }
 
 // the next op of the row's CIGAR; true when an op was finished by it (*out, op number n_out - 1)
-HLMI_HD inline bool row_walk_op(RowWalk &w, uint32_t word, RowOp *out) {
+HLMI_HD bool row_walk_op(RowWalk &w, uint32_t word, RowOp *out) {
     const uint32_t len = word >> 4;
     if (!len) return false;
     if ((word & 15u) == ROW_OP_I) {
@@ -75,7 +71,7 @@ HLMI_HD inline bool row_walk_op(RowWalk &w, uint32_t word, RowOp *out) {
 }
 
 // behind the last op
-HLMI_HD inline bool row_walk_end(RowWalk &w, RowOp *out) { return row_walk_flush(w, out); }
+HLMI_HD bool row_walk_end(RowWalk &w, RowOp *out) { return row_walk_flush(w, out); }
 
 }  // namespace pol
 }  // namespace hlmi

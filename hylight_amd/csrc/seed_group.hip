@@ -55,7 +55,7 @@ struct NzRec { uint32_t off, lo, zq, cnt; };       // a query minimizer with par
 static_assert(sizeof(NzRec) == 16, "NzRec is read as one 16-byte word");
 static_assert(SG_MAXD + SG_WG < SG_PAIRS, "the partner table keeps a free slot while insertions are in flight");
 
-inline dim3 grid1(size_t n) { return dim3(cdiv(n ? n : 1, WG)); }
+inline dim3 grid1(size_t n) { return grid_for(n, WG); }
 
 // ---- once per index: 32-bit entries ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(WG) void y32_kernel(const uint64_t *y, const uint32_t *dense_of_t, size_t n, int sh, uint32_t *y32) {

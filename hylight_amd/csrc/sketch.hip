@@ -18,7 +18,7 @@ namespace hlmi {
 
 namespace {
 constexpr int WG = 256;
-inline dim3 grid1(size_t n) { return dim3(cdiv(n ? n : 1, WG)); }
+inline dim3 grid1(size_t n) { return grid_for(n, WG); }
 
 __global__ void encode_kernel(uint8_t *b, size_t n) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;

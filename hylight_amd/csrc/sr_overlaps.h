@@ -1,15 +1,10 @@
 // sr_overlaps.h - one kept PAF row as a SAVAGE overlap record: the arithmetic of minimap22sfo.py (capi.cpp:200-216) and of
 // sfo2overlaps.py --num_pairs 0 (sfo.cpp:43-95) on integers, shared by the kernels of sr_overlaps.hip and by the host check
-// tests/capi/sr_record_host_check.cpp (which compiles this file with a host compiler only).
+// tests/capi/dec_text_host_check.cpp (which compiles this file with a host compiler only).
 #pragma once
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define HLMI_HD __host__ __device__ __forceinline__
-#else
-#define HLMI_HD inline
-#endif
+#include "dec_text.h"
 
 namespace hlmi {
 
@@ -51,13 +46,8 @@ HLMI_HD SrRec sr_record(const SrRowIn &r) {
 
 // ---- the byte order of two decimal texts that are followed by the same byte below '-' and the digits (TAB, or the end of
 // the line): '-' sorts below the digits, and of two digit strings where one is a prefix of the other the shorter is smaller
-HLMI_HD int sr_dec_len(uint64_t v) {
-    int n = 1;
-    while (v >= 10) { v /= 10; ++n; }
-    return n;
-}
 HLMI_HD int sr_cmp_digits(uint64_t a, uint64_t b) {        // a, b < 10^18
-    const int la = sr_dec_len(a), lb = sr_dec_len(b);
+    const int la = dec_len(a), lb = dec_len(b);
     uint64_t x = a, y = b;
     for (int i = la; i < lb; ++i) x *= 10;                  // left-aligned: the shorter one padded with zeros
     for (int i = lb; i < la; ++i) y *= 10;

@@ -24,7 +24,7 @@ namespace hlmi {
 
 namespace {
 constexpr int WG = 256;
-inline dim3 grid1(size_t n) { return dim3(cdiv(n ? n : 1, WG)); }
+inline dim3 grid1(size_t n) { return grid_for(n, WG); }
 
 struct SrTables {
     const uint32_t *num_of_rank;      // name rank (the overlapper's qid / tid) -> rank of the name's NUMBER
@@ -69,15 +69,6 @@ __global__ __launch_bounds__(WG) void sr_tie_kernel(const SrRec *__restrict__ re
     order[s + before] = me;
 }
 
-__device__ __forceinline__ int signed_len(int64_t v) { return v < 0 ? 1 + sr_dec_len((uint64_t)-v) : sr_dec_len((uint64_t)v); }
-__device__ __forceinline__ char *put_signed(char *p, int64_t v) {
-    uint64_t u = (uint64_t)v;
-    if (v < 0) { *p++ = '-'; u = (uint64_t)-v; }
-    const int n = sr_dec_len(u);
-    for (int i = n - 1; i >= 0; --i) { p[i] = (char)('0' + (int)(u % 10)); u /= 10; }
-    return p + n;
-}
-
 // len[p]: bytes of the line at place p with its newline, 0 when it repeats the line before it.  *bad: a row whose shorter
 // read would have no bases (sfo.cpp:88 refuses the file).
 __global__ __launch_bounds__(WG) void sr_len_kernel(const SrRec *__restrict__ recs, const uint32_t *__restrict__ order, size_t n,
@@ -88,8 +79,8 @@ __global__ __launch_bounds__(WG) void sr_len_kernel(const SrRec *__restrict__ re
     if (l.minlen <= 0) { atomicOr(bad, 1u); len[p] = 0; return; }
     if (p > 0 && sr_line_equal(l, sr_line(recs[order[p - 1]]))) { len[p] = 0; return; }
     // id1 id2 pos1 - - ori1 ori2 perc - ovlen - s s
-    len[p] = (uint32_t)(signed_len(t.val_of_num[l.n1]) + signed_len(t.val_of_num[l.n2]) + signed_len(l.pos1) + signed_len(l.perc) +
-                        signed_len(l.ovlen)) + 8u /* - - o o - - s s */ + 12u /* TABs */ + 1u;
+    len[p] = (uint32_t)(dec_len_signed(t.val_of_num[l.n1]) + dec_len_signed(t.val_of_num[l.n2]) + dec_len_signed(l.pos1) +
+                        dec_len_signed(l.perc) + dec_len_signed(l.ovlen)) + 8u /* - - o o - - s s */ + 12u /* TABs */ + 1u;
 }
 
 __global__ __launch_bounds__(WG) void sr_write_kernel(const SrRec *__restrict__ recs, const uint32_t *__restrict__ order, size_t n,
@@ -99,14 +90,14 @@ __global__ __launch_bounds__(WG) void sr_write_kernel(const SrRec *__restrict__ 
     if (p >= n || !len[p]) return;
     const SrLine l = sr_line(recs[order[p]]);
     char *q = text + off[p];
-    q = put_signed(q, t.val_of_num[l.n1]); *q++ = '\t';
-    q = put_signed(q, t.val_of_num[l.n2]); *q++ = '\t';
-    q = put_signed(q, l.pos1); *q++ = '\t';
+    q = put_dec_signed(q, t.val_of_num[l.n1]); *q++ = '\t';
+    q = put_dec_signed(q, t.val_of_num[l.n2]); *q++ = '\t';
+    q = put_dec_signed(q, l.pos1); *q++ = '\t';
     *q++ = '-'; *q++ = '\t'; *q++ = '-'; *q++ = '\t';
     *q++ = l.ori1; *q++ = '\t'; *q++ = l.ori2; *q++ = '\t';
-    q = put_signed(q, l.perc); *q++ = '\t';
+    q = put_dec_signed(q, l.perc); *q++ = '\t';
     *q++ = '-'; *q++ = '\t';
-    q = put_signed(q, l.ovlen); *q++ = '\t';
+    q = put_dec_signed(q, l.ovlen); *q++ = '\t';
     *q++ = '-'; *q++ = '\t'; *q++ = 's'; *q++ = '\t'; *q++ = 's'; *q++ = '\n';
 }
 

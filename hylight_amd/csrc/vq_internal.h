@@ -53,7 +53,8 @@ constexpr int WG = 256;
 constexpr int WAVES = WG / 64;
 constexpr uint32_t SET_CAP = 2048;                 // LDS hash slots per wave: vertices with up to SET_CAP / 2 out-edges
 constexpr uint32_t EMPTY = 0xffffffffu;
-inline dim3 grid1(size_t n) { return dim3((unsigned)cdiv(n ? n : 1, (size_t)WG)); }
+constexpr int SEARCH_STEPS = 33;                 // a binary search over fewer than 2^32 entries ends within this many steps
+inline dim3 grid1(size_t n) { return grid_for(n, WG); }
 // blocks of a one-wave-per-item kernel that strides over its items
 inline unsigned waves_grid(size_t n_items) { return (unsigned)std::max<size_t>(1, std::min<size_t>(cdiv(n_items, (size_t)WAVES), 256 * 16)); }
 
@@ -351,7 +352,7 @@ constexpr int WG = 256;
 constexpr int WAVE = 64;
 constexpr uint32_t MAX_DIFF = 100;               // findDiffPos keeps the first 100 positions of a pair (:703)
 constexpr uint32_t NONE = 0xffffffffu;
-constexpr int SEARCH_STEPS = 33;                 // a binary search over fewer than 2^32 entries ends within this many steps
+using vqk::SEARCH_STEPS;
 struct Pair {                                    // one compared neighbour pair: sequence a from `rel` on against b from 0
     uint32_t a, b;                               // vertices
     uint32_t rel, len;                           // len >= 1 common bases
@@ -423,7 +424,7 @@ namespace vqn {
 constexpr int WG = 256;
 constexpr uint32_t NONE = 0xffffffffu;
 constexpr uint32_t LINE_WIDTH = 64;              // lines up to this many bytes are ordered on the device (8 words of 8 bytes)
-constexpr int SEARCH_STEPS = 33;                 // a binary search over fewer than 2^32 entries ends within this many steps
+using vqk::SEARCH_STEPS;
 }  // namespace vqn
 // What SRBuilder leaves per vertex for updateOverlap: nodes_to_SR as a CSR over the vertices, one (new id, findCliqueIndex)
 // per entry in ascending id, and the new reads' lengths.  An unvisited vertex that was copied is a list of one entry, its new

@@ -10,18 +10,13 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "dec_text.h"
 #include "dev_prims.h"
 #include "vq_internal.h"
 
 namespace hlmi {
 namespace vqm {
 namespace {
-
-__device__ __forceinline__ uint32_t dec_width(uint32_t v) {
-    uint32_t w = 1;
-    for (int k = 0; k < 9 && v >= 10; ++k) { v /= 10; ++w; }
-    return w;
-}
 
 __global__ __launch_bounds__(WG) void read_n_kernel(const uint8_t *bases, const uint64_t *off, uint32_t n_reads, uint32_t *n_count) {
     const uint32_t r = blockIdx.x * (WG / WAVE) + threadIdx.x / WAVE;
@@ -40,7 +35,7 @@ __global__ void rec_size_kernel(const Rec *rec, uint32_t n_rec, uint32_t *len, u
     if (r > n_rec) return;
     if (r == n_rec) { len[r] = 0; bytes[r] = 0; return; }
     len[r] = rec[r].len;
-    bytes[r] = 2u + dec_width(rec[r].id) + 2u * rec[r].len + 4u;
+    bytes[r] = 2u + (uint32_t)dec_len(rec[r].id) + 2u * rec[r].len + 4u;
 }
 
 // the record that holds position c: the largest r in [lo, hi] with pos0[r] <= c
@@ -111,15 +106,14 @@ __global__ __launch_bounds__(WG) void merge_kernel(const Rec *rec, const uint64_
                 }
             }
             if (WRITE) {
-                const uint32_t w = dec_width(R.id);
+                const uint32_t w = (uint32_t)dec_len(R.id);
                 uint8_t *o = out + byte0[r];
                 const uint64_t seq0 = 2u + w;
                 o[seq0 + x] = ob;
                 o[seq0 + R.len + 3u + x] = oq;
                 if (x == 0) {                                              // the record's own bytes: "@<id>\n", "\n+\n", "\n"
                     o[0] = '@';
-                    uint32_t v = R.id;
-                    for (uint32_t d = 0; d < w && d < 10; ++d) { o[w - d] = (uint8_t)('0' + v % 10); v /= 10; }
+                    put_dec((char *)o + 1, R.id);                          // (w bytes: the thread of x == 0 writes the whole id)
                     o[1 + w] = '\n';
                     o[seq0 + R.len] = '\n';
                     o[seq0 + R.len + 1] = '+';

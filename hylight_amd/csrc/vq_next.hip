@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "dec_text.h"
 #include "dev_prims.h"
 #include "vq_internal.h"
 
@@ -225,15 +226,9 @@ __global__ void owner_kernel(const uint64_t *key, const uint32_t *seq, const uin
     if (key[h] != NO_KEY) owner[seq[h]] = 1;
 }
 
-__device__ inline uint32_t digits_u(uint32_t v) {
-    uint32_t w = 1;
-    for (int k = 0; k < 9 && v >= 10; ++k) { v /= 10; ++w; }
-    return w;
-}
-__device__ inline uint32_t digits_i(int32_t v) { return v < 0 ? 1 + digits_u(0u - (uint32_t)v) : digits_u((uint32_t)v); }
 __device__ inline uint32_t line_len(const Line &l) {
-    return digits_u(l.a) + digits_u(l.b) + digits_i(l.pos1) + digits_i(l.pos2) + digits_i(l.perc) + digits_i(l.len1) +
-           digits_i(l.len2) + 6 + 12;                        // ord, ori1, ori2, "0", "s", "s"; 12 tabs
+    return dec_len(l.a) + dec_len(l.b) + dec_len_signed(l.pos1) + dec_len_signed(l.pos2) + dec_len_signed(l.perc) +
+           dec_len_signed(l.len1) + dec_len_signed(l.len2) + 6 + 12;      // ord, ori1, ori2, "0", "s", "s"; 12 tabs
 }
 
 // one thread per candidate: the copied edges and the owners of a key produce their line's numbers (computeOverlapData)
@@ -300,33 +295,23 @@ __global__ void eval_kernel(const VqSrcEdge *rec, const Cand *cand, const uint8_
     }
 }
 
-__device__ inline uint8_t *put_u(uint8_t *o, uint32_t v) {
-    const uint32_t w = digits_u(v);
-    for (uint32_t d = 0; d < w && d < 10; ++d) { o[w - 1 - d] = (uint8_t)('0' + v % 10); v /= 10; }
-    return o + w;
-}
-__device__ inline uint8_t *put_i(uint8_t *o, int32_t v) {
-    if (v < 0) { *o++ = '-'; return put_u(o, 0u - (uint32_t)v); }
-    return put_u(o, (uint32_t)v);
-}
-
 // one thread per line: its text at text[start[i] .. start[i] + llen[i]) (no line end: the order reads the bare string)
 __global__ void text_kernel(const Line *line, const uint32_t *llen, const uint64_t *start, uint32_t n, uint8_t *text) {
     const uint32_t i = blockIdx.x * WG + threadIdx.x;
     if (i >= n || !llen[i]) return;
     const Line l = line[i];
-    uint8_t *o = text + start[i];
-    o = put_u(o, l.a); *o++ = '\t';
-    o = put_u(o, l.b); *o++ = '\t';
-    o = put_i(o, l.pos1); *o++ = '\t';
-    o = put_i(o, l.pos2); *o++ = '\t';
-    *o++ = (uint8_t)l.ord; *o++ = '\t';
-    *o++ = (uint8_t)l.o1; *o++ = '\t';
-    *o++ = (uint8_t)l.o2; *o++ = '\t';
-    o = put_i(o, l.perc); *o++ = '\t';
+    char *o = (char *)text + start[i];
+    o = put_dec(o, l.a); *o++ = '\t';
+    o = put_dec(o, l.b); *o++ = '\t';
+    o = put_dec_signed(o, l.pos1); *o++ = '\t';
+    o = put_dec_signed(o, l.pos2); *o++ = '\t';
+    *o++ = l.ord; *o++ = '\t';
+    *o++ = l.o1; *o++ = '\t';
+    *o++ = l.o2; *o++ = '\t';
+    o = put_dec_signed(o, l.perc); *o++ = '\t';
     *o++ = '0'; *o++ = '\t';
-    o = put_i(o, l.len1); *o++ = '\t';
-    o = put_i(o, l.len2); *o++ = '\t';
+    o = put_dec_signed(o, l.len1); *o++ = '\t';
+    o = put_dec_signed(o, l.len2); *o++ = '\t';
     *o++ = 's'; *o++ = '\t'; *o++ = 's';
 }
 

@@ -57,3 +57,29 @@ def test_short_mode_rows_from_the_device_formatter(tmp_path, monkeypatch):
     h, _ = _stage(tmp_path, sfa, con, "host.paf", monkeypatch, "HLMI_TEXT_HOST", **kw)
     assert g == h and g.count(b"\n") > 3000
     assert sg["rows_text_on_gpu"] >= g.count(b"\n")
+
+
+WIDTH_SEED = 101      # chosen on the commit before the formatters were shared: its rows hold all the widths asserted below
+
+def _two_length_classes(seed):
+    """About 60 reads of two populations: lengths 900-1100 (three and four digits) and 9000-11000 (four and five digits)."""
+    small, _ = S.simulate_reads(seed=seed, n_reads=30, n_strains=2, genome_len=4000, mean_len=1000, min_len=900, max_len=1100,
+                                name_prefix="a")
+    large, _ = S.simulate_reads(seed=seed + 1, n_reads=30, n_strains=2, genome_len=40000, mean_len=10000, min_len=9000,
+                                max_len=11000, name_prefix="b")
+    return small + large
+
+
+def test_rows_at_the_decimal_width_edges(tmp_path, monkeypatch):
+    """Reads of 900-1100 and of 9000-11000 bases in one FASTA: the rows' integer columns take one to five digits, so every
+    width the decimal formatter of the kernels steps through up to there is written and compared with the host's bytes."""
+    fa = tmp_path / "two.fa"
+    S.write_fasta(_two_length_classes(WIDTH_SEED), fa)
+    kw = dict(len_over=500, mc=2, iden=0.95, long=True)
+    g, sg = _stage(tmp_path, fa, fa, "gpu.paf", monkeypatch, "HLMI_TEXT_GPU", **kw)
+    h, _ = _stage(tmp_path, fa, fa, "host.paf", monkeypatch, "HLMI_TEXT_HOST", **kw)
+    assert g == h
+    assert sg["rows_text_on_gpu"] > 0 and sg["rows_text_left_to_host"] == 0
+    rows = [line.split(b"\t") for line in g.split(b"\n")[:-1]]
+    assert {len(r[1]) for r in rows} >= {3, 4, 5}                      # column 2: the query's length
+    assert 1 in {len(r[c]) for r in rows for c in (2, 7)}              # columns 3 and 8: where the overlap starts

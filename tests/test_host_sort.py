@@ -5,6 +5,7 @@ lines by column 12 (numeric, descending; ties by reversed whole-line byte order,
 and writes them back.  The stage uses the same sort on views into its text buffers."""
 import os
 import random
+import shutil
 import subprocess
 
 import pytest
@@ -84,3 +85,19 @@ def test_fixed4_formatter_writes_what_printf_writes(tmp_path):
                     "-L", libdir, "-lhylight_mi", f"-Wl,-rpath,{libdir}", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "mismatches 0" in r.stdout, r.stdout + r.stderr
+
+
+def test_shared_text_formatters_host_program(tmp_path):
+    """The number and row text the kernels write comes from headers a host compiler reads too (csrc/dec_text.h, row_score.h,
+    sr_overlaps.h): tests/capi/dec_text_host_check.cpp compares every function in them with printf, strtod and the host
+    converters restated over text.  Built like the library, without contraction: the scores are doubles in a fixed order."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler on PATH")
+    exe = tmp_path / "dec_text_host_check"
+    subprocess.run([cxx, "-std=c++17", "-O1", "-ffp-contract=off", os.path.join(root, "tests", "capi", "dec_text_host_check.cpp"),
+                    "-o", str(exe)], check=True, cwd=root)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "dec_text_host_check: ok" in r.stdout
