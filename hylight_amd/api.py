@@ -136,6 +136,17 @@ class PolishStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in POLISH_STATS] + [(k, C.c_double) for k in POLISH_MS]
 
 
+class PolishQOpts(C.Structure):
+    _fields_ = PolishOpts._fields_ + [("qual_weight", C.c_int), ("min_avg_qual", C.c_double)]
+
+
+POLISH_QSTATS = ("reads_with_qual", "rows_low_qual")
+
+
+class PolishQStats(C.Structure):
+    _fields_ = [("base", PolishStats)] + [(k, C.c_uint64) for k in POLISH_QSTATS]
+
+
 ABI_VERSION = 7          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
@@ -218,6 +229,11 @@ SYMBOLS = {
     "hlmi_polish": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PolishOpts), C.c_char_p, C.POINTER(PolishStats)]),
     "hlmi_polish_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PolishOpts), C.c_char_p,
                                     C.POINTER(PolishStats)]),
+    # the same two calls with base qualities: weighted votes and the read-quality floor
+    "hlmi_polish_qopts_default": (None, [C.POINTER(PolishQOpts)]),
+    "hlmi_polish_q": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PolishQOpts), C.c_char_p, C.POINTER(PolishQStats)]),
+    "hlmi_polish_reads_q": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PolishQOpts), C.c_char_p,
+                                      C.POINTER(PolishQStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -631,7 +647,14 @@ def polish(contigs, reads, paf, out_fa, **opts):
     """hlmi_polish: the pile-up consensus of `contigs` (FASTA / FASTQ) under the rows of `paf` (cg:Z: CIGARs in = X I D, as
     api.ava writes them) of `reads`, written to out_fa - the native stand-in for `racon --no-trimming -u` (a function of
     this project's own: include/hylight_mi.h states it, tests/polish_model.py is its contract).  Options: the fields of
-    hlmi_polish_opts (min_len 0, min_iden 0.0, min_cov 3, include_unpolished 1).  -> dict of the stats (hlmi_polish_stats)."""
+    hlmi_polish_opts (min_len 0, min_iden 0.0, min_cov 3, include_unpolished 1).  -> dict of the stats (hlmi_polish_stats).
+    With qual_weight= or min_avg_qual= the call is hlmi_polish_q (votes weighted by the reads' base qualities, rows of reads
+    whose mean Phred is below min_avg_qual dropped; the one not given is off: 0 / 0.0; tests/polish_qual_model.py is the
+    contract) and the dict also holds reads_with_qual and rows_low_qual."""
+    if _wants_qual(opts):
+        o, st = _polish_qopts("polish", opts), PolishQStats()
+        _check(load().hlmi_polish_q(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(out_fa), C.byref(st)))
+        return _polish_qstats(st)
     o = _polish_opts("polish", opts)
     st = PolishStats()
     _check(load().hlmi_polish(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(out_fa), C.byref(st)))
@@ -648,11 +671,39 @@ def _polish_opts(who, opts):
     return o
 
 
+def _wants_qual(opts):
+    return "qual_weight" in opts or "min_avg_qual" in opts
+
+
+def _polish_qopts(who, opts):
+    """hlmi_polish_qopts: the base fields at hlmi_polish's defaults, the two quality options off unless given"""
+    o = PolishQOpts()
+    load().hlmi_polish_qopts_default(C.byref(o))
+    o.qual_weight, o.min_avg_qual = 0, 0.0
+    for k, v in opts.items():
+        if k not in dict(PolishQOpts._fields_):
+            raise TypeError(f"{who}: unknown option {k!r}")
+        setattr(o, k, int(v) if isinstance(v, bool) else v)
+    return o
+
+
+def _polish_qstats(st):
+    d = {k: getattr(st.base, k) for k in POLISH_STATS + POLISH_MS}
+    d.update({k: getattr(st, k) for k in POLISH_QSTATS})
+    return d
+
+
 def polish_reads(contigs, reads, out_fa, ava_opts=None, **polish_opts):
     """hlmi_polish_reads: `ava(contigs, reads, P, ava_opts)` and `polish(contigs, reads, P, out_fa, **polish_opts)` in one
     call without the PAF P - the same file and the same integer stats, the overlapper's rows never leaving the device.
     ava_opts None: the long constants.  Refused (HlmiError, code -1) besides what polish refuses: a name twice among the reads
-    or among the contigs, ava_opts.stub_oh >= 0.  -> dict of the stats (hlmi_polish_stats)."""
+    or among the contigs, ava_opts.stub_oh >= 0.  -> dict of the stats (hlmi_polish_stats).  qual_weight= / min_avg_qual=: as
+    for polish (hlmi_polish_reads_q)."""
+    if _wants_qual(polish_opts):
+        o, st = _polish_qopts("polish_reads", polish_opts), PolishQStats()
+        _check(load().hlmi_polish_reads_q(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
+                                          _b(out_fa), C.byref(st)))
+        return _polish_qstats(st)
     o = _polish_opts("polish_reads", polish_opts)
     st = PolishStats()
     _check(load().hlmi_polish_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),

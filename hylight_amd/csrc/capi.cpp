@@ -7,6 +7,7 @@
 #include "filter_stage.h"
 #include "graph.h"
 #include "paf_io.h"
+#include "polish_internal.h"
 #include "stage.h"
 #include "textpass.h"
 #include "vq_internal.h"
@@ -14,10 +15,6 @@
 namespace hlmi {
 void init_device(int device, int threads);
 void cluster_run(const char *paf, const char *fastq, const hlmi_cluster_opts &o, const char *out_dir, hlmi_cluster_stats *st);
-void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
-                hlmi_polish_stats *st);
-void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
-                      const char *out_fa, hlmi_polish_stats *st);
 void sr_overlaps_run(const char *reads, int min_ovlp_len, double min_identity, int o, double r, const char *out_overlaps,
                      uint64_t *n_lines);
 void shutdown_device();
@@ -519,6 +516,44 @@ int hlmi_polish_reads(const char *contigs, const char *reads, const hlmi_ava_opt
         if (!contigs || !reads || !po || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish_reads: NULL argument");
         require_device();
         polish_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), *po, out_fa, st);
+    });
+}
+
+void hlmi_polish_qopts_default(hlmi_polish_qopts *o) {
+    if (o) *o = hlmi_polish_qopts{0, 0.0, 3, 1, 1, 10.0};
+}
+
+namespace {
+hlmi_polish_opts polish_base_opts(const hlmi_polish_qopts &q) { return hlmi_polish_opts{q.min_len, q.min_iden, q.min_cov, q.include_unpolished}; }
+}  // namespace
+
+int hlmi_polish_q(const char *contigs, const char *reads, const char *paf, const hlmi_polish_qopts *o, const char *out_fa,
+                  hlmi_polish_qstats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish_q: NULL argument");
+        require_device();
+        *st = hlmi_polish_qstats{};
+        pol::PolQualCall qc;
+        qc.qual_weight = o->qual_weight != 0;
+        qc.min_avg_qual = o->min_avg_qual;
+        polish_run(contigs, reads, paf, polish_base_opts(*o), out_fa, &st->base, &qc);
+        st->reads_with_qual = qc.reads_with_qual;
+        st->rows_low_qual = qc.rows_low_qual;
+    });
+}
+
+int hlmi_polish_reads_q(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_qopts *po,
+                        const char *out_fa, hlmi_polish_qstats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !po || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish_reads_q: NULL argument");
+        require_device();
+        *st = hlmi_polish_qstats{};
+        pol::PolQualCall qc;
+        qc.qual_weight = po->qual_weight != 0;
+        qc.min_avg_qual = po->min_avg_qual;
+        polish_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), polish_base_opts(*po), out_fa, &st->base, &qc);
+        st->reads_with_qual = qc.reads_with_qual;
+        st->rows_low_qual = qc.rows_low_qual;
     });
 }
 

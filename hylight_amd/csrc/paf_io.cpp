@@ -284,20 +284,7 @@ void read_seqs(const char *path, SeqSet &out) { read_seqs_subset(path, nullptr, 
 void read_seqs_subset(const char *path, const std::function<bool(std::string_view)> *want, SeqSet &out) {
     const FileView file(path);
     const std::string_view d(file.p, file.n);
-    size_t N = d.size(), pos = 0;
-    uint32_t line_no = 0;
-    out.off.push_back(0);
-    auto next_line = [&](std::string_view &L) -> bool {
-        if (pos >= N) return false;
-        size_t e = d.find('\n', pos);
-        if (e == std::string::npos) e = N;
-        size_t end = e;
-        if (end > pos && d[end - 1] == '\r') --end;
-        L = d.substr(pos, end - pos);
-        pos = e + 1;
-        ++line_no;
-        return true;
-    };
+    const size_t N = d.size();
     out.n_lines = want ? 0 : (uint64_t)std::count(d.begin(), d.end(), '\n');     // (only the stage's chunking asks for it)
     if (!want) {                                     // one allocation instead of a gigabyte grown by doubling
         out.bases.reserve(N);
@@ -305,36 +292,16 @@ void read_seqs_subset(const char *path, const std::function<bool(std::string_vie
         out.off.reserve(out.n_lines / 2 + 2);
         out.first_line.reserve(out.n_lines / 2 + 1);
     }
-    std::string_view L;
-    bool have = next_line(L);
-    while (have) {
-        if (L.empty() || (L[0] != '>' && L[0] != '@')) {  // kseq skips to the next header
-            have = next_line(L);
-            continue;
-        }
-        bool fq = L[0] == '@';
-        size_t ws = L.find_first_of(" \t", 1);
-        const std::string_view name = L.substr(1, (ws == std::string_view::npos ? L.size() : ws) - 1);
-        const bool keep = !want || (*want)(name);             // a record that is not wanted keeps its name, with no bases
-        out.names.emplace_back(name);
-        out.first_line.push_back(line_no - 1);
-        size_t slen = 0;
-        have = next_line(L);
-        while (have && !(L.size() && (L[0] == '>' || L[0] == '@' || L[0] == '+'))) {
-            if (keep) out.bases.append(L);
-            slen += L.size();
-            have = next_line(L);
-        }
-        if (fq && have && L.size() && L[0] == '+') {
-            size_t q = 0;
-            have = next_line(L);
-            while (have && q < slen) {
-                q += L.size();
-                have = next_line(L);
-            }
-        }
-        out.off.push_back(out.bases.size());
-    }
+    scan_seq_records<false>(d, want, out, nullptr);
+}
+
+void read_seqs_qual(const char *path, SeqSet &out, SeqQual &qual) {
+    const FileView file(path);
+    const std::string_view d(file.p, file.n);
+    out.n_lines = (uint64_t)std::count(d.begin(), d.end(), '\n');
+    out.bases.reserve(d.size() / 2 + 1);
+    qual.quals.reserve(d.size() / 2 + 1);
+    scan_seq_records<true>(d, nullptr, out, &qual);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "row_score.h"
+#include "seq_scan.h"
 
 namespace hlmi {
 
@@ -35,20 +36,14 @@ struct PafText {
 // last-resort comparison under LC_ALL=C).
 void read_paf(const char *path, PafText &out, bool need_tie_rank);
 
-// Sequence file reader with the record detection of kseq (FASTA '>' / FASTQ '@', multi-line).
-struct SeqSet {
-    std::vector<std::string> names;
-    std::string bases;               // concatenated, as in the file (no case folding)
-    std::vector<uint64_t> off;       // size n+1
-    std::vector<uint32_t> first_line;  // 0-based line number of each record's header line
-    uint64_t n_lines = 0;            // `wc -l` of the file (utils.py:44)
-    size_t size() const { return names.size(); }
-    uint32_t len(size_t i) const { return (uint32_t)(off[i + 1] - off[i]); }
-};
+// SeqSet, SeqQual and the record scan (kseq's detection: FASTA '>' / FASTQ '@', multi-line): seq_scan.h
 void read_seqs(const char *path, SeqSet &out);
 // the same scan, but only the records `want` accepts bring their bases along (the others keep their name and have
 // length 0; n_lines is not counted)
 void read_seqs_subset(const char *path, const std::function<bool(std::string_view)> *want, SeqSet &out);
+// read_seqs, and the quality strings at the bases' offsets with a per-record "has quality" flag (SeqQual, seq_scan.h): the
+// polisher's _q calls.  Nothing is refused here: pol::quality_facts judges the strings.
+void read_seqs_qual(const char *path, SeqSet &out, SeqQual &qual);
 
 // Final 14-column row of filter_overlap_slr2.py:142-151 (with the trailing TAB); returns
 // false when the row is dropped by the identity test `float(score2) < iden` (slr2:146).

@@ -9,6 +9,10 @@
 //                length counters of each opened slot, then, the lengths decided, into the 16 x 4 base counters
 //   write        a thread per position: output length, a device scan for the offsets, one kernel for the bytes
 // Every counter is 32 bits wide: coverage needs no overflow path.  Every loop is bounded by a count known at its head.
+// QW (hlmi_polish_q with qual_weight = 1): a vote weighs max(1, quality byte - 33) of its read base.  The count pass then keeps a
+// ninth LDS counter per position - the number of voting columns, which the coverage test and the slot's span still are - and the
+// five symbol counters hold weight sums; the slot passes add weights where they added 1.  QW = false is the kernels as they
+// were: no quality byte is read, eight counters.
 // polish_device uploads what polish_host.cpp built and runs polish_core; hlmi_polish_reads (polish_rows.hip) runs polish_core
 // over rows, CIGARs and reads that are in device memory already - its reads as the overlapper's codes (column_symbol).
 #include <hip/hip_runtime.h>
@@ -24,6 +28,7 @@ namespace {
 
 constexpr int POLISH_WG = 256, POLISH_WAVES = POLISH_WG / 64;
 constexpr int C_OTHER = 5, C_START = 6, C_INS = 7, POLISH_CNT = 8;     // counters behind the five symbols
+constexpr int C_VOTES = 8, POLISH_CNT_QW = 9;                          // QW: voting columns, behind the others
 constexpr uint32_t SHORT_RUN = 16;         // a lane votes a run of up to this many columns itself; longer ones take the wave
 constexpr uint32_t NO_SLOT = 0xffffffffu;
 
@@ -45,6 +50,20 @@ __device__ __forceinline__ uint32_t column_symbol(const PolRow &r, const uint8_t
     return r.rev && k < 4 ? 3u - k : k;
 }
 
+// weight of alignment column `col` of row r: max(1, Phred), the byte fetched at the index column_symbol fetches the base at
+__device__ __forceinline__ uint32_t column_weight(const PolRow &r, const uint8_t *__restrict__ quals, uint32_t col) {
+    if (col >= r.qn) return 1u;                                        // (validated on the host: never)
+    const uint32_t q = quals[r.read_off + (r.rev ? r.qn - 1 - col : col)];
+    return q > 34u ? q - 33u : 1u;
+}
+// weight of a D op whose first query column behind it is qc: the lower of its flanks, of those inside [0, qn); none: 1
+__device__ __forceinline__ uint32_t del_weight(const PolRow &r, const uint8_t *__restrict__ quals, uint32_t qc) {
+    uint32_t w = 0xffffffffu;
+    if (qc >= 1 && qc - 1 < r.qn) w = column_weight(r, quals, qc - 1);
+    if (qc < r.qn) w = min(w, column_weight(r, quals, qc));
+    return w == 0xffffffffu ? 1u : w;
+}
+
 // One wave walks the CIGAR of r: f(code, len, first target position, first query column) for every op, lane = op; stops
 // in front of the first 64 ops that start at t_stop or behind it.  All 64 lanes call f together.
 template <typename F>
@@ -63,24 +82,34 @@ __device__ __forceinline__ void walk_row(const PolRow &r, const uint32_t *__rest
     }
 }
 
-template <int ENC>
+template <int ENC, bool QW>
 __global__ __launch_bounds__(POLISH_WG) void polish_count_kernel(const PolRow *__restrict__ rows, const uint32_t *__restrict__ ops,
                                                                  const uint8_t *__restrict__ reads, const uint8_t *__restrict__ contig,
                                                                  const PolTile *__restrict__ tiles, int min_cov,
-                                                                 uint8_t *__restrict__ sym, uint8_t *__restrict__ open) {
-    __shared__ uint32_t s_cnt[POLISH_CNT][POLISH_TILE];
+                                                                 uint8_t *__restrict__ sym, uint8_t *__restrict__ open,
+                                                                 const uint8_t *__restrict__ quals) {
+    constexpr int N_CNT = QW ? POLISH_CNT_QW : POLISH_CNT;
+    __shared__ uint32_t s_cnt[N_CNT][POLISH_TILE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const PolTile t = tiles[blockIdx.x];
     const uint32_t t_end = t.t0 + t.n_pos;
-    for (int i = tid; i < POLISH_CNT * POLISH_TILE; i += POLISH_WG) (&s_cnt[0][0])[i] = 0;
+    for (int i = tid; i < N_CNT * POLISH_TILE; i += POLISH_WG) (&s_cnt[0][0])[i] = 0;
     __syncthreads();
     for (uint32_t k = t.row_lo + (uint32_t)wave; k < t.row_hi; k += POLISH_WAVES) {
         const PolRow r = rows[k];
         if (r.te <= t.t0 || r.ts >= t_end) continue;
         if (lane == 0 && r.ts >= t.t0) atomicAdd(&s_cnt[C_START][r.ts - t.t0], 1u);
-        auto vote = [&](uint32_t p, uint32_t code, uint32_t tp0, uint32_t qc0) {
+        // wd: the weight of the op's columns when it is a D op (QW only)
+        auto vote = [&](uint32_t p, uint32_t code, uint32_t tp0, uint32_t qc0, uint32_t wd) {
             const uint32_t s = code == OP_D ? (uint32_t)SYM_DEL : column_symbol<ENC>(r, reads, qc0 + (p - tp0));
-            atomicAdd(&s_cnt[s][p - t.t0], 1u);
+            if constexpr (QW) {
+                if (s == C_OTHER) atomicAdd(&s_cnt[C_OTHER][p - t.t0], 1u);
+                else {
+                    atomicAdd(&s_cnt[s][p - t.t0], code == OP_D ? wd : column_weight(r, quals, qc0 + (p - tp0)));
+                    atomicAdd(&s_cnt[C_VOTES][p - t.t0], 1u);
+                }
+            } else
+                atomicAdd(&s_cnt[s][p - t.t0], 1u);
         };
         walk_row(r, ops, lane, t_end, [&](uint32_t code, uint32_t len, uint32_t tp0, uint32_t qc0) {
             if (code == OP_I && len >= 1 && len <= (uint32_t)POLISH_INS_CAP && tp0 > r.ts && tp0 < r.te && tp0 >= t.t0 && tp0 < t_end)
@@ -92,8 +121,11 @@ __global__ __launch_bounds__(POLISH_WG) void polish_count_kernel(const PolRow *_
                 b = max(a, min(tp0 + len, t_end));
             }
             const uint32_t n = b - a;
+            uint32_t wd = 1u;                                          // a D op's weight: once per op, by its lane
+            if constexpr (QW)
+                if (code == OP_D && n) wd = del_weight(r, quals, qc0);
             if (n <= SHORT_RUN)
-                for (uint32_t p = a; p < b; ++p) vote(p, code, tp0, qc0);
+                for (uint32_t p = a; p < b; ++p) vote(p, code, tp0, qc0, wd);
             unsigned long long longs = __ballot(n > SHORT_RUN);
             for (int it = 0; it < 64 && longs; ++it) {                 // the long runs, one after the other, 64 columns a step
                 const int src = __ffsll(longs) - 1;
@@ -101,7 +133,9 @@ __global__ __launch_bounds__(POLISH_WG) void polish_count_kernel(const PolRow *_
                 const uint32_t a2 = (uint32_t)__shfl((int)a, src), b2 = (uint32_t)__shfl((int)b, src);
                 const uint32_t code2 = (uint32_t)__shfl((int)code, src), tp2 = (uint32_t)__shfl((int)tp0, src),
                                qc2 = (uint32_t)__shfl((int)qc0, src);
-                for (uint32_t p = a2 + (uint32_t)lane; p < b2; p += 64) vote(p, code2, tp2, qc2);
+                uint32_t wd2 = 1u;
+                if constexpr (QW) wd2 = (uint32_t)__shfl((int)wd, src);
+                for (uint32_t p = a2 + (uint32_t)lane; p < b2; p += 64) vote(p, code2, tp2, qc2, wd2);
             }
         });
     }
@@ -110,6 +144,7 @@ __global__ __launch_bounds__(POLISH_WG) void polish_count_kernel(const PolRow *_
         uint32_t v[5], c = 0, top = 0;
 #pragma unroll
         for (int k = 0; k < 5; ++k) { v[k] = s_cnt[k][i]; c += v[k]; top = max(top, v[k]); }
+        if constexpr (QW) c = s_cnt[C_VOTES][i];                       // the coverage test stays a count; v[] and top are weight sums
         const size_t g = (size_t)t.cbase + t.t0 + i;
         uint8_t d = SYM_KEEP;
         if (c >= (uint32_t)min_cov) {
@@ -131,11 +166,13 @@ __global__ void slot_index_kernel(const uint32_t *__restrict__ open_pos, uint32_
 }
 
 // MODE 0: the length every inserting row votes for at its opened slots; MODE 1: its bases, where its length won
-template <int MODE, int ENC>
+// QW: the length vote weighs the lowest weight among the row's inserted bases, a base vote the base's own
+template <int MODE, int ENC, bool QW>
 __global__ __launch_bounds__(POLISH_WG) void polish_slot_kernel(const PolRow *__restrict__ rows, uint32_t n_rows,
                                                                 const uint32_t *__restrict__ ops, const uint8_t *__restrict__ reads,
                                                                 const uint32_t *__restrict__ slot_of, const uint8_t *__restrict__ win_len,
-                                                                uint32_t *__restrict__ len_cnt, uint32_t *__restrict__ base_cnt) {
+                                                                uint32_t *__restrict__ len_cnt, uint32_t *__restrict__ base_cnt,
+                                                                const uint8_t *__restrict__ quals) {
     const int lane = threadIdx.x & 63;
     const uint32_t w = blockIdx.x * POLISH_WAVES + (threadIdx.x >> 6);
     if (w >= n_rows) return;
@@ -144,11 +181,18 @@ __global__ __launch_bounds__(POLISH_WG) void polish_slot_kernel(const PolRow *__
         if (code != OP_I || len < 1 || len > (uint32_t)POLISH_INS_CAP || tp0 <= r.ts || tp0 >= r.te) return;
         const uint32_t s = slot_of[(size_t)r.cbase + tp0];
         if (s == NO_SLOT) return;
-        if (MODE == 0) atomicAdd(&len_cnt[(size_t)s * POLISH_INS_CAP + len - 1], 1u);
-        else if (win_len[s] == len)
+        if (MODE == 0) {
+            uint32_t w = 1u;
+            if constexpr (QW) {
+                w = 0xffffffffu;
+                for (uint32_t j = 0; j < (uint32_t)POLISH_INS_CAP; ++j)
+                    if (j < len) w = min(w, column_weight(r, quals, qc0 + j));
+            }
+            atomicAdd(&len_cnt[(size_t)s * POLISH_INS_CAP + len - 1], w);
+        } else if (win_len[s] == len)
             for (uint32_t j = 0; j < len; ++j) {
                 const uint32_t k = column_symbol<ENC>(r, reads, qc0 + j);
-                if (k < 4) atomicAdd(&base_cnt[((size_t)s * POLISH_INS_CAP + j) * 4 + k], 1u);
+                if (k < 4) atomicAdd(&base_cnt[((size_t)s * POLISH_INS_CAP + j) * 4 + k], QW ? column_weight(r, quals, qc0 + j) : 1u);
             }
     });
 }
@@ -205,26 +249,41 @@ __global__ void gather_off_kernel(const uint64_t *__restrict__ off, const uint32
     if (i < n) out[i] = off[at[i]];
 }
 
-template <int ENC>
+template <int ENC, bool QW>
 void launch_count(const PolCoreIn &in, uint8_t *d_sym, uint8_t *d_open) {
-    hipLaunchKernelGGL(polish_count_kernel<ENC>, dim3((unsigned)in.n_tiles), dim3(POLISH_WG), 0, stream(), in.rows, in.ops, in.reads,
-                       in.contig, in.tiles, in.min_cov, d_sym, d_open);
+    hipLaunchKernelGGL((polish_count_kernel<ENC, QW>), dim3((unsigned)in.n_tiles), dim3(POLISH_WG), 0, stream(), in.rows, in.ops, in.reads,
+                       in.contig, in.tiles, in.min_cov, d_sym, d_open, in.quals);
 }
-template <int MODE, int ENC>
+template <int MODE, int ENC, bool QW>
 void launch_slot(const PolCoreIn &in, const uint32_t *d_slot_of, const uint8_t *d_win_len, uint32_t *d_len_cnt, uint32_t *d_base_cnt) {
-    hipLaunchKernelGGL((polish_slot_kernel<MODE, ENC>), dim3(cdiv(in.n_rows, POLISH_WAVES)), dim3(POLISH_WG), 0, stream(), in.rows,
-                       in.n_rows, in.ops, in.reads, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+    hipLaunchKernelGGL((polish_slot_kernel<MODE, ENC, QW>), dim3(cdiv(in.n_rows, POLISH_WAVES)), dim3(POLISH_WG), 0, stream(), in.rows,
+                       in.n_rows, in.ops, in.reads, d_slot_of, d_win_len, d_len_cnt, d_base_cnt, in.quals);
+}
+// the instantiation of the call: the reads' encoding, weighted or not
+template <int MODE>
+void launch_slot_for(const PolCoreIn &in, const uint32_t *d_slot_of, const uint8_t *d_win_len, uint32_t *d_len_cnt, uint32_t *d_base_cnt) {
+    const bool codes = in.enc == READS_CODES;
+    if (in.quals) {
+        if (codes) launch_slot<MODE, READS_CODES, true>(in, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+        else launch_slot<MODE, READS_ASCII, true>(in, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+    } else {
+        if (codes) launch_slot<MODE, READS_CODES, false>(in, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+        else launch_slot<MODE, READS_ASCII, false>(in, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+    }
 }
 
 }  // namespace
 
 void polish_device(const PolDevIn &in, PolDevOut &out) {
-    DBuf<uint8_t> d_contig, d_reads;
+    DBuf<uint8_t> d_contig, d_reads, d_quals;
     DBuf<PolRow> d_rows;
     DBuf<uint32_t> d_ops, d_cbase;
     DBuf<PolTile> d_tiles;
     d_contig.upload((const uint8_t *)in.contigs.data(), in.contigs.size());
     d_reads.upload((const uint8_t *)in.reads.data(), in.reads.size());
+    const bool weighted = !in.quals.empty();                 // (as long as `reads`: polish_host.cpp appends both)
+    if (weighted && in.quals.size() != in.reads.size()) fail(HLMI_EINVAL, "hlmi_polish_q: quality bytes and read bytes differ in number");
+    if (weighted) d_quals.upload((const uint8_t *)in.quals.data(), in.quals.size());
     d_rows.upload(in.rows);
     d_ops.upload(in.ops);
     d_tiles.upload(in.tiles);
@@ -233,6 +292,7 @@ void polish_device(const PolDevIn &in, PolDevOut &out) {
     c.rows = d_rows.p; c.n_rows = (uint32_t)in.rows.size();
     c.ops = d_ops.p;
     c.reads = d_reads.p; c.enc = READS_ASCII;
+    c.quals = weighted ? d_quals.p : nullptr;
     c.contig = d_contig.p; c.n_contig = in.contigs.size();
     c.tiles = d_tiles.p; c.n_tiles = in.tiles.size();
     c.cbase = d_cbase.p; c.n_cbase = in.cbase.size();
@@ -252,8 +312,13 @@ void polish_core(const PolCoreIn &in, PolDevOut &out) {
     d_open.zero();
     if (in.n_tiles) {
         KTimer kt("polish_count");
-        if (codes) launch_count<READS_CODES>(in, d_sym.p, d_open.p);
-        else launch_count<READS_ASCII>(in, d_sym.p, d_open.p);
+        if (in.quals) {
+            if (codes) launch_count<READS_CODES, true>(in, d_sym.p, d_open.p);
+            else launch_count<READS_ASCII, true>(in, d_sym.p, d_open.p);
+        } else {
+            if (codes) launch_count<READS_CODES, false>(in, d_sym.p, d_open.p);
+            else launch_count<READS_ASCII, false>(in, d_sym.p, d_open.p);
+        }
         HIP_CHECK(hipGetLastError());
     }
     DBuf<uint32_t> d_open_pos(G), d_slot_of(G);
@@ -266,11 +331,9 @@ void polish_core(const PolCoreIn &in, PolDevOut &out) {
         d_len_cnt.zero();
         d_base_cnt.zero();
         hipLaunchKernelGGL(slot_index_kernel, dim3(cdiv(n_open, B)), dim3(B), 0, stream(), d_open_pos.p, (uint32_t)n_open, d_slot_of.p);
-        if (codes) launch_slot<0, READS_CODES>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
-        else launch_slot<0, READS_ASCII>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
+        launch_slot_for<0>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
         hipLaunchKernelGGL(slot_len_kernel, dim3(cdiv(n_open, B)), dim3(B), 0, stream(), d_len_cnt.p, (uint32_t)n_open, d_win_len.p);
-        if (codes) launch_slot<1, READS_CODES>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
-        else launch_slot<1, READS_ASCII>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
+        launch_slot_for<1>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
         HIP_CHECK(hipGetLastError());
     }
     DBuf<uint32_t> d_out_len(G + 1);

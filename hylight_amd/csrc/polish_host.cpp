@@ -40,13 +40,17 @@ struct Sel {
 }  // namespace
 
 void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
-                hlmi_polish_stats *st) {
+                hlmi_polish_stats *st, PolQualCall *qc) {
     const double t_begin = now_ms();
     *st = hlmi_polish_stats{};
     if (o.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish: min_cov %d (< 1)", o.min_cov);
     SeqSet cs, rs;
+    SeqQual rq;
+    std::vector<uint8_t> low;                                // hlmi_polish_q: per read record, its mean quality is below the floor
     read_seqs(contigs, cs);
-    read_seqs(reads, rs);
+    if (qc) low = polish_read_quals("hlmi_polish_q", reads, qc->min_avg_qual, rs, rq, *qc);
+    else read_seqs(reads, rs);
+    const bool weighted = qc && qc->qual_weight;
     const auto contig_named = first_records(cs, contigs), read_named = first_records(rs, reads);
     PafText pt;
     read_paf(paf, pt, false);
@@ -98,7 +102,9 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
         if (n_t != (uint64_t)(r.te - r.ts)) fail(HLMI_EINVAL, "%s:%zu: the CIGAR has %llu target columns, te - ts = %u", paf, i + 1, (unsigned long long)n_t, r.te - r.ts);
         if (n_q != (uint64_t)(r.qe - r.qs)) fail(HLMI_EINVAL, "%s:%zu: the CIGAR has %llu query columns, qe - qs = %u", paf, i + 1, (unsigned long long)n_q, r.qe - r.qs);
         const uint32_t span = r.te - r.ts;
-        if (r.qid == r.tid || span == 0 || (int64_t)span < (int64_t)o.min_len) continue;
+        if (r.qid == r.tid) continue;
+        if (!low.empty() && low[ri]) { ++qc->rows_low_qual; continue; }
+        if (span == 0 || (int64_t)span < (int64_t)o.min_len) continue;
         if ((double)n_eq / (double)n_all < o.min_iden) continue;
         const auto it = best.find(r.qid);
         if (it == best.end()) best.emplace(r.qid, Sel{i, ci, ri});
@@ -113,6 +119,7 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
         return sa != sb ? sa < sb : a.line < b.line;
     });
     st->rows_selected = sel.size();
+    polish_check_weight_width("hlmi_polish_q", qc, sel.size());
 
     // the device's input: polished contigs side by side, the aligned stretch of every read, compact CIGARs, tiles
     std::vector<PolSpan> spans;
@@ -133,6 +140,7 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
         row.rev = (r.flags & PF_REV) ? 1u : 0u;
         row.cbase = L.cbase[L.slot_of_contig[s.contig]];
         in.reads.append(rs.bases, rs.off[s.read] + r.qs, row.qn);
+        if (weighted) in.quals.append(rq.quals, rs.off[s.read] + r.qs, row.qn);
         RowWalk w;                                           // polish_rows.h: drop, merge, ins_edge, ins_long
         RowOp done;
         row_walk_begin(w, r.ts, r.te);
@@ -158,6 +166,26 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
 }
 
 namespace pol {
+
+std::vector<uint8_t> polish_read_quals(const char *who, const char *reads, double min_avg_qual, SeqSet &rs, SeqQual &rq, PolQualCall &qc) {
+    if (!(min_avg_qual >= 0.0)) fail(HLMI_EINVAL, "%s: min_avg_qual %g (negative or not a number)", who, min_avg_qual);
+    read_seqs_qual(reads, rs, rq);
+    QualFacts f = quality_facts(rs, rq, min_avg_qual);
+    if (f.bad_kind == 1)
+        fail(HLMI_EINVAL, "%s: %s: record %s has %u bases and %llu quality bytes", who, reads, rs.names[f.bad_rec].c_str(),
+             rs.len(f.bad_rec), (unsigned long long)rq.qual_len[f.bad_rec]);
+    if (f.bad_kind == 2)
+        fail(HLMI_EINVAL, "%s: %s: record %s: quality byte %u at base %llu (outside 33..126)", who, reads, rs.names[f.bad_rec].c_str(),
+             (unsigned)f.bad_byte, (unsigned long long)f.bad_at);
+    qc.reads_with_qual = f.reads_with_qual;
+    qc.rows_low_qual = 0;
+    return std::move(f.low);
+}
+
+void polish_check_weight_width(const char *who, const PolQualCall *qc, uint64_t rows_selected) {
+    if (qc && qc->qual_weight && !weight_sums_fit(rows_selected))
+        fail(HLMI_EINVAL, "%s: %llu selected rows of weight 93 at the most do not fit the 32-bit sums", who, (unsigned long long)rows_selected);
+}
 
 void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, hlmi_polish_stats *st) {
     L = PolLayout{};

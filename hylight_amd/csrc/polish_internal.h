@@ -1,5 +1,6 @@
 // polish_internal.h - what polish_host.cpp (validation, selection, text) and polish.hip (the votes and the bases) share.
-// The rules are those of include/hylight_mi.h (hlmi_polish); tests/polish_model.py restates them.
+// The rules are those of include/hylight_mi.h (hlmi_polish, hlmi_polish_q); tests/polish_model.py and
+// tests/polish_qual_model.py restate them.
 #pragma once
 #include <string>
 #include <vector>
@@ -32,6 +33,7 @@ struct PolTile {
 
 struct PolDevIn {
     std::string contigs, reads;         // concatenated: polished contigs; aligned read stretches
+    std::string quals;                  // the stretches' quality bytes, parallel to `reads`; empty: every vote weighs 1
     std::vector<uint32_t> cbase;        // start of every polished contig in `contigs`, and the total behind the last
     std::vector<PolRow> rows;
     std::vector<uint32_t> ops;          // len << 4 | OP_*: zero-length ops dropped, neighbouring I ops merged
@@ -55,6 +57,7 @@ struct PolCoreIn {
     uint32_t n_rows = 0;
     const uint32_t *ops = nullptr;
     const uint8_t *reads = nullptr;
+    const uint8_t *quals = nullptr;     // quality bytes (33..126), indexed exactly like `reads` by PolRow::read_off; nullptr: unweighted
     ReadEnc enc = READS_ASCII;
     const uint8_t *contig = nullptr;    // the polished contigs side by side, ASCII as in the file (their case reaches the output)
     size_t n_contig = 0;
@@ -84,12 +87,26 @@ void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char
 void polish_emit(const SeqSet &cs, const PolLayout &L, const PolDevOut &out, const hlmi_polish_opts &o, const char *out_fa,
                  hlmi_polish_stats *st);
 
+// The quality part of a _q call (nullptr: hlmi_polish / hlmi_polish_reads as they were).  In: the two options; out: the two
+// counters of hlmi_polish_qstats.
+struct PolQualCall {
+    int qual_weight = 0;
+    double min_avg_qual = 0.0;
+    uint64_t reads_with_qual = 0, rows_low_qual = 0;
+};
+// Reads `reads` with its quality strings and judges them (seq_scan.h: quality_facts): a string of another length than its
+// bases or a byte outside 33..126 is HLMI_EINVAL naming the record; sets qc.reads_with_qual; -> per record "this read is low"
+// (empty when min_avg_qual == 0.0).  Both entry points start with it.
+std::vector<uint8_t> polish_read_quals(const char *who, const char *reads, double min_avg_qual, SeqSet &rs, SeqQual &rq, PolQualCall &qc);
+// qual_weight = 1: rows_selected x 93 must fit the 32-bit weight sums
+void polish_check_weight_width(const char *who, const PolQualCall *qc, uint64_t rows_selected);
+
 }  // namespace pol
 
 void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
-                hlmi_polish_stats *st);
+                hlmi_polish_stats *st, pol::PolQualCall *qc = nullptr);
 // hlmi_polish_reads (polish_rows.hip): the overlapper's rows selected, ordered and compacted where they are
 void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
-                      const char *out_fa, hlmi_polish_stats *st);
+                      const char *out_fa, hlmi_polish_stats *st, pol::PolQualCall *qc = nullptr);
 
 }  // namespace hlmi

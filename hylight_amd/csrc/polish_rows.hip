@@ -10,6 +10,8 @@
 //   pr_write_kernel    the same walk once more behind a scan: the compact ops and the PolRow table
 // The reads are voted from the overlapper's resident codes (PolRow::read_off points into DevReads::codes()); the votes, the
 // decisions and the bases are polish.hip's (polish_core), headers and file polish_host.cpp's (polish_layout, polish_emit).
+// hlmi_polish_reads_q: the resident reads hold codes only, so the quality bytes go up as one array at the offsets of
+// DevReads::codes() (PolRow::read_off indexes both), and the read floor is one byte per name rank that pr_facts_kernel looks up.
 //
 // Why a wave per row in the first kernel and a thread per row in the last two: the first reads the ops of EVERY row (all of
 // the CIGAR traffic of this file), needs two sums and nothing else of them, so 64 consecutive words per load and a DPP sum fit;
@@ -40,13 +42,19 @@ constexpr uint32_t NO_REC = 0xffffffffu;
 inline dim3 grid1(size_t n) { return dim3((unsigned)std::min<size_t>(cdiv(n ? n : 1, WG), MAX_GRID)); }
 
 __global__ __launch_bounds__(WG) void pr_facts_kernel(const PafRec *__restrict__ recs, size_t n_rows, const uint32_t *__restrict__ ops_base,
-                                                      int min_len, double min_iden, unsigned long long *__restrict__ best) {
+                                                      int min_len, double min_iden, unsigned long long *__restrict__ best,
+                                                      const uint8_t *__restrict__ low_of_rank, unsigned long long *__restrict__ n_low) {
     const int lane = threadIdx.x & 63;
     const size_t n_waves = (size_t)gridDim.x * WAVES;
     for (size_t i = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); i < n_rows; i += n_waves) {
         const PafRec r = recs[i];
         const uint32_t span = r.te - r.ts;
-        if (r.qid == r.tid || span == 0 || (int64_t)span < (int64_t)min_len) continue;          // (the same in every lane)
+        if (r.qid == r.tid) continue;                                                           // (the same in every lane)
+        if (low_of_rank && low_of_rank[r.qid]) {        // the read floor (nullptr: off): the row claims nothing, and is counted
+            if (lane == 0) atomicAdd(n_low, 1ull);
+            continue;
+        }
+        if (span == 0 || (int64_t)span < (int64_t)min_len) continue;
         const uint32_t *o = ops_base + r.cig_off;
         uint32_t eq = 0, all = 0;               // a row's op lengths add up to less than 2^29 (two sequences below 2^28)
         for (uint32_t k0 = 0; k0 < r.cig_n; k0 += 64) {
@@ -151,15 +159,19 @@ std::vector<uint32_t> record_of_rank(const SeqSet &s, const std::vector<uint32_t
 }  // namespace
 
 void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
-                      const char *out_fa, hlmi_polish_stats *st) {
+                      const char *out_fa, hlmi_polish_stats *st, PolQualCall *qc) {
     const double t_begin = now_ms();
     *st = hlmi_polish_stats{};
     stat_reset();
     if (po.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish_reads: min_cov %d (< 1)", po.min_cov);
     if (ao.stub_oh >= 0) fail(HLMI_EINVAL, "hlmi_polish_reads: stub_oh %d: the bare rows of stub candidates have no CIGAR", ao.stub_oh);
     SeqSet cs, rs;
+    SeqQual rq;
+    std::vector<uint8_t> low;                   // hlmi_polish_reads_q: per read record, its mean quality is below the floor
     read_seqs(contigs, cs);
-    read_seqs(reads, rs);
+    if (qc) low = polish_read_quals("hlmi_polish_reads_q", reads, qc->min_avg_qual, rs, rq, *qc);
+    else read_seqs(reads, rs);
+    const bool weighted = qc && qc->qual_weight;
     const double t_dev = now_ms();
     AvaPairCall call;
     call.setup(cs, rs, ao);
@@ -179,15 +191,24 @@ void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opt
     if (R) {
         KTimer kt("polish_rows");
         DBuf<unsigned long long> best(n_ranks);
-        DBuf<uint8_t> flag(R);
+        DBuf<uint8_t> flag(R), d_low;
+        DBuf<unsigned long long> n_low(1);
         best.zero();
+        n_low.zero();
+        if (!low.empty()) {
+            std::vector<uint8_t> low_of_rank(n_ranks, 0);
+            for (size_t i = 0; i < rs.size(); ++i) low_of_rank[call.rq[i]] = low[i];
+            d_low.upload(low_of_rank);
+        }
         hipLaunchKernelGGL(pr_facts_kernel, dim3((unsigned)std::min<size_t>(cdiv(R, WAVES), MAX_GRID)), dim3(WG), 0, stream(), rows.recs.p,
-                           R, rows.ops_base, po.min_len, po.min_iden, best.p);
+                           R, rows.ops_base, po.min_len, po.min_iden, best.p, low.empty() ? nullptr : d_low.p, n_low.p);
         hipLaunchKernelGGL(pr_winner_kernel, grid1(R), dim3(WG), 0, stream(), rows.recs.p, R, best.p, flag.p);
         HIP_CHECK(hipGetLastError());
         S = select_flagged_indices(flag.p, idx.p, R);
+        if (qc) qc->rows_low_qual = download_one(n_low.p);
     }
     st->rows_selected = S;
+    polish_check_weight_width("hlmi_polish_reads_q", qc, S);
     std::vector<PolSpan> spans;
     DBuf<uint32_t> cig_n(std::max<size_t>(S, 1));
     DBuf<uint64_t> cig_off(std::max<size_t>(S, 1));
@@ -221,7 +242,8 @@ void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opt
     DBuf<PolRow> d_rows(std::max<size_t>(S, 1));
     DBuf<uint32_t> d_ops(std::max<uint64_t>(n_ops, 1)), d_cbase, d_cbase_of_crec;
     DBuf<PolTile> d_tiles;
-    DBuf<uint8_t> d_contig;
+    DBuf<uint8_t> d_contig, d_quals;
+    if (weighted) d_quals.upload((const uint8_t *)rq.quals.data(), rq.quals.size());      // rs.off is DevReads::off of call.dQ
     if (S) {
         std::vector<uint32_t> cbase_of_crec(cs.size(), 0);
         for (size_t c = 0; c < cs.size(); ++c)
@@ -245,6 +267,7 @@ void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opt
     c.rows = d_rows.p; c.n_rows = (uint32_t)S;
     c.ops = d_ops.p;
     c.reads = call.dQ.codes(); c.enc = READS_CODES;
+    c.quals = weighted && !rq.quals.empty() ? d_quals.p : nullptr;
     c.contig = d_contig.p; c.n_contig = L.contigs.size();
     c.tiles = d_tiles.p; c.n_tiles = L.tiles.size();
     c.cbase = d_cbase.p; c.n_cbase = L.cbase.size();

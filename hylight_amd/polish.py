@@ -8,6 +8,8 @@ calls of HyLight.py:152,182,203.  Not racon's function - a column vote over the 
 --paf holds rows with a cg:Z: CIGAR in = X I D as the last field, reads against contigs, as `api.ava(contigs, reads, paf)`
 writes them.  Without --paf the reads are aligned to the contigs in the same call (hlmi_polish_reads: the overlapper's long
 constants, --short: its short-read ones; every pair, pair_once = 0, as the driver's polishing sites do) and no PAF exists.
+--qual_weight weighs every vote by the read base's Phred quality and --min_avg_qual Q drops the rows of reads whose mean quality
+is below Q (hlmi_polish_q / hlmi_polish_reads_q; FASTQ reads - a FASTA read's bases weigh 1 and it is never dropped).
 Prints the stats as one JSON line.  Exit status 0 on success.
 """
 from __future__ import annotations
@@ -32,6 +34,9 @@ def build_parser():
     p.add_argument("--min_iden", type=float, default=0.0, help="drop rows with a smaller share of '=' columns")
     p.add_argument("--min_cov", type=int, default=3, help="votes a position needs, rows a slot needs")
     p.add_argument("--drop_unpolished", action="store_true", help="leave out contigs no row was selected on")
+    p.add_argument("--qual_weight", action="store_true", help="weigh votes by the reads' base qualities (FASTQ reads)")
+    p.add_argument("--min_avg_qual", type=float, default=None, metavar="Q",
+                   help="drop rows of reads whose mean Phred quality is below Q (racon -q; not given: no such test)")
     return p
 
 
@@ -46,6 +51,10 @@ def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
     opts = dict(min_len=a.min_len, min_iden=a.min_iden, min_cov=a.min_cov, include_unpolished=not a.drop_unpolished)
+    if a.qual_weight:
+        opts["qual_weight"] = 1
+    if a.min_avg_qual is not None:
+        opts["min_avg_qual"] = a.min_avg_qual
     if a.paf is not None:
         if a.short:
             parser.error("--short chooses the alignment of a call without --paf")

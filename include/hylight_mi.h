@@ -751,6 +751,59 @@ int hlmi_polish(const char *contigs, const char *reads, const char *paf, const h
 int hlmi_polish_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_opts *po,
                       const char *out_fa, hlmi_polish_stats *st);
 
+/* ---- polishing with base qualities (racon weights every base of a FASTQ read by its Phred score and, -q 10, drops reads of a
+ * mean quality below 10).  hlmi_polish_q and hlmi_polish_reads_q are hlmi_polish and hlmi_polish_reads with these two rules as
+ * options; the two older calls keep their signatures and their bytes, and HLMI_ABI_VERSION stays where it is (new symbols, as
+ * for the hlmi_vq_*_mq calls).  A function of the project's own like hlmi_polish: PARITY with racon UNPINNED;
+ * tests/polish_qual_model.py is the contract, byte for byte. */
+typedef struct {
+    int min_len;              /* the four fields of hlmi_polish_opts, with their meaning                                  */
+    double min_iden;
+    int min_cov;
+    int include_unpolished;
+    int qual_weight;          /* 0: every vote weighs 1 (hlmi_polish's function); 1: the rules below                      */
+    double min_avg_qual;      /* 0.0: off; else rows of reads whose mean Phred is below it are dropped (racon -q)          */
+} hlmi_polish_qopts;
+void hlmi_polish_qopts_default(hlmi_polish_qopts *o);   /* 0, 0.0, 3, 1, 1, 10.0 */
+typedef struct {
+    hlmi_polish_stats base;
+    uint64_t reads_with_qual;   /* records of `reads` that have a quality string                                           */
+    uint64_t rows_low_qual;     /* rows dropped because their query's mean quality is below min_avg_qual                   */
+} hlmi_polish_qstats;
+/* Where a rule below is silent, hlmi_polish's rule holds unchanged.
+ * Qualities: a FASTQ record's quality string must be as long as its bases and every quality byte must be in 33..126;
+ * otherwise the call returns HLMI_EINVAL, names the record, and writes nothing (whatever the two options are; also
+ * min_avg_qual negative or not a number).  Weight of a read base: w = max(1, byte - 33).  A FASTA record has no qualities:
+ * each of its bases weighs 1, and min_avg_qual never drops it.  reads_with_qual = the number of records that have a quality
+ * string.
+ * Read floor: a read with qualities is low when (double)sum(byte - 33) / (double)len < min_avg_qual, the sum over the whole
+ * record (a record of no bases is never low).  Rows whose query is a low read are dropped directly after the
+ * qname == tname skip and counted in rows_low_qual (every row is still checked as hlmi_polish checks it).  With
+ * min_avg_qual == 0.0 the test is not made.
+ * Alignment-column order: on strand '-' the qualities are reversed together with the bases: column i has the quality of
+ * read[qe - 1 - i].
+ * Position votes (qual_weight = 1): an = / X column with an A C G T base adds its w to that symbol.  A D op adds the same weight
+ * to `del` on each of its columns: min(w of query column qc - 1, w of query column qc), qc the first query column behind
+ * the op, only the columns that exist inside [0, qe - qs) counting; with neither present the weight is 1.  The coverage test
+ * stays a count: c = number of voting columns, decided when c >= min_cov.  The winner is the symbol with the largest weight
+ * sum; on a tie the contig's own upper-cased base if it is among the tied, otherwise the first of A, C, G, T, del.
+ * Slots: spanning rows, inserting rows and the opening test (s >= min_cov and 2 i > s) stay counts, as do ins_long and
+ * ins_edge.  An inserting row's length vote weighs the minimum w over its 1..16 inserted bases; the length with the largest
+ * sum wins, on a tie the smallest.  Base j: among the rows that insert exactly the winning length each adds the w of its
+ * base j; the largest sum wins, on a tie the first of A, C, G, T; with no A C G T there the base is N.
+ * Counter width: counters stay 32 bits wide; with qual_weight = 1 a call whose rows_selected x 93 >= 2^32 is HLMI_EINVAL
+ * before anything is written.
+ * Identities: with qual_weight = 0 and min_avg_qual = 0.0 both calls give hlmi_polish's / hlmi_polish_reads's file and `base`
+ * stats byte for byte; so they do with qual_weight = 1 on a FASTA read file or on a FASTQ file whose qualities are all '"'
+ * (Q1): every weight is then 1. */
+int hlmi_polish_q(const char *contigs, const char *reads, const char *paf, const hlmi_polish_qopts *o, const char *out_fa,
+                  hlmi_polish_qstats *st);
+/* hlmi_polish_reads with the same options: the file and every integer stat equal the chain hlmi_ava -> hlmi_polish_q; the three
+ * stated differences of hlmi_polish_reads still apply.  The read floor is applied where the rows are selected (a low row
+ * claims nothing, so it cannot shadow a shorter row of another read); rows_low_qual comes from a device counter. */
+int hlmi_polish_reads_q(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_qopts *po,
+                        const char *out_fa, hlmi_polish_qstats *st);
+
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
  * reads into a caller-owned device buffer (16 B per minimizer: two uint64), the caller
