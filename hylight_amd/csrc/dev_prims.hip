@@ -18,6 +18,42 @@ namespace hlmi {
 namespace {
 constexpr int WG = 256;
 
+// The library's merge-sort path (1025 .. 2^20 elements of a partial bit range) compares keys under the mask
+// ((1 << end_bit) - 1) ^ ((1 << begin_bit) - 1): with end_bit at the key's width the first shift is by the type's width, the
+// mask comes out as the bits BELOW begin_bit, and the array is ordered by those.  A range that starts above bit 0 and ends at
+// the key's top bit therefore never takes that path: merge_sort_limit 0 sends it to onesweep at every size above one block.
+// Every other range goes the way it always went.
+template <typename Sweep>
+using NoMergeSort = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, Sweep, 0>;
+template <typename K>
+bool top_range(int b0, int b1) { return b0 > 0 && b1 == (int)(8 * sizeof(K)); }
+
+template <typename Config, typename K, typename V>
+void radix_pairs_cfg(rocprim::double_buffer<K> &dk, rocprim::double_buffer<V> &dv, size_t n, int b0, int b1) {
+    size_t tmp_bytes = 0;
+    HIP_CHECK(rocprim::radix_sort_pairs<Config>(nullptr, tmp_bytes, dk, dv, n, b0, b1, stream()));
+    DBuf<char> tmp(tmp_bytes ? tmp_bytes : 1);
+    HIP_CHECK(rocprim::radix_sort_pairs<Config>(tmp.p, tmp_bytes, dk, dv, n, b0, b1, stream()));
+}
+template <typename Config, typename K>
+void radix_keys_cfg(rocprim::double_buffer<K> &dk, size_t n, int b0, int b1) {
+    size_t tmp_bytes = 0;
+    HIP_CHECK(rocprim::radix_sort_keys<Config>(nullptr, tmp_bytes, dk, n, b0, b1, stream()));
+    DBuf<char> tmp(tmp_bytes ? tmp_bytes : 1);
+    HIP_CHECK(rocprim::radix_sort_keys<Config>(tmp.p, tmp_bytes, dk, n, b0, b1, stream()));
+}
+// Config: the call's configuration (default_config: the library's own), Sweep: its onesweep part
+template <typename Config, typename Sweep, typename K, typename V>
+void radix_pairs(rocprim::double_buffer<K> &dk, rocprim::double_buffer<V> &dv, size_t n, int b0, int b1) {
+    if (top_range<K>(b0, b1)) radix_pairs_cfg<NoMergeSort<Sweep>>(dk, dv, n, b0, b1);
+    else radix_pairs_cfg<Config>(dk, dv, n, b0, b1);
+}
+template <typename Config, typename Sweep, typename K>
+void radix_keys(rocprim::double_buffer<K> &dk, size_t n, int b0, int b1) {
+    if (top_range<K>(b0, b1)) radix_keys_cfg<NoMergeSort<Sweep>>(dk, n, b0, b1);
+    else radix_keys_cfg<Config>(dk, n, b0, b1);
+}
+
 template <typename K, typename V>
 void sort_pairs_impl(K *keys, V *vals, size_t n, int b0, int b1) {
     if (n < 2) return;
@@ -25,10 +61,7 @@ void sort_pairs_impl(K *keys, V *vals, size_t n, int b0, int b1) {
     DBuf<V> v2(n);
     rocprim::double_buffer<K> dk(keys, k2.p);
     rocprim::double_buffer<V> dv(vals, v2.p);
-    size_t tmp_bytes = 0;
-    HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, dk, dv, n, b0, b1, stream()));
-    DBuf<char> tmp(tmp_bytes ? tmp_bytes : 1);
-    HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, dk, dv, n, b0, b1, stream()));
+    radix_pairs<rocprim::default_config, rocprim::default_config>(dk, dv, n, b0, b1);
     if (dk.current() != keys)
         HIP_CHECK(hipMemcpyAsync(keys, dk.current(), n * sizeof(K), hipMemcpyDeviceToDevice, stream()));
     if (dv.current() != vals)
@@ -53,10 +86,9 @@ __global__ __launch_bounds__(WG) void flag_scatter_kernel(const uint8_t *flags, 
 
 // (64-bit key + 32-bit value, the SNP event sort: 1024 x 6 per sort block measured 9.9 ms against 10.9 ms with the
 // default 512 x 16; 1024 x 8, 512 x 8 and 512 x 12 were slower)
-using PairsOnesweep = rocprim::radix_sort_config<
-    rocprim::default_config, rocprim::default_config,
-    rocprim::radix_sort_onesweep_config<rocprim::kernel_config<1024, 16>, rocprim::kernel_config<1024, 6>, 8,
-                                        rocprim::block_radix_rank_algorithm::match>>;
+using PairsSweep = rocprim::radix_sort_onesweep_config<rocprim::kernel_config<1024, 16>, rocprim::kernel_config<1024, 6>, 8,
+                                                       rocprim::block_radix_rank_algorithm::match>;
+using PairsOnesweep = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, PairsSweep>;
 
 void sort_pairs_u64_u32(uint64_t *k, uint32_t *v, size_t n, int b0, int b1) { sort_pairs_impl(k, v, n, b0, b1); }
 // (64-bit key + 64-bit value: the index and the anchor batches that do not fit one word; same shape as PairsOnesweep)
@@ -64,10 +96,7 @@ void sort_pairs_u64_u64(uint64_t *keys, uint64_t *vals, size_t n, int b0, int b1
     if (n < 2) return;
     DBuf<uint64_t> k2(n), v2(n);
     rocprim::double_buffer<uint64_t> dk(keys, k2.p), dv(vals, v2.p);
-    size_t tmp_bytes = 0;
-    HIP_CHECK(rocprim::radix_sort_pairs<PairsOnesweep>(nullptr, tmp_bytes, dk, dv, n, b0, b1, stream()));
-    DBuf<char> tmp(tmp_bytes ? tmp_bytes : 1);
-    HIP_CHECK(rocprim::radix_sort_pairs<PairsOnesweep>(tmp.p, tmp_bytes, dk, dv, n, b0, b1, stream()));
+    radix_pairs<PairsOnesweep, PairsSweep>(dk, dv, n, b0, b1);
     if (dk.current() != keys) HIP_CHECK(hipMemcpyAsync(keys, dk.current(), n * 8, hipMemcpyDeviceToDevice, stream()));
     if (dv.current() != vals) HIP_CHECK(hipMemcpyAsync(vals, dv.current(), n * 8, hipMemcpyDeviceToDevice, stream()));
 }
@@ -76,10 +105,7 @@ void sort_pairs_u32_u32(DBuf<uint32_t> &keys, DBuf<uint32_t> &vals, size_t n, in
     if (n < 2) return;
     DBuf<uint32_t> k2(keys.n), v2(vals.n);
     rocprim::double_buffer<uint32_t> dk(keys.p, k2.p), dv(vals.p, v2.p);
-    size_t tmp_bytes = 0;
-    HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, dk, dv, n, b0, b1, stream()));
-    DBuf<char> tmp(tmp_bytes ? tmp_bytes : 1);
-    HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, dk, dv, n, b0, b1, stream()));
+    radix_pairs<rocprim::default_config, rocprim::default_config>(dk, dv, n, b0, b1);
     if (dk.current() != keys.p) std::swap(keys, k2);
     if (dv.current() != vals.p) std::swap(vals, v2);
 }
@@ -93,10 +119,7 @@ static void sort_small_key_pairs(DBuf<K> &keys, DBuf<uint64_t> &vals, size_t n, 
     DBuf<uint64_t> v2(vals.n);
     rocprim::double_buffer<K> dk(keys.p, k2.p);
     rocprim::double_buffer<uint64_t> dv(vals.p, v2.p);
-    size_t tmp_bytes = 0;
-    HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, dk, dv, n, b0, b1, stream()));
-    DBuf<char> tmp(tmp_bytes ? tmp_bytes : 1);
-    HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, dk, dv, n, b0, b1, stream()));
+    radix_pairs<rocprim::default_config, rocprim::default_config>(dk, dv, n, b0, b1);
     if (dk.current() != keys.p) std::swap(keys, k2);
     if (dv.current() != vals.p) std::swap(vals, v2);
 }
@@ -107,10 +130,7 @@ void sort_keys_u64(uint64_t *keys, size_t n, int b0, int b1) {
     if (n < 2) return;
     DBuf<uint64_t> k2(n);
     rocprim::double_buffer<uint64_t> dk(keys, k2.p);
-    size_t tmp_bytes = 0;
-    HIP_CHECK(rocprim::radix_sort_keys(nullptr, tmp_bytes, dk, n, b0, b1, stream()));
-    DBuf<char> tmp(tmp_bytes ? tmp_bytes : 1);
-    HIP_CHECK(rocprim::radix_sort_keys(tmp.p, tmp_bytes, dk, n, b0, b1, stream()));
+    radix_keys<rocprim::default_config, rocprim::default_config>(dk, n, b0, b1);
     if (dk.current() != keys)
         HIP_CHECK(hipMemcpyAsync(keys, dk.current(), n * sizeof(uint64_t), hipMemcpyDeviceToDevice, stream()));
 }
@@ -121,10 +141,7 @@ void sort_pairs_u64_u32(DBuf<uint64_t> &keys, DBuf<uint32_t> &vals, size_t n, in
     DBuf<uint32_t> v2(vals.n);
     rocprim::double_buffer<uint64_t> dk(keys.p, k2.p);
     rocprim::double_buffer<uint32_t> dv(vals.p, v2.p);
-    size_t tmp_bytes = 0;
-    HIP_CHECK(rocprim::radix_sort_pairs<PairsOnesweep>(nullptr, tmp_bytes, dk, dv, n, b0, b1, stream()));
-    DBuf<char> tmp(tmp_bytes ? tmp_bytes : 1);
-    HIP_CHECK(rocprim::radix_sort_pairs<PairsOnesweep>(tmp.p, tmp_bytes, dk, dv, n, b0, b1, stream()));
+    radix_pairs<PairsOnesweep, PairsSweep>(dk, dv, n, b0, b1);
     if (dk.current() != keys.p) std::swap(keys, k2);
     if (dv.current() != vals.p) std::swap(vals, v2);
 }
@@ -132,19 +149,15 @@ void sort_pairs_u64_u32(DBuf<uint64_t> &keys, DBuf<uint32_t> &vals, size_t n, in
 // Onesweep shape for the big keys-only sorts (the anchor batches): 1024 x 8 keys per sort block, 1024 x 16 per histogram
 // block measured 18.1 ms per C2 step against 20.1 ms with the library's gfx950 default (512 x 8); 512 x 16, 256 x 16,
 // 1024 x 4 and 256 x 32 were slower.
-using KeysOnesweep = rocprim::radix_sort_config<
-    rocprim::default_config, rocprim::default_config,
-    rocprim::radix_sort_onesweep_config<rocprim::kernel_config<1024, 16>, rocprim::kernel_config<1024, 8>, 8,
-                                        rocprim::block_radix_rank_algorithm::match>>;
+using KeysSweep = rocprim::radix_sort_onesweep_config<rocprim::kernel_config<1024, 16>, rocprim::kernel_config<1024, 8>, 8,
+                                                      rocprim::block_radix_rank_algorithm::match>;
+using KeysOnesweep = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, KeysSweep>;
 
 void sort_keys_u64(DBuf<uint64_t> &keys, size_t n, int b0, int b1) {
     if (n < 2) return;
     DBuf<uint64_t> k2(keys.n);
     rocprim::double_buffer<uint64_t> dk(keys.p, k2.p);
-    size_t tmp_bytes = 0;
-    HIP_CHECK(rocprim::radix_sort_keys<KeysOnesweep>(nullptr, tmp_bytes, dk, n, b0, b1, stream()));
-    DBuf<char> tmp(tmp_bytes ? tmp_bytes : 1);
-    HIP_CHECK(rocprim::radix_sort_keys<KeysOnesweep>(tmp.p, tmp_bytes, dk, n, b0, b1, stream()));
+    radix_keys<KeysOnesweep, KeysSweep>(dk, n, b0, b1);
     if (dk.current() != keys.p) std::swap(keys, k2);      // the result sits in the other buffer: keep that one
 }
 
