@@ -147,6 +147,13 @@ class PolishQStats(C.Structure):
     _fields_ = [("base", PolishStats)] + [(k, C.c_uint64) for k in POLISH_QSTATS]
 
 
+POLISH_PSTATS = ("pairs_listed", "pairs_unknown", "rows_not_listed")
+
+
+class PolishPStats(C.Structure):
+    _fields_ = [("q", PolishQStats)] + [(k, C.c_uint64) for k in POLISH_PSTATS]
+
+
 ABI_VERSION = 7          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
@@ -234,6 +241,10 @@ SYMBOLS = {
     "hlmi_polish_q": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PolishQOpts), C.c_char_p, C.POINTER(PolishQStats)]),
     "hlmi_polish_reads_q": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PolishQOpts), C.c_char_p,
                                       C.POINTER(PolishQStats)]),
+    "hlmi_polish_pairs": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PolishQOpts), C.c_char_p, C.c_char_p,
+                                    C.POINTER(PolishPStats)]),
+    "hlmi_polish_reads_pairs": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PolishQOpts), C.c_char_p, C.c_char_p,
+                                          C.POINTER(PolishPStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -643,14 +654,21 @@ def cluster_short(paf, fastq, out_dir, size=15000, threads=20, **opts):
     return {k: getattr(st, k) for k in CLUSTER_STATS + CLUSTER_MS}
 
 
-def polish(contigs, reads, paf, out_fa, **opts):
+def polish(contigs, reads, paf, out_fa, pairs=None, **opts):
     """hlmi_polish: the pile-up consensus of `contigs` (FASTA / FASTQ) under the rows of `paf` (cg:Z: CIGARs in = X I D, as
     api.ava writes them) of `reads`, written to out_fa - the native stand-in for `racon --no-trimming -u` (a function of
     this project's own: include/hylight_mi.h states it, tests/polish_model.py is its contract).  Options: the fields of
     hlmi_polish_opts (min_len 0, min_iden 0.0, min_cov 3, include_unpolished 1).  -> dict of the stats (hlmi_polish_stats).
     With qual_weight= or min_avg_qual= the call is hlmi_polish_q (votes weighted by the reads' base qualities, rows of reads
     whose mean Phred is below min_avg_qual dropped; the one not given is off: 0 / 0.0; tests/polish_qual_model.py is the
-    contract) and the dict also holds reads_with_qual and rows_low_qual."""
+    contract) and the dict also holds reads_with_qual and rows_low_qual.
+    pairs=path: hlmi_polish_pairs - only rows whose (read, contig) pair is named by a row of that PAF-like list vote (fields 1
+    and 6, either order; tests/polish_pairs_model.py is the contract); the dict also holds the quality stats and pairs_listed,
+    pairs_unknown and rows_not_listed."""
+    if pairs is not None:
+        o, st = _polish_qopts("polish", opts), PolishPStats()
+        _check(load().hlmi_polish_pairs(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(pairs), _b(out_fa), C.byref(st)))
+        return _polish_pstats(st)
     if _wants_qual(opts):
         o, st = _polish_qopts("polish", opts), PolishQStats()
         _check(load().hlmi_polish_q(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(out_fa), C.byref(st)))
@@ -693,12 +711,23 @@ def _polish_qstats(st):
     return d
 
 
-def polish_reads(contigs, reads, out_fa, ava_opts=None, **polish_opts):
+def _polish_pstats(st):
+    d = _polish_qstats(st.q)
+    d.update({k: getattr(st, k) for k in POLISH_PSTATS})
+    return d
+
+
+def polish_reads(contigs, reads, out_fa, ava_opts=None, pairs=None, **polish_opts):
     """hlmi_polish_reads: `ava(contigs, reads, P, ava_opts)` and `polish(contigs, reads, P, out_fa, **polish_opts)` in one
     call without the PAF P - the same file and the same integer stats, the overlapper's rows never leaving the device.
     ava_opts None: the long constants.  Refused (HlmiError, code -1) besides what polish refuses: a name twice among the reads
     or among the contigs, ava_opts.stub_oh >= 0.  -> dict of the stats (hlmi_polish_stats).  qual_weight= / min_avg_qual=: as
-    for polish (hlmi_polish_reads_q)."""
+    for polish (hlmi_polish_reads_q).  pairs=path: as for polish (hlmi_polish_reads_pairs; the list is parsed on the device)."""
+    if pairs is not None:
+        o, st = _polish_qopts("polish_reads", polish_opts), PolishPStats()
+        _check(load().hlmi_polish_reads_pairs(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
+                                              _b(pairs), _b(out_fa), C.byref(st)))
+        return _polish_pstats(st)
     if _wants_qual(polish_opts):
         o, st = _polish_qopts("polish_reads", polish_opts), PolishQStats()
         _check(load().hlmi_polish_reads_q(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),

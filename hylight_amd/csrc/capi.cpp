@@ -557,6 +557,51 @@ int hlmi_polish_reads_q(const char *contigs, const char *reads, const hlmi_ava_o
     });
 }
 
+namespace {
+// what the two _pairs calls hand polish_run / polish_reads_run, and how it comes back
+struct PairsCall {
+    pol::PolQualCall qc;
+    pol::PolPairCall pc;
+    PairsCall(const hlmi_polish_qopts &o, const char *pairs_paf) {
+        qc.qual_weight = o.qual_weight != 0;
+        qc.min_avg_qual = o.min_avg_qual;
+        pc.path = pairs_paf;
+    }
+    pol::PolPairCall *list() { return pc.path ? &pc : nullptr; }      // no list: the _q call
+    void to(hlmi_polish_pstats *st) const {
+        st->q.reads_with_qual = qc.reads_with_qual;
+        st->q.rows_low_qual = qc.rows_low_qual;
+        st->pairs_listed = pc.pairs_listed;
+        st->pairs_unknown = pc.pairs_unknown;
+        st->rows_not_listed = pc.rows_not_listed;
+    }
+};
+}  // namespace
+
+int hlmi_polish_pairs(const char *contigs, const char *reads, const char *paf, const hlmi_polish_qopts *o, const char *pairs_paf,
+                      const char *out_fa, hlmi_polish_pstats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish_pairs: NULL argument");
+        require_device();
+        *st = hlmi_polish_pstats{};
+        PairsCall c(*o, pairs_paf);
+        polish_run(contigs, reads, paf, polish_base_opts(*o), out_fa, &st->q.base, &c.qc, c.list());
+        c.to(st);
+    });
+}
+
+int hlmi_polish_reads_pairs(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_qopts *po,
+                            const char *pairs_paf, const char *out_fa, hlmi_polish_pstats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !po || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish_reads_pairs: NULL argument");
+        require_device();
+        *st = hlmi_polish_pstats{};
+        PairsCall c(*po, pairs_paf);
+        polish_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), polish_base_opts(*po), out_fa, &st->q.base, &c.qc, c.list());
+        c.to(st);
+    });
+}
+
 hlmi_job *hlmi_job_open(const char *reads_fa, const char *ref_fa, int nsplit, int long_mode) {
     hlmi_job *j = nullptr;
     guarded([&] {

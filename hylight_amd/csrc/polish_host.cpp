@@ -5,6 +5,7 @@
 // PARITY UNPINNED: racon is not part of the reference tree; tests/polish_model.py is the contract.
 #include <algorithm>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <string_view>
 #include <unordered_map>
@@ -12,6 +13,7 @@
 
 #include "common.h"
 #include "paf_io.h"
+#include "pair_list.h"
 #include "polish_internal.h"
 #include "polish_rows.h"
 
@@ -40,7 +42,7 @@ struct Sel {
 }  // namespace
 
 void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
-                hlmi_polish_stats *st, PolQualCall *qc) {
+                hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
     const double t_begin = now_ms();
     *st = hlmi_polish_stats{};
     if (o.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish: min_cov %d (< 1)", o.min_cov);
@@ -76,6 +78,32 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
         read_of[k] = r == read_named.end() ? -1 : (int64_t)r->second;
     }
 
+    // hlmi_polish_pairs: the list (pair_list.h) over the names of this call.  What is wrong with the list itself is reported
+    // behind the refusals of the rows below; until then no row is tested against it.
+    std::string list_text;
+    PairSet listed;
+    std::unique_ptr<Error> list_error;
+    std::vector<uint32_t> known_of;                          // PAF name id -> id among the call's names (every row's names are known)
+    if (pc) {
+        KnownNames known;
+        known.add(rs.names);
+        known.add(cs.names);
+        try {
+            list_text = read_file(pc->path);
+            std::vector<PairLine> lines;
+            if (const uint64_t bad = scan_pair_list(list_text, lines))
+                fail(HLMI_EINVAL, "hlmi_polish_pairs: %s:%llu: a list row has fewer than 6 fields", pc->path, (unsigned long long)bad);
+            listed = make_pair_set(lines, known);
+        } catch (const Error &e) {
+            list_error = std::make_unique<Error>(e);
+        }
+        known_of.resize(pt.dict.names.size());
+        for (size_t k = 0; k < pt.dict.names.size(); ++k) known_of[k] = (uint32_t)std::max<int64_t>(known.find(pt.dict.names[k]), 0);
+        pc->pairs_listed = listed.listed;
+        pc->pairs_unknown = listed.unknown;
+        pc->rows_not_listed = 0;
+    }
+
     // the refusals, row by row, and the selection
     std::unordered_map<uint32_t, Sel> best;                  // query name -> its row so far
     for (size_t i = 0; i < n; ++i) {
@@ -104,12 +132,14 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
         const uint32_t span = r.te - r.ts;
         if (r.qid == r.tid) continue;
         if (!low.empty() && low[ri]) { ++qc->rows_low_qual; continue; }
+        if (pc && !list_error && !listed.has(known_of[r.qid], known_of[r.tid])) { ++pc->rows_not_listed; continue; }
         if (span == 0 || (int64_t)span < (int64_t)o.min_len) continue;
         if ((double)n_eq / (double)n_all < o.min_iden) continue;
         const auto it = best.find(r.qid);
         if (it == best.end()) best.emplace(r.qid, Sel{i, ci, ri});
         else if (span > pt.recs[it->second.line].te - pt.recs[it->second.line].ts) it->second = Sel{i, ci, ri};
     }
+    if (list_error) throw *list_error;
     std::vector<Sel> sel;
     sel.reserve(best.size());
     for (const auto &kv : best) sel.push_back(kv.second);

@@ -101,12 +101,28 @@ std::vector<uint8_t> polish_read_quals(const char *who, const char *reads, doubl
 // qual_weight = 1: rows_selected x 93 must fit the 32-bit weight sums
 void polish_check_weight_width(const char *who, const PolQualCall *qc, uint64_t rows_selected);
 
+// The pair list of a _pairs call (nullptr: no list, every row may vote).  In: the list's path; out: the three counters of
+// hlmi_polish_pstats.  The list's text is scanned by pair_list.h in hlmi_polish_pairs and by polish_pairs.hip in the fused call.
+struct PolPairCall {
+    const char *path = nullptr;
+    uint64_t pairs_listed = 0, pairs_unknown = 0, rows_not_listed = 0;
+};
+// hlmi_polish_reads_pairs (polish_pairs.hip): the list parsed on the device against the call's name ranks (AvaPairCall::
+// name_of_rank, the qid / tid space of the overlapper's rows) -> the distinct keys rank_a << 32 | rank_b of the listed pairs in
+// both orders, ascending (at least one element is allocated: a null pointer means "no list" to pr_facts_kernel).  A line with
+// fewer than 6 fields is HLMI_EINVAL naming `who` and the line.  Sets pc.pairs_listed and pc.pairs_unknown.
+struct PairKeys {
+    DBuf<uint64_t> keys;
+    size_t n = 0;
+};
+void pair_keys_device(const char *who, const std::vector<std::string> &name_of_rank, PolPairCall &pc, PairKeys &out);
+
 }  // namespace pol
 
 void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
-                hlmi_polish_stats *st, pol::PolQualCall *qc = nullptr);
+                hlmi_polish_stats *st, pol::PolQualCall *qc = nullptr, pol::PolPairCall *pc = nullptr);
 // hlmi_polish_reads (polish_rows.hip): the overlapper's rows selected, ordered and compacted where they are
 void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
-                      const char *out_fa, hlmi_polish_stats *st, pol::PolQualCall *qc = nullptr);
+                      const char *out_fa, hlmi_polish_stats *st, pol::PolQualCall *qc = nullptr, pol::PolPairCall *pc = nullptr);
 
 }  // namespace hlmi

@@ -12,6 +12,8 @@
 // decisions and the bases are polish.hip's (polish_core), headers and file polish_host.cpp's (polish_layout, polish_emit).
 // hlmi_polish_reads_q: the resident reads hold codes only, so the quality bytes go up as one array at the offsets of
 // DevReads::codes() (PolRow::read_off indexes both), and the read floor is one byte per name rank that pr_facts_kernel looks up.
+// hlmi_polish_reads_pairs: the list becomes a sorted array of keys qid << 32 | tid on the device (polish_pairs.hip), and
+// pr_facts_kernel looks a row's key up with the whole wave (wave_search.h) directly behind the floor.
 //
 // Why a wave per row in the first kernel and a thread per row in the last two: the first reads the ops of EVERY row (all of
 // the CIGAR traffic of this file), needs two sums and nothing else of them, so 64 consecutive words per load and a DPP sum fit;
@@ -27,6 +29,7 @@
 #include "polish_internal.h"
 #include "polish_rows.h"
 #include "wave_ops.h"
+#include "wave_search.h"
 
 namespace hlmi {
 
@@ -43,7 +46,9 @@ inline dim3 grid1(size_t n) { return dim3((unsigned)std::min<size_t>(cdiv(n ? n 
 
 __global__ __launch_bounds__(WG) void pr_facts_kernel(const PafRec *__restrict__ recs, size_t n_rows, const uint32_t *__restrict__ ops_base,
                                                       int min_len, double min_iden, unsigned long long *__restrict__ best,
-                                                      const uint8_t *__restrict__ low_of_rank, unsigned long long *__restrict__ n_low) {
+                                                      const uint8_t *__restrict__ low_of_rank, unsigned long long *__restrict__ n_low,
+                                                      const uint64_t *__restrict__ pair_keys, size_t n_keys,
+                                                      unsigned long long *__restrict__ n_unlisted) {
     const int lane = threadIdx.x & 63;
     const size_t n_waves = (size_t)gridDim.x * WAVES;
     for (size_t i = (size_t)blockIdx.x * WAVES + (threadIdx.x >> 6); i < n_rows; i += n_waves) {
@@ -52,6 +57,10 @@ __global__ __launch_bounds__(WG) void pr_facts_kernel(const PafRec *__restrict__
         if (r.qid == r.tid) continue;                                                           // (the same in every lane)
         if (low_of_rank && low_of_rank[r.qid]) {        // the read floor (nullptr: off): the row claims nothing, and is counted
             if (lane == 0) atomicAdd(n_low, 1ull);
+            continue;
+        }
+        if (pair_keys && !wave_contains_u64(pair_keys, n_keys, (uint64_t)r.qid << 32 | r.tid)) {    // the pair list (nullptr: off)
+            if (lane == 0) atomicAdd(n_unlisted, 1ull);
             continue;
         }
         if (span == 0 || (int64_t)span < (int64_t)min_len) continue;
@@ -159,7 +168,7 @@ std::vector<uint32_t> record_of_rank(const SeqSet &s, const std::vector<uint32_t
 }  // namespace
 
 void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
-                      const char *out_fa, hlmi_polish_stats *st, PolQualCall *qc) {
+                      const char *out_fa, hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
     const double t_begin = now_ms();
     *st = hlmi_polish_stats{};
     stat_reset();
@@ -184,6 +193,8 @@ void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opt
     if (R >= (1ull << 32)) fail(HLMI_EINVAL, "hlmi_polish_reads: %zu overlapper rows (2^32 and more)", R);
     st->rows = R;
     st->contigs = cs.size();
+    PairKeys pk;                                // hlmi_polish_reads_pairs: the list's own refusal comes behind the ones above
+    if (pc) pair_keys_device("hlmi_polish_reads_pairs", call.name_of_rank, *pc, pk);
 
     // ---- selection and order ----------------------------------------------------------------------------------------------------
     size_t S = 0;
@@ -192,7 +203,7 @@ void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opt
         KTimer kt("polish_rows");
         DBuf<unsigned long long> best(n_ranks);
         DBuf<uint8_t> flag(R), d_low;
-        DBuf<unsigned long long> n_low(1);
+        DBuf<unsigned long long> n_low(2);      // rows of low reads, rows whose pair is not listed
         best.zero();
         n_low.zero();
         if (!low.empty()) {
@@ -200,12 +211,18 @@ void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opt
             for (size_t i = 0; i < rs.size(); ++i) low_of_rank[call.rq[i]] = low[i];
             d_low.upload(low_of_rank);
         }
-        hipLaunchKernelGGL(pr_facts_kernel, dim3((unsigned)std::min<size_t>(cdiv(R, WAVES), MAX_GRID)), dim3(WG), 0, stream(), rows.recs.p,
-                           R, rows.ops_base, po.min_len, po.min_iden, best.p, low.empty() ? nullptr : d_low.p, n_low.p);
+        // a wave per row up to MAX_GRID workgroups (262 144 rows), then a wave takes several; the hook lowers the cap so that
+        // the tests reach that with a few dozen rows
+        unsigned facts_grid = MAX_GRID;
+        if (const char *e = hook("HLMI_POLISH_ROWS_GRID")) facts_grid = (unsigned)std::min<long>(std::max<long>(1, atol(e)), MAX_GRID);
+        hipLaunchKernelGGL(pr_facts_kernel, dim3((unsigned)std::min<size_t>(cdiv(R, WAVES), facts_grid)), dim3(WG), 0, stream(), rows.recs.p,
+                           R, rows.ops_base, po.min_len, po.min_iden, best.p, low.empty() ? nullptr : d_low.p, n_low.p,
+                           pc ? pk.keys.p : nullptr, pk.n, n_low.p + 1);
         hipLaunchKernelGGL(pr_winner_kernel, grid1(R), dim3(WG), 0, stream(), rows.recs.p, R, best.p, flag.p);
         HIP_CHECK(hipGetLastError());
         S = select_flagged_indices(flag.p, idx.p, R);
         if (qc) qc->rows_low_qual = download_one(n_low.p);
+        if (pc) pc->rows_not_listed = download_one(n_low.p + 1);
     }
     st->rows_selected = S;
     polish_check_weight_width("hlmi_polish_reads_q", qc, S);

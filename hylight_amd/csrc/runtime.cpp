@@ -198,6 +198,7 @@ const char *const HOOK_NAMES[] = {
     "HLMI_NARROW_LONG_UNPACKED",
     "HLMI_NARROW_UNPACKED",
     "HLMI_NO_EXT_CERT",
+    "HLMI_POLISH_ROWS_GRID",
     "HLMI_NO_GAP1_CERT",
     "HLMI_NO_GAP2_CERT",
     "HLMI_NO_ONE_PIECE_CERT",

@@ -164,15 +164,19 @@ def extend_con(input_con, outdir1, out_file, threads=30, len_c=50000000, stageb_
     return n
 
 
-def polish_native(k, reads, contigs, out_fa, tmp, min_len, iden, short=False, append=False, direct=False, qual=None):
+def polish_native(k, reads, contigs, out_fa, tmp, min_len, iden, short=False, append=False, direct=False, qual=None, pairs=None):
     """One racon site with the library's own polisher (`--polish_native`): the reads are aligned to the contigs once more
     (hlmi_ava, every pair: the stage's scored PAF carries no CIGAR) into tmp/polish_<k>.paf, and hlmi_polish votes over those
     rows.  `direct` (`--polish_direct`): both in one call (hlmi_polish_reads) with the same options - the same file, and no
     tmp/polish_<k>.paf.  `append`: out_fa grows, as the `>>` of HyLight.py:182 does.  `qual` (`--polish_qual`): the read floor Q -
-    votes weighted by base quality and rows of reads below mean quality Q dropped (hlmi_polish_q / hlmi_polish_reads_q)."""
+    votes weighted by base quality and rows of reads below mean quality Q dropped (hlmi_polish_q / hlmi_polish_reads_q).  `pairs`
+    (`--polish_strain`): the stage's filtered PAF of this site - only its (read, contig) pairs vote (hlmi_polish_pairs /
+    hlmi_polish_reads_pairs), as racon only ever sees those rows in the reference."""
     popts = dict(min_len=min_len, min_iden=iden)
     if qual is not None:
         popts.update(qual_weight=1, min_avg_qual=qual)
+    if pairs is not None:
+        popts.update(pairs=pairs)
     o = api.ava_opts_short() if short else api.ava_opts_long()
     o.pair_once = 0
     part = out_fa + ".part" if append else out_fa
@@ -246,6 +250,10 @@ def build_parser():
                    help="(extension) with --polish_native or --polish_direct: weigh the polisher's votes by the reads' base "
                         "qualities and drop reads of low mean quality (hlmi_polish_q; the short-read FASTQ of the third site "
                         "carries qualities, the long-read FASTA of the first two does not)")
+    p.add_argument("--polish_strain", action="store_true",
+                   help="(extension) with --polish_native or --polish_direct: only the (read, contig) pairs the overlap stage's "
+                        "SNP filter kept vote at the three polishing sites (hlmi_polish_pairs with ov_long_ref.paf, the round's "
+                        "ov_long_ref2.paf and shortr1.paf), as the reference's racon calls see only those rows")
     p.add_argument("--polish_min_avg_qual", type=float, default=10.0, metavar="Q",
                    help="with --polish_qual: reads whose mean Phred quality is below Q do not vote (racon's -q)")
     return p
@@ -362,6 +370,8 @@ def main(argv=None):
         raise SystemExit("--polyte_native and --polyte_cmd are two ways to run the same step: give one of them")
     if args.polish_qual and not (args.polish_native or args.polish_direct):
         raise SystemExit("--polish_qual is an option of the library's polisher: give --polish_native or --polish_direct with it")
+    if args.polish_strain and not (args.polish_native or args.polish_direct):
+        raise SystemExit("--polish_strain is an option of the library's polisher: give --polish_native or --polish_direct with it")
     if args.polish_native and args.polish_direct:
         raise SystemExit("--polish_native and --polish_direct are two ways to run the same step: give one of them")
     refuse_polyte_workers(args)
@@ -432,7 +442,8 @@ def _pipeline(args, pool):
     racon = None if native else _tool("racon")
     p1, p2 = tmp + "polish1.fa", tmp + "polish2.fa"
     if native:
-        polish_native(1, infile, long_con, p1, tmp, len_over, iden, direct=args.polish_direct, qual=pqual)
+        polish_native(1, infile, long_con, p1, tmp, len_over, iden, direct=args.polish_direct, qual=pqual,
+                      pairs=ov_long_ref if args.polish_strain else None)      # (as it is now: it grows below)
     else:
         _run(f"{racon} --no-trimming -u -t 30 {infile} {ov_long_ref} {long_con} > {p1}", cwd=tmp)
     ti = 0
@@ -450,7 +461,7 @@ def _pipeline(args, pool):
         ov2 = stage(infile, remain_con, nsplit, tmp + "ov_long_ref2.paf", len_over, 2, iden)
         if native:
             polish_native(2 if ti == 0 else f"2_{ti}", infile, remain_con, p2, tmp, len_over, iden, append=True, direct=args.polish_direct,
-                          qual=pqual)
+                          qual=pqual, pairs=ov2 if args.polish_strain else None)
             with open(ov2, "rb") as f, open(ov_long_ref, "ab") as w:
                 shutil.copyfileobj(f, w)
         else:
@@ -475,7 +486,8 @@ def _pipeline(args, pool):
     ov_short = stage(short_reads, long_con2, nsplit, tmp + "shortr1.paf", 70, 3, iden, long=False)
     long_con3 = os.path.join(outdir, "long_con_polished.fa")
     if native:
-        polish_native(3, short_reads, long_con2, long_con3, tmp, 70, iden, short=True, direct=args.polish_direct, qual=pqual)
+        polish_native(3, short_reads, long_con2, long_con3, tmp, 70, iden, short=True, direct=args.polish_direct, qual=pqual,
+                      pairs=ov_short if args.polish_strain else None)
     else:
         _run(f"{racon} --no-trimming -u -t 30 {short_reads} {ov_short} {long_con2} > {long_con3}", cwd=outdir)
     remain_short = pick_up(ov_short, tmp, short_reads)

@@ -10,6 +10,8 @@ writes them.  Without --paf the reads are aligned to the contigs in the same cal
 constants, --short: its short-read ones; every pair, pair_once = 0, as the driver's polishing sites do) and no PAF exists.
 --qual_weight weighs every vote by the read base's Phred quality and --min_avg_qual Q drops the rows of reads whose mean quality
 is below Q (hlmi_polish_q / hlmi_polish_reads_q; FASTQ reads - a FASTA read's bases weigh 1 and it is never dropped).
+--pairs FILE lets only the rows vote whose (read, contig) pair a row of FILE names (hlmi_polish_pairs / hlmi_polish_reads_pairs:
+a PAF-like list, fields 1 and 6, either order - the overlap stage's filtered rows make the polisher strain-aware).
 Prints the stats as one JSON line.  Exit status 0 on success.
 """
 from __future__ import annotations
@@ -37,6 +39,8 @@ def build_parser():
     p.add_argument("--qual_weight", action="store_true", help="weigh votes by the reads' base qualities (FASTQ reads)")
     p.add_argument("--min_avg_qual", type=float, default=None, metavar="Q",
                    help="drop rows of reads whose mean Phred quality is below Q (racon -q; not given: no such test)")
+    p.add_argument("--pairs", default=None, metavar="FILE",
+                   help="PAF-like list (fields 1 and 6): only rows of a listed (read, contig) pair vote (not given: every row may)")
     return p
 
 
@@ -55,6 +59,8 @@ def main(argv=None):
         opts["qual_weight"] = 1
     if a.min_avg_qual is not None:
         opts["min_avg_qual"] = a.min_avg_qual
+    if a.pairs is not None:
+        opts["pairs"] = a.pairs
     if a.paf is not None:
         if a.short:
             parser.error("--short chooses the alignment of a call without --paf")

@@ -804,6 +804,46 @@ int hlmi_polish_q(const char *contigs, const char *reads, const char *paf, const
 int hlmi_polish_reads_q(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_qopts *po,
                         const char *out_fa, hlmi_polish_qstats *st);
 
+/* ---- strain-aware polishing: only the pairs a list names vote.  HyLight's strain awareness is the SNP-support filter of its
+ * overlap stage (filter_overlap_slr2.py), and the reference hands racon the FILTERED read-to-contig rows (HyLight.py:152,182,203:
+ * ov_long_ref.paf, ov_long_ref2.paf, shortr1.paf).  hlmi_polish_pairs and hlmi_polish_reads_pairs are hlmi_polish_q and
+ * hlmi_polish_reads_q with such a list as an option; the older calls keep their signatures and their bytes, and HLMI_ABI_VERSION
+ * stays where it is (new symbols).  A rule of the project's own: PARITY with racon UNPINNED; tests/polish_pairs_model.py is the
+ * contract, byte for byte. */
+typedef struct {
+    hlmi_polish_qstats q;
+    uint64_t pairs_listed;     /* distinct unordered pairs of two different names of the list with BOTH names known          */
+    uint64_t pairs_unknown;    /* list rows with a name that is neither a read nor a contig of this call (ignored)           */
+    uint64_t rows_not_listed;  /* alignment rows dropped because their pair is not listed                                    */
+} hlmi_polish_pstats;
+/* Where a rule below is silent, hlmi_polish_q's rule holds unchanged.
+ * No list: with pairs_paf == NULL the call is hlmi_polish_q: the same file, the same `q` stats, the three counters 0.
+ * List file format: a PAF-like text, in practice the stage's scored 14-column rows.  Lines end at '\n'; a last line without
+ * one counts; a '\r' in front of the '\n' belongs to the line's last field and is not stripped.  Fields are split at TAB and
+ * only fields 1 and 6 are read: 12-column PAF, the stage's 14-column rows and rows with tags are all accepted.  A line with fewer
+ * than 6 fields, an empty line included, is HLMI_EINVAL; the message names the 1-based line and nothing is written.  An empty
+ * file is a valid list of no pairs: no row votes.
+ * Meaning: a name is known when it is the name of a record of `reads` or of `contigs`.  A list row with an unknown name is
+ * ignored and counted in pairs_unknown (the driver's ov_long_ref.paf grows by rows against other contig sets).  An alignment
+ * row (query q, target t) is listed when some list row of two known names has fields (1, 6) equal to (q, t) or to (t, q),
+ * compared byte for byte: the order inside a list row does not matter.  Duplicate list rows are allowed.  A list row that names
+ * one name twice lists nothing (rows with qname == tname are skipped before the list is asked) and counts nowhere.
+ * Where in the selection: qname == tname skip; the read floor (rows_low_qual); a row that is not listed is dropped and counted
+ * in rows_not_listed; then te == ts / min_len; min_iden; one row per read.  A row that is not listed claims nothing: it cannot
+ * shadow a shorter listed row of the same read.
+ * Refusals: every refusal of hlmi_polish_q about the options, the files and the rows comes first, in its order; then a list that
+ * cannot be read (HLMI_EIO) or has a short line; then the refusals about the selected rows (the counter width, 2^31 contig
+ * bases).  Nothing is written in any of these cases. */
+int hlmi_polish_pairs(const char *contigs, const char *reads, const char *paf, const hlmi_polish_qopts *o, const char *pairs_paf,
+                      const char *out_fa, hlmi_polish_pstats *st);
+/* hlmi_polish_reads_q with the same option: the file and every integer stat equal the chain hlmi_ava -> hlmi_polish_pairs.  The
+ * list never visits the host's parser: its bytes go to the device, where the lines are split, fields 1 and 6 are looked up in a
+ * hash table of the call's names and the listed pairs become a sorted array of keys that the row selection searches
+ * (csrc/polish_pairs.hip).  The aligner still aligns every pair; the list only decides who votes.  One more refusal: a list of
+ * 2^31 bytes or more is HLMI_EINVAL. */
+int hlmi_polish_reads_pairs(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_qopts *po,
+                            const char *pairs_paf, const char *out_fa, hlmi_polish_pstats *st);
+
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
  * reads into a caller-owned device buffer (16 B per minimizer: two uint64), the caller
