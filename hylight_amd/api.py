@@ -154,6 +154,18 @@ class PolishPStats(C.Structure):
     _fields_ = [("q", PolishQStats)] + [(k, C.c_uint64) for k in POLISH_PSTATS]
 
 
+class DepthOpts(C.Structure):
+    _fields_ = [("min_len", C.c_int), ("min_iden", C.c_double)]
+
+
+DEPTH_STATS = ("rows", "rows_selected", "contigs", "contigs_covered", "positions", "covered", "bases", "runs", "pairs_listed",
+               "pairs_unknown", "rows_not_listed")
+
+
+class DepthStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in DEPTH_STATS] + [(k, C.c_double) for k in POLISH_MS]
+
+
 ABI_VERSION = 7          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
@@ -245,6 +257,12 @@ SYMBOLS = {
                                     C.POINTER(PolishPStats)]),
     "hlmi_polish_reads_pairs": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PolishQOpts), C.c_char_p, C.c_char_p,
                                           C.POINTER(PolishPStats)]),
+    # read depth and abundance per contig
+    "hlmi_depth_opts_default": (None, [C.POINTER(DepthOpts)]),
+    "hlmi_depth": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(DepthOpts), C.c_char_p, C.c_char_p, C.c_char_p,
+                             C.POINTER(DepthStats)]),
+    "hlmi_depth_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(DepthOpts), C.c_char_p, C.c_char_p, C.c_char_p,
+                                   C.POINTER(DepthStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -738,6 +756,37 @@ def polish_reads(contigs, reads, out_fa, ava_opts=None, pairs=None, **polish_opt
     _check(load().hlmi_polish_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
                                     _b(out_fa), C.byref(st)))
     return {k: getattr(st, k) for k in POLISH_STATS + POLISH_MS}
+
+
+def _depth_opts(who, opts):
+    o = DepthOpts()
+    load().hlmi_depth_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(DepthOpts._fields_):
+            raise TypeError(f"{who}: unknown option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def depth(contigs, reads, paf, out_tsv, out_bedgraph=None, pairs=None, **opts):
+    """hlmi_depth: read depth and relative abundance of every contig of `contigs` under the rows of `paf` (as api.polish reads
+    them; one row per read, api.polish's selection with pairs=, without a quality floor).  Writes the table out_tsv (contig,
+    length, reads, bases, covered, mean_depth, median_depth, abundance) and, when given, the runs of equal depth as the
+    bedGraph out_bedgraph.  Options: min_len 0, min_iden 0.0.  A function of this project's own: include/hylight_mi.h states
+    it, tests/depth_model.py is its contract.  -> dict of the stats (hlmi_depth_stats)."""
+    o, st = _depth_opts("depth", opts), DepthStats()
+    _check(load().hlmi_depth(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(pairs), _b(out_tsv), _b(out_bedgraph), C.byref(st)))
+    return {k: getattr(st, k) for k in DEPTH_STATS + POLISH_MS}
+
+
+def depth_reads(contigs, reads, out_tsv, out_bedgraph=None, ava_opts=None, pairs=None, **opts):
+    """hlmi_depth_reads: `ava(contigs, reads, P, ava_opts)` and `depth(contigs, reads, P, ...)` in one call without the PAF P:
+    the same files and the same integer stats.  ava_opts None: the long constants.  Refused besides what depth refuses:
+    ava_opts.stub_oh >= 0.  -> dict of the stats (hlmi_depth_stats)."""
+    o, st = _depth_opts("depth_reads", opts), DepthStats()
+    _check(load().hlmi_depth_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), _b(pairs),
+                                   _b(out_tsv), _b(out_bedgraph), C.byref(st)))
+    return {k: getattr(st, k) for k in DEPTH_STATS + POLISH_MS}
 
 
 DEVICE = "cuda"          # where the buffers that cross the C ABI live (stage.py allocates them with torch)

@@ -4,6 +4,7 @@
 
 #include "ava.h"
 #include "common.h"
+#include "depth_internal.h"
 #include "filter_stage.h"
 #include "graph.h"
 #include "paf_io.h"
@@ -599,6 +600,28 @@ int hlmi_polish_reads_pairs(const char *contigs, const char *reads, const hlmi_a
         PairsCall c(*po, pairs_paf);
         polish_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), polish_base_opts(*po), out_fa, &st->q.base, &c.qc, c.list());
         c.to(st);
+    });
+}
+
+void hlmi_depth_opts_default(hlmi_depth_opts *o) {
+    if (o) *o = hlmi_depth_opts{0, 0.0};
+}
+
+int hlmi_depth(const char *contigs, const char *reads, const char *paf, const hlmi_depth_opts *o, const char *pairs_paf,
+               const char *out_tsv, const char *out_bedgraph, hlmi_depth_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_tsv || !st) fail(HLMI_EINVAL, "hlmi_depth: NULL argument");
+        require_device();
+        depth_run(contigs, reads, paf, *o, pairs_paf, out_tsv, out_bedgraph, st);
+    });
+}
+
+int hlmi_depth_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_depth_opts *o,
+                     const char *pairs_paf, const char *out_tsv, const char *out_bedgraph, hlmi_depth_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !o || !out_tsv || !st) fail(HLMI_EINVAL, "hlmi_depth_reads: NULL argument");
+        require_device();
+        depth_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_tsv, out_bedgraph, st);
     });
 }
 

@@ -2,6 +2,8 @@
 // tiles the device works on (sorted by contig and start), the statistics, the headers and the file.  The votes, the
 // decisions and the bases are polish.hip's.  The layout (contigs side by side, tiles) and the output (statistics, headers,
 // file) are functions of their own: hlmi_polish_reads (polish_rows.hip) selects its rows on the device and shares them.
+// The reading, the refusals and the row selection are pol::select_paf_rows (polish_select.h), which hlmi_depth (depth_host.cpp)
+// calls as well.
 // PARITY UNPINNED: racon is not part of the reference tree; tests/polish_model.py is the contract.
 #include <algorithm>
 #include <cstdio>
@@ -16,6 +18,7 @@
 #include "pair_list.h"
 #include "polish_internal.h"
 #include "polish_rows.h"
+#include "polish_select.h"
 
 namespace hlmi {
 
@@ -24,42 +27,32 @@ using namespace pol;
 namespace {
 
 // name -> first record of that name
-std::unordered_map<std::string_view, uint32_t> first_records(const SeqSet &s, const char *path) {
+std::unordered_map<std::string_view, uint32_t> first_records(const SeqSet &s, const char *path, const SelectNames &who) {
     std::unordered_map<std::string_view, uint32_t> m;
     m.reserve(s.size() * 2);
     for (size_t i = 0; i < s.size(); ++i) {
-        if (s.len(i) >= MAX_SEQ) fail(HLMI_EINVAL, "hlmi_polish: %s: %s has 2^28 bases or more", path, s.names[i].c_str());
-        m.emplace(s.names[i], (uint32_t)i);
+        if (s.len(i) >= MAX_SEQ) fail(HLMI_EINVAL, "%s: %s: %s has 2^28 bases or more", who.seqs, path, s.names[i].c_str());
+        if (!m.emplace(s.names[i], (uint32_t)i).second && who.unique_names)
+            fail(HLMI_EINVAL, "%s: %s: two records are named %s", who.seqs, path, s.names[i].c_str());
     }
     return m;
 }
 
-struct Sel {
-    size_t line;            // 0-based PAF line
-    uint32_t contig, read;
-};
-
 }  // namespace
 
-void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
-                hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
-    const double t_begin = now_ms();
-    *st = hlmi_polish_stats{};
-    if (o.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish: min_cov %d (< 1)", o.min_cov);
-    SeqSet cs, rs;
-    SeqQual rq;
+namespace pol {
+
+void select_paf_rows(const char *contigs, const char *reads, const char *paf, int min_len, double min_iden, const SelectNames &who,
+                     PolQualCall *qc, PolPairCall *pc, PafSelection &out) {
+    SeqSet &cs = out.cs, &rs = out.rs;
+    PafText &pt = out.pt;
     std::vector<uint8_t> low;                                // hlmi_polish_q: per read record, its mean quality is below the floor
     read_seqs(contigs, cs);
-    if (qc) low = polish_read_quals("hlmi_polish_q", reads, qc->min_avg_qual, rs, rq, *qc);
+    if (qc) low = polish_read_quals(who.quals, reads, qc->min_avg_qual, rs, out.rq, *qc);
     else read_seqs(reads, rs);
-    const bool weighted = qc && qc->qual_weight;
-    const auto contig_named = first_records(cs, contigs), read_named = first_records(rs, reads);
-    PafText pt;
+    const auto contig_named = first_records(cs, contigs, who), read_named = first_records(rs, reads, who);
     read_paf(paf, pt, false);
     const size_t n = pt.recs.size();
-    st->rows = n;
-    st->contigs = cs.size();
-
     // what read_paf lets through and this call does not: a row of 11 columns, a CIGAR that ends in a number
     std::vector<uint8_t> has_tag(n), is_star(n);
     for (size_t i = 0; i < n; ++i) {
@@ -92,7 +85,7 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
             list_text = read_file(pc->path);
             std::vector<PairLine> lines;
             if (const uint64_t bad = scan_pair_list(list_text, lines))
-                fail(HLMI_EINVAL, "hlmi_polish_pairs: %s:%llu: a list row has fewer than 6 fields", pc->path, (unsigned long long)bad);
+                fail(HLMI_EINVAL, "%s: %s:%llu: a list row has fewer than 6 fields", who.list, pc->path, (unsigned long long)bad);
             listed = make_pair_set(lines, known);
         } catch (const Error &e) {
             list_error = std::make_unique<Error>(e);
@@ -105,7 +98,7 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
     }
 
     // the refusals, row by row, and the selection
-    std::unordered_map<uint32_t, Sel> best;                  // query name -> its row so far
+    std::unordered_map<uint32_t, PafSel> best;                  // query name -> its row so far
     for (size_t i = 0; i < n; ++i) {
         const PafRec &r = pt.recs[i];
         const uint32_t *op = pt.ops.data() + r.cig_off;
@@ -133,34 +126,53 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
         if (r.qid == r.tid) continue;
         if (!low.empty() && low[ri]) { ++qc->rows_low_qual; continue; }
         if (pc && !list_error && !listed.has(known_of[r.qid], known_of[r.tid])) { ++pc->rows_not_listed; continue; }
-        if (span == 0 || (int64_t)span < (int64_t)o.min_len) continue;
-        if ((double)n_eq / (double)n_all < o.min_iden) continue;
+        if (span == 0 || (int64_t)span < (int64_t)min_len) continue;
+        if ((double)n_eq / (double)n_all < min_iden) continue;
         const auto it = best.find(r.qid);
-        if (it == best.end()) best.emplace(r.qid, Sel{i, ci, ri});
-        else if (span > pt.recs[it->second.line].te - pt.recs[it->second.line].ts) it->second = Sel{i, ci, ri};
+        if (it == best.end()) best.emplace(r.qid, PafSel{i, ci, ri});
+        else if (span > pt.recs[it->second.line].te - pt.recs[it->second.line].ts) it->second = PafSel{i, ci, ri};
     }
     if (list_error) throw *list_error;
-    std::vector<Sel> sel;
+    std::vector<PafSel> &sel = out.sel;
+    sel.clear();
     sel.reserve(best.size());
     for (const auto &kv : best) sel.push_back(kv.second);
-    std::sort(sel.begin(), sel.end(), [&](const Sel &a, const Sel &b) {      // by (contig, start), the line last
+    std::sort(sel.begin(), sel.end(), [&](const PafSel &a, const PafSel &b) {      // by (contig, start), the line last
         if (a.contig != b.contig) return a.contig < b.contig;
         const uint32_t sa = pt.recs[a.line].ts, sb = pt.recs[b.line].ts;
         return sa != sb ? sa < sb : a.line < b.line;
     });
+}
+
+}  // namespace pol
+
+void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
+                hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
+    const double t_begin = now_ms();
+    *st = hlmi_polish_stats{};
+    if (o.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish: min_cov %d (< 1)", o.min_cov);
+    PafSelection S;
+    select_paf_rows(contigs, reads, paf, o.min_len, o.min_iden, SelectNames{}, qc, pc, S);
+    const SeqSet &cs = S.cs, &rs = S.rs;
+    const SeqQual &rq = S.rq;
+    const PafText &pt = S.pt;
+    const std::vector<PafSel> &sel = S.sel;
+    const bool weighted = qc && qc->qual_weight;
+    st->rows = pt.recs.size();
+    st->contigs = cs.size();
     st->rows_selected = sel.size();
     polish_check_weight_width("hlmi_polish_q", qc, sel.size());
 
     // the device's input: polished contigs side by side, the aligned stretch of every read, compact CIGARs, tiles
     std::vector<PolSpan> spans;
     spans.reserve(sel.size());
-    for (const Sel &s : sel) spans.push_back(PolSpan{s.contig, pt.recs[s.line].ts, pt.recs[s.line].te});
+    for (const PafSel &s : sel) spans.push_back(PolSpan{s.contig, pt.recs[s.line].ts, pt.recs[s.line].te});
     PolLayout L;
     polish_layout(cs, spans, "hlmi_polish", L, st);
     PolDevIn in;
     in.min_cov = o.min_cov;
     in.rows.reserve(sel.size());
-    for (const Sel &s : sel) {
+    for (const PafSel &s : sel) {
         const PafRec &r = pt.recs[s.line];
         const uint32_t *op = pt.ops.data() + r.cig_off;
         PolRow row{};
@@ -217,21 +229,23 @@ void polish_check_weight_width(const char *who, const PolQualCall *qc, uint64_t 
         fail(HLMI_EINVAL, "%s: %llu selected rows of weight 93 at the most do not fit the 32-bit sums", who, (unsigned long long)rows_selected);
 }
 
-void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, hlmi_polish_stats *st) {
+void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, hlmi_polish_stats *st, bool with_bytes) {
     L = PolLayout{};
     L.rc.assign(cs.size(), 0);
     L.slot_of_contig.assign(cs.size(), 0);
     for (const PolSpan &s : sel) ++L.rc[s.contig];
     uint32_t n_polished = 0;
+    uint64_t total = 0;
     for (uint32_t c = 0; c < cs.size(); ++c)
         if (L.rc[c]) {
             L.slot_of_contig[c] = n_polished++;
-            if (L.contigs.size() + cs.len(c) >= (1ull << 31)) fail(HLMI_EINVAL, "%s: 2^31 contig bases or more to polish in one call", who);
-            L.cbase.push_back((uint32_t)L.contigs.size());
-            L.contigs.append(cs.bases, cs.off[c], cs.len(c));
+            if (total + cs.len(c) >= (1ull << 31)) fail(HLMI_EINVAL, "%s: 2^31 contig bases or more to polish in one call", who);
+            L.cbase.push_back((uint32_t)total);
+            if (with_bytes) L.contigs.append(cs.bases, cs.off[c], cs.len(c));
+            total += cs.len(c);
         }
-    L.cbase.push_back((uint32_t)L.contigs.size());
-    st->contigs_polished = n_polished;
+    L.cbase.push_back((uint32_t)total);
+    if (st) st->contigs_polished = n_polished;
     for (size_t r0 = 0; r0 < sel.size();) {
         size_t r1 = r0;
         while (r1 < sel.size() && sel[r1].contig == sel[r0].contig) ++r1;

@@ -81,8 +81,10 @@ struct PolLayout {
     std::string contigs;                    // PolDevIn::contigs
     std::vector<PolTile> tiles;
 };
-// who: the entry point's name for the refusal of 2^31 contig bases; sets contigs_polished
-void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, hlmi_polish_stats *st);
+// who: the entry point's name for the refusal of 2^31 contig bases; sets contigs_polished (st may be nullptr).  with_bytes
+// false: L.contigs stays empty (the depth call reads no contig byte)
+void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, hlmi_polish_stats *st,
+                   bool with_bytes = true);
 // slots_opened, inserted_bases, substituted, deleted, the headers and the file
 void polish_emit(const SeqSet &cs, const PolLayout &L, const PolDevOut &out, const hlmi_polish_opts &o, const char *out_fa,
                  hlmi_polish_stats *st);

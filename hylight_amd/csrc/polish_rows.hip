@@ -15,6 +15,9 @@
 // hlmi_polish_reads_pairs: the list becomes a sorted array of keys qid << 32 | tid on the device (polish_pairs.hip), and
 // pr_facts_kernel looks a row's key up with the whole wave (wave_search.h) directly behind the floor.
 //
+// The first three kernels with the flag-select and the sort are pol::select_device_rows (polish_select.h): hlmi_depth_reads
+// (depth_host.cpp) selects its rows with the same call.
+//
 // Why a wave per row in the first kernel and a thread per row in the last two: the first reads the ops of EVERY row (all of
 // the CIGAR traffic of this file), needs two sums and nothing else of them, so 64 consecutive words per load and a DPP sum fit;
 // the walk of polish_rows.h is sequential by nature (an op's fate depends on the op before it), runs over the winners only (one
@@ -28,6 +31,7 @@
 #include "paf_io.h"
 #include "polish_internal.h"
 #include "polish_rows.h"
+#include "polish_select.h"
 #include "wave_ops.h"
 #include "wave_search.h"
 
@@ -155,11 +159,11 @@ __global__ __launch_bounds__(WG) void pr_unvote_kernel(uint8_t *__restrict__ cod
 }
 
 // the refusals that need the sequences only: 2^28 bases, a name twice in one file; -> name rank -> record (NO_REC: none)
-std::vector<uint32_t> record_of_rank(const SeqSet &s, const std::vector<uint32_t> &rank, size_t n_ranks, const char *path) {
+std::vector<uint32_t> record_of_rank(const SeqSet &s, const std::vector<uint32_t> &rank, size_t n_ranks, const char *path, const char *who) {
     std::vector<uint32_t> rec(n_ranks, NO_REC);
     for (size_t i = 0; i < s.size(); ++i) {
-        if (s.len(i) >= MAX_SEQ) fail(HLMI_EINVAL, "hlmi_polish_reads: %s: %s has 2^28 bases or more", path, s.names[i].c_str());
-        if (rec[rank[i]] != NO_REC) fail(HLMI_EINVAL, "hlmi_polish_reads: %s: two records are named %s", path, s.names[i].c_str());
+        if (s.len(i) >= MAX_SEQ) fail(HLMI_EINVAL, "%s: %s: %s has 2^28 bases or more", who, path, s.names[i].c_str());
+        if (rec[rank[i]] != NO_REC) fail(HLMI_EINVAL, "%s: %s: two records are named %s", who, path, s.names[i].c_str());
         rec[rank[i]] = (uint32_t)i;
     }
     return rec;
@@ -167,38 +171,33 @@ std::vector<uint32_t> record_of_rank(const SeqSet &s, const std::vector<uint32_t
 
 }  // namespace
 
-void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
-                      const char *out_fa, hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
-    const double t_begin = now_ms();
-    *st = hlmi_polish_stats{};
-    stat_reset();
-    if (po.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish_reads: min_cov %d (< 1)", po.min_cov);
-    if (ao.stub_oh >= 0) fail(HLMI_EINVAL, "hlmi_polish_reads: stub_oh %d: the bare rows of stub candidates have no CIGAR", ao.stub_oh);
-    SeqSet cs, rs;
-    SeqQual rq;
+namespace pol {
+
+void select_device_rows(const char *contigs, const char *reads, const hlmi_ava_opts &ao, int min_len, double min_iden,
+                        const SelectNames &who, PolQualCall *qc, PolPairCall *pc, RowSelection &out) {
+    if (ao.stub_oh >= 0) fail(HLMI_EINVAL, "%s: stub_oh %d: the bare rows of stub candidates have no CIGAR", who.seqs, ao.stub_oh);
+    SeqSet &cs = out.cs, &rs = out.rs;
     std::vector<uint8_t> low;                   // hlmi_polish_reads_q: per read record, its mean quality is below the floor
     read_seqs(contigs, cs);
-    if (qc) low = polish_read_quals("hlmi_polish_reads_q", reads, qc->min_avg_qual, rs, rq, *qc);
+    if (qc) low = polish_read_quals(who.quals, reads, qc->min_avg_qual, rs, out.rq, *qc);
     else read_seqs(reads, rs);
-    const bool weighted = qc && qc->qual_weight;
-    const double t_dev = now_ms();
-    AvaPairCall call;
+    out.t_dev = now_ms();
+    AvaPairCall &call = out.call;
     call.setup(cs, rs, ao);
     const size_t n_ranks = call.name_of_rank.size();
-    const std::vector<uint32_t> crec_of_rank = record_of_rank(cs, call.rt, n_ranks, contigs),      // (refusals: before the overlapper runs)
-                                qrec_of_rank = record_of_rank(rs, call.rq, n_ranks, reads);
-    AvaRows rows;
+    out.crec_of_rank = record_of_rank(cs, call.rt, n_ranks, contigs, who.seqs);      // (refusals: before the overlapper runs)
+    out.qrec_of_rank = record_of_rank(rs, call.rq, n_ranks, reads, who.seqs);
+    AvaRows &rows = out.rows;
     ava_device(call.in, ao, rows);
     const size_t R = rows.n_rows;
-    if (R >= (1ull << 32)) fail(HLMI_EINVAL, "hlmi_polish_reads: %zu overlapper rows (2^32 and more)", R);
-    st->rows = R;
-    st->contigs = cs.size();
+    if (R >= (1ull << 32)) fail(HLMI_EINVAL, "%s: %zu overlapper rows (2^32 and more)", who.seqs, R);
+    out.n_rows = R;
     PairKeys pk;                                // hlmi_polish_reads_pairs: the list's own refusal comes behind the ones above
-    if (pc) pair_keys_device("hlmi_polish_reads_pairs", call.name_of_rank, *pc, pk);
+    if (pc) pair_keys_device(who.list, call.name_of_rank, *pc, pk);
 
-    // ---- selection and order ----------------------------------------------------------------------------------------------------
     size_t S = 0;
-    DBuf<uint32_t> idx(std::max<size_t>(R, 1)), d_crec_of_rank, d_qrec_of_rank;
+    DBuf<uint32_t> &idx = out.idx;
+    idx.alloc(std::max<size_t>(R, 1));
     if (R) {
         KTimer kt("polish_rows");
         DBuf<unsigned long long> best(n_ranks);
@@ -216,7 +215,7 @@ void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opt
         unsigned facts_grid = MAX_GRID;
         if (const char *e = hook("HLMI_POLISH_ROWS_GRID")) facts_grid = (unsigned)std::min<long>(std::max<long>(1, atol(e)), MAX_GRID);
         hipLaunchKernelGGL(pr_facts_kernel, dim3((unsigned)std::min<size_t>(cdiv(R, WAVES), facts_grid)), dim3(WG), 0, stream(), rows.recs.p,
-                           R, rows.ops_base, po.min_len, po.min_iden, best.p, low.empty() ? nullptr : d_low.p, n_low.p,
+                           R, rows.ops_base, min_len, min_iden, best.p, low.empty() ? nullptr : d_low.p, n_low.p,
                            pc ? pk.keys.p : nullptr, pk.n, n_low.p + 1);
         hipLaunchKernelGGL(pr_winner_kernel, grid1(R), dim3(WG), 0, stream(), rows.recs.p, R, best.p, flag.p);
         HIP_CHECK(hipGetLastError());
@@ -224,19 +223,49 @@ void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opt
         if (qc) qc->rows_low_qual = download_one(n_low.p);
         if (pc) pc->rows_not_listed = download_one(n_low.p + 1);
     }
+    out.n_sel = S;
+    if (S) {                                    // the order (contig, ts, line): the select left the lines ascending, the sort is stable
+        KTimer kt("polish_rows");
+        out.d_crec_of_rank.upload(out.crec_of_rank);
+        out.d_qrec_of_rank.upload(out.qrec_of_rank);
+        DBuf<uint64_t> key(S);
+        hipLaunchKernelGGL(pr_key_kernel, grid1(S), dim3(WG), 0, stream(), rows.recs.p, idx.p, S, out.d_crec_of_rank.p, key.p);
+        HIP_CHECK(hipGetLastError());
+        sort_pairs_u64_u32(key.p, idx.p, S, 0, 28 + bits_for(cs.size() - 1));
+    }
+}
+
+}  // namespace pol
+
+void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
+                      const char *out_fa, hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
+    const double t_begin = now_ms();
+    *st = hlmi_polish_stats{};
+    stat_reset();
+    if (po.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish_reads: min_cov %d (< 1)", po.min_cov);
+    RowSelection sel;
+    select_device_rows(contigs, reads, ao, po.min_len, po.min_iden,
+                       SelectNames{"hlmi_polish_reads", "hlmi_polish_reads_q", "hlmi_polish_reads_pairs", true}, qc, pc, sel);
+    const SeqSet &cs = sel.cs, &rs = sel.rs;
+    const SeqQual &rq = sel.rq;
+    const AvaPairCall &call = sel.call;
+    const AvaRows &rows = sel.rows;
+    const DBuf<uint32_t> &idx = sel.idx, &d_crec_of_rank = sel.d_crec_of_rank, &d_qrec_of_rank = sel.d_qrec_of_rank;
+    const bool weighted = qc && qc->qual_weight;
+    const double t_dev = sel.t_dev;
+    const size_t S = sel.n_sel;
+    st->rows = sel.n_rows;
+    st->contigs = cs.size();
     st->rows_selected = S;
     polish_check_weight_width("hlmi_polish_reads_q", qc, S);
+
+    // ---- the compact CIGARs' sizes and the spans --------------------------------------------------------------------------------
     std::vector<PolSpan> spans;
     DBuf<uint32_t> cig_n(std::max<size_t>(S, 1));
     DBuf<uint64_t> cig_off(std::max<size_t>(S, 1));
     uint64_t n_ops = 0;
     if (S) {
         KTimer kt("polish_rows");
-        d_crec_of_rank.upload(crec_of_rank);
-        d_qrec_of_rank.upload(qrec_of_rank);
-        DBuf<uint64_t> key(S);
-        hipLaunchKernelGGL(pr_key_kernel, grid1(S), dim3(WG), 0, stream(), rows.recs.p, idx.p, S, d_crec_of_rank.p, key.p);
-        sort_pairs_u64_u32(key.p, idx.p, S, 0, 28 + bits_for(cs.size() - 1));
         DBuf<PolSpan> d_span(S);
         DBuf<unsigned long long> totals(2);
         totals.zero();

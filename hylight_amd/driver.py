@@ -193,6 +193,25 @@ def polish_native(k, reads, contigs, out_fa, tmp, min_len, iden, short=False, ap
     return st
 
 
+def depth_tables(final, long_reads, short_reads, outdir, device=None):
+    """`--depth`: read depth and relative abundance of the final contigs (hlmi_depth_reads: the reads are aligned to the contigs
+    in the call, every pair, one row per read).  The long reads - the filtered ones the overlap stage read - with the
+    overlapper's long constants give outdir/final_contigs.long.depth.tsv and .bedgraph; short reads, when there are any, with
+    the short constants give final_contigs.short.depth.tsv and .bedgraph.  `device`: the GPU to initialise the library on
+    (None: the caller has done so).  -> {"long": stats, "short": stats}."""
+    if device is not None:
+        api.init(device)
+    out = {}
+    for kind, reads in (("long", long_reads), ("short", short_reads)):
+        if not reads:
+            continue
+        o = api.ava_opts_short() if kind == "short" else api.ava_opts_long()
+        o.pair_once = 0
+        stem = os.path.join(outdir, f"final_contigs.{kind}.depth")
+        out[kind] = api.depth_reads(final, reads, stem + ".tsv", stem + ".bedgraph", o)
+    return out
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m hylight_amd.driver",
                                 description="Haplotype-aware de novo assembly of metagenome from hybrid sequencing data "
@@ -256,6 +275,10 @@ def build_parser():
                         "ov_long_ref2.paf and shortr1.paf), as the reference's racon calls see only those rows")
     p.add_argument("--polish_min_avg_qual", type=float, default=10.0, metavar="Q",
                    help="with --polish_qual: reads whose mean Phred quality is below Q do not vote (racon's -q)")
+    p.add_argument("--depth", action="store_true",
+                   help="(extension) when final_contigs.fa is written: read depth and relative abundance of its contigs "
+                        "(hlmi_depth_reads) into final_contigs.long.depth.tsv and .bedgraph, and with -s also "
+                        "final_contigs.short.depth.tsv and .bedgraph")
     return p
 
 
@@ -499,7 +522,10 @@ def _pipeline(args, pool):
         sys.stderr.write(f"hylight-mi: {st['files'] // 2} short-read clusters in tmp/fq_{args.size}/\n")
         if args.stop_after == "clusters":
             return 0
-        return _short_branch(args, tmp, outdir, long_con3, pool)
+        rc = _short_branch(args, tmp, outdir, long_con3, pool)
+        if rc == 0 and args.depth:
+            depth_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir)
+        return rc
     # HyLight.py:211-262 (read clustering, POLYTE per cluster) is the short-read branch: not part of this path.  Its
     # contigs can be handed in; the contig-overlap half of extend_con runs either way (HyLight.py:264-280).
     sys.stderr.write("hylight-mi: short-read clustering and POLYTE (HyLight.py:211-262) are outside this implementation"
@@ -533,6 +559,8 @@ def _pipeline(args, pool):
                          "was not written (pass --stageb_native to run the library's, or --stageb_cmd for the reference's): "
                          f"exit status {EXIT_NO_FINAL}\n")
         return EXIT_NO_FINAL
+    if args.depth:
+        depth_tables(final, infile, short_reads, outdir)
     return 0
 
 

@@ -844,6 +844,63 @@ int hlmi_polish_pairs(const char *contigs, const char *reads, const char *paf, c
 int hlmi_polish_reads_pairs(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_qopts *po,
                             const char *pairs_paf, const char *out_fa, hlmi_polish_pstats *st);
 
+/* ---- read depth and relative abundance per contig: how many of the selected reads lie over every position of the contigs, and
+ * each contig's share of the sample.  hlmi_depth reads a PAF as hlmi_polish_pairs does, hlmi_depth_reads aligns in the call as
+ * hlmi_polish_reads_pairs does.  New symbols: the older calls keep their signatures and their bytes, and HLMI_ABI_VERSION stays
+ * where it is.  A function of the project's own (the reference's build_abundance_between_contigs*.py are overlap filters, not an
+ * abundance estimate): PARITY UNPINNED; tests/depth_model.py is the contract, byte for byte. */
+typedef struct {
+    int min_len;              /* rows with te - ts below this are dropped                                                 */
+    double min_iden;          /* rows with (sum of '=' lengths) / (sum of all op lengths) below this are dropped         */
+} hlmi_depth_opts;
+void hlmi_depth_opts_default(hlmi_depth_opts *o);   /* 0, 0.0 */
+typedef struct {
+    uint64_t rows;              /* PAF rows / overlapper rows                                                               */
+    uint64_t rows_selected;     /* rows that count (one per read at most)                                                   */
+    uint64_t contigs;           /* records of `contigs`                                                                     */
+    uint64_t contigs_covered;   /* ... with a selected row                                                                  */
+    uint64_t positions;         /* bases of ALL contigs                                                                     */
+    uint64_t covered;           /* positions with depth >= 1, over all contigs                                              */
+    uint64_t bases;             /* sum of the depths, over all contigs                                                      */
+    uint64_t runs;              /* bedGraph lines written (0 when out_bedgraph is NULL)                                     */
+    uint64_t pairs_listed;      /* the three counters of hlmi_polish_pstats; 0 without a list                              */
+    uint64_t pairs_unknown;
+    uint64_t rows_not_listed;
+    double ms_device;           /* wall time of the device part: uploads, kernels, read-backs                               */
+    double ms_total;
+} hlmi_depth_stats;
+/* contigs, reads, paf: as for hlmi_polish_pairs.  pairs_paf and out_bedgraph may be NULL.
+ * Selection: exactly hlmi_polish_pairs's without the quality floor: rows with qname == tname are skipped; with a list, a row
+ * whose pair is not listed is dropped and counted in rows_not_listed; rows with te == ts or te - ts < min_len are dropped; rows
+ * with (double)n_eq / (double)n_all < min_iden are dropped; per query name the row with the largest te - ts stays, the earliest
+ * line on a tie.  The list's format and meaning are hlmi_polish_pairs's, word for word (pairs_paf == NULL: no list, every row
+ * may count; an empty file: a valid list of no pairs, no row counts).  The polisher and this call run one implementation.
+ * Depth: a selected row covers every position of [ts, te) of its contig, the columns of its D ops included; depth[p] is the
+ * number of selected rows that cover p.  No CIGAR op is read behind the selection.
+ * Per contig, in file order, EVERY contig: length; reads = selected rows on it; bases = sum of its depths; covered = positions
+ * with depth >= 1; mean_depth = (double)bases / (double)length; median_depth = element (length - 1) / 2 (integer division) of
+ * its depths in ascending order; abundance = mean_depth / (sum of all mean_depth), the sum taken in file order with one double
+ * addition per contig, 0.000000 when the sum is 0.  A contig of 0 bases gets a row of zeros.
+ * out_tsv (under a temporary name, renamed on success): the line
+ * "#contig\tlength\treads\tbases\tcovered\tmean_depth\tmedian_depth\tabundance", then one line per contig; mean_depth and
+ * abundance print as %.6f, everything else is an integer.
+ * out_bedgraph (optional): lines "name\tstart\tend\tdepth": the maximal runs of equal depth inside one contig, depth 0 included,
+ * contigs in file order, runs ascending; a run never continues into the next contig; a contig without a selected row is one run
+ * [0, length) of depth 0, a contig of 0 bases writes nothing.
+ * Refusals (HLMI_EINVAL unless said otherwise, nothing is written): every refusal hlmi_polish_pairs makes about the files, the rows
+ * and the list, in its order (min_cov and the counter width do not apply); 2^31 bases or more of contigs with a selected row;
+ * depths and sort keys that do not fit the device's memory.  Two records of one name in `contigs`, or in `reads`, are refused
+ * when the files are read: the table is keyed by name. */
+int hlmi_depth(const char *contigs, const char *reads, const char *paf, const hlmi_depth_opts *o, const char *pairs_paf,
+               const char *out_tsv, const char *out_bedgraph, hlmi_depth_stats *st);
+/* The two calls hlmi_ava(contigs, reads, ao, P) and hlmi_depth(contigs, reads, P, o, pairs_paf, ...) in one, without the PAF P:
+ * both files and every integer field of *st are byte for byte what that chain gives (ao NULL: the long constants).  The
+ * overlapper's rows are selected where they are, by the kernels hlmi_polish_reads_pairs selects with; a selected row's span is
+ * all that is read of it (csrc/depth.hip).  The three stated differences of hlmi_polish_reads apply (a name twice, stub_oh >= 0,
+ * 2^32 rows), the list refusals of hlmi_polish_reads_pairs, a sequence of 2^28 bases or more, and 2^31 contig bases. */
+int hlmi_depth_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_depth_opts *o,
+                     const char *pairs_paf, const char *out_tsv, const char *out_bedgraph, hlmi_depth_stats *st);
+
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
  * reads into a caller-owned device buffer (16 B per minimizer: two uint64), the caller
