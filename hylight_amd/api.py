@@ -166,6 +166,18 @@ class DepthStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in DEPTH_STATS] + [(k, C.c_double) for k in POLISH_MS]
 
 
+class VariantOpts(C.Structure):
+    _fields_ = [("min_len", C.c_int), ("min_iden", C.c_double), ("min_cov", C.c_int), ("min_alt", C.c_int), ("min_frac", C.c_double)]
+
+
+VARIANT_STATS = ("rows", "rows_selected", "contigs", "contigs_covered", "positions", "callable", "ref_other", "sites", "sites_base",
+                 "sites_del", "pairs_listed", "pairs_unknown", "rows_not_listed")
+
+
+class VariantStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in VARIANT_STATS] + [(k, C.c_double) for k in POLISH_MS]
+
+
 ABI_VERSION = 7          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
@@ -263,6 +275,12 @@ SYMBOLS = {
                              C.POINTER(DepthStats)]),
     "hlmi_depth_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(DepthOpts), C.c_char_p, C.c_char_p, C.c_char_p,
                                    C.POINTER(DepthStats)]),
+    # variant sites per contig
+    "hlmi_variant_opts_default": (None, [C.POINTER(VariantOpts)]),
+    "hlmi_variants": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VariantOpts), C.c_char_p, C.c_char_p, C.c_char_p,
+                                C.POINTER(VariantStats)]),
+    "hlmi_variants_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(VariantOpts), C.c_char_p, C.c_char_p,
+                                      C.c_char_p, C.POINTER(VariantStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -787,6 +805,39 @@ def depth_reads(contigs, reads, out_tsv, out_bedgraph=None, ava_opts=None, pairs
     _check(load().hlmi_depth_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), _b(pairs),
                                    _b(out_tsv), _b(out_bedgraph), C.byref(st)))
     return {k: getattr(st, k) for k in DEPTH_STATS + POLISH_MS}
+
+
+def _variant_opts(who, opts):
+    o = VariantOpts()
+    load().hlmi_variant_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(VariantOpts._fields_):
+            raise TypeError(f"{who}: unknown option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def variants(contigs, reads, paf, out_sites, out_summary=None, pairs=None, **opts):
+    """hlmi_variants: the variant sites of every contig of `contigs` under the rows of `paf` (selected as api.depth selects them,
+    pairs= included; voted as api.polish votes positions, unweighted): a position is a site when the symbol other than the
+    contig's own base with the most votes has min_alt votes and min_frac of the position's votes.  Writes the sites out_sites
+    (contig, pos, ref, depth, A, C, G, T, del, alt, alt_count, alt_frac) and, when given, one line per contig out_summary
+    (contig, length, reads, callable, sites, site_rate).  Options: min_len 0, min_iden 0.0, min_cov 3, min_alt 2, min_frac 0.2.
+    A function of this project's own: include/hylight_mi.h states it, tests/variants_model.py is its contract.
+    -> dict of the stats (hlmi_variant_stats)."""
+    o, st = _variant_opts("variants", opts), VariantStats()
+    _check(load().hlmi_variants(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(pairs), _b(out_sites), _b(out_summary), C.byref(st)))
+    return {k: getattr(st, k) for k in VARIANT_STATS + POLISH_MS}
+
+
+def variants_reads(contigs, reads, out_sites, out_summary=None, ava_opts=None, pairs=None, **opts):
+    """hlmi_variants_reads: `ava(contigs, reads, P, ava_opts)` and `variants(contigs, reads, P, ...)` in one call without the PAF
+    P: the same files and the same integer stats.  ava_opts None: the long constants.  Refused besides what variants refuses:
+    ava_opts.stub_oh >= 0.  -> dict of the stats (hlmi_variant_stats)."""
+    o, st = _variant_opts("variants_reads", opts), VariantStats()
+    _check(load().hlmi_variants_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), _b(pairs),
+                                      _b(out_sites), _b(out_summary), C.byref(st)))
+    return {k: getattr(st, k) for k in VARIANT_STATS + POLISH_MS}
 
 
 DEVICE = "cuda"          # where the buffers that cross the C ABI live (stage.py allocates them with torch)

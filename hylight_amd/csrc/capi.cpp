@@ -11,6 +11,7 @@
 #include "polish_internal.h"
 #include "stage.h"
 #include "textpass.h"
+#include "variants_internal.h"
 #include "vq_internal.h"
 
 namespace hlmi {
@@ -622,6 +623,28 @@ int hlmi_depth_reads(const char *contigs, const char *reads, const hlmi_ava_opts
         if (!contigs || !reads || !o || !out_tsv || !st) fail(HLMI_EINVAL, "hlmi_depth_reads: NULL argument");
         require_device();
         depth_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_tsv, out_bedgraph, st);
+    });
+}
+
+void hlmi_variant_opts_default(hlmi_variant_opts *o) {
+    if (o) *o = hlmi_variant_opts{0, 0.0, 3, 2, 0.2};
+}
+
+int hlmi_variants(const char *contigs, const char *reads, const char *paf, const hlmi_variant_opts *o, const char *pairs_paf,
+                  const char *out_sites, const char *out_summary, hlmi_variant_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_variants: NULL argument");
+        require_device();
+        variants_run(contigs, reads, paf, *o, pairs_paf, out_sites, out_summary, st);
+    });
+}
+
+int hlmi_variants_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_variant_opts *o,
+                        const char *pairs_paf, const char *out_sites, const char *out_summary, hlmi_variant_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_variants_reads: NULL argument");
+        require_device();
+        variants_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_sites, out_summary, st);
     });
 }
 

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "depth_internal.h"
 #include "dev_prims.h"
+#include "polish_walk.h"
 #include "wave_ops.h"
 
 namespace hlmi {
@@ -32,17 +33,6 @@ constexpr int PER = POLISH_TILE / WG;           // consecutive positions of a ti
 static_assert(PER == 4 && PER * WG == POLISH_TILE, "a thread reads its 4 difference words as one 16-byte LDS load");
 constexpr unsigned MAX_GRID = 1u << 16;         // blocks of a strided launch
 inline dim3 grid1(size_t n) { return dim3((unsigned)std::min<size_t>(cdiv(n ? n : 1, WG), MAX_GRID)); }
-
-// the slot whose positions hold p: the last j < n_slots with cbase[j] <= p (cbase ascends strictly: a slot has a position)
-__device__ __forceinline__ uint32_t slot_of_position(const uint32_t *__restrict__ cbase, uint32_t n_slots, uint32_t p) {
-    uint32_t lo = 0, hi = n_slots;              // the answer lies in [lo, hi)
-    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (cbase[mid] <= p) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(WG) void depth_span_kernel(const PafRec *__restrict__ recs, const uint32_t *__restrict__ idx, size_t n_sel,
                                                         const uint32_t *__restrict__ crec_of_rank, PolSpan *__restrict__ span) {

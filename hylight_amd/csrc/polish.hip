@@ -15,40 +15,23 @@
 // were: no quality byte is read, eight counters.
 // polish_device uploads what polish_host.cpp built and runs polish_core; hlmi_polish_reads (polish_rows.hip) runs polish_core
 // over rows, CIGARs and reads that are in device memory already - its reads as the overlapper's codes (column_symbol).
+// column_symbol, walk_row and the lane / wave switch of the vote loop are polish_walk.h's, shared with variants.hip.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
 #include "dev_prims.h"
 #include "polish_internal.h"
+#include "polish_select.h"
+#include "polish_walk.h"
 #include "wave_ops.h"
 
 namespace hlmi {
 namespace pol {
 namespace {
 
-constexpr int POLISH_WG = 256, POLISH_WAVES = POLISH_WG / 64;
-constexpr int C_OTHER = 5, C_START = 6, C_INS = 7, POLISH_CNT = 8;     // counters behind the five symbols
+constexpr int C_START = 6, C_INS = 7, POLISH_CNT = 8;                  // counters behind the five symbols and C_OTHER (polish_walk.h)
 constexpr int C_VOTES = 8, POLISH_CNT_QW = 9;                          // QW: voting columns, behind the others
-constexpr uint32_t SHORT_RUN = 16;         // a lane votes a run of up to this many columns itself; longer ones take the wave
 constexpr uint32_t NO_SLOT = 0xffffffffu;
-
-// symbol of alignment column `col` of row r: 0..3, or C_OTHER for anything that is not A C G T.
-// ENC = READS_ASCII: `reads` holds the file's bytes, folded to upper case here.  ENC = READS_CODES: it holds the overlapper's
-// resident codes (DevReads::codes(): 0..3 = A C G T of either case, 4 = anything else).  Code 4 is exactly the set of bytes the
-// ASCII form refuses to count after `& 0xdf` - with one exception the encoder makes for the aligner, U / u -> 3: the caller
-// (polish_rows.hip) sets those bases to 4 once the alignment is done, so that both forms count the same columns.
-template <int ENC>
-__device__ __forceinline__ uint32_t column_symbol(const PolRow &r, const uint8_t *__restrict__ reads, uint32_t col) {
-    if (col >= r.qn) return C_OTHER;                                   // (validated on the host: never)
-    uint8_t c = reads[r.read_off + (r.rev ? r.qn - 1 - col : col)];
-    uint32_t k;
-    if (ENC == READS_CODES) k = c < 4 ? (uint32_t)c : (uint32_t)C_OTHER;
-    else {
-        c &= 0xdfu;                                                    // upper case
-        k = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : (uint32_t)C_OTHER;
-    }
-    return r.rev && k < 4 ? 3u - k : k;
-}
 
 // weight of alignment column `col` of row r: max(1, Phred), the byte fetched at the index column_symbol fetches the base at
 __device__ __forceinline__ uint32_t column_weight(const PolRow &r, const uint8_t *__restrict__ quals, uint32_t col) {
@@ -62,24 +45,6 @@ __device__ __forceinline__ uint32_t del_weight(const PolRow &r, const uint8_t *_
     if (qc >= 1 && qc - 1 < r.qn) w = column_weight(r, quals, qc - 1);
     if (qc < r.qn) w = min(w, column_weight(r, quals, qc));
     return w == 0xffffffffu ? 1u : w;
-}
-
-// One wave walks the CIGAR of r: f(code, len, first target position, first query column) for every op, lane = op; stops
-// in front of the first 64 ops that start at t_stop or behind it.  All 64 lanes call f together.
-template <typename F>
-__device__ __forceinline__ void walk_row(const PolRow &r, const uint32_t *__restrict__ ops, int lane, uint32_t t_stop, F &&f) {
-    uint32_t tb = r.ts, qb = 0;
-    const uint32_t *o = ops + r.cig_off;
-    for (uint32_t k0 = 0; k0 < r.cig_n && tb < t_stop; k0 += 64) {
-        const uint32_t idx = k0 + (uint32_t)lane;
-        const uint32_t op = idx < r.cig_n ? o[idx] : 0u;
-        const uint32_t len = op >> 4, code = op & 15u;
-        const uint32_t tl = code == OP_I ? 0u : len, ql = code == OP_D ? 0u : len;
-        const uint32_t te = wave_prefix_sum_incl_dpp(tl), qe = wave_prefix_sum_incl_dpp(ql);
-        f(code, len, tb + te - tl, qb + qe - ql);
-        tb += (uint32_t)__builtin_amdgcn_readlane((int)te, 63);
-        qb += (uint32_t)__builtin_amdgcn_readlane((int)qe, 63);
-    }
 }
 
 template <int ENC, bool QW>
@@ -124,19 +89,7 @@ __global__ __launch_bounds__(POLISH_WG) void polish_count_kernel(const PolRow *_
             uint32_t wd = 1u;                                          // a D op's weight: once per op, by its lane
             if constexpr (QW)
                 if (code == OP_D && n) wd = del_weight(r, quals, qc0);
-            if (n <= SHORT_RUN)
-                for (uint32_t p = a; p < b; ++p) vote(p, code, tp0, qc0, wd);
-            unsigned long long longs = __ballot(n > SHORT_RUN);
-            for (int it = 0; it < 64 && longs; ++it) {                 // the long runs, one after the other, 64 columns a step
-                const int src = __ffsll(longs) - 1;
-                longs &= longs - 1;
-                const uint32_t a2 = (uint32_t)__shfl((int)a, src), b2 = (uint32_t)__shfl((int)b, src);
-                const uint32_t code2 = (uint32_t)__shfl((int)code, src), tp2 = (uint32_t)__shfl((int)tp0, src),
-                               qc2 = (uint32_t)__shfl((int)qc0, src);
-                uint32_t wd2 = 1u;
-                if constexpr (QW) wd2 = (uint32_t)__shfl((int)wd, src);
-                for (uint32_t p = a2 + (uint32_t)lane; p < b2; p += 64) vote(p, code2, tp2, qc2, wd2);
-            }
+            vote_columns<QW>(a, b, code, tp0, qc0, wd, lane, vote);
         });
     }
     __syncthreads();
@@ -274,30 +227,31 @@ void launch_slot_for(const PolCoreIn &in, const uint32_t *d_slot_of, const uint8
 
 }  // namespace
 
-void polish_device(const PolDevIn &in, PolDevOut &out) {
-    DBuf<uint8_t> d_contig, d_reads, d_quals;
-    DBuf<PolRow> d_rows;
-    DBuf<uint32_t> d_ops, d_cbase;
-    DBuf<PolTile> d_tiles;
-    d_contig.upload((const uint8_t *)in.contigs.data(), in.contigs.size());
-    d_reads.upload((const uint8_t *)in.reads.data(), in.reads.size());
+void polish_upload(const PolDevIn &in, PolUploaded &up) {
+    up.contig.upload((const uint8_t *)in.contigs.data(), in.contigs.size());
+    up.reads.upload((const uint8_t *)in.reads.data(), in.reads.size());
     const bool weighted = !in.quals.empty();                 // (as long as `reads`: polish_host.cpp appends both)
     if (weighted && in.quals.size() != in.reads.size()) fail(HLMI_EINVAL, "hlmi_polish_q: quality bytes and read bytes differ in number");
-    if (weighted) d_quals.upload((const uint8_t *)in.quals.data(), in.quals.size());
-    d_rows.upload(in.rows);
-    d_ops.upload(in.ops);
-    d_tiles.upload(in.tiles);
-    d_cbase.upload(in.cbase);
-    PolCoreIn c;
-    c.rows = d_rows.p; c.n_rows = (uint32_t)in.rows.size();
-    c.ops = d_ops.p;
-    c.reads = d_reads.p; c.enc = READS_ASCII;
-    c.quals = weighted ? d_quals.p : nullptr;
-    c.contig = d_contig.p; c.n_contig = in.contigs.size();
-    c.tiles = d_tiles.p; c.n_tiles = in.tiles.size();
-    c.cbase = d_cbase.p; c.n_cbase = in.cbase.size();
+    if (weighted) up.quals.upload((const uint8_t *)in.quals.data(), in.quals.size());
+    up.rows.upload(in.rows);
+    up.ops.upload(in.ops);
+    up.tiles.upload(in.tiles);
+    up.cbase.upload(in.cbase);
+    PolCoreIn &c = up.core;
+    c.rows = up.rows.p; c.n_rows = (uint32_t)in.rows.size();
+    c.ops = up.ops.p;
+    c.reads = up.reads.p; c.enc = READS_ASCII;
+    c.quals = weighted ? up.quals.p : nullptr;
+    c.contig = up.contig.p; c.n_contig = in.contigs.size();
+    c.tiles = up.tiles.p; c.n_tiles = in.tiles.size();
+    c.cbase = up.cbase.p; c.n_cbase = in.cbase.size();
     c.min_cov = in.min_cov;
-    polish_core(c, out);
+}
+
+void polish_device(const PolDevIn &in, PolDevOut &out) {
+    PolUploaded up;
+    polish_upload(in, up);
+    polish_core(up.core, out);
 }
 
 void polish_core(const PolCoreIn &in, PolDevOut &out) {

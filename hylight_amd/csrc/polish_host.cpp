@@ -144,6 +144,34 @@ void select_paf_rows(const char *contigs, const char *reads, const char *paf, in
     });
 }
 
+void paf_rows_input(const PafSelection &S, const PolLayout &L, bool weighted, PolDevIn &in, uint64_t &ins_edge, uint64_t &ins_long) {
+    const PafText &pt = S.pt;
+    const SeqSet &rs = S.rs;
+    in.rows.reserve(S.sel.size());
+    for (const PafSel &s : S.sel) {
+        const PafRec &r = pt.recs[s.line];
+        const uint32_t *op = pt.ops.data() + r.cig_off;
+        PolRow row{};
+        row.read_off = in.reads.size();
+        row.cig_off = in.ops.size();
+        row.ts = r.ts; row.te = r.te; row.qn = r.qe - r.qs;
+        row.rev = (r.flags & PF_REV) ? 1u : 0u;
+        row.cbase = L.cbase[L.slot_of_contig[s.contig]];
+        in.reads.append(rs.bases, rs.off[s.read] + r.qs, row.qn);
+        if (weighted) in.quals.append(S.rq.quals, rs.off[s.read] + r.qs, row.qn);
+        RowWalk w;                                           // polish_rows.h: drop, merge, ins_edge, ins_long
+        RowOp done;
+        row_walk_begin(w, r.ts, r.te);
+        for (uint32_t k = 0; k < r.cig_n; ++k)
+            if (row_walk_op(w, op[k], &done)) in.ops.push_back(done.word);
+        if (row_walk_end(w, &done)) in.ops.push_back(done.word);
+        ins_edge += w.ins_edge;
+        ins_long += w.ins_long;
+        row.cig_n = w.n_out;
+        in.rows.push_back(row);
+    }
+}
+
 }  // namespace pol
 
 void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
@@ -153,8 +181,7 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
     if (o.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish: min_cov %d (< 1)", o.min_cov);
     PafSelection S;
     select_paf_rows(contigs, reads, paf, o.min_len, o.min_iden, SelectNames{}, qc, pc, S);
-    const SeqSet &cs = S.cs, &rs = S.rs;
-    const SeqQual &rq = S.rq;
+    const SeqSet &cs = S.cs;
     const PafText &pt = S.pt;
     const std::vector<PafSel> &sel = S.sel;
     const bool weighted = qc && qc->qual_weight;
@@ -171,29 +198,7 @@ void polish_run(const char *contigs, const char *reads, const char *paf, const h
     polish_layout(cs, spans, "hlmi_polish", L, st);
     PolDevIn in;
     in.min_cov = o.min_cov;
-    in.rows.reserve(sel.size());
-    for (const PafSel &s : sel) {
-        const PafRec &r = pt.recs[s.line];
-        const uint32_t *op = pt.ops.data() + r.cig_off;
-        PolRow row{};
-        row.read_off = in.reads.size();
-        row.cig_off = in.ops.size();
-        row.ts = r.ts; row.te = r.te; row.qn = r.qe - r.qs;
-        row.rev = (r.flags & PF_REV) ? 1u : 0u;
-        row.cbase = L.cbase[L.slot_of_contig[s.contig]];
-        in.reads.append(rs.bases, rs.off[s.read] + r.qs, row.qn);
-        if (weighted) in.quals.append(rq.quals, rs.off[s.read] + r.qs, row.qn);
-        RowWalk w;                                           // polish_rows.h: drop, merge, ins_edge, ins_long
-        RowOp done;
-        row_walk_begin(w, r.ts, r.te);
-        for (uint32_t k = 0; k < r.cig_n; ++k)
-            if (row_walk_op(w, op[k], &done)) in.ops.push_back(done.word);
-        if (row_walk_end(w, &done)) in.ops.push_back(done.word);
-        st->ins_edge += w.ins_edge;
-        st->ins_long += w.ins_long;
-        row.cig_n = w.n_out;
-        in.rows.push_back(row);
-    }
+    paf_rows_input(S, L, weighted, in, st->ins_edge, st->ins_long);
     in.contigs = std::move(L.contigs);
     in.cbase = L.cbase;
     in.tiles = std::move(L.tiles);

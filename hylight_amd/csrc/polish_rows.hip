@@ -235,29 +235,14 @@ void select_device_rows(const char *contigs, const char *reads, const hlmi_ava_o
     }
 }
 
-}  // namespace pol
-
-void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
-                      const char *out_fa, hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
-    const double t_begin = now_ms();
-    *st = hlmi_polish_stats{};
-    stat_reset();
-    if (po.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish_reads: min_cov %d (< 1)", po.min_cov);
-    RowSelection sel;
-    select_device_rows(contigs, reads, ao, po.min_len, po.min_iden,
-                       SelectNames{"hlmi_polish_reads", "hlmi_polish_reads_q", "hlmi_polish_reads_pairs", true}, qc, pc, sel);
+void device_rows_input(const RowSelection &sel, const char *who, bool weighted, hlmi_polish_stats *st, DeviceRowsInput &out) {
     const SeqSet &cs = sel.cs, &rs = sel.rs;
     const SeqQual &rq = sel.rq;
     const AvaPairCall &call = sel.call;
     const AvaRows &rows = sel.rows;
     const DBuf<uint32_t> &idx = sel.idx, &d_crec_of_rank = sel.d_crec_of_rank, &d_qrec_of_rank = sel.d_qrec_of_rank;
-    const bool weighted = qc && qc->qual_weight;
-    const double t_dev = sel.t_dev;
     const size_t S = sel.n_sel;
-    st->rows = sel.n_rows;
-    st->contigs = cs.size();
-    st->rows_selected = S;
-    polish_check_weight_width("hlmi_polish_reads_q", qc, S);
+    PolLayout &L = out.L;
 
     // ---- the compact CIGARs' sizes and the spans --------------------------------------------------------------------------------
     std::vector<PolSpan> spans;
@@ -275,21 +260,20 @@ void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opt
         exclusive_scan_u32_to_u64(cig_n.p, cig_off.p, S);
         n_ops = download_one(cig_off.p + (S - 1)) + download_one(cig_n.p + (S - 1));
         const std::vector<unsigned long long> t = totals.download(2);
-        st->ins_edge = t[0];
-        st->ins_long = t[1];
+        out.ins_edge = t[0];
+        out.ins_long = t[1];
         spans = d_span.download(S);
         for (const PolSpan &s : spans)
-            if (s.contig >= cs.size()) fail(HLMI_EINVAL, "hlmi_polish_reads: a row names a target that is no contig");    // (never)
+            if (s.contig >= cs.size()) fail(HLMI_EINVAL, "%s: a row names a target that is no contig", who);    // (never)
     }
-    PolLayout L;
-    polish_layout(cs, spans, "hlmi_polish_reads", L, st);
+    polish_layout(cs, spans, who, L, st);
 
-    // ---- CIGARs and rows, then the votes ----------------------------------------------------------------------------------------
-    DBuf<PolRow> d_rows(std::max<size_t>(S, 1));
-    DBuf<uint32_t> d_ops(std::max<uint64_t>(n_ops, 1)), d_cbase, d_cbase_of_crec;
-    DBuf<PolTile> d_tiles;
-    DBuf<uint8_t> d_contig, d_quals;
-    if (weighted) d_quals.upload((const uint8_t *)rq.quals.data(), rq.quals.size());      // rs.off is DevReads::off of call.dQ
+    // ---- CIGARs and rows ----------------------------------------------------------------------------------------------------------
+    DBuf<PolRow> &d_rows = out.rows;
+    DBuf<uint32_t> &d_ops = out.ops, d_cbase_of_crec;
+    d_rows.alloc(std::max<size_t>(S, 1));
+    d_ops.alloc(std::max<uint64_t>(n_ops, 1));
+    if (weighted) out.quals.upload((const uint8_t *)rq.quals.data(), rq.quals.size());      // rs.off is DevReads::off of call.dQ
     if (S) {
         std::vector<uint32_t> cbase_of_crec(cs.size(), 0);
         for (size_t c = 0; c < cs.size(); ++c)
@@ -306,17 +290,45 @@ void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opt
                            d_qrec_of_rank.p, call.dQ.off.p, d_cbase_of_crec.p, (uint32_t)cs.size(), cig_off.p, cig_n.p, d_rows.p, d_ops.p);
         HIP_CHECK(hipGetLastError());
     }
-    d_contig.upload((const uint8_t *)L.contigs.data(), L.contigs.size());
-    d_cbase.upload(L.cbase);
-    d_tiles.upload(L.tiles);
-    PolCoreIn c;
+    out.contig.upload((const uint8_t *)L.contigs.data(), L.contigs.size());
+    out.cbase.upload(L.cbase);
+    out.tiles.upload(L.tiles);
+    PolCoreIn &c = out.core;
     c.rows = d_rows.p; c.n_rows = (uint32_t)S;
     c.ops = d_ops.p;
     c.reads = call.dQ.codes(); c.enc = READS_CODES;
-    c.quals = weighted && !rq.quals.empty() ? d_quals.p : nullptr;
-    c.contig = d_contig.p; c.n_contig = L.contigs.size();
-    c.tiles = d_tiles.p; c.n_tiles = L.tiles.size();
-    c.cbase = d_cbase.p; c.n_cbase = L.cbase.size();
+    c.quals = weighted && !rq.quals.empty() ? out.quals.p : nullptr;
+    c.contig = out.contig.p; c.n_contig = L.contigs.size();
+    c.tiles = out.tiles.p; c.n_tiles = L.tiles.size();
+    c.cbase = out.cbase.p; c.n_cbase = L.cbase.size();
+}
+
+}  // namespace pol
+
+void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
+                      const char *out_fa, hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
+    const double t_begin = now_ms();
+    *st = hlmi_polish_stats{};
+    stat_reset();
+    if (po.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish_reads: min_cov %d (< 1)", po.min_cov);
+    RowSelection sel;
+    select_device_rows(contigs, reads, ao, po.min_len, po.min_iden,
+                       SelectNames{"hlmi_polish_reads", "hlmi_polish_reads_q", "hlmi_polish_reads_pairs", true}, qc, pc, sel);
+    const SeqSet &cs = sel.cs;
+    const bool weighted = qc && qc->qual_weight;
+    const double t_dev = sel.t_dev;
+    const size_t S = sel.n_sel;
+    st->rows = sel.n_rows;
+    st->contigs = cs.size();
+    st->rows_selected = S;
+    polish_check_weight_width("hlmi_polish_reads_q", qc, S);
+
+    DeviceRowsInput in;
+    device_rows_input(sel, "hlmi_polish_reads", weighted, st, in);
+    st->ins_edge = in.ins_edge;
+    st->ins_long = in.ins_long;
+    const PolLayout &L = in.L;
+    PolCoreIn &c = in.core;
     c.min_cov = po.min_cov;
     PolDevOut out;
     polish_core(c, out);

@@ -1,7 +1,9 @@
 // polish_select.h - the row selection of include/hylight_mi.h (hlmi_polish_pairs: qname == tname, the read floor, the pair
 // list, te == ts / min_len, min_iden, one row per read) as two functions, one per kind of entry point, so that every caller
 // runs one implementation: the polisher (polish_host.cpp: polish_run, polish_rows.hip: polish_reads_run) and the depth call
-// (depth_host.cpp).  What a caller does with the selected rows - compact CIGARs and votes, or spans alone - is its own.
+// (depth_host.cpp) and the variant call (variants_host.cpp).  What a caller does with the selected rows is its own: spans
+// alone (depth), or PolRow + compact CIGARs + reads, built by the second pair of functions below for the polisher and the
+// variant call alike.
 #pragma once
 #include <string>
 #include <vector>
@@ -54,6 +56,37 @@ struct RowSelection {
 // radix sort by contig record << 28 | ts.  Refusals: stub_oh >= 0, 2^28 bases, a name twice, 2^32 rows, the list's.
 void select_device_rows(const char *contigs, const char *reads, const hlmi_ava_opts &ao, int min_len, double min_iden,
                         const SelectNames &who, PolQualCall *qc, PolPairCall *pc, RowSelection &out);
+
+// ---- the selected rows as the device part's input (hlmi_polish*, hlmi_variants*) ----------------------------------------------
+// PolRow, compact CIGARs (polish_rows.h), the aligned read stretches, tiles: what polish_core and variants_core read.  One
+// implementation per kind of entry point, as for the selection.
+//
+// Over a PAF (polish_host.cpp): in.rows, in.ops, in.reads and, when weighted, in.quals from the selection, in its order; L is
+// polish_layout's over the same rows.  Adds the rows' ins_edge and ins_long to the two counters.
+void paf_rows_input(const PafSelection &S, const PolLayout &L, bool weighted, PolDevIn &in, uint64_t &ins_edge, uint64_t &ins_long);
+// PolDevIn in device memory (polish.hip); core.min_cov is in.min_cov
+struct PolUploaded {
+    DBuf<uint8_t> contig, reads, quals;
+    DBuf<PolRow> rows;
+    DBuf<uint32_t> ops, cbase;
+    DBuf<PolTile> tiles;
+    PolCoreIn core;
+};
+void polish_upload(const PolDevIn &in, PolUploaded &up);
+
+// Over the overlapper's rows (polish_rows.hip): pr_count_kernel, the scan, polish_layout (who: the entry point's name in its
+// refusal; st: contigs_polished, may be nullptr), pr_unvote_kernel, pr_write_kernel and the uploads of the layout.  The reads
+// stay the overlapper's codes (sel.call.dQ, which core points into); core.min_cov is left to the caller.
+struct DeviceRowsInput {
+    PolLayout L;
+    DBuf<PolRow> rows;
+    DBuf<uint32_t> ops, cbase;
+    DBuf<PolTile> tiles;
+    DBuf<uint8_t> contig, quals;
+    PolCoreIn core;
+    uint64_t ins_edge = 0, ins_long = 0;
+};
+void device_rows_input(const RowSelection &sel, const char *who, bool weighted, hlmi_polish_stats *st, DeviceRowsInput &out);
 
 }  // namespace pol
 }  // namespace hlmi

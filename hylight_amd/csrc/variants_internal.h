@@ -1,0 +1,23 @@
+// variants_internal.h - what variants_host.cpp (the two entry points, the files) and variants.hip (the kernels) share.  The rules
+// are those of include/hylight_mi.h (hlmi_variants, hlmi_variants_reads); tests/variants_model.py restates them.
+#pragma once
+#include "common.h"
+#include "polish_internal.h"
+#include "variants_text.h"
+
+namespace hlmi {
+namespace var {
+
+// The device part over the polisher's input (rows, compact CIGARs, reads as ASCII or codes, contig bytes, tiles, cbase - in.quals
+// and in.min_cov are not read): the three counters per slot and the sites' records, ascending.  o: validated by the caller.
+void variants_core(const pol::PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &out);
+
+}  // namespace var
+
+// pairs_paf, out_summary: may be nullptr
+void variants_run(const char *contigs, const char *reads, const char *paf, const hlmi_variant_opts &o, const char *pairs_paf,
+                  const char *out_sites, const char *out_summary, hlmi_variant_stats *st);
+void variants_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_variant_opts &o,
+                        const char *pairs_paf, const char *out_sites, const char *out_summary, hlmi_variant_stats *st);
+
+}  // namespace hlmi

@@ -212,6 +212,27 @@ def depth_tables(final, long_reads, short_reads, outdir, device=None):
     return out
 
 
+def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None):
+    """`--variants`: the variant sites of the final contigs (hlmi_variants_reads: the reads are aligned to the contigs in the
+    call, every pair, one row per read) - is each contig one strain?  The long reads - the filtered ones the overlap stage read -
+    with the overlapper's long constants give outdir/final_contigs.long.variants.tsv and .long.variants.summary.tsv; short reads,
+    when there are any, with the short constants give the .short. pair.  long_pairs / short_pairs (`--polish_strain`: the run's
+    ov_long_ref.paf / shortr1.paf): only the (read, contig) pairs the list names vote; a list row whose names this call does not
+    know counts in pairs_unknown.  `device`: the GPU to initialise the library on (None: the caller has done so).
+    -> {"long": stats, "short": stats}."""
+    if device is not None:
+        api.init(device)
+    out = {}
+    for kind, reads, pairs in (("long", long_reads, long_pairs), ("short", short_reads, short_pairs)):
+        if not reads:
+            continue
+        o = api.ava_opts_short() if kind == "short" else api.ava_opts_long()
+        o.pair_once = 0
+        stem = os.path.join(outdir, f"final_contigs.{kind}.variants")
+        out[kind] = api.variants_reads(final, reads, stem + ".tsv", stem + ".summary.tsv", o, pairs=pairs)
+    return out
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m hylight_amd.driver",
                                 description="Haplotype-aware de novo assembly of metagenome from hybrid sequencing data "
@@ -279,6 +300,10 @@ def build_parser():
                    help="(extension) when final_contigs.fa is written: read depth and relative abundance of its contigs "
                         "(hlmi_depth_reads) into final_contigs.long.depth.tsv and .bedgraph, and with -s also "
                         "final_contigs.short.depth.tsv and .bedgraph")
+    p.add_argument("--variants", action="store_true",
+                   help="(extension) when final_contigs.fa is written: the variant sites of its contigs and a summary per contig "
+                        "(hlmi_variants_reads) into final_contigs.long.variants.tsv and .long.variants.summary.tsv, and with -s "
+                        "also the .short. pair; with --polish_strain only the pairs of ov_long_ref.paf / shortr1.paf vote")
     return p
 
 
@@ -525,6 +550,9 @@ def _pipeline(args, pool):
         rc = _short_branch(args, tmp, outdir, long_con3, pool)
         if rc == 0 and args.depth:
             depth_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir)
+        if rc == 0 and args.variants:
+            variant_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
+                           long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None)
         return rc
     # HyLight.py:211-262 (read clustering, POLYTE per cluster) is the short-read branch: not part of this path.  Its
     # contigs can be handed in; the contig-overlap half of extend_con runs either way (HyLight.py:264-280).
@@ -561,6 +589,9 @@ def _pipeline(args, pool):
         return EXIT_NO_FINAL
     if args.depth:
         depth_tables(final, infile, short_reads, outdir)
+    if args.variants:
+        variant_tables(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
+                       short_pairs=ov_short if args.polish_strain else None)
     return 0
 
 

@@ -901,6 +901,69 @@ int hlmi_depth(const char *contigs, const char *reads, const char *paf, const hl
 int hlmi_depth_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_depth_opts *o,
                      const char *pairs_paf, const char *out_tsv, const char *out_bedgraph, hlmi_depth_stats *st);
 
+/* ---- variant sites per contig: the positions where a second symbol has real support among the selected reads' votes - a
+ * collapsed strain, a mis-join or a polishing error - and per contig how many there are.  A contig without a site is strain-pure
+ * as far as the reads can tell.  hlmi_variants reads a PAF as hlmi_depth does, hlmi_variants_reads aligns in the call as
+ * hlmi_depth_reads does.  New symbols: the older calls keep their signatures and their bytes, and HLMI_ABI_VERSION stays where it
+ * is.  A function of the project's own: PARITY UNPINNED; tests/variants_model.py is the contract, byte for byte. */
+typedef struct {
+    int min_len;              /* selection, as hlmi_depth_opts                                                             */
+    double min_iden;
+    int min_cov;              /* votes a position needs to be callable (>= 1)                                              */
+    int min_alt;              /* votes the alternative symbol needs (>= 1)                                                 */
+    double min_frac;          /* ... and its share of the position's votes, in [0, 1]                                      */
+} hlmi_variant_opts;
+void hlmi_variant_opts_default(hlmi_variant_opts *o);   /* 0, 0.0, 3, 2, 0.2 */
+typedef struct {
+    uint64_t rows;              /* PAF rows / overlapper rows                                                               */
+    uint64_t rows_selected;     /* rows that vote (one per read at most)                                                    */
+    uint64_t contigs;           /* records of `contigs`                                                                     */
+    uint64_t contigs_covered;   /* ... with a selected row                                                                  */
+    uint64_t positions;         /* bases of ALL contigs                                                                     */
+    uint64_t callable;          /* positions with votes >= min_cov whose own base is A C G T                                */
+    uint64_t ref_other;         /* positions with votes >= min_cov whose own byte is not A C G T                            */
+    uint64_t sites;             /* sites = sites_base + sites_del                                                           */
+    uint64_t sites_base;        /* ... whose alternative is a base                                                          */
+    uint64_t sites_del;         /* ... whose alternative is del                                                             */
+    uint64_t pairs_listed;      /* the three counters of hlmi_polish_pstats; 0 without a list                              */
+    uint64_t pairs_unknown;
+    uint64_t rows_not_listed;
+    double ms_device;           /* wall time of the device part: uploads, kernels, read-backs                               */
+    double ms_total;
+} hlmi_variant_stats;
+/* contigs, reads, paf: as for hlmi_depth.  pairs_paf and out_summary may be NULL.
+ * Selection: exactly hlmi_depth's, run by the same code: hlmi_polish_pairs's selection without the quality floor, the list's
+ * format and meaning word for word (pairs_paf == NULL: no list, every row may vote; an empty file: a valid list of no pairs, no
+ * row votes).
+ * Votes: exactly hlmi_polish's position votes, unweighted.  A selected row's '=' or 'X' column votes its read base at the
+ * column's contig position if that base is A, C, G or T of either case (strand '-': its complement) and nothing otherwise; a 'D'
+ * column votes del.  Slots (the columns of I ops) and base qualities take no part.
+ * Site rule at position p: v[A], v[C], v[G], v[T], v[del] are the votes and c their sum; own is the contig's byte, upper-cased.
+ * c < min_cov: the position is not callable.  c >= min_cov and own is not A C G T: the position counts in ref_other and is never a
+ * site.  Otherwise the position is callable; alt is the symbol other than own with the most votes, on a tie the first in the
+ * order A, C, G, T, del; the position is a site iff v[alt] >= min_alt and (double)v[alt] / (double)c >= min_frac (one IEEE
+ * division).  own may be the minority symbol: the position is still a site, with alt chosen by the same rule.
+ * out_sites (under a temporary name, renamed on success): the line
+ * "#contig\tpos\tref\tdepth\tA\tC\tG\tT\tdel\talt\talt_count\talt_frac", then one line per site, contigs in file order,
+ * positions ascending: pos is 1-based, ref the upper-cased own base, depth is c, then the five votes, alt the letter or '*' for
+ * del, alt_count = v[alt], alt_frac the quotient above as %.6f.  With no site the file is the header line alone.
+ * out_summary (optional): the line "#contig\tlength\treads\tcallable\tsites\tsite_rate", then one line per contig in file order,
+ * EVERY contig, those without a selected row and those of 0 bases included (zeros): reads = selected rows on it; site_rate =
+ * (double)sites / (double)callable as %.6f, 0.000000 when callable is 0.
+ * Refusals (HLMI_EINVAL unless said otherwise, nothing is written): min_cov < 1, min_alt < 1, min_frac outside [0, 1] or not a
+ * number; then every refusal hlmi_depth makes about the files, the rows and the list, in its order: two records of one name in
+ * `contigs` or in `reads` (the tables are keyed by name), and 2^31 bases or more of contigs with a selected row, among them. */
+int hlmi_variants(const char *contigs, const char *reads, const char *paf, const hlmi_variant_opts *o, const char *pairs_paf,
+                  const char *out_sites, const char *out_summary, hlmi_variant_stats *st);
+/* The two calls hlmi_ava(contigs, reads, ao, P) and hlmi_variants(contigs, reads, P, o, pairs_paf, ...) in one, without the PAF P:
+ * both files and every integer field of *st are byte for byte what that chain gives (ao NULL: the long constants).  The
+ * overlapper's rows are selected and compacted where they are, by the kernels hlmi_polish_reads_pairs runs, and voted from the
+ * overlapper's resident read codes (csrc/variants.hip).  The three stated differences of hlmi_polish_reads apply (a name twice,
+ * stub_oh >= 0, 2^32 rows), the list refusals of hlmi_polish_reads_pairs, a sequence of 2^28 bases or more, and 2^31 contig
+ * bases. */
+int hlmi_variants_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_variant_opts *o,
+                        const char *pairs_paf, const char *out_sites, const char *out_summary, hlmi_variant_stats *st);
+
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
  * reads into a caller-owned device buffer (16 B per minimizer: two uint64), the caller
