@@ -1,25 +1,30 @@
-// ava_align.hip - S5 of the overlapper spec: base-level alignment of the chain pieces.
+// ava_align.hip - S5 of the overlapper spec: base-level alignment of the chain pieces.  The kernels by family, then the host
+// driver (align_span, align_pieces).
 //
 // Every piece is a list of fixed points; consecutive fixed points bound an independent global
 // alignment block (|diagonal shift| <= 39, any length) and the two piece ends get a local
 // extension (up to max(256, max_gap) rows, z-drop).  Blocks of more than 256 rows or columns and
-// extensions of more than 256 rows are LONG tasks (align_long_kernel: the band walks the task in
-// tiles of 256 rows, its traceback planes live in a scratch area per wave).  Passes:
-//   make_tasks   one self-contained 32-byte record per block / extension
-//   classify     lane per task: square blocks with <= kmax substitutions are finished on the spot (proof at the
-//                kernel), the rest is split into near-diagonal (16-diagonal band) and wide (64 diagonals) lists
-//   align_narrow four tasks per wave (one per DPP row), align (wide) one task per wave.  Lanes = diagonals, rows one
-//                by one; affine gaps (Gotoh): F from lane d+1 of the previous row, E from a max-plus prefix scan
-//                across the lanes (E(d) = max_{d'<d} Ht(d') - open - ext*(d-d')); the five traceback bits of a cell
-//                stay with its lane as bit planes; the traceback jumps along diagonals with count-trailing-ones
-//   assemble     wave per piece: merged CIGAR + PafRec
+// extensions of more than 256 rows are LONG tasks.  One pass over a span of pieces (align_span):
+//   tasks        8-byte references of the blocks / extensions of every piece and the piece's geometry
+//   classify     lane per task: tasks a certificate settles are finished on the spot (proofs at classify_kernel), the rest
+//                gets its 32-byte record and a class; one list per class
+//   LONG first   their kernels walk a task in tiles of 256 rows and last longest
+//   narrow       16-diagonal band, eight tasks per wave in the packed form, else four
+//   wide         64-diagonal band, one task per wave; bandwidth 0: the diagonal alone
+//   score-only   the tasks of stub candidates, whose rows nobody reads
+//   stub rule    count, then a late round for the candidates that need their end extensions after all
+//   join, and a retry with a larger CIGAR run pool when it overflowed
+//   assemble     merged CIGAR + PafRec per piece
 // The recurrences, tie rules and the best-cell rule of the extensions are those of
 // oracle/ava_oracle.c:band_dp.  VALU bound by nature: reads ~1 B per
 // DP row per sequence from HBM.
 #include <algorithm>
 #include <memory>
+#include <string>
 #include <type_traits>
+#include <vector>
 
+#include "align_score_setup.h"
 #include "ava_internal.h"
 #include "dev_prims.h"
 #include "wave_ops.h"
@@ -280,6 +285,14 @@ constexpr int NR_SMALL = 64;                    // narrow tasks with fewer rows 
 constexpr uint8_t CLS_LONG = 5;                 // class of the LONG tasks (align_long_kernel)
 constexpr uint8_t CLS_LONG32 = 7;               // LONG tasks in the 32-diagonal band, two to a wave (align_long32_kernel)
 constexpr uint8_t CLS_UNGAPPED = 6;             // bandwidth 0: every task a certificate does not settle (align_ungapped_kernel)
+// The DP launches of a pass: timer name, slot of the per-launch statistics ("align_n.<name>", "align_bases.<name>") and the
+// slot class_bases_kernel sums a task's bases into.
+enum DpKind { DP_NARROW_SMALL = 0, DP_NARROW, DP_NARROW_LONG, DP_WIDE, DP_WIDE_SHORT, DP_LONG, DP_SCORE_NARROW, DP_SCORE_NARROW_LONG,
+              DP_SCORE_WIDE, DP_SCORE_WIDE_SHORT, DP_SCORE_LONG, DP_UNGAPPED, DP_LONG32, DP_SCORE_LONG32, N_DP_KINDS };
+constexpr const char *DP_NAMES[N_DP_KINDS] = {"align_narrow_small", "align_narrow", "align_narrow_long", "align_wide", "align_wide_short",
+                                              "align_long", "align_score_narrow", "align_score_narrow_long", "align_score_wide",
+                                              "align_score_wide_short", "align_score_long", "align_ungapped", "align_long32",
+                                              "align_score_long32"};
 
 // 8 window elements x .. x+7 (byte 0 = element x); same conventions as load_window4
 __device__ __forceinline__ uint64_t load_codes8(const uint8_t *base, long long idx, long long total) {
@@ -2620,23 +2633,25 @@ __global__ void late_tasks_kernel(const uint32_t *plist, size_t n, const Piece *
 }
 
 // (rows + columns) of the DP tasks per kernel that runs them, after a classification pass: the algorithmic bytes of the DP
-// launches (bench.py's roofline table).  Slots: LB_NAMES in align_span.
+// launches (bench.py's roofline table).  Slots: DpKind.
 __global__ __launch_bounds__(WG) void class_bases_kernel(const uint8_t *cls, const uint8_t *cls_bare, const Task *tasks, size_t n,
                                                           unsigned long long *out) {
-    __shared__ unsigned long long s_sum[14];
-    if (threadIdx.x < 14) s_sum[threadIdx.x] = 0;
+    __shared__ unsigned long long s_sum[N_DP_KINDS];
+    if (threadIdx.x < N_DP_KINDS) s_sum[threadIdx.x] = 0;
     __syncthreads();
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const int c = cls[i], cb = cls_bare ? cls_bare[i] : 0;
         if (!c && !cb) continue;
         const Task &t = tasks[i];
         int slot;
-        if (c) slot = c == 1 ? ((int)t.m < NR_SMALL ? 0 : 1) : c == 3 ? 2 : c == 2 ? 3 : c == 4 ? 4 : c == CLS_LONG ? 5 : c == CLS_LONG32 ? 12 : 11;
-        else slot = cb == 1 ? 6 : cb == 3 ? 7 : cb == 2 ? 8 : cb == 4 ? 9 : cb == CLS_LONG ? 10 : cb == CLS_LONG32 ? 13 : 11;
+        if (c) slot = c == 1 ? ((int)t.m < NR_SMALL ? DP_NARROW_SMALL : DP_NARROW) : c == 3 ? DP_NARROW_LONG : c == 2 ? DP_WIDE : c == 4 ? DP_WIDE_SHORT
+                  : c == CLS_LONG ? DP_LONG : c == CLS_LONG32 ? DP_LONG32 : DP_UNGAPPED;
+        else slot = cb == 1 ? DP_SCORE_NARROW : cb == 3 ? DP_SCORE_NARROW_LONG : cb == 2 ? DP_SCORE_WIDE : cb == 4 ? DP_SCORE_WIDE_SHORT
+                  : cb == CLS_LONG ? DP_SCORE_LONG : cb == CLS_LONG32 ? DP_SCORE_LONG32 : DP_UNGAPPED;
         atomicAdd(&s_sum[slot], (unsigned long long)((int)t.m + (int)t.n));
     }
     __syncthreads();
-    if (threadIdx.x < 14 && s_sum[threadIdx.x]) atomicAdd(&out[threadIdx.x], s_sum[threadIdx.x]);
+    if (threadIdx.x < N_DP_KINDS && s_sum[threadIdx.x]) atomicAdd(&out[threadIdx.x], s_sum[threadIdx.x]);
 }
 
 // LONG task list: how many of the tasks are end extensions, and their rows (statistics: align_long_ext / align_long_ext_rows)
@@ -2743,130 +2758,265 @@ __global__ __launch_bounds__(WG) void move_fixed_points_kernel(Piece *pieces, si
 }
 }  // namespace
 
+namespace {
+static_assert(SETUP_BLOCK_MAX == BLOCK_MAX && SETUP_NARROW_W == NARROW_W && SETUP_EXT_MAX == EXT_MAX &&
+              SETUP_LONG_ROWS_EXTRA == BLOCK_MIN + SHIFT_MAX + BAND_W + 1, "align_score_setup.h: spec constants");
+
+constexpr size_t MAX_BLOCKS = 256 * 16;
+
+// ---- host side.  The grid rules of the DP families and of the assembly ----
+void launch_narrow(DpKind kind, const AlignArgs &a, bool packed) {
+    if (packed) {
+        const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>(((a.n_list + 7) / 8 + PK_WAVES - 1) / PK_WAVES, 256 * 32))), wg(64 * PK_WAVES);
+        switch (kind) {
+        case DP_NARROW_SMALL: hipLaunchKernelGGL(align_narrow_pk_kernel<NR_SMALL>, grid, wg, 0, stream(), a); break;
+        case DP_NARROW: hipLaunchKernelGGL(align_narrow_pk_kernel<NR_SHORT>, grid, wg, 0, stream(), a); break;
+        case DP_NARROW_LONG: hipLaunchKernelGGL(align_narrow_pk_kernel<BLOCK_MAX>, grid, wg, 0, stream(), a); break;
+        case DP_SCORE_NARROW: hipLaunchKernelGGL((align_narrow_pk_kernel<NR_SHORT, false>), grid, wg, 0, stream(), a); break;
+        case DP_SCORE_NARROW_LONG: hipLaunchKernelGGL((align_narrow_pk_kernel<BLOCK_MAX, false>), grid, wg, 0, stream(), a); break;
+        default: fail(HLMI_ESTATE, "launch_narrow: %s has no packed near-diagonal kernel", DP_NAMES[kind]);
+        }
+    } else {
+        const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>(((a.n_list + 3) / 4 + WAVES - 1) / WAVES, 256 * 16)));
+        if (kind == DP_NARROW) hipLaunchKernelGGL(align_narrow_kernel<NR_SHORT>, grid, dim3(WG), 0, stream(), a);
+        else if (kind == DP_NARROW_LONG) hipLaunchKernelGGL(align_narrow_kernel<BLOCK_MAX>, grid, dim3(WG), 0, stream(), a);
+        else fail(HLMI_ESTATE, "launch_narrow: %s has no near-diagonal kernel", DP_NAMES[kind]);
+    }
+}
+void launch_wide(DpKind kind, const AlignArgs &a) {
+    const dim3 grid((unsigned)std::max<size_t>(1, std::min<size_t>((a.n_list + WAVES - 1) / WAVES, 256 * 16)));
+    switch (kind) {
+    case DP_WIDE: hipLaunchKernelGGL(align_kernel<EXT_MAX>, grid, dim3(WG), 0, stream(), a); break;
+    case DP_WIDE_SHORT: hipLaunchKernelGGL(align_kernel<WIDE_SHORT>, grid, dim3(WG), 0, stream(), a); break;
+    case DP_SCORE_WIDE: hipLaunchKernelGGL((align_kernel<EXT_MAX, false>), grid, dim3(WG), 0, stream(), a); break;
+    case DP_SCORE_WIDE_SHORT: hipLaunchKernelGGL((align_kernel<WIDE_SHORT, false>), grid, dim3(WG), 0, stream(), a); break;
+    default: fail(HLMI_ESTATE, "launch_wide: %s has no 64-diagonal kernel", DP_NAMES[kind]);
+    }
+}
+void launch_long(DpKind kind, const AlignArgs &a, const LongArgs &la, unsigned blocks, hipStream_t on) {
+    const bool two = a.go2 > 0;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(WG), 0, on, a, la); };
+    switch (kind) {      // (the 32-diagonal band knows the first piece of the gap cost alone: section 5 of DESIGN.md)
+    case DP_LONG32: go(align_long32_kernel<false, true>); break;
+    case DP_SCORE_LONG32: go(align_long32_kernel<false, false>); break;
+    case DP_LONG: if (two) go(align_long_kernel<true, true>); else go(align_long_kernel<false, true>); break;
+    case DP_SCORE_LONG: if (two) go(align_long_kernel<true, false>); else go(align_long_kernel<false, false>); break;
+    default: fail(HLMI_ESTATE, "launch_long: %s is no LONG launch", DP_NAMES[kind]);
+    }
+}
+// pieces per wave (wave form) or per lane (lane form: pieces of half a dozen tasks)
+static dim3 assemble_grid(const AsmArgs &a, bool small_pieces) {
+    return small_pieces ? grid1(a.n_pieces) : dim3((unsigned)std::min<size_t>(cdiv(a.n_pieces, (size_t)WAVES), 256 * 32));
+}
+void launch_assemble_count(const AsmArgs &a, bool small_pieces, uint32_t *n_ops, uint8_t *valid) {
+    KTimer kt("assemble_count");
+    if (small_pieces) hipLaunchKernelGGL(assemble_lane_kernel<false>, assemble_grid(a, true), dim3(WG), 0, stream(), a, n_ops, valid, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr);
+    else hipLaunchKernelGGL(assemble_kernel<false>, assemble_grid(a, false), dim3(WG), 0, stream(), a, n_ops, valid, nullptr, nullptr, nullptr,
+                            nullptr, nullptr);
+}
+void launch_assemble_write(const AsmArgs &a, bool small_pieces, uint8_t *valid, const uint64_t *ops_off, uint32_t *ops, PafRec *recs,
+                           uint64_t *ord_hi, uint64_t *ord_lo) {
+    KTimer kt("assemble_write");
+    if (small_pieces) hipLaunchKernelGGL(assemble_lane_kernel<true>, assemble_grid(a, true), dim3(WG), 0, stream(), a, nullptr, valid, ops_off, ops,
+                                         recs, ord_hi, ord_lo);
+    else hipLaunchKernelGGL(assemble_kernel<true>, assemble_grid(a, false), dim3(WG), 0, stream(), a, nullptr, valid, ops_off, ops, recs, ord_hi,
+                            ord_lo);
+}
+// 8 workgroups of 4 waves per CU: the walks of the tasks wait on memory.  (Fewer - to leave wave slots to the kernels on the
+// compute stream - was measured on a C5 chunk: 1.46 s with 2 048 workgroups, 1.45 with 1 024, 1.40 with 512, 1.43 with the long
+// kernels in line on the compute stream: the card is busy either way, what runs beside a kernel runs that much slower.)
+constexpr unsigned LONG_BLOCKS_MAX = 256 * 8;
+
 // pieces [0, P) of `pieces` with n_fp fixed points between them
 struct PieceSpan { struct { const Piece *p; } pieces; size_t n_pieces, n_fp; struct { const FixPt *p; } fps; };
-static void align_span(const AvaInput &in, const hlmi_ava_opts &o, const uint32_t *d_qlen, const uint32_t *d_tlen,
-                       const PieceSpan &ch, AlignOut &out) {
-    out = AlignOut();
-    const size_t P = ch.n_pieces;
-    if (!P) return;
-    DBuf<uint32_t> tcnt(P), toff(P);
-    hipLaunchKernelGGL(piece_task_count_kernel, grid1(P), dim3(WG), 0, stream(), ch.pieces.p, P, tcnt.p);
-    exclusive_scan_u32(tcnt.p, toff.p, P);
-    const size_t NT = ch.n_fp + P;              // a piece of n fixed points has n - 1 blocks and two extensions
-    DBuf<Task> tasks(NT);
-    if (P >= (1u << 30)) fail(HLMI_EINVAL, "more than 2^30 alignment pieces in one batch");
-    DBuf<TaskRef> task_ref(NT);
-    DBuf<PieceGeom> pgeom(P);
-    if (NT <= 17 * P)                  // pieces of a handful of tasks: a lane each
-        hipLaunchKernelGGL(task_ref_lane_kernel, grid1(P), dim3(WG), 0, stream(), ch.pieces.p, toff.p, P, d_qlen, d_tlen, in.Q->off.p, in.T->off.p,
-                           ch.fps.p, o.stub_oh, ext_rows(o), task_ref.p, pgeom.p);
-    else
-    hipLaunchKernelGGL(task_ref_kernel, dim3((unsigned)std::min<size_t>(cdiv(P, (size_t)WAVES), 256 * 32)), dim3(WG), 0, stream(),
-                       ch.pieces.p, toff.p, P, d_qlen, d_tlen, in.Q->off.p, in.T->off.p, ch.fps.p, o.stub_oh, ext_rows(o), task_ref.p, pgeom.p);
-    HIP_CHECK(hipGetLastError());
-    DBuf<TaskOut> tout(NT);
-    DBuf<uint32_t> counters(2);
-    DBuf<unsigned long long> astats(N_ALIGN_STATS);
-    // runs + one open chunk per allocating lane of every launch: classify and the two align_kernel (one per wave), the two
-    // align_narrow_kernel instances (one per 16-lane group)
-    constexpr size_t MAX_BLOCKS = 256 * 16;
-    // (a pool that overflows costs a second run of every DP kernel: 12 runs per task cover read sets with a few per cent
-    // of errors, where the average is 8)
-    const size_t open_chunks = MAX_BLOCKS * (4 * WAVES * RUN_CHUNK + 2 * 4 * WAVES * RUN_CHUNK_SMALL) +
-                               (size_t)3 * 256 * 32 * 8 * PK_WAVES * RUN_CHUNK_SMALL;  // (three packed launches: 8 allocating lanes per wave)
-    size_t run_share = std::max<size_t>(NT * 12, 1 << 16);
-    DBuf<uint32_t> runs;
-    AsmArgs as{};
-    as.pieces = ch.pieces.p; as.fps = ch.fps.p; as.task_off = toff.p; as.tout = tout.p; as.n_pieces = P;
-    as.min_dp_score = o.min_dp_score; as.end_bonus = o.end_bonus;
-    as.qlen = d_qlen; as.tlen = d_tlen; as.rank_q = in.d_rank_q; as.rank_t = in.d_rank_t; as.chunk_of_t = in.d_chunk_of_t;
-    as.pg = pgeom.p; as.stub_score = o.min_dp_score + std::max(0, o.end_bonus);
-    as.stage_cap = (uint32_t)ASM_STAGE;
-    if (const char *e = hook("HLMI_ASM_STAGE_CAP")) as.stage_cap = (uint32_t)std::min(ASM_STAGE, std::max(0, atoi(e)));
-    DBuf<uint32_t> nops(P);
-    DBuf<uint8_t> valid(P), late(o.stub_oh >= 0 ? P : 0);
-    DBuf<uint32_t> late_idx(o.stub_oh >= 0 ? P : 0);
-    size_t n_late = 0;
-    const unsigned nba = (unsigned)std::min<size_t>(cdiv(P, (size_t)WAVES), 256 * 32);
-    const bool small_pieces = NT <= 17 * P && !hook("HLMI_ASM_WAVE");      // half a dozen tasks per piece: the lane forms of the piece kernels
-    // packed form of the near-diagonal DP (two tasks per lane, 16-bit scores): block scores must stay within +-4096 of the bias
-    const int worst = std::max(std::max(o.match, o.mismatch), std::max(o.ambi, o.gap_open + o.gap_ext));
-    const bool packed = worst > 0 && (long long)worst * (BLOCK_MAX + NARROW_W + 2) <= 4000 && o.match >= 0 && o.mismatch >= 0 &&
-                        o.ambi >= 0 && o.gap_open >= 0 && o.gap_ext >= 0 && !hook("HLMI_NARROW_UNPACKED");
-    // stub rule, second half: nobody reads the content of a stub candidate's row, so its tasks report scores only (score-only
-    // instances of the packed and the 64-diagonal kernel; HLMI_STUB_FULL_ROWS keeps the candidates' CIGARs: test hook)
-    const bool bare = o.stub_oh >= 0 && packed && !hook("HLMI_STUB_FULL_ROWS");
-    as.bare = bare ? 1 : 0;
-    // LONG tasks (align_long_kernel).  Sizes of a wave's scratch areas from the options: a chain link spans at most max_gap
-    // bases and an extension ext_rows(o) rows.
-    if (long_rows_cap(o) > 32000) fail(HLMI_EINVAL, "max_gap %d: alignment tasks are limited to 32 000 rows", o.max_gap);
-    // An extension of <= EXT_MAX rows runs in the 64-diagonal kernels, which know no z-drop: it cannot matter there when a
-    // drop of more than zdrop (at most D per row, D = the dearest single step) plus the climb back above the old best cell
-    // (at most `match` per row) need more rows than EXT_MAX - otherwise every extension is a LONG task.
-    bool ext_all_long = false;
-    if (o.zdrop > 0) {
-        const int D = std::max(std::max(o.mismatch, o.ambi), o.gap_open + o.gap_ext);
-        const int rows_down = D > 0 ? (o.zdrop + D - 1) / D : EXT_MAX;
-        // (the best cell is ranked with the end bonus: a row that reaches the query end counts end_bonus more)
-        ext_all_long = (long long)o.match * (EXT_MAX - rows_down) + std::max(o.end_bonus, 0) > o.zdrop;
+
+// The LONG launches of a pass, the only state that spans two streams.  The LONG tasks of a batch are few (C3: ~10 000 per
+// batch) and serial in their rows: alone on the card their launch lasts as long as its longest task.  Every launch keeps its
+// own list / scratch / control words from prepare() until the streams are joined (join) in front of whatever reads the task
+// results and the control words are read (check).  In line on the compute stream by default; HLMI_LONG_SIDE_STREAM: on the
+// second stream, beside the DP kernels that follow - measured equal, C3 slice 957 vs 961 ms, C5 chunk 3.55 vs 3.56 s: the card
+// is busy either way, and kernels that share it stretch each other's timers, which is why the default is the one stream.
+class LongLaunches {
+public:
+    explicit LongLaunches(const hlmi_ava_opts &o)
+        : chunks_cap_((uint32_t)(long_rows_cap(o) + 31) / 32), runs_cap_((uint32_t)(2 * long_rows_cap(o) + 64)), zdrop_(o.zdrop),
+          on_side_(hook("HLMI_LONG_SIDE_STREAM") != nullptr) {}
+    LongLaunches(const LongLaunches &) = delete;
+    LongLaunches &operator=(const LongLaunches &) = delete;
+    ~LongLaunches() {       // an exception on the way out must not free buffers the side stream still uses
+        if (hipStream_t s = side_stream_if_created()) (void)hipStreamSynchronize(s);      // (never creates it, never throws)
+        if (done_) (void)hipEventDestroy(done_);
     }
-    const uint32_t long_chunks_cap = (uint32_t)(long_rows_cap(o) + 31) / 32, long_runs_cap = (uint32_t)(2 * long_rows_cap(o) + 64);
-    // 8 workgroups of 4 waves per CU: the walks of the tasks wait on memory.  (Fewer - to leave wave slots to the kernels on the
-    // compute stream - was measured on a C5 chunk: 1.46 s with 2 048 workgroups, 1.45 with 1 024, 1.40 with 512, 1.43 with the long
-    // kernels in line on the compute stream: the card is busy either way, what runs beside a kernel runs that much slower.)
-    constexpr unsigned LONG_BLOCKS_MAX = 256 * 8;
-    // The LONG tasks of a batch are few (C3: ~10 000 per batch) and serial in their rows: alone on the card their launch lasts as
-    // long as its longest task.  They run on the side stream beside the batch's other DP kernels; every launch keeps its own
-    // list / scratch / control words until the streams are joined (join_long) in front of whatever reads the task results.
-    struct LongLaunch { DBuf<uint32_t> list, planes, runs, ctl; };
-    std::vector<std::unique_ptr<LongLaunch>> long_launches;
-    struct LongReady { AlignArgs al; LongArgs la; unsigned nb; bool half, tb; const char *timer; };
-    std::vector<LongReady> long_ready;                   // prepared, not yet launched
-    hipEvent_t long_done = nullptr;
-    bool long_pending = false, long_on_side = false;     // launches not yet joined / some of them on the second stream
-    struct SideGuard {                                   // an exception on the way out must not free buffers the side stream still uses
-        ~SideGuard() { if (hipStream_t s = side_stream_if_created()) (void)hipStreamSynchronize(s); }      // (never creates it, never throws)
-    } side_guard;
-    auto join_long = [&]() {
-        if (!long_pending) return;
-        if (long_on_side) {                              // (in line on the compute stream - the default - there is nothing to join)
-            if (!long_done) HIP_CHECK(hipEventCreateWithFlags(&long_done, hipEventDisableTiming));
-            HIP_CHECK(hipEventRecord(long_done, side_stream()));
-            HIP_CHECK(hipStreamWaitEvent(stream(), long_done, 0));
-            long_on_side = false;
+    bool on_side() const { return on_side_; }
+    double side_launches() const { return side_launches_; }
+
+    // One launch over the nl tasks `ids` (CLS_LONG: 64 diagonals, a task per wave; CLS_LONG32: 32 diagonals, two per wave):
+    // its own list, scratch areas sized from the options and control words.  Prepared only: start() launches it.
+    void prepare(DpKind kind, const Task *tasks, const uint32_t *ids, size_t nl) {
+        const bool half = kind == DP_LONG32 || kind == DP_SCORE_LONG32, tb = kind == DP_LONG || kind == DP_LONG32;
+        launches_.emplace_back(new Launch());
+        Launch &L = *launches_.back();
+        L.kind = kind; L.n = nl;
+        {   // longest first: the work queue then ends with the short tasks (and the two tasks of a wave are equally long)
+            DBuf<uint32_t> key(nl);
+            hipLaunchKernelGGL(task_rows_desc_key_kernel, grid1(nl), dim3(WG), 0, stream(), tasks, ids, nl, key.p);
+            L.list.alloc(nl);
+            HIP_CHECK(hipMemcpyAsync(L.list.p, ids, nl * 4, hipMemcpyDeviceToDevice, stream()));
+            sort_pairs_u32_u32(key, L.list, nl, 0, 16);
         }
-        long_pending = false;
-    };
-    DBuf<uint8_t> long_flag;
-    DBuf<uint32_t> long_list, long_n(1);
-    size_t n_long_tb = 0, n_long_bare = 0;
+        const size_t units = half ? (nl + 1) / 2 : nl;           // waves' worth of work
+        L.blocks = (unsigned)std::min<size_t>((units + WAVES - 1) / WAVES, LONG_BLOCKS_MAX);
+        const size_t n_waves = (size_t)L.blocks * WAVES;
+        if (tb) {
+            L.planes.alloc(n_waves * (size_t)N_WPLANES * chunks_cap_ * 64);
+            L.runs.alloc(n_waves * (size_t)runs_cap_ * (half ? 2 : 1));
+            L.la.planes = L.planes.p; L.la.run_scratch = L.runs.p;
+        }
+        L.la.chunks_cap = chunks_cap_; L.la.runs_cap = runs_cap_; L.la.zdrop = zdrop_;
+        L.ctl.alloc(4);
+        L.ctl.zero();
+        L.la.next = L.ctl.p; L.la.too_long = L.ctl.p + 1; L.la.rows_run = (unsigned long long *)(L.ctl.p + 2);
+    }
+    // every prepared LONG launch starts after ALL their lists are built: on the second stream (HLMI_LONG_SIDE_STREAM) a selection
+    // pass queued behind a running long kernel waits for the whole of it (its first round of tasks fills every SIMD; measured:
+    // a 40 us scan took 31 ms), and with it everything the compute stream was to run beside the long kernel
+    // launch(kind, list, n, stream, LongArgs, blocks)
+    template <class F>
+    void start(F &&launch) {
+        if (n_started_ == launches_.size()) return;
+        sync();                                                  // lists, keys and control words are in place
+        hipStream_t ls = on_side_ ? side_stream() : stream();
+        for (; n_started_ < launches_.size(); ++n_started_) {
+            const Launch &L = *launches_[n_started_];
+            launch(L.kind, L.list.p, L.n, ls, L.la, L.blocks);
+            if (on_side_) side_launches_ += 1;
+        }
+        HIP_CHECK(hipGetLastError());
+        pending_ = true;
+    }
+    // in front of whatever reads the task results (in line on the compute stream - the default - there is nothing to join)
+    void join() {
+        if (pending_ && on_side_) {
+            if (!done_) HIP_CHECK(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+            HIP_CHECK(hipEventRecord(done_, side_stream()));
+            HIP_CHECK(hipStreamWaitEvent(stream(), done_, 0));
+        }
+        pending_ = false;
+    }
+    // after a join and a wait for the stream: did a LONG task exceed its scratch area?  Returns the rows the tasks ran.
+    double check() {
+        double rows_run = 0;
+        for (auto &L : launches_) {
+            const std::vector<uint32_t> c = L->ctl.download(4);
+            if (c[1]) fail(HLMI_EINVAL, "an alignment task exceeds the scratch area of align_long_kernel");
+            rows_run += (double)((unsigned long long)c[3] << 32 | c[2]);
+        }
+        // (read once; the launches are over - joined and waited for -: their planes (GBs at max_gap 10 000), runs and lists go
+        //  back to the pool now, not when align_span returns: a retry of the span allocates them again)
+        launches_.clear();
+        n_started_ = 0;
+        return rows_run;
+    }
+
+private:
+    struct Launch { DpKind kind; size_t n; unsigned blocks; LongArgs la{}; DBuf<uint32_t> list, planes, runs, ctl; };
+    std::vector<std::unique_ptr<Launch>> launches_;
+    size_t n_started_ = 0;                  // launches_[n_started_ ..) are prepared, not yet launched
+    const uint32_t chunks_cap_, runs_cap_;  // a wave's scratch areas: a chain link spans at most max_gap bases, an extension ext_rows(o) rows
+    const int zdrop_;
+    const bool on_side_;
+    bool pending_ = false;                  // launches not yet joined
+    hipEvent_t done_ = nullptr;
+    double side_launches_ = 0;
+};
+
+// what a DP launch needs beyond kind, list and stream
+struct DpExtra {
+    const LongArgs *la = nullptr;    // LONG kinds: scratch areas and control words, workgroups
+    unsigned blocks = 0;
+    bool traceback = true;           // DP_UNGAPPED: one kind for both forms of its kernel
+};
+
+// One alignment pass over a span of pieces: its buffers and the steps of align_span, in the order they run.
+struct AlignPass {
+    const AvaInput &in;
+    const hlmi_ava_opts &o;
+    const PieceSpan &ch;
+    const AlignScoreSetup &sc;
+    const size_t P, NT;              // a piece of n fixed points has n - 1 blocks and two extensions
+    const bool small_pieces;         // half a dozen tasks per piece: the lane forms of the piece kernels
+    DBuf<uint32_t> toff, counters, runs, nops, late_idx;
+    DBuf<Task> tasks;
+    DBuf<TaskRef> task_ref;
+    DBuf<PieceGeom> pgeom;
+    DBuf<TaskOut> tout;
+    DBuf<unsigned long long> astats, lb_bases;        // lb_bases: per DpKind, + 2: end extensions among the LONG tasks, their rows
+    DBuf<uint8_t> valid, late;
+    // of one attempt
+    DBuf<uint8_t> cls, f1, cls_bare, sel_flag;
+    DBuf<uint32_t> list1, list2, list3, list4, list_n, sel_list, sel_n;
+    AlignArgs aa{};
+    AsmArgs as{};
+    LongLaunches longs;
+    double lb_n[N_DP_KINDS] = {};    // per DP launch kind: tasks ("align_n.<timer>"; their bases: class_bases_kernel)
+    size_t n1 = 0, n2 = 0, n3 = 0, n4 = 0, n_late = 0, n_wide_late = 0, n_bare_tasks = 0, n_long_tb = 0, n_long_bare = 0;
+    unsigned long long long_seen = 0;
     double long_rows_run = 0;
-    // per DP launch: tasks and bases (rows + columns) - "align_n.<timer>", "align_bases.<timer>" of the statistics
-    static const char *const LB_NAMES[] = {"align_narrow_small", "align_narrow", "align_narrow_long", "align_wide", "align_wide_short",
-                                           "align_long", "align_score_narrow", "align_score_narrow_long", "align_score_wide",
-                                           "align_score_wide_short", "align_score_long", "align_ungapped", "align_long32",
-                                           "align_score_long32"};
-    constexpr int N_LB = 14;
-    DBuf<unsigned long long> lb_bases(N_LB + 2);              // (+ 2: end extensions among the LONG tasks, their rows)
-    std::vector<double> lb_n(N_LB, 0.0);
-    lb_bases.zero();
-    auto note_list = [&](const char *timer, const Task *tk, const uint32_t *lst, size_t n) {
-        if (!n) return;
-        int slot = 0;
-        while (slot < N_LB && strcmp(LB_NAMES[slot], timer) != 0) ++slot;
-        if (slot == N_LB) return;
-        lb_n[slot] += (double)n;             // (their bases: class_bases_kernel, once per classification pass)
-        (void)tk; (void)lst;
-    };
-    for (int attempt = 0;; ++attempt) {
+
+    AlignPass(const AvaInput &in_, const hlmi_ava_opts &o_, const uint32_t *d_qlen, const uint32_t *d_tlen, const PieceSpan &ch_,
+              const AlignScoreSetup &sc_)
+        : in(in_), o(o_), ch(ch_), sc(sc_), P(ch_.n_pieces), NT(ch_.n_fp + ch_.n_pieces),
+          small_pieces(NT <= 17 * P && !hook("HLMI_ASM_WAVE")), longs(o_) {
+        DBuf<uint32_t> tcnt(P);
+        toff.alloc(P);
+        hipLaunchKernelGGL(piece_task_count_kernel, grid1(P), dim3(WG), 0, stream(), ch.pieces.p, P, tcnt.p);
+        exclusive_scan_u32(tcnt.p, toff.p, P);
+        tasks.alloc(NT);
+        if (P >= (1u << 30)) fail(HLMI_EINVAL, "more than 2^30 alignment pieces in one batch");
+        task_ref.alloc(NT);
+        pgeom.alloc(P);
+        if (NT <= 17 * P)                  // pieces of a handful of tasks: a lane each
+            hipLaunchKernelGGL(task_ref_lane_kernel, grid1(P), dim3(WG), 0, stream(), ch.pieces.p, toff.p, P, d_qlen, d_tlen, in.Q->off.p, in.T->off.p,
+                               ch.fps.p, o.stub_oh, ext_rows(o), task_ref.p, pgeom.p);
+        else
+            hipLaunchKernelGGL(task_ref_kernel, dim3((unsigned)std::min<size_t>(cdiv(P, (size_t)WAVES), 256 * 32)), dim3(WG), 0, stream(),
+                               ch.pieces.p, toff.p, P, d_qlen, d_tlen, in.Q->off.p, in.T->off.p, ch.fps.p, o.stub_oh, ext_rows(o), task_ref.p, pgeom.p);
+        HIP_CHECK(hipGetLastError());
+        tout.alloc(NT);
+        counters.alloc(2);
+        astats.alloc(N_ALIGN_STATS);
+        as.pieces = ch.pieces.p; as.fps = ch.fps.p; as.task_off = toff.p; as.tout = tout.p; as.n_pieces = P;
+        as.min_dp_score = o.min_dp_score; as.end_bonus = o.end_bonus;
+        as.qlen = d_qlen; as.tlen = d_tlen; as.rank_q = in.d_rank_q; as.rank_t = in.d_rank_t; as.chunk_of_t = in.d_chunk_of_t;
+        as.pg = pgeom.p; as.stub_score = o.min_dp_score + std::max(0, o.end_bonus);
+        as.stage_cap = (uint32_t)ASM_STAGE;
+        if (const char *e = hook("HLMI_ASM_STAGE_CAP")) as.stage_cap = (uint32_t)std::min(ASM_STAGE, std::max(0, atoi(e)));
+        as.bare = sc.bare ? 1 : 0;
+        nops.alloc(P);
+        valid.alloc(P);
+        late.alloc(o.stub_oh >= 0 ? P : 0);
+        late_idx.alloc(o.stub_oh >= 0 ? P : 0);
+        sel_n.alloc(1);
+        lb_bases.alloc(N_DP_KINDS + 2);
+    }
+
+    // a fresh run pool with room for run_share runs, the kernel arguments, the buffers of the classification
+    void begin_attempt(size_t run_share) {
+        // runs + one open chunk per allocating lane of every launch: classify and the two align_kernel (one per wave), the two
+        // align_narrow_kernel instances (one per 16-lane group)
+        // (a pool that overflows costs a second run of every DP kernel: 12 runs per task cover read sets with a few per cent
+        // of errors, where the average is 8)
+        const size_t open_chunks = MAX_BLOCKS * (4 * WAVES * RUN_CHUNK + 2 * 4 * WAVES * RUN_CHUNK_SMALL) +
+                                   (size_t)3 * 256 * 32 * 8 * PK_WAVES * RUN_CHUNK_SMALL;  // (three packed launches: 8 allocating lanes per wave)
         const size_t cap_runs = run_share + open_chunks;
         if (cap_runs >= (1ull << 32)) fail(HLMI_ENOMEM, "CIGAR run pool exceeds 4G entries");
         runs.alloc(cap_runs);
         counters.zero();
         lb_bases.zero();
-        std::fill(lb_n.begin(), lb_n.end(), 0.0);
-        AlignArgs aa{};
+        std::fill(lb_n, lb_n + N_DP_KINDS, 0.0);
+        n_bare_tasks = 0;
+        aa = AlignArgs{};
         aa.tasks = tasks.p; aa.n_tasks = NT;
         aa.geom = TaskGeom{task_ref.p, pgeom.p, ch.fps.p};
         aa.qcodes = in.Q->codes(); aa.tcodes = in.T->codes();
@@ -2878,203 +3028,79 @@ static void align_span(const AvaInput &in, const hlmi_ava_opts &o, const uint32_
         }
         aa.end_bonus = o.end_bonus;
         aa.ext_max = ext_rows(o);
-        aa.ext_all_long = ext_all_long ? 1 : 0;
+        aa.ext_all_long = sc.ext_all_long ? 1 : 0;
         aa.ungapped = o.bandwidth == 0 ? 1 : 0;
         aa.match = o.match; aa.mismatch = o.mismatch; aa.go = o.gap_open; aa.ge = o.gap_ext; aa.ambi = o.ambi;
-        aa.go2 = o.gap_open2 > 0 ? o.gap_open2 : 0; aa.ge2 = o.gap_open2 > 0 ? o.gap_ext2 : 0;
-        // the 16-diagonal kernels (gaps of at most 15 bases) know the first piece only
-        if (aa.go2 && aa.go2 + aa.ge2 * (NARROW_W - 1) < aa.go + aa.ge * (NARROW_W - 1))
-            fail(HLMI_EINVAL, "two-piece gap cost: the second piece must not be the cheaper one below %d bases", NARROW_W);
-        {   // largest k with k*(match+mismatch) < match + 2*(open+ext), capped at 3 (7 runs)
-            const int den = o.match + o.mismatch, num = o.match + 2 * (o.gap_open + o.gap_ext);
-            aa.kmax = den > 0 && num > 0 ? std::min(3, (num - 1) / den) : 0;
-            if (o.match <= 0 || o.gap_open < 0 || o.gap_ext <= 0) aa.kmax = -1;   // proof needs sane scores
-            // fourth certificate: with k = kmax + 1 substitutions the only gapped paths that reach the diagonal's score
-            // have one inserted + one deleted base and no mismatch; paths with a further gap base pair lose another
-            // match + 2 ext, paths with a further gap another open + ext + match (three positions fit the run buffer)
-            const int k = aa.kmax + 1, U = den, T = num;
-            // fifth certificate: one substitution gains less than a further inserted + deleted base costs
-            aa.kgap1 = aa.kmax >= 0 && U < o.gap_open + 2 * o.gap_ext + o.match && !hook("HLMI_NO_GAP1_CERT") ? 1 : 0;
-            {   // seventh certificate: see classify_kernel (c(L) = the cheaper piece's cost of a gap of L bases)
-                auto c = [&](int L) { int v = o.gap_open + o.gap_ext * L; if (o.gap_open2 > 0) v = std::min(v, o.gap_open2 + o.gap_ext2 * L); return v; };
-                aa.kgap2 = aa.kgap1 && U < o.match + c(2) && 2 * U < o.match + 2 * c(1) && 2 * U < 2 * o.match + c(2) + c(3) - c(1) &&
-                           c(2) == o.gap_open + 2 * o.gap_ext && c(1) == o.gap_open + o.gap_ext && !hook("HLMI_NO_GAP2_CERT") ? 1 : 0;
-            }
-            aa.kshift = aa.kmax >= 0 && k <= 3 && k * U > T && k * U < T + o.match + std::min(2 * o.gap_ext, o.gap_open + o.gap_ext) &&
-                        !hook("HLMI_NO_SHIFT_CERT") ? 1 : 0;
-        }
-        aa.trim_ok = hook("HLMI_NO_SUFFIX_TRIM") ? 0 : 1;
-        aa.one_ok = hook("HLMI_NO_ONE_PIECE_CERT") ? 0 : 1;
-        {   // sixth certificate (classify_kernel: extensions with one or two substitutions); G = cheapest one-base gap
-            const int U = o.match + o.mismatch;
-            int G = o.gap_open + o.gap_ext;
-            if (aa.go2 > 0) G = std::min(G, aa.go2 + aa.ge2);
-            const bool sane = aa.kmax >= 0 && o.match > 0 && o.mismatch >= 0 && !hook("HLMI_NO_EXT_CERT");
-            aa.kext_plain = sane && G >= U && U < 2 * G + o.match ? 1 : 0;
-            aa.kext_bonus = 0;
-            for (int k = 1; k <= 2; ++k)
-                if (sane && o.end_bonus > 0 && k * U < G && k * U < o.end_bonus + o.match && k * U < 2 * G + o.match) aa.kext_bonus = k;
-        }
+        aa.go2 = sc.go2; aa.ge2 = sc.ge2;
+        aa.kmax = sc.kmax; aa.kgap1 = sc.kgap1; aa.kgap2 = sc.kgap2; aa.kshift = sc.kshift;
+        aa.trim_ok = sc.trim_ok; aa.one_ok = sc.one_ok; aa.kext_plain = sc.kext_plain; aa.kext_bonus = sc.kext_bonus;
         aa.out = tout.p; aa.runs = runs.p; aa.cap_runs = (uint32_t)cap_runs; aa.counters = counters.p;
         as.runs = runs.p;
         aa.run_buf_cap = 0xffffffffu;
         if (const char *e = hook("HLMI_RUN_BUF_CAP")) aa.run_buf_cap = (uint32_t)std::max(0, atoi(e));
-        // pass 1: classify every task, finish the diagonal fast path right away
-        DBuf<uint8_t> cls(NT), f1(NT), cls_bare(bare ? NT : 0);
-        DBuf<uint32_t> list1(NT), list2(NT), list3(NT), list4(NT);
-        DBuf<uint32_t> list_n(4);
-        aa.cls_bare = bare ? cls_bare.p : nullptr;
-        // LONG tasks of one class array (cls: with traceback, cls_bare: scores only): list, then align_long_kernel
-        // the tasks of one class outside the four of select_classes4_async -> long_list; returns their number
-        auto class_list = [&](const uint8_t *cls_arr, uint8_t v) -> size_t {
-            if (long_flag.n < NT) { long_flag.alloc(NT); long_list.alloc(NT); }
-            hipLaunchKernelGGL(class_flag_kernel, grid1(NT), dim3(WG), 0, stream(), cls_arr, NT, v, long_flag.p);
-            select_flagged_indices_async(long_flag.p, long_list.p, NT, long_n.p);
-            return (size_t)long_n.download(1)[0];
-        };
-        // bandwidth 0: everything the certificates left over, along the diagonal
-        auto run_ungapped = [&](const uint8_t *cls_arr, bool tb) -> size_t {
-            if (!aa.ungapped) return 0;
-            const size_t nl = class_list(cls_arr, CLS_UNGAPPED);
-            if (!nl) return 0;
-            aa.list = long_list.p; aa.n_list = nl;
-            note_list("align_ungapped", tasks.p, long_list.p, nl);
-            KTimer kt("align_ungapped");
-            const unsigned nb = (unsigned)std::min<size_t>(cdiv(nl, (size_t)WG), MAX_BLOCKS);
-            if (tb) hipLaunchKernelGGL(align_ungapped_kernel<true>, dim3(nb), dim3(WG), 0, stream(), aa, o.zdrop);
-            else hipLaunchKernelGGL(align_ungapped_kernel<false>, dim3(nb), dim3(WG), 0, stream(), aa, o.zdrop);
+        cls.alloc(NT); f1.alloc(NT); cls_bare.alloc(sc.bare ? NT : 0);
+        list1.alloc(NT); list2.alloc(NT); list3.alloc(NT); list4.alloc(NT);
+        list_n.alloc(4);
+        aa.cls_bare = sc.bare ? cls_bare.p : nullptr;
+    }
+
+    // The one DP launch: timer name, statistics slot and grid rule follow from the kind; a list of no tasks launches nothing.
+    void launch_dp(DpKind k, const uint32_t *list, size_t n, hipStream_t on, const DpExtra &x = {}) {
+        if (!n) return;
+        aa.list = list; aa.n_list = n;
+        lb_n[k] += (double)n;
+        KTimer kt(DP_NAMES[k], on);
+        switch (k) {
+        case DP_NARROW_SMALL: case DP_NARROW: case DP_SCORE_NARROW: case DP_SCORE_NARROW_LONG: launch_narrow(k, aa, sc.packed); break;
+        // blocks of more than NR_SHORT rows (divergent reads: C5 has as many of these as of the short ones) in the packed
+        // form as well: eight tasks per wave at twice the plane LDS (25 KB per wave) instead of four
+        case DP_NARROW_LONG: launch_narrow(k, aa, sc.packed && !hook("HLMI_NARROW_LONG_UNPACKED")); break;
+        case DP_WIDE: case DP_WIDE_SHORT: case DP_SCORE_WIDE: case DP_SCORE_WIDE_SHORT: launch_wide(k, aa); break;
+        case DP_UNGAPPED: {
+            const dim3 grid((unsigned)std::min<size_t>(cdiv(n, (size_t)WG), MAX_BLOCKS));
+            if (x.traceback) hipLaunchKernelGGL(align_ungapped_kernel<true>, grid, dim3(WG), 0, stream(), aa, o.zdrop);
+            else hipLaunchKernelGGL(align_ungapped_kernel<false>, grid, dim3(WG), 0, stream(), aa, o.zdrop);
             HIP_CHECK(hipGetLastError());
-            return nl;
-        };
-        // LONG tasks of class cv (CLS_LONG: 64 diagonals, a task per wave; CLS_LONG32: 32 diagonals, two tasks per wave)
-        auto run_long_class = [&](const uint8_t *cls_arr, bool tb, uint8_t cv) -> size_t {
-            const bool half = cv == CLS_LONG32;
-            const char *timer = half ? (tb ? "align_long32" : "align_score_long32") : (tb ? "align_long" : "align_score_long");
-            const size_t nl = class_list(cls_arr, cv);               // (waits for the stream: the task records are written)
-            if (!nl) return 0;
-            note_list(timer, tasks.p, long_list.p, nl);
-            hipLaunchKernelGGL(list_ext_kernel, dim3((unsigned)std::min<size_t>(cdiv(nl, (size_t)WG), 1024)), dim3(WG), 0, stream(), tasks.p,
-                               long_list.p, nl, lb_bases.p + N_LB);
-            long_launches.emplace_back(new LongLaunch());
-            LongLaunch &L = *long_launches.back();
-            {   // longest first: the work queue then ends with the short tasks (and the two tasks of a wave are equally long)
-                DBuf<uint32_t> key(nl);
-                hipLaunchKernelGGL(task_rows_desc_key_kernel, grid1(nl), dim3(WG), 0, stream(), tasks.p, long_list.p, nl, key.p);
-                L.list.alloc(nl);
-                HIP_CHECK(hipMemcpyAsync(L.list.p, long_list.p, nl * 4, hipMemcpyDeviceToDevice, stream()));
-                sort_pairs_u32_u32(key, L.list, nl, 0, 16);
-            }
-            const size_t units = half ? (nl + 1) / 2 : nl;           // waves' worth of work
-            const unsigned nb = (unsigned)std::min<size_t>((units + WAVES - 1) / WAVES, LONG_BLOCKS_MAX);
-            const size_t n_waves = (size_t)nb * WAVES;
-            LongArgs la{};
-            if (tb) {
-                L.planes.alloc(n_waves * (size_t)N_WPLANES * long_chunks_cap * 64);
-                L.runs.alloc(n_waves * (size_t)long_runs_cap * (half ? 2 : 1));
-                la.planes = L.planes.p; la.run_scratch = L.runs.p;
-            }
-            la.chunks_cap = long_chunks_cap; la.runs_cap = long_runs_cap; la.zdrop = o.zdrop;
-            L.ctl.alloc(4);
-            L.ctl.zero();
-            la.next = L.ctl.p; la.too_long = L.ctl.p + 1; la.rows_run = (unsigned long long *)(L.ctl.p + 2);
-            AlignArgs al = aa;
-            al.list = L.list.p; al.n_list = nl;
-            long_ready.push_back(LongReady{al, la, nb, half, tb, timer});
-            return nl;
-        };
-        // every prepared LONG launch starts after ALL their lists are built: on the second stream (HLMI_LONG_SIDE_STREAM) a selection
-        // pass queued behind a running long kernel waits for the whole of it (its first round of tasks fills every SIMD; measured:
-        // a 40 us scan took 31 ms), and with it everything the compute stream was to run beside the long kernel
-        auto launch_long_ready = [&]() {
-            if (long_ready.empty()) return;
-            sync();                                                  // lists, keys and control words are in place
-            // in line on the compute stream.  (HLMI_LONG_SIDE_STREAM: on the second stream, beside the DP kernels that follow -
-            // measured equal, C3 slice 957 vs 961 ms, C5 chunk 3.55 vs 3.56 s: the card is busy either way, and kernels that
-            // share it stretch each other's timers, which is why the default is the one stream)
-            const bool on_side = hook("HLMI_LONG_SIDE_STREAM") != nullptr;
-            hipStream_t ls = on_side ? side_stream() : stream();
-            long_on_side = long_on_side || on_side;
-            for (const LongReady &r : long_ready) {
-                KTimer kt(r.timer, ls);
-                const bool two = aa.go2 > 0;
-                auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(r.nb), dim3(WG), 0, ls, r.al, r.la); };
-                if (r.half) {      // (the 32-diagonal band knows the first piece of the gap cost alone: section 5 of DESIGN.md)
-                    if (r.tb) go(align_long32_kernel<false, true>); else go(align_long32_kernel<false, false>);
-                } else {
-                    if (r.tb) { if (two) go(align_long_kernel<true, true>); else go(align_long_kernel<false, true>); }
-                    else { if (two) go(align_long_kernel<true, false>); else go(align_long_kernel<false, false>); }
-                }
-            }
-            HIP_CHECK(hipGetLastError());
-            long_ready.clear();
-            long_pending = true;
-        };
-        auto run_long = [&](const uint8_t *cls_arr, bool tb) -> size_t {
-            if (aa.ungapped) return run_ungapped(cls_arr, tb);       // (no LONG class there: every DP task is CLS_UNGAPPED)
-            // (prepared only: launch_long_ready() starts them)
-            const size_t n32 = run_long_class(cls_arr, tb, CLS_LONG32);
-            return n32 + run_long_class(cls_arr, tb, CLS_LONG);
-        };
-        // after a join and a wait for the stream: did a LONG task exceed its scratch area?
-        auto check_long = [&]() {
-            for (auto &L : long_launches) {
-                if (!L->ctl.n) continue;
-                const std::vector<uint32_t> c = L->ctl.download(4);
-                if (c[1]) fail(HLMI_EINVAL, "an alignment task exceeds the scratch area of align_long_kernel");
-                long_rows_run += (double)((unsigned long long)c[3] << 32 | c[2]);
-                // (read once; the launch is over - joined and waited for -: its planes (GBs at max_gap 10 000), runs and list go
-                //  back to the pool now, not when align_span returns: a retry of the span allocates them again)
-                L->ctl.release(); L->planes.release(); L->runs.release(); L->list.release();
-            }
-        };
-        // the tasks of stub candidates (cls_bare): score-only kernels over their own four lists
-        size_t n_bare_tasks = 0;
-        auto run_bare_long = [&]() {
-            if (!bare) return;
-            const size_t nl = run_long(cls_bare.p, false);
-            n_bare_tasks += nl; n_long_bare += nl;
-        };
-        auto run_bare = [&](bool with_long) {             // (the lists of the four classes are rebuilt here: after the kernels that use them)
-            if (!bare) return;
-            if (with_long) { run_bare_long(); launch_long_ready(); }
-            select_classes4_async(cls_bare.p, NT, list1.p, list2.p, list3.p, list4.p, list_n.p);
-            const std::vector<uint32_t> hb = list_n.download(4);
-            n_bare_tasks += (size_t)hb[0] + hb[1] + hb[2] + hb[3];
-            for (int which = 0; which < 2; ++which) {            // near-diagonal lists in ascending row order (octets run equally long)
-                DBuf<uint32_t> &lst = which ? list3 : list1;
-                const size_t nl = which ? hb[2] : hb[0];
-                if (nl < 8) continue;
-                DBuf<uint32_t> key(nl);
-                hipLaunchKernelGGL(task_rows_key_kernel, grid1(nl), dim3(WG), 0, stream(), tasks.p, lst.p, nl, key.p);
-                sort_pairs_u32_u32(key, lst, nl, 0, 7);
-            }
-            auto pk_grid = [](size_t n) { return dim3((unsigned)std::max<size_t>(1, std::min<size_t>(((n + 7) / 8 + PK_WAVES - 1) / PK_WAVES, 256 * 32))); };
-            auto w_grid = [](size_t n) { return dim3((unsigned)std::max<size_t>(1, std::min<size_t>((n + WAVES - 1) / WAVES, 256 * 16))); };
-            if (hb[0]) {
-                note_list("align_score_narrow", tasks.p, list1.p, hb[0]);
-                KTimer kt("align_score_narrow");
-                aa.list = list1.p; aa.n_list = hb[0];
-                hipLaunchKernelGGL((align_narrow_pk_kernel<NR_SHORT, false>), pk_grid(hb[0]), dim3(64 * PK_WAVES), 0, stream(), aa);
-            }
-            if (hb[2]) {
-                note_list("align_score_narrow_long", tasks.p, list3.p, hb[2]);
-                KTimer kt("align_score_narrow_long");
-                aa.list = list3.p; aa.n_list = hb[2];
-                hipLaunchKernelGGL((align_narrow_pk_kernel<BLOCK_MAX, false>), pk_grid(hb[2]), dim3(64 * PK_WAVES), 0, stream(), aa);
-            }
-            if (hb[1]) {
-                note_list("align_score_wide", tasks.p, list2.p, hb[1]);
-                KTimer kt("align_score_wide");
-                aa.list = list2.p; aa.n_list = hb[1];
-                hipLaunchKernelGGL((align_kernel<EXT_MAX, false>), w_grid(hb[1]), dim3(WG), 0, stream(), aa);
-            }
-            if (hb[3]) {
-                note_list("align_score_wide_short", tasks.p, list4.p, hb[3]);
-                KTimer kt("align_score_wide_short");
-                aa.list = list4.p; aa.n_list = hb[3];
-                hipLaunchKernelGGL((align_kernel<WIDE_SHORT, false>), w_grid(hb[3]), dim3(WG), 0, stream(), aa);
-            }
-        };
+            break;
+        }
+        case DP_LONG: case DP_LONG32: case DP_SCORE_LONG: case DP_SCORE_LONG32:
+            if (!x.la) fail(HLMI_ESTATE, "launch_dp: %s without its scratch areas", DP_NAMES[k]);
+            launch_long(k, aa, *x.la, x.blocks, on);
+            break;
+        default: fail(HLMI_ESTATE, "launch_dp: unknown launch kind %d", (int)k);
+        }
+    }
+    // (rows + columns) of the classified DP tasks per launch kind: "align_bases.<timer>"
+    void sum_class_bases() {
+        hipLaunchKernelGGL(class_bases_kernel, dim3((unsigned)std::min<size_t>(cdiv(NT, (size_t)WG), 2048)), dim3(WG), 0, stream(), cls.p,
+                           sc.bare ? cls_bare.p : nullptr, tasks.p, NT, lb_bases.p);
+    }
+
+    // near-diagonal list in ascending row order: key rows / 4, so the tasks of a wave run about equally long
+    void sort_list_by_rows(DBuf<uint32_t> &list, size_t n) {
+        if (n < 8) return;
+        DBuf<uint32_t> key(n);
+        hipLaunchKernelGGL(task_rows_key_kernel, grid1(n), dim3(WG), 0, stream(), tasks.p, list.p, n, key.p);
+        sort_pairs_u32_u32(key, list, n, 0, 7);
+    }
+    // the four DP task lists of a class array, the near-diagonal ones sorted
+    std::vector<uint32_t> class_lists(const uint8_t *cls_arr) {
+        select_classes4_async(cls_arr, NT, list1.p, list2.p, list3.p, list4.p, list_n.p);
+        const std::vector<uint32_t> h = list_n.download(4);
+        sort_list_by_rows(list1, h[0]);
+        sort_list_by_rows(list3, h[2]);
+        return h;
+    }
+    // the tasks of one class outside the four of select_classes4_async -> sel_list; returns their number
+    size_t class_list(const uint8_t *cls_arr, uint8_t v) {
+        if (sel_flag.n < NT) { sel_flag.alloc(NT); sel_list.alloc(NT); }
+        hipLaunchKernelGGL(class_flag_kernel, grid1(NT), dim3(WG), 0, stream(), cls_arr, NT, v, sel_flag.p);
+        select_flagged_indices_async(sel_flag.p, sel_list.p, NT, sel_n.p);
+        return (size_t)sel_n.download(1)[0];         // (waits for the stream: the task records are written)
+    }
+
+    // pass 1: classify every task, finish the diagonal fast path right away; then the lists of the four classes
+    void classify() {
         {
             KTimer kt("align_classify");
             const unsigned nbc = (unsigned)std::min<size_t>(cdiv(NT, (size_t)WG), MAX_BLOCKS);
@@ -3083,172 +3109,143 @@ static void align_span(const AvaInput &in, const hlmi_ava_opts &o, const uint32_
             aa.defer_list = list1.p; aa.defer_count = list_n.p;
             hipLaunchKernelGGL(classify_kernel<1>, dim3(nbc ? nbc : 1), dim3(WG), 0, stream(), aa, cls.p, astats.p);
             select_flagged_indices_async(f1.p, list1.p, NT, list_n.p);
-            const unsigned nb2 = std::max(1u, nbc / 4);
-            hipLaunchKernelGGL(classify_kernel<2>, dim3(nb2), dim3(WG), 0, stream(), aa, cls.p, astats.p);
+            hipLaunchKernelGGL(classify_kernel<2>, dim3(std::max(1u, nbc / 4)), dim3(WG), 0, stream(), aa, cls.p, astats.p);
         }
         HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(class_bases_kernel, dim3((unsigned)std::min<size_t>(cdiv(NT, (size_t)WG), 2048)), dim3(WG), 0, stream(), cls.p,
-                           bare ? cls_bare.p : nullptr, tasks.p, NT, lb_bases.p);
-        select_classes4_async(cls.p, NT, list1.p, list2.p, list3.p, list4.p, list_n.p);      // the four DP task lists
-        const std::vector<uint32_t> hn = list_n.download(4);
-        const size_t n1 = hn[0], n2 = hn[1], n3 = hn[2], n4 = hn[3];
-        for (int which = 0; which < 2; ++which) {
-            DBuf<uint32_t> &lst = which ? list3 : list1;
-            const size_t nl = which ? n3 : n1;
-            if (nl < 8) continue;
-            DBuf<uint32_t> key(nl);
-            hipLaunchKernelGGL(task_rows_key_kernel, grid1(nl), dim3(WG), 0, stream(), tasks.p, lst.p, nl, key.p);
-            sort_pairs_u32_u32(key, lst, nl, 0, 7);
-        }
-        // the LONG tasks first, on the side stream, and the score-only tasks of the stub candidates: everything below runs beside them
-        // (the candidates' few LONG tasks first: list building behind a running align_long_kernel is slowed down tenfold - the
-        //  long kernel's first round of tasks fills every SIMD)
-        // (the classifier counted them: most batches of a clean read set have none left once their pieces are set aside, and
-        //  building an empty list is four passes over the class arrays)
-        unsigned long long long_seen = astats.download(N_ALIGN_STATS)[ST_LONG];
-        if (long_seen || aa.ungapped) {
-            run_bare_long();
-            n_long_tb += run_long(cls.p, true);
-            launch_long_ready();
-        }
-        // pass 2a: near-diagonal blocks, four per wave in the 16-diagonal band
-        if (n1 && packed) {
-            // the list is in ascending row order: its head (fewer than NR_SMALL rows, counted by the classifier)
-            // runs in the instance with half the plane LDS and twice the resident waves
-            size_t n_small = 0;
-            if (n1 >= 8) n_small = std::min<size_t>(n1, (size_t)astats.download(N_ALIGN_STATS)[ST_NARROW_SMALL]);
-            if (n_small) {
-                note_list("align_narrow_small", tasks.p, list1.p, n_small);
-                KTimer kt("align_narrow_small");
-                aa.list = list1.p; aa.n_list = n_small;
-                const unsigned nb = (unsigned)std::min<size_t>(((n_small + 7) / 8 + PK_WAVES - 1) / PK_WAVES, 256 * 32);
-                hipLaunchKernelGGL(align_narrow_pk_kernel<NR_SMALL>, dim3(nb ? nb : 1), dim3(64 * PK_WAVES), 0, stream(), aa);
-            }
-            if (n1 > n_small) {
-                note_list("align_narrow", tasks.p, list1.p + n_small, n1 - n_small);
-                KTimer kt("align_narrow");
-                aa.list = list1.p + n_small; aa.n_list = n1 - n_small;
-                const unsigned nb = (unsigned)std::min<size_t>(((aa.n_list + 7) / 8 + PK_WAVES - 1) / PK_WAVES, 256 * 32);
-                hipLaunchKernelGGL(align_narrow_pk_kernel<NR_SHORT>, dim3(nb ? nb : 1), dim3(64 * PK_WAVES), 0, stream(), aa);
-            }
-        } else if (n1) {
-            note_list("align_narrow", tasks.p, list1.p, n1);
-            KTimer kt("align_narrow");
-            aa.list = list1.p; aa.n_list = n1;
-            const unsigned nb = (unsigned)std::min<size_t>(((n1 + 3) / 4 + WAVES - 1) / WAVES, 256 * 16);
-            hipLaunchKernelGGL(align_narrow_kernel<NR_SHORT>, dim3(nb ? nb : 1), dim3(WG), 0, stream(), aa);
-        }
-        if (n3 && packed && !hook("HLMI_NARROW_LONG_UNPACKED")) {
-            // blocks of more than NR_SHORT rows (divergent reads: C5 has as many of these as of the short ones) in the packed
-            // form as well: eight tasks per wave at twice the plane LDS (25 KB per wave) instead of four
-            note_list("align_narrow_long", tasks.p, list3.p, n3);
-            KTimer kt("align_narrow_long");
-            aa.list = list3.p; aa.n_list = n3;
-            const unsigned nb = (unsigned)std::min<size_t>(((n3 + 7) / 8 + PK_WAVES - 1) / PK_WAVES, 256 * 32);
-            hipLaunchKernelGGL(align_narrow_pk_kernel<BLOCK_MAX>, dim3(nb ? nb : 1), dim3(64 * PK_WAVES), 0, stream(), aa);
-        } else if (n3) {
-            note_list("align_narrow_long", tasks.p, list3.p, n3);
-            KTimer kt("align_narrow_long");
-            aa.list = list3.p; aa.n_list = n3;
-            const unsigned nb = (unsigned)std::min<size_t>(((n3 + 3) / 4 + WAVES - 1) / WAVES, 256 * 16);
-            hipLaunchKernelGGL(align_narrow_kernel<BLOCK_MAX>, dim3(nb ? nb : 1), dim3(WG), 0, stream(), aa);
-        }
-        // pass 2b: the rest (wide blocks, end extensions) in the 64-diagonal band
-        auto run_wide = [&](size_t n_long, size_t n_short) {
-            if (n_long) {
-                note_list("align_wide", tasks.p, list2.p, n_long);
-                KTimer kt("align_wide");
-                aa.list = list2.p; aa.n_list = n_long;
-                const unsigned nb = (unsigned)std::min<size_t>((n_long + WAVES - 1) / WAVES, 256 * 16);
-                hipLaunchKernelGGL(align_kernel<EXT_MAX>, dim3(nb ? nb : 1), dim3(WG), 0, stream(), aa);
-            }
-            if (n_short) {
-                note_list("align_wide_short", tasks.p, list4.p, n_short);
-                KTimer kt("align_wide_short");
-                aa.list = list4.p; aa.n_list = n_short;
-                const unsigned nb = (unsigned)std::min<size_t>((n_short + WAVES - 1) / WAVES, 256 * 16);
-                hipLaunchKernelGGL(align_kernel<WIDE_SHORT>, dim3(nb ? nb : 1), dim3(WG), 0, stream(), aa);
-            }
-        };
-        run_wide(n2, n4);
-        run_bare(false);
-        size_t n_wide_late = 0;
-        if (o.stub_oh >= 0) {
-            // Stub rule (hlmi_ava_opts::stub_oh; proof at oracle/ava_oracle.c:is_stub).  The end extensions of the stub
-            // candidates were held back.  Their blocks are scored now: a candidate that is certain to be reported without them
-            // (blocks >= min_dp_score + end_bonus: an extension adds a positive score, or at least 1 - end_bonus when it
-            // reaches the query end) stays without - its row can only be dropped by the consumer's overhang test; the others
-            // get their extensions in a second round.
-            as.plist = nullptr; as.n_pieces = P; as.late = late.p;
-            join_long();
-            {
-                KTimer kt("assemble_count");
-                if (small_pieces) hipLaunchKernelGGL(assemble_lane_kernel<false>, grid1(as.n_pieces), dim3(WG), 0, stream(), as, nops.p, valid.p,
-                                                     nullptr, nullptr, nullptr, nullptr, nullptr);
-                else
-                hipLaunchKernelGGL(assemble_kernel<false>, dim3(nba), dim3(WG), 0, stream(), as, nops.p, valid.p, nullptr, nullptr,
-                                   nullptr, nullptr, nullptr);
-            }
-            as.late = nullptr;
-            n_late = select_flagged_indices(late.p, late_idx.p, P);
-            if (n_late) {
-                hipLaunchKernelGGL(late_tasks_kernel, grid1(n_late), dim3(WG), 0, stream(), late_idx.p, n_late, ch.pieces.p, toff.p,
-                                   list1.p, list_n.p);
-                HIP_CHECK(hipMemsetAsync(cls.p, 0, NT, stream()));
-                if (bare) HIP_CHECK(hipMemsetAsync(cls_bare.p, 0, NT, stream()));
-                {
-                    KTimer kt("align_classify");
-                    aa.defer_list = list1.p; aa.defer_count = list_n.p;
-                    const unsigned nb2 = (unsigned)std::min<size_t>(cdiv(2 * n_late, (size_t)WG), MAX_BLOCKS);
-                    hipLaunchKernelGGL(classify_kernel<2>, dim3(nb2 ? nb2 : 1), dim3(WG), 0, stream(), aa, cls.p, astats.p);
-                }
-                hipLaunchKernelGGL(class_bases_kernel, dim3((unsigned)std::min<size_t>(cdiv(NT, (size_t)WG), 2048)), dim3(WG), 0, stream(), cls.p,
-                                   bare ? cls_bare.p : nullptr, tasks.p, NT, lb_bases.p);
-                if (bare) {                        // (every late task belongs to a candidate)
-                    const size_t before = n_bare_tasks;
-                    const bool more_long = astats.download(N_ALIGN_STATS)[ST_LONG] > long_seen || aa.ungapped;
-                    run_bare(more_long);
-                    n_wide_late = n_bare_tasks - before;
-                } else {
-                    select_classes4_async(cls.p, NT, list1.p, list2.p, list3.p, list4.p, list_n.p);
-                    const std::vector<uint32_t> hl = list_n.download(4);
-                    run_wide(hl[1], hl[3]);
-                    const bool more_long = astats.download(N_ALIGN_STATS)[ST_LONG] > long_seen || aa.ungapped;
-                    const size_t nl = more_long ? run_long(cls.p, true) : 0;
-                    launch_long_ready();
-                    n_long_tb += nl;
-                    n_wide_late = (size_t)hl[1] + hl[3] + nl;
-                }
-                as.plist = late_idx.p; as.n_pieces = n_late;
-                const unsigned nbl = (unsigned)std::min<size_t>(cdiv(n_late, (size_t)WAVES), 256 * 32);
-                join_long();
-                {
-                    KTimer kt("assemble_count");
-                    if (small_pieces) hipLaunchKernelGGL(assemble_lane_kernel<false>, grid1(as.n_pieces), dim3(WG), 0, stream(), as, nops.p, valid.p,
-                                                         nullptr, nullptr, nullptr, nullptr, nullptr);
-                    else
-                    hipLaunchKernelGGL(assemble_kernel<false>, dim3(nbl), dim3(WG), 0, stream(), as, nops.p, valid.p, nullptr, nullptr,
-                                       nullptr, nullptr, nullptr);
-                }
-                as.plist = nullptr; as.n_pieces = P;
-            }
-        }
-        if (attempt == 0) {
-            stat_add("align_tasks_narrow", (double)(n1 + n3)); stat_add("align_tasks_wide", (double)(n2 + n4 + (bare ? 0 : n_wide_late)));
-            stat_add("align_tasks_score_only", (double)n_bare_tasks);
-            stat_add("align_tasks_long", (double)n_long_tb); stat_add("align_tasks_long_score_only", (double)n_long_bare);
-        }
-        HIP_CHECK(hipGetLastError());
-        join_long();
-        std::vector<uint32_t> hc = counters.download(2);
-        check_long();
-        if (!hc[1]) break;
-        if (attempt >= 3) fail(HLMI_ENOMEM, "CIGAR run pool overflow");
-        run_share *= 4;
+        sum_class_bases();
+        const std::vector<uint32_t> hn = class_lists(cls.p);
+        n1 = hn[0]; n2 = hn[1]; n3 = hn[2]; n4 = hn[3];
     }
-    stat_add("align_tasks", (double)NT);
-    {
-        std::vector<unsigned long long> h = astats.download(N_ALIGN_STATS);
+
+    // LONG tasks of one class array (cls: with traceback, cls_bare: scores only): their lists, launches prepared (start_long
+    // starts them).  Bandwidth 0 has no LONG class - every DP task is CLS_UNGAPPED - and runs them along the diagonal at once.
+    size_t prepare_long(const uint8_t *cls_arr, bool tb) {
+        if (aa.ungapped) {
+            const size_t nl = class_list(cls_arr, CLS_UNGAPPED);
+            launch_dp(DP_UNGAPPED, sel_list.p, nl, stream(), {nullptr, 0, tb});
+            return nl;
+        }
+        size_t total = 0;
+        for (const bool half : {true, false}) {
+            const size_t nl = class_list(cls_arr, half ? CLS_LONG32 : CLS_LONG);
+            if (!nl) continue;
+            hipLaunchKernelGGL(list_ext_kernel, dim3((unsigned)std::min<size_t>(cdiv(nl, (size_t)WG), 1024)), dim3(WG), 0, stream(), tasks.p,
+                               sel_list.p, nl, lb_bases.p + N_DP_KINDS);
+            longs.prepare(half ? (tb ? DP_LONG32 : DP_SCORE_LONG32) : (tb ? DP_LONG : DP_SCORE_LONG), tasks.p, sel_list.p, nl);
+            total += nl;
+        }
+        return total;
+    }
+    void prepare_long_score_only() {
+        if (!sc.bare) return;
+        const size_t nl = prepare_long(cls_bare.p, false);
+        n_bare_tasks += nl; n_long_bare += nl;
+    }
+    void start_long() {
+        longs.start([&](DpKind k, const uint32_t *list, size_t n, hipStream_t on, const LongArgs &la, unsigned blocks) {
+            launch_dp(k, list, n, on, {&la, blocks});
+        });
+    }
+    // the LONG tasks first, and the score-only tasks of the stub candidates: everything below runs beside them on the side stream
+    // (the candidates' few LONG tasks first: list building behind a running align_long_kernel is slowed down tenfold - the
+    //  long kernel's first round of tasks fills every SIMD)
+    // (the classifier counted them: most batches of a clean read set have none left once their pieces are set aside, and
+    //  building an empty list is four passes over the class arrays)
+    void long_first() {
+        long_seen = astats.download(N_ALIGN_STATS)[ST_LONG];
+        if (!long_seen && !aa.ungapped) return;
+        prepare_long_score_only();
+        n_long_tb += prepare_long(cls.p, true);
+        start_long();
+    }
+    bool more_long() { return astats.download(N_ALIGN_STATS)[ST_LONG] > long_seen || aa.ungapped; }
+
+    // pass 2a: near-diagonal blocks in the 16-diagonal band
+    void run_narrow() {
+        // packed: the list is in ascending row order: its head (fewer than NR_SMALL rows, counted by the classifier)
+        // runs in the instance with half the plane LDS and twice the resident waves
+        size_t n_small = 0;
+        if (sc.packed && n1 >= 8) n_small = std::min<size_t>(n1, (size_t)astats.download(N_ALIGN_STATS)[ST_NARROW_SMALL]);
+        launch_dp(DP_NARROW_SMALL, list1.p, n_small, stream());
+        launch_dp(DP_NARROW, list1.p + n_small, n1 - n_small, stream());
+        launch_dp(DP_NARROW_LONG, list3.p, n3, stream());
+    }
+    // pass 2b: the rest (wide blocks, end extensions) in the 64-diagonal band
+    void run_wide(size_t n_long, size_t n_short) {
+        launch_dp(DP_WIDE, list2.p, n_long, stream());
+        launch_dp(DP_WIDE_SHORT, list4.p, n_short, stream());
+    }
+    // the tasks of stub candidates (cls_bare): score-only kernels over their own four lists
+    // (the lists of the four classes are rebuilt here: after the kernels that use them)
+    void run_score_only(bool with_long) {
+        if (!sc.bare) return;
+        if (with_long) { prepare_long_score_only(); start_long(); }
+        const std::vector<uint32_t> hb = class_lists(cls_bare.p);
+        n_bare_tasks += (size_t)hb[0] + hb[1] + hb[2] + hb[3];
+        launch_dp(DP_SCORE_NARROW, list1.p, hb[0], stream());
+        launch_dp(DP_SCORE_NARROW_LONG, list3.p, hb[2], stream());
+        launch_dp(DP_SCORE_WIDE, list2.p, hb[1], stream());
+        launch_dp(DP_SCORE_WIDE_SHORT, list4.p, hb[3], stream());
+    }
+
+    // Stub rule (hlmi_ava_opts::stub_oh; proof at oracle/ava_oracle.c:is_stub).  The end extensions of the stub
+    // candidates were held back.  Their blocks are scored now: a candidate that is certain to be reported without them
+    // (blocks >= min_dp_score + end_bonus: an extension adds a positive score, or at least 1 - end_bonus when it
+    // reaches the query end) stays without - its row can only be dropped by the consumer's overhang test; the others
+    // get their extensions in a second round.
+    void late_round() {
+        as.plist = nullptr; as.n_pieces = P; as.late = late.p;
+        longs.join();
+        launch_assemble_count(as, small_pieces, nops.p, valid.p);
+        as.late = nullptr;
+        n_late = select_flagged_indices(late.p, late_idx.p, P);
+        n_wide_late = 0;
+        if (!n_late) return;
+        hipLaunchKernelGGL(late_tasks_kernel, grid1(n_late), dim3(WG), 0, stream(), late_idx.p, n_late, ch.pieces.p, toff.p, list1.p, list_n.p);
+        HIP_CHECK(hipMemsetAsync(cls.p, 0, NT, stream()));
+        if (sc.bare) HIP_CHECK(hipMemsetAsync(cls_bare.p, 0, NT, stream()));
+        {
+            KTimer kt("align_classify");
+            aa.defer_list = list1.p; aa.defer_count = list_n.p;
+            const unsigned nb2 = (unsigned)std::min<size_t>(cdiv(2 * n_late, (size_t)WG), MAX_BLOCKS);
+            hipLaunchKernelGGL(classify_kernel<2>, dim3(nb2 ? nb2 : 1), dim3(WG), 0, stream(), aa, cls.p, astats.p);
+        }
+        sum_class_bases();
+        if (sc.bare) {                        // (every late task belongs to a candidate)
+            const size_t before = n_bare_tasks;
+            run_score_only(more_long());
+            n_wide_late = n_bare_tasks - before;
+        } else {
+            select_classes4_async(cls.p, NT, list1.p, list2.p, list3.p, list4.p, list_n.p);
+            const std::vector<uint32_t> hl = list_n.download(4);
+            run_wide(hl[1], hl[3]);
+            const size_t nl = more_long() ? prepare_long(cls.p, true) : 0;
+            start_long();
+            n_long_tb += nl;
+            n_wide_late = (size_t)hl[1] + hl[3] + nl;
+        }
+        as.plist = late_idx.p; as.n_pieces = n_late;
+        longs.join();
+        launch_assemble_count(as, small_pieces, nops.p, valid.p);
+        as.plist = nullptr; as.n_pieces = P;
+    }
+
+    void report_task_counts() {
+        stat_add("align_tasks_narrow", (double)(n1 + n3)); stat_add("align_tasks_wide", (double)(n2 + n4 + (sc.bare ? 0 : n_wide_late)));
+        stat_add("align_tasks_score_only", (double)n_bare_tasks);
+        stat_add("align_tasks_long", (double)n_long_tb); stat_add("align_tasks_long_score_only", (double)n_long_bare);
+    }
+    // join the LONG launches and wait; false: the run pool overflowed, the attempt is void
+    bool end_attempt() {
+        HIP_CHECK(hipGetLastError());
+        longs.join();
+        const std::vector<uint32_t> hc = counters.download(2);
+        long_rows_run += longs.check();
+        return !hc[1];
+    }
+    void report_stats() {
+        stat_add("align_tasks", (double)NT);
+        const std::vector<unsigned long long> h = astats.download(N_ALIGN_STATS);
         stat_add("align_tasks_fast", (double)h[ST_FAST]);
         stat_add("align_tasks_packed", (double)h[ST_PACKED]);          // compared by the classifier from the 2-bit arrays
         stat_add("align_tasks_dp", (double)h[ST_DP]);
@@ -3258,14 +3255,15 @@ static void align_span(const AvaInput &in, const hlmi_ava_opts &o, const uint32_
         stat_add("align_bases_narrow", (double)h[ST_BASES_NARROW]);
         stat_add("align_bases_wide", (double)h[ST_BASES_WIDE]);
         stat_add("align_bases_long", (double)h[ST_BASES_LONG]);
-        const std::vector<unsigned long long> lb = lb_bases.download(N_LB + 2);
+        const std::vector<unsigned long long> lb = lb_bases.download(N_DP_KINDS + 2);
         stat_add("align_long_rows_run", long_rows_run);
-        stat_add("align_long_ext", (double)lb[N_LB]);
-        stat_add("align_long_ext_rows", (double)lb[N_LB + 1]);
-        for (int k = 0; k < N_LB; ++k)
+        stat_add("align_long_ext", (double)lb[N_DP_KINDS]);
+        stat_add("align_long_ext_rows", (double)lb[N_DP_KINDS + 1]);
+        if (longs.on_side()) stat_add("align_long_side_launches", longs.side_launches());
+        for (int k = 0; k < N_DP_KINDS; ++k)
             if (lb_n[k] > 0) {
-                stat_add(std::string("align_n.") + LB_NAMES[k], lb_n[k]);
-                stat_add(std::string("align_bases.") + LB_NAMES[k], (double)lb[k]);
+                stat_add(std::string("align_n.") + DP_NAMES[k], lb_n[k]);
+                stat_add(std::string("align_bases.") + DP_NAMES[k], (double)lb[k]);
             }
         stat_add("align_tasks_wide_one_piece", (double)h[ST_WIDE_ONE]);
         stat_add("align_ext_certified", (double)h[ST_EXT_CERT]);
@@ -3274,43 +3272,65 @@ static void align_span(const AvaInput &in, const hlmi_ava_opts &o, const uint32_
         stat_add("align_ext_held", (double)h[ST_STUB_EXT]);            // end extensions of stub candidates ...
         stat_add("align_ext_late", (double)(2 * n_late));              // ... of which these had to run after all
     }
-    // assemble
-    if (o.stub_oh < 0) {
-        KTimer kt("assemble_count");
-        if (small_pieces) hipLaunchKernelGGL(assemble_lane_kernel<false>, grid1(as.n_pieces), dim3(WG), 0, stream(), as, nops.p, valid.p,
-                                             nullptr, nullptr, nullptr, nullptr, nullptr);
-        else
-        hipLaunchKernelGGL(assemble_kernel<false>, dim3(nba), dim3(WG), 0, stream(), as, nops.p, valid.p, nullptr, nullptr,
-                           nullptr, nullptr, nullptr);
+
+    // task results -> rows (the stub rule has counted already)
+    void assemble(AlignOut &out) {
+        for (DBuf<uint8_t> *b : {&cls, &f1, &cls_bare, &sel_flag}) b->release();       // (the attempt's buffers: not needed any more)
+        for (DBuf<uint32_t> *b : {&list1, &list2, &list3, &list4, &list_n, &sel_list}) b->release();
+        if (o.stub_oh < 0) launch_assemble_count(as, small_pieces, nops.p, valid.p);
+        HIP_CHECK(hipGetLastError());
+        DBuf<uint64_t> ooff(P);
+        exclusive_scan_u32_to_u64(nops.p, ooff.p, P);
+        const size_t n_ops = (size_t)(download_one(ooff.p + (P - 1)) + download_one(nops.p + (P - 1)));
+        DBuf<uint32_t> vidx(P);
+        const size_t R = select_flagged_indices(valid.p, vidx.p, P);
+        if (!R) return;
+        out.ops.alloc(n_ops ? n_ops : 1);
+        DBuf<PafRec> recs(P);
+        DBuf<uint64_t> hi(P), lo(P);
+        launch_assemble_write(as, small_pieces, valid.p, ooff.p, out.ops.p, recs.p, hi.p, lo.p);
+        HIP_CHECK(hipGetLastError());
+        out.recs.alloc(R);
+        out.ord_hi.alloc(R);
+        out.ord_lo.alloc(R);
+        hipLaunchKernelGGL(compact_rows_kernel, grid1(R), dim3(WG), 0, stream(), vidx.p, R, recs.p, hi.p, lo.p, out.recs.p, out.ord_hi.p, out.ord_lo.p);
+        HIP_CHECK(hipGetLastError());
+        sync();
+        out.n_rows = R;
+        out.n_ops = n_ops;
     }
-    HIP_CHECK(hipGetLastError());
-    DBuf<uint64_t> ooff(P);
-    exclusive_scan_u32_to_u64(nops.p, ooff.p, P);
-    const size_t n_ops = (size_t)(download_one(ooff.p + (P - 1)) + download_one(nops.p + (P - 1)));
-    DBuf<uint32_t> vidx(P);
-    const size_t R = select_flagged_indices(valid.p, vidx.p, P);
-    if (!R) return;
-    out.ops.alloc(n_ops ? n_ops : 1);
-    DBuf<PafRec> recs(P);
-    DBuf<uint64_t> hi(P), lo(P);
-    {
-        KTimer kt("assemble_write");
-        if (small_pieces) hipLaunchKernelGGL(assemble_lane_kernel<true>, grid1(as.n_pieces), dim3(WG), 0, stream(), as, nullptr, valid.p, ooff.p,
-                                             out.ops.p, recs.p, hi.p, lo.p);
-        else
-        hipLaunchKernelGGL(assemble_kernel<true>, dim3(nba), dim3(WG), 0, stream(), as, nullptr, valid.p, ooff.p, out.ops.p,
-                           recs.p, hi.p, lo.p);
+};
+}  // namespace
+
+static void align_span(const AvaInput &in, const hlmi_ava_opts &o, const uint32_t *d_qlen, const uint32_t *d_tlen,
+                       const PieceSpan &ch, AlignOut &out) {
+    out = AlignOut();
+    if (!ch.n_pieces) return;
+    AlignScoreHooks hk;
+    hk.narrow_unpacked = hook("HLMI_NARROW_UNPACKED"); hk.stub_full_rows = hook("HLMI_STUB_FULL_ROWS");
+    hk.no_gap1_cert = hook("HLMI_NO_GAP1_CERT"); hk.no_gap2_cert = hook("HLMI_NO_GAP2_CERT"); hk.no_shift_cert = hook("HLMI_NO_SHIFT_CERT");
+    hk.no_ext_cert = hook("HLMI_NO_EXT_CERT"); hk.no_one_piece_cert = hook("HLMI_NO_ONE_PIECE_CERT"); hk.no_suffix_trim = hook("HLMI_NO_SUFFIX_TRIM");
+    const AlignScoreSetup sc = align_score_setup(o, hk);
+    if (sc.error == ALIGN_SCORE_ROWS) fail(HLMI_EINVAL, "max_gap %d: alignment tasks are limited to 32 000 rows", o.max_gap);
+    if (sc.error == ALIGN_SCORE_GAP2_CHEAP)
+        fail(HLMI_EINVAL, "two-piece gap cost: the second piece must not be the cheaper one below %d bases", NARROW_W);
+    AlignPass ps(in, o, d_qlen, d_tlen, ch, sc);
+    size_t run_share = std::max<size_t>(ps.NT * 12, 1 << 16);
+    for (int attempt = 0;; ++attempt) {
+        ps.begin_attempt(run_share);
+        ps.classify();
+        ps.long_first();
+        ps.run_narrow();
+        ps.run_wide(ps.n2, ps.n4);
+        ps.run_score_only(false);
+        if (o.stub_oh >= 0) ps.late_round();
+        if (attempt == 0) ps.report_task_counts();
+        if (ps.end_attempt()) break;
+        if (attempt >= 3) fail(HLMI_ENOMEM, "CIGAR run pool overflow");
+        run_share *= 4;
     }
-    HIP_CHECK(hipGetLastError());
-    out.recs.alloc(R);
-    out.ord_hi.alloc(R);
-    out.ord_lo.alloc(R);
-    hipLaunchKernelGGL(compact_rows_kernel, grid1(R), dim3(WG), 0, stream(), vidx.p, R, recs.p, hi.p, lo.p, out.recs.p,
-                       out.ord_hi.p, out.ord_lo.p);
-    HIP_CHECK(hipGetLastError());
-    sync();
-    out.n_rows = R;
-    out.n_ops = n_ops;
+    ps.report_stats();
+    ps.assemble(out);
 }
 
 }  // namespace hlmi

@@ -37,7 +37,7 @@ HOOKS = {
     "HLMI_NO_ONE_PIECE_CERT": "long", "HLMI_NO_EXT_CERT": "long", "HLMI_NARROW_UNPACKED": "long",
     "HLMI_NARROW_LONG_UNPACKED": "long", "HLMI_CHAIN_NO_DP16": "long", "HLMI_CHAIN_NO_SMALL": "short",
     "HLMI_CHAIN_UNPACKED": "long", "HLMI_SEED_GROUP": "long", "HLMI_ASM_WAVE": "short", "HLMI_NO_RANK_WORD": "long",
-    "HLMI_ANCHOR_PAIRS": "long", "HLMI_LANES": "long",
+    "HLMI_ANCHOR_PAIRS": "long", "HLMI_LANES": "long", "HLMI_LONG_SIDE_STREAM": "long",
 }
 
 
@@ -189,6 +189,9 @@ def test_fallback_forms_are_taken(sweep):
     st = sweep[("HLMI_SEED_GROUP", "long0")][1]
     assert st["anchors_grouped_in_lds"] + st.get("seed_group_gave_up", 0) > 0
     assert sweep[(None, "long0")][1].get("anchors_grouped_in_lds", 0) == 0
+    # long0 runs about 23 000 LONG tasks: with the hook their launches go to the second stream
+    assert sweep[("HLMI_LONG_SIDE_STREAM", "long0")][1]["align_long_side_launches"] >= 1
+    assert "align_long_side_launches" not in sweep[(None, "long0")][1]
 
 
 # the statistic that a certificate's hook must lower; measured (default forms -> hook set) on long0 (438 617 tasks) and on

@@ -83,6 +83,33 @@ def test_rows_with_stubs_match_the_oracle(divergent, structural, mode):
         assert st["align_ext_held"] > st["align_ext_late"] > 0  # some held-back extensions had to run after all
 
 
+@pytest.mark.parametrize("mode", ["long", "short_constants"])
+def test_side_stream_rows_equal_the_default(divergent, structural, mode, monkeypatch):
+    """HLMI_LONG_SIDE_STREAM puts the LONG launches on the second stream; with the stub rule on, the late round joins the two
+    streams a second time.  Same bytes as the default (in line on the compute stream), on the inputs of the test above: the
+    structural one runs LONG tasks, the short constants hold back extensions that run late."""
+    d, fa = structural if mode == "long" else divergent
+    og = api.ava_opts_long() if mode == "long" else api.ava_opts_short()
+    og.pair_once = 1
+    og.stub_oh = 3
+    api.ava(fa, fa, d / f"side_off_{mode}.paf", og)
+    st_off = api.last_stats()
+    monkeypatch.setenv("HLMI_LONG_SIDE_STREAM", "1")
+    api.ava(fa, fa, d / f"side_on_{mode}.paf", og)
+    st_on = api.last_stats()
+    print(mode, {k: st_on.get(k) for k in ("align_ext_held", "align_ext_late", "align_tasks_long", "align_long_side_launches")})
+    assert open(d / f"side_on_{mode}.paf").read() == open(d / f"side_off_{mode}.paf").read() and os.path.getsize(d / f"side_off_{mode}.paf") > 0
+    assert "align_long_side_launches" not in st_off
+    for k in ("align_ext_held", "align_ext_late", "align_tasks_long", "align_tasks_score_only", "cigar_ops", "ava_rows"):
+        assert st_on.get(k) == st_off.get(k), k
+    if mode == "long":
+        # a late round (extensions held back that ran after all) with LONG launches on the second stream: both joins are taken
+        assert st_on["align_ext_held"] > st_on["align_ext_late"] > 0 and st_on["align_tasks_long"] > 0
+        assert st_on["align_long_side_launches"] >= 1
+    else:
+        assert st_on["align_ext_held"] > st_on["align_ext_late"] > 0
+
+
 def test_stage_output_does_not_depend_on_the_rule(structural, monkeypatch):
     d, fa = structural
     stage = dict(len_over=1500, mc=2, iden=0.90)
