@@ -178,6 +178,18 @@ class VariantStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in VARIANT_STATS] + [(k, C.c_double) for k in POLISH_MS]
 
 
+class PhaseOpts(C.Structure):
+    _fields_ = list(VariantOpts._fields_) + [("min_link", C.c_int), ("min_agree", C.c_double)]
+
+
+PHASE_STATS = VARIANT_STATS + ("links", "links_phased", "blocks", "blocks_multi", "sites_phased", "alleles", "read_records", "reads_a",
+                               "reads_b", "reads_tie")
+
+
+class PhaseStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in PHASE_STATS] + [(k, C.c_double) for k in POLISH_MS]
+
+
 ABI_VERSION = 7          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
@@ -281,6 +293,12 @@ SYMBOLS = {
                                 C.POINTER(VariantStats)]),
     "hlmi_variants_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(VariantOpts), C.c_char_p, C.c_char_p,
                                       C.c_char_p, C.POINTER(VariantStats)]),
+    # phased variant sites
+    "hlmi_phase_opts_default": (None, [C.POINTER(PhaseOpts)]),
+    "hlmi_phase": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PhaseOpts), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                             C.POINTER(PhaseStats)]),
+    "hlmi_phase_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PhaseOpts), C.c_char_p, C.c_char_p, C.c_char_p,
+                                   C.c_char_p, C.POINTER(PhaseStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -838,6 +856,42 @@ def variants_reads(contigs, reads, out_sites, out_summary=None, ava_opts=None, p
     _check(load().hlmi_variants_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), _b(pairs),
                                       _b(out_sites), _b(out_summary), C.byref(st)))
     return {k: getattr(st, k) for k in VARIANT_STATS + POLISH_MS}
+
+
+def _phase_opts(who, opts):
+    o = PhaseOpts()
+    load().hlmi_phase_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(PhaseOpts._fields_):
+            raise TypeError(f"{who}: unknown option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def phase(contigs, reads, paf, out_sites, out_links=None, out_reads=None, pairs=None, **opts):
+    """hlmi_phase: the variant sites of api.variants (same selection, pairs= included, same votes, same site rule) phased from the
+    reads.  Every selected row reads one allele at every site it spans (0 own, 1 alt, 2 another symbol, none); a link between two
+    consecutive sites of a contig counts the rows with 0 or 1 at both (n00 n01 n10 n11) and is phased when min_link of them are
+    informative and min_agree of those lie on its majority side (cis or trans); phased links chain sites into blocks with a phase
+    bit per site, and every row gets hap_a / hap_b / other counts per block.  Writes out_sites (contig, pos, ref, alt, depth,
+    ref_count, alt_count, block, phase) and, when given, out_links (contig, pos1, pos2, n00, n01, n10, n11, informative, agree,
+    phased) and out_reads (read, contig, block, spanned, hap_a, hap_b, other, hap).  Options: those of api.variants, min_link 3,
+    min_agree 0.8.  A function of this project's own: include/hylight_mi.h states it, tests/phase_model.py is its contract.
+    -> dict of the stats (hlmi_phase_stats)."""
+    o, st = _phase_opts("phase", opts), PhaseStats()
+    _check(load().hlmi_phase(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(pairs), _b(out_sites), _b(out_links), _b(out_reads),
+                             C.byref(st)))
+    return {k: getattr(st, k) for k in PHASE_STATS + POLISH_MS}
+
+
+def phase_reads(contigs, reads, out_sites, out_links=None, out_reads=None, ava_opts=None, pairs=None, **opts):
+    """hlmi_phase_reads: `ava(contigs, reads, P, ava_opts)` and `phase(contigs, reads, P, ...)` in one call without the PAF P: the
+    same files and the same integer stats.  ava_opts None: the long constants.  Refused besides what phase refuses:
+    ava_opts.stub_oh >= 0.  -> dict of the stats (hlmi_phase_stats)."""
+    o, st = _phase_opts("phase_reads", opts), PhaseStats()
+    _check(load().hlmi_phase_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), _b(pairs),
+                                   _b(out_sites), _b(out_links), _b(out_reads), C.byref(st)))
+    return {k: getattr(st, k) for k in PHASE_STATS + POLISH_MS}
 
 
 DEVICE = "cuda"          # where the buffers that cross the C ABI live (stage.py allocates them with torch)

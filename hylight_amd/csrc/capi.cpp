@@ -11,6 +11,7 @@
 #include "polish_internal.h"
 #include "stage.h"
 #include "textpass.h"
+#include "phase_internal.h"
 #include "variants_internal.h"
 #include "vq_internal.h"
 
@@ -645,6 +646,28 @@ int hlmi_variants_reads(const char *contigs, const char *reads, const hlmi_ava_o
         if (!contigs || !reads || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_variants_reads: NULL argument");
         require_device();
         variants_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_sites, out_summary, st);
+    });
+}
+
+void hlmi_phase_opts_default(hlmi_phase_opts *o) {
+    if (o) *o = hlmi_phase_opts{0, 0.0, 3, 2, 0.2, 3, 0.8};
+}
+
+int hlmi_phase(const char *contigs, const char *reads, const char *paf, const hlmi_phase_opts *o, const char *pairs_paf,
+               const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_phase: NULL argument");
+        require_device();
+        phase_run(contigs, reads, paf, *o, pairs_paf, out_sites, out_links, out_reads, st);
+    });
+}
+
+int hlmi_phase_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_phase_opts *o, const char *pairs_paf,
+                     const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_phase_reads: NULL argument");
+        require_device();
+        phase_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_sites, out_links, out_reads, st);
     });
 }
 

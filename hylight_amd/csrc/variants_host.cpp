@@ -19,13 +19,13 @@ namespace hlmi {
 using namespace pol;
 using namespace var;
 
-namespace {
-
-void check_opts(const char *who, const hlmi_variant_opts &o) {
+void var::check_variant_opts(const char *who, const hlmi_variant_opts &o) {
     if (o.min_cov < 1) fail(HLMI_EINVAL, "%s: min_cov %d (< 1)", who, o.min_cov);
     if (o.min_alt < 1) fail(HLMI_EINVAL, "%s: min_alt %d (< 1)", who, o.min_alt);
     if (!(o.min_frac >= 0.0 && o.min_frac <= 1.0)) fail(HLMI_EINVAL, "%s: min_frac %g (outside [0, 1] or not a number)", who, o.min_frac);
 }
+
+namespace {
 
 // what both entry points do behind the device part: the records, the statistics and the two files
 void variants_emit(const char *who, const SeqSet &cs, const PolLayout &L, const DeviceVariants &dev, const char *out_sites,
@@ -70,7 +70,7 @@ void variants_run(const char *contigs, const char *reads, const char *paf, const
     const double t_begin = now_ms();
     *st = hlmi_variant_stats{};
     stat_reset();
-    check_opts("hlmi_variants", o);
+    check_variant_opts("hlmi_variants", o);
     PolQualCall qc;                             // no floor and no weights: the quality strings are only checked, as hlmi_depth does
     PolPairCall pc;
     pc.path = pairs_paf;
@@ -110,7 +110,7 @@ void variants_reads_run(const char *contigs, const char *reads, const hlmi_ava_o
     const double t_begin = now_ms();
     *st = hlmi_variant_stats{};
     stat_reset();
-    check_opts("hlmi_variants_reads", o);
+    check_variant_opts("hlmi_variants_reads", o);
     PolPairCall pc;
     pc.path = pairs_paf;
     RowSelection sel;

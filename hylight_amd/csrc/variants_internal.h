@@ -11,6 +11,8 @@ namespace var {
 // The device part over the polisher's input (rows, compact CIGARs, reads as ASCII or codes, contig bytes, tiles, cbase - in.quals
 // and in.min_cov are not read): the three counters per slot and the sites' records, ascending.  o: validated by the caller.
 void variants_core(const pol::PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &out);
+// the option refusals of both entry points, in the header's order (hlmi_phase makes them first, under its own name)
+void check_variant_opts(const char *who, const hlmi_variant_opts &o);
 
 }  // namespace var
 

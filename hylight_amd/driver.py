@@ -233,6 +233,25 @@ def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pai
     return out
 
 
+def phase_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None):
+    """`--phase`: the variant sites of the final contigs phased from the reads (hlmi_phase_reads: the reads are aligned to the
+    contigs in the call, every pair, one row per read).  The long reads with the overlapper's long constants give
+    outdir/final_contigs.long.phase.sites.tsv, .links.tsv and .reads.tsv; short reads, when there are any, with the short
+    constants give the .short. triple.  long_pairs / short_pairs: as for variant_tables.  `device`: the GPU to initialise the
+    library on (None: the caller has done so).  -> {"long": stats, "short": stats}."""
+    if device is not None:
+        api.init(device)
+    out = {}
+    for kind, reads, pairs in (("long", long_reads, long_pairs), ("short", short_reads, short_pairs)):
+        if not reads:
+            continue
+        o = api.ava_opts_short() if kind == "short" else api.ava_opts_long()
+        o.pair_once = 0
+        stem = os.path.join(outdir, f"final_contigs.{kind}.phase")
+        out[kind] = api.phase_reads(final, reads, stem + ".sites.tsv", stem + ".links.tsv", stem + ".reads.tsv", o, pairs=pairs)
+    return out
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m hylight_amd.driver",
                                 description="Haplotype-aware de novo assembly of metagenome from hybrid sequencing data "
@@ -304,6 +323,10 @@ def build_parser():
                    help="(extension) when final_contigs.fa is written: the variant sites of its contigs and a summary per contig "
                         "(hlmi_variants_reads) into final_contigs.long.variants.tsv and .long.variants.summary.tsv, and with -s "
                         "also the .short. pair; with --polish_strain only the pairs of ov_long_ref.paf / shortr1.paf vote")
+    p.add_argument("--phase", action="store_true",
+                   help="(extension) when final_contigs.fa is written: its variant sites phased from the reads (hlmi_phase_reads) "
+                        "into final_contigs.long.phase.sites.tsv, .links.tsv and .reads.tsv, and with -s also the .short. triple; "
+                        "independent of --variants; with --polish_strain only the pairs of ov_long_ref.paf / shortr1.paf vote")
     return p
 
 
@@ -553,6 +576,9 @@ def _pipeline(args, pool):
         if rc == 0 and args.variants:
             variant_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
                            long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None)
+        if rc == 0 and args.phase:
+            phase_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
+                         long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None)
         return rc
     # HyLight.py:211-262 (read clustering, POLYTE per cluster) is the short-read branch: not part of this path.  Its
     # contigs can be handed in; the contig-overlap half of extend_con runs either way (HyLight.py:264-280).
@@ -592,6 +618,9 @@ def _pipeline(args, pool):
     if args.variants:
         variant_tables(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
                        short_pairs=ov_short if args.polish_strain else None)
+    if args.phase:
+        phase_tables(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
+                     short_pairs=ov_short if args.polish_strain else None)
     return 0
 
 

@@ -964,6 +964,87 @@ int hlmi_variants(const char *contigs, const char *reads, const char *paf, const
 int hlmi_variants_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_variant_opts *o,
                         const char *pairs_paf, const char *out_sites, const char *out_summary, hlmi_variant_stats *st);
 
+/* ---- phased variant sites: do the minor alleles of neighbouring sites ride on the same reads (a collapsed sister strain that can
+ * be separated) or not (noise, a mis-join, a polishing error), and which read belongs to which side.  hlmi_phase reads a PAF as
+ * hlmi_variants does, hlmi_phase_reads aligns in the call as hlmi_variants_reads does.  New symbols: the older calls keep their
+ * signatures and their bytes, and HLMI_ABI_VERSION stays where it is.  A function of the project's own: PARITY UNPINNED;
+ * tests/phase_model.py is the contract, byte for byte. */
+typedef struct {
+    int min_len;              /* the five fields of hlmi_variant_opts, same meaning and defaults                           */
+    double min_iden;
+    int min_cov;
+    int min_alt;
+    double min_frac;
+    int min_link;             /* informative rows a link needs to be phased (>= 1)                                         */
+    double min_agree;         /* ... and the share of them on the link's majority side, in (0.5, 1]                        */
+} hlmi_phase_opts;
+void hlmi_phase_opts_default(hlmi_phase_opts *o);   /* 0, 0.0, 3, 2, 0.2, 3, 0.8 */
+typedef struct {
+    uint64_t rows;              /* the thirteen integer fields of hlmi_variant_stats, with hlmi_variants's values         */
+    uint64_t rows_selected;
+    uint64_t contigs;
+    uint64_t contigs_covered;
+    uint64_t positions;
+    uint64_t callable;
+    uint64_t ref_other;
+    uint64_t sites;
+    uint64_t sites_base;
+    uint64_t sites_del;
+    uint64_t pairs_listed;
+    uint64_t pairs_unknown;
+    uint64_t rows_not_listed;
+    uint64_t links;             /* pairs of consecutive sites of one contig                                                 */
+    uint64_t links_phased;
+    uint64_t blocks;
+    uint64_t blocks_multi;      /* blocks of two or more sites                                                              */
+    uint64_t sites_phased;      /* sites inside blocks of two or more sites                                                 */
+    uint64_t alleles;           /* sum over the selected rows of the sites inside [ts, te): the size of the allele table    */
+    uint64_t read_records;      /* lines of out_reads (counted also when out_reads is NULL)                                 */
+    uint64_t reads_a;           /* ... with hap A, B, -                                                                     */
+    uint64_t reads_b;
+    uint64_t reads_tie;
+    double ms_device;           /* wall time of the device part: uploads, kernels, read-backs                               */
+    double ms_total;
+} hlmi_phase_stats;
+/* contigs, reads, paf: as for hlmi_variants.  pairs_paf, out_links and out_reads may be NULL.
+ * Sites: exactly hlmi_variants's - the same selection (the pair list included, an empty list included), the same votes, the same
+ * site rule, run by the same code.  A site has own (A C G T) and alt (A C G T del).
+ * A row's allele at a site p of its contig: the symbol the row votes at p under hlmi_variants's vote rule is 0 if it is own, 1
+ * if it is alt, 2 if it is another of the five symbols; none if the row does not cover p or its column at p votes nothing (an N
+ * of the read).  A D column votes del.  I columns take no part, but they do shift the query column.
+ * Links: one per pair of consecutive sites of one contig, in ascending order; a link never joins two contigs.  Over the rows whose
+ * allele is 0 or 1 at both sites: n00, n01, n10, n11, the first digit the allele at the left site; cis = n00 + n11, trans = n01 +
+ * n10, inf = cis + trans, top = max(cis, trans).  The link is phased iff inf >= min_link and (double)top / (double)inf >= min_agree
+ * (one IEEE division); its direction is cis if cis > trans, otherwise trans.
+ * Blocks: a maximal run of consecutive sites of one contig joined by phased links; a site with no phased link is a block of one.
+ * A block's id is the 1-based position of its first site.  Phase bit: 0 at the block's first site, at each following site the
+ * previous bit XOR (the link is trans).  Hap A carries own where the bit is 0 and alt where it is 1, hap B the other allele.
+ * Reads: for a selected row and a block, over the block's sites inside the row's [ts, te): hap_a = sites whose allele is 0 or 1
+ * with allele XOR bit == 0, hap_b = those with that XOR 1, other = sites with allele 2, spanned = all of those sites, none
+ * included.  The pair (row, block) gets a record iff hap_a + hap_b + other >= 1; hap is A if hap_a > hap_b, B if hap_b > hap_a,
+ * - on a tie.
+ * Files, each under a temporary name and renamed on success:
+ * out_sites: the line "#contig\tpos\tref\talt\tdepth\tref_count\talt_count\tblock\tphase", then one line per site, contigs in
+ * file order, positions ascending: pos 1-based, alt as hlmi_variants prints it, depth, ref_count = v[own] and alt_count = v[alt]
+ * from the site's five votes, phase "0|1" for bit 0 and "1|0" for bit 1.  With no site the file is the header line alone.
+ * out_links (optional): the line "#contig\tpos1\tpos2\tn00\tn01\tn10\tn11\tinformative\tagree\tphased", then one line per link;
+ * agree is the quotient above as %.6f, 0.000000 when inf is 0; phased is cis, trans or -.
+ * out_reads (optional): the line "#read\tcontig\tblock\tspanned\thap_a\thap_b\tother\thap", then one line per record: contigs in
+ * file order, rows in selection order (contig, ts, line), a row's blocks ascending.
+ * Refusals (HLMI_EINVAL unless said otherwise, nothing is written): hlmi_variants's option refusals, in its order; min_link < 1;
+ * min_agree not a number, <= 0.5 or > 1 (with agreement above one half a tie can never phase); then every refusal hlmi_variants
+ * makes about the files, the rows and the list, in its order; the sum over the selected rows of the sites inside [ts, te) is 2^32
+ * or more, or does not fit the device's free memory.
+ * The allele table (one byte per row and spanned site) and the link counters live and are read in device memory
+ * (csrc/phase.hip); 16 bytes per link and 24 bytes per (row, block) come to the host. */
+int hlmi_phase(const char *contigs, const char *reads, const char *paf, const hlmi_phase_opts *o, const char *pairs_paf,
+               const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st);
+/* The two calls hlmi_ava(contigs, reads, ao, P) and hlmi_phase(contigs, reads, P, o, pairs_paf, ...) in one, without the PAF P: the
+ * three files and every integer field of *st are byte for byte what that chain gives (ao NULL: the long constants).  The stated
+ * differences of hlmi_variants_reads apply; the selected rows' read names cost 4 bytes per row on the way to the host. */
+int hlmi_phase_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_phase_opts *o, const char *pairs_paf,
+                     const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st);
+
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
  * reads into a caller-owned device buffer (16 B per minimizer: two uint64), the caller
