@@ -190,6 +190,18 @@ class PhaseStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in PHASE_STATS] + [(k, C.c_double) for k in POLISH_MS]
 
 
+class HaplotigOpts(C.Structure):
+    _fields_ = list(PhaseOpts._fields_) + [("min_side", C.c_int), ("include_unpolished", C.c_int)]
+
+
+HAPLOTIG_STATS = ("blocks_split", "contigs_split", "positions_split", "diff_positions", "records", "substituted", "deleted",
+                  "inserted_bases", "slots_opened", "ins_long", "ins_edge")
+
+
+class HaplotigStats(C.Structure):
+    _fields_ = [("phase", PhaseStats)] + [(k, C.c_uint64) for k in HAPLOTIG_STATS] + [(k, C.c_double) for k in POLISH_MS]
+
+
 ABI_VERSION = 7          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
@@ -299,6 +311,12 @@ SYMBOLS = {
                              C.POINTER(PhaseStats)]),
     "hlmi_phase_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PhaseOpts), C.c_char_p, C.c_char_p, C.c_char_p,
                                    C.c_char_p, C.POINTER(PhaseStats)]),
+    # haplotigs
+    "hlmi_haplotig_opts_default": (None, [C.POINTER(HaplotigOpts)]),
+    "hlmi_haplotigs": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(HaplotigOpts), C.c_char_p, C.c_char_p, C.c_char_p,
+                                 C.POINTER(HaplotigStats)]),
+    "hlmi_haplotigs_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(HaplotigOpts), C.c_char_p, C.c_char_p,
+                                       C.c_char_p, C.POINTER(HaplotigStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -892,6 +910,46 @@ def phase_reads(contigs, reads, out_sites, out_links=None, out_reads=None, ava_o
     _check(load().hlmi_phase_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), _b(pairs),
                                    _b(out_sites), _b(out_links), _b(out_reads), C.byref(st)))
     return {k: getattr(st, k) for k in PHASE_STATS + POLISH_MS}
+
+
+def _haplotig_opts(who, opts):
+    o = HaplotigOpts()
+    load().hlmi_haplotig_opts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(HaplotigOpts._fields_):
+            raise TypeError(f"{who}: unknown option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def _haplotig_stats(st):
+    out = {k: getattr(st.phase, k) for k in PHASE_STATS}
+    out.update({k: getattr(st, k) for k in HAPLOTIG_STATS + POLISH_MS})
+    return out
+
+
+def haplotigs(contigs, reads, paf, out_fa, out_blocks=None, pairs=None, **opts):
+    """hlmi_haplotigs: the contigs polished as api.polish polishes them, once per side of every phased block the reads split.  The
+    phasing is api.phase's (same selection, pairs= included, sites, links, blocks, every row's side per block).  A block of two or
+    more sites is split when min_side of its rows read side A and min_side side B; inside its extent [first site, last site] a row
+    votes only on its own side, everywhere else on both.  A contig with a split block gives two records (name_hapA, name_hapB with
+    HB:i: split blocks and HP:i: positions inside them), every other contig api.polish's record byte for byte.  Writes out_fa and,
+    when given, out_blocks (contig, block, start, end, sites, rows_a, rows_b, split, diff_positions).  Options: those of api.phase,
+    min_side 3, include_unpolished 1.  A function of this project's own: include/hylight_mi.h states it, tests/haplotigs_model.py
+    is its contract.  -> dict of the stats (hlmi_haplotig_stats, the phasing's integer stats among them)."""
+    o, st = _haplotig_opts("haplotigs", opts), HaplotigStats()
+    _check(load().hlmi_haplotigs(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(pairs), _b(out_fa), _b(out_blocks), C.byref(st)))
+    return _haplotig_stats(st)
+
+
+def haplotigs_reads(contigs, reads, out_fa, out_blocks=None, ava_opts=None, pairs=None, **opts):
+    """hlmi_haplotigs_reads: `ava(contigs, reads, P, ava_opts)` and `haplotigs(contigs, reads, P, ...)` in one call without the PAF
+    P: the same files and the same integer stats.  ava_opts None: the long constants.  Refused besides what haplotigs refuses:
+    ava_opts.stub_oh >= 0.  -> dict of the stats (hlmi_haplotig_stats)."""
+    o, st = _haplotig_opts("haplotigs_reads", opts), HaplotigStats()
+    _check(load().hlmi_haplotigs_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), _b(pairs),
+                                       _b(out_fa), _b(out_blocks), C.byref(st)))
+    return _haplotig_stats(st)
 
 
 DEVICE = "cuda"          # where the buffers that cross the C ABI live (stage.py allocates them with torch)

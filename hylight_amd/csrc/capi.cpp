@@ -11,6 +11,7 @@
 #include "polish_internal.h"
 #include "stage.h"
 #include "textpass.h"
+#include "haplotigs_internal.h"
 #include "phase_internal.h"
 #include "variants_internal.h"
 #include "vq_internal.h"
@@ -668,6 +669,28 @@ int hlmi_phase_reads(const char *contigs, const char *reads, const hlmi_ava_opts
         if (!contigs || !reads || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_phase_reads: NULL argument");
         require_device();
         phase_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_sites, out_links, out_reads, st);
+    });
+}
+
+void hlmi_haplotig_opts_default(hlmi_haplotig_opts *o) {
+    if (o) *o = hlmi_haplotig_opts{0, 0.0, 3, 2, 0.2, 3, 0.8, 3, 1};
+}
+
+int hlmi_haplotigs(const char *contigs, const char *reads, const char *paf, const hlmi_haplotig_opts *o, const char *pairs_paf,
+                   const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_haplotigs: NULL argument");
+        require_device();
+        haplotigs_run(contigs, reads, paf, *o, pairs_paf, out_fa, out_blocks, st);
+    });
+}
+
+int hlmi_haplotigs_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_haplotig_opts *o,
+                         const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_haplotigs_reads: NULL argument");
+        require_device();
+        haplotigs_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_fa, out_blocks, st);
     });
 }
 

@@ -198,8 +198,10 @@ std::vector<uint32_t> selected_query_ranks(const PafRec *recs, const uint32_t *i
     return d.download(n_sel);
 }
 
-void phase_core(const char *who, const PolCoreIn &in, const std::vector<PSite> &sites, const hlmi_phase_opts &o, DevicePhase &out) {
+void phase_core(const char *who, const PolCoreIn &in, const std::vector<PSite> &sites, const hlmi_phase_opts &o, DevicePhase &out,
+                DevRecs *keep) {
     out = DevicePhase{};
+    if (keep) *keep = DevRecs{};
     const size_t N = sites.size(), R = in.n_rows;
     if (!N) {
         out.blocks = build_blocks(sites, out.links, o.min_link, o.min_agree);
@@ -282,6 +284,12 @@ void phase_core(const char *who, const PolCoreIn &in, const std::vector<PSite> &
                                d_bit.p, d_slots.p, d_rec_off.p, d_recs.p);
             HIP_CHECK(hipGetLastError());
             out.recs = d_recs.download(n_recs);
+            if (keep) {
+                keep->recs = std::move(d_recs);
+                keep->off = std::move(d_rec_off);
+                keep->cnt = std::move(d_slots);
+                keep->n = n_recs;
+            }
         }
     }
 }

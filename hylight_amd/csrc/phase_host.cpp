@@ -28,7 +28,11 @@ namespace {
 
 hlmi_variant_opts variant_part(const hlmi_phase_opts &o) { return hlmi_variant_opts{o.min_len, o.min_iden, o.min_cov, o.min_alt, o.min_frac}; }
 
-void check_opts(const char *who, const hlmi_phase_opts &o) {
+}  // namespace
+
+namespace ph {
+
+void check_phase_opts(const char *who, const hlmi_phase_opts &o) {
     check_variant_opts(who, variant_part(o));
     if (o.min_link < 1) fail(HLMI_EINVAL, "%s: min_link %d (< 1)", who, o.min_link);
     if (!(o.min_agree > 0.5 && o.min_agree <= 1.0)) fail(HLMI_EINVAL, "%s: min_agree %g (outside (0.5, 1] or not a number)", who, o.min_agree);
@@ -41,24 +45,16 @@ void set_pair_stats(const PolPairCall &pc, bool given, hlmi_phase_stats *st) {
     st->rows_not_listed = pc.rows_not_listed;
 }
 
-struct Phased {
-    DeviceVariants var;
-    std::vector<PSite> sites;
-    DevicePhase dev;
-};
-
-// the device part of both entry points over the same input: hlmi_variants's sites, then the phasing
-void phase_device(const char *who, const SeqSet &cs, const PolLayout &L, const PolCoreIn &core, const hlmi_phase_opts &o, Phased &P) {
+void phase_device(const char *who, const SeqSet &cs, const PolLayout &L, const PolCoreIn &core, const hlmi_phase_opts &o, Phased &P,
+                  DevRecs *keep) {
     variants_core(core, variant_part(o), P.var);
     std::vector<std::string_view> seq(cs.size());
     for (size_t c = 0; c < cs.size(); ++c) seq[c] = std::string_view(cs.bases).substr(cs.off[c], cs.len(c));
     if (!phase_sites(seq, L.rc, L.slot_of_contig, L.cbase, P.var, P.sites))
         fail(HLMI_ESTATE, "%s: the sites' records do not fit the contigs", who);                                    // (never)
-    phase_core(who, core, P.sites, o, P.dev);
+    phase_core(who, core, P.sites, o, P.dev, keep);
 }
 
-// what both entry points do behind the device part: the statistics and the three files.  read_of_row: the read record of every
-// selected row, asked for only when out_reads has a line to write
 void phase_emit(const char *who, const SeqSet &cs, const SeqSet &rs, const PolLayout &L, const Phased &P, const hlmi_phase_opts &o,
                 const std::function<std::vector<uint32_t>()> &read_of_row, const char *out_sites, const char *out_links,
                 const char *out_reads, hlmi_phase_stats *st) {
@@ -90,8 +86,8 @@ void phase_emit(const char *who, const SeqSet &cs, const SeqSet &rs, const PolLa
     stat_set("variants_tiles", (double)P.var.tiles);
     stat_set("variants_tiles_revisited", (double)P.var.tiles_revisited);
 
-    const std::vector<std::string> sites = phase_site_lines(cs.names, P.sites, B);
-    std::vector<std::string> links, reads;
+    std::vector<std::string> sites, links, reads;
+    if (out_sites) sites = phase_site_lines(cs.names, P.sites, B);
     if (out_links) links = phase_link_lines(cs.names, P.sites, P.dev.links, o.min_link, o.min_agree);
     ReadTotals rt;
     std::vector<uint32_t> rows_read;
@@ -102,19 +98,19 @@ void phase_emit(const char *who, const SeqSet &cs, const SeqSet &rs, const PolLa
     st->reads_a = rt.a;
     st->reads_b = rt.b;
     st->reads_tie = rt.tie;
-    write_lines(out_sites, sites);
+    if (out_sites) write_lines(out_sites, sites);
     if (out_links) write_lines(out_links, links);
     if (out_reads) write_lines(out_reads, reads);
 }
 
-}  // namespace
+}  // namespace ph
 
 void phase_run(const char *contigs, const char *reads, const char *paf, const hlmi_phase_opts &o, const char *pairs_paf,
                const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st) {
     const double t_begin = now_ms();
     *st = hlmi_phase_stats{};
     stat_reset();
-    check_opts("hlmi_phase", o);
+    check_phase_opts("hlmi_phase", o);
     PolQualCall qc;                             // no floor and no weights: the quality strings are only checked, as hlmi_variants does
     PolPairCall pc;
     pc.path = pairs_paf;
@@ -158,7 +154,7 @@ void phase_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts
     const double t_begin = now_ms();
     *st = hlmi_phase_stats{};
     stat_reset();
-    check_opts("hlmi_phase_reads", o);
+    check_phase_opts("hlmi_phase_reads", o);
     PolPairCall pc;
     pc.path = pairs_paf;
     RowSelection sel;

@@ -16,6 +16,8 @@
 // polish_device uploads what polish_host.cpp built and runs polish_core; hlmi_polish_reads (polish_rows.hip) runs polish_core
 // over rows, CIGARs and reads that are in device memory already - its reads as the overlapper's codes (column_symbol).
 // column_symbol, walk_row and the lane / wave switch of the vote loop are polish_walk.h's, shared with variants.hip.
+// polish_tail is everything behind the count pass - slot index, slot passes, lengths, scan, write - over any position space:
+// hlmi_haplotigs (haplotigs.hip) runs it over two sides side by side with slot votes of its own.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -260,7 +262,6 @@ void polish_core(const PolCoreIn &in, PolDevOut &out) {
     out = PolDevOut{};
     out.start.assign(in.n_cbase, 0);
     if (!G) return;
-    constexpr int B = 256;
     DBuf<uint8_t> d_sym(G), d_open(G);
     HIP_CHECK(hipMemsetAsync(d_sym.p, SYM_KEEP, G, stream()));
     d_open.zero();
@@ -275,19 +276,31 @@ void polish_core(const PolCoreIn &in, PolDevOut &out) {
         }
         HIP_CHECK(hipGetLastError());
     }
+    polish_tail(PolTailIn{in.contig, G, &d_sym, &d_open, in.cbase, in.n_cbase, "polish_slots"},
+                [&](int mode, const uint32_t *d_slot_of, const uint8_t *d_win_len, uint32_t *d_len_cnt, uint32_t *d_base_cnt) {
+                    if (mode == 0) launch_slot_for<0>(in, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+                    else launch_slot_for<1>(in, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+                },
+                out);
+}
+
+void polish_tail(const PolTailIn &in, const PolSlotVotes &votes, PolDevOut &out) {
+    const size_t G = in.n;
+    constexpr int B = 256;
+    const DBuf<uint8_t> &d_sym = *in.sym, &d_open = *in.open;
     DBuf<uint32_t> d_open_pos(G), d_slot_of(G);
     const size_t n_open = select_flagged_indices(d_open.p, d_open_pos.p, G);
     d_slot_of.fill_ff();
     DBuf<uint32_t> d_len_cnt(std::max<size_t>(n_open, 1) * POLISH_INS_CAP), d_base_cnt(std::max<size_t>(n_open, 1) * POLISH_INS_CAP * 4);
     DBuf<uint8_t> d_win_len(std::max<size_t>(n_open, 1));
     if (n_open) {
-        KTimer kt("polish_slots");
+        KTimer kt(in.slots_timer);
         d_len_cnt.zero();
         d_base_cnt.zero();
         hipLaunchKernelGGL(slot_index_kernel, dim3(cdiv(n_open, B)), dim3(B), 0, stream(), d_open_pos.p, (uint32_t)n_open, d_slot_of.p);
-        launch_slot_for<0>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
+        votes(0, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
         hipLaunchKernelGGL(slot_len_kernel, dim3(cdiv(n_open, B)), dim3(B), 0, stream(), d_len_cnt.p, (uint32_t)n_open, d_win_len.p);
-        launch_slot_for<1>(in, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
+        votes(1, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
         HIP_CHECK(hipGetLastError());
     }
     DBuf<uint32_t> d_out_len(G + 1);
@@ -307,7 +320,7 @@ void polish_core(const PolCoreIn &in, PolDevOut &out) {
     out.start = d_start.download();
     const std::vector<uint8_t> bytes = d_out.download((size_t)total);
     out.bases.assign((const char *)bytes.data(), bytes.size());
-    out.sym = d_sym.download();
+    out.sym = d_sym.download(G);
     out.open_pos = d_open_pos.download(n_open);
     out.open_len = d_win_len.download(n_open);
 }

@@ -2,6 +2,7 @@
 // The rules are those of include/hylight_mi.h (hlmi_polish, hlmi_polish_q); tests/polish_model.py and
 // tests/polish_qual_model.py restate them.
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -68,6 +69,23 @@ struct PolCoreIn {
     int min_cov = 3;
 };
 void polish_core(const PolCoreIn &in, PolDevOut &out);
+
+// polish_core behind its count pass, over any position space: n positions with their contig bytes, decisions and slot flags
+// (device memory), the start of every output record in it (cbase, n_cbase entries, the total last).  Opened slots get their
+// index; votes(0, ...) adds every inserting row's length vote to len_cnt[slot * POLISH_INS_CAP + len - 1], the lengths are
+// decided, votes(1, ...) adds the base votes to base_cnt[(slot * POLISH_INS_CAP + j) * 4 + base] where win_len[slot] is the
+// row's length; then output lengths, the scan and the bytes.  slots_timer: the kernel timer's name of the slot passes.
+struct PolTailIn {
+    const uint8_t *contig;
+    size_t n;
+    const DBuf<uint8_t> *sym, *open;
+    const uint32_t *cbase;
+    size_t n_cbase;
+    const char *slots_timer;
+};
+using PolSlotVotes = std::function<void(int mode, const uint32_t *slot_of, const uint8_t *win_len, uint32_t *len_cnt, uint32_t *base_cnt)>;
+void polish_tail(const PolTailIn &in, const PolSlotVotes &votes, PolDevOut &out);
+constexpr uint32_t POLISH_NO_SLOT = 0xffffffffu;        // slot_of of a position whose slot stays shut
 
 // ---- what both entry points do on the host around the device part (polish_host.cpp) ----------------------------------------
 // a selected row as the layout sees it: contig record, [ts, te); in the order (contig, ts, line)

@@ -252,6 +252,25 @@ def phase_tables(final, long_reads, short_reads, outdir, device=None, long_pairs
     return out
 
 
+def haplotig_files(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None):
+    """`--haplotigs`: the final contigs polished once per side of every phased block the reads split (hlmi_haplotigs_reads: the
+    reads are aligned to the contigs in the call, every pair, one row per read).  The long reads with the overlapper's long
+    constants give outdir/final_contigs.long.haplotigs.fa and .long.haplotigs.blocks.tsv; short reads, when there are any, with
+    the short constants give the .short. pair.  long_pairs / short_pairs: as for phase_tables.  `device`: the GPU to initialise
+    the library on (None: the caller has done so).  -> {"long": stats, "short": stats}."""
+    if device is not None:
+        api.init(device)
+    out = {}
+    for kind, reads, pairs in (("long", long_reads, long_pairs), ("short", short_reads, short_pairs)):
+        if not reads:
+            continue
+        o = api.ava_opts_short() if kind == "short" else api.ava_opts_long()
+        o.pair_once = 0
+        stem = os.path.join(outdir, f"final_contigs.{kind}.haplotigs")
+        out[kind] = api.haplotigs_reads(final, reads, stem + ".fa", stem + ".blocks.tsv", o, pairs=pairs)
+    return out
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m hylight_amd.driver",
                                 description="Haplotype-aware de novo assembly of metagenome from hybrid sequencing data "
@@ -327,6 +346,11 @@ def build_parser():
                    help="(extension) when final_contigs.fa is written: its variant sites phased from the reads (hlmi_phase_reads) "
                         "into final_contigs.long.phase.sites.tsv, .links.tsv and .reads.tsv, and with -s also the .short. triple; "
                         "independent of --variants; with --polish_strain only the pairs of ov_long_ref.paf / shortr1.paf vote")
+    p.add_argument("--haplotigs", action="store_true",
+                   help="(extension) when final_contigs.fa is written: its contigs polished once per side of every phased block "
+                        "the reads split (hlmi_haplotigs_reads) into final_contigs.long.haplotigs.fa and "
+                        ".long.haplotigs.blocks.tsv, and with -s also the .short. pair; independent of --phase; with "
+                        "--polish_strain only the pairs of ov_long_ref.paf / shortr1.paf vote")
     return p
 
 
@@ -579,6 +603,9 @@ def _pipeline(args, pool):
         if rc == 0 and args.phase:
             phase_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
                          long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None)
+        if rc == 0 and args.haplotigs:
+            haplotig_files(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
+                           long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None)
         return rc
     # HyLight.py:211-262 (read clustering, POLYTE per cluster) is the short-read branch: not part of this path.  Its
     # contigs can be handed in; the contig-overlap half of extend_con runs either way (HyLight.py:264-280).
@@ -621,6 +648,9 @@ def _pipeline(args, pool):
     if args.phase:
         phase_tables(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
                      short_pairs=ov_short if args.polish_strain else None)
+    if args.haplotigs:
+        haplotig_files(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
+                       short_pairs=ov_short if args.polish_strain else None)
     return 0
 
 

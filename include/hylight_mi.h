@@ -1045,6 +1045,83 @@ int hlmi_phase(const char *contigs, const char *reads, const char *paf, const hl
 int hlmi_phase_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_phase_opts *o, const char *pairs_paf,
                      const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st);
 
+/* ---- haplotigs: polish each side of a phased block on its own.  hlmi_polish lets every read vote in every column, so inside a phased
+ * block the majority strain wins; these calls give two consensus sequences where the reads prove two sides, and hlmi_polish's bytes
+ * everywhere else.  hlmi_haplotigs reads a PAF as hlmi_phase does, hlmi_haplotigs_reads aligns in the call as hlmi_phase_reads does.
+ * New symbols: the older calls keep their signatures and their bytes, and HLMI_ABI_VERSION stays where it is.  A function of the
+ * project's own: PARITY UNPINNED; tests/haplotigs_model.py is the contract, byte for byte. */
+typedef struct {
+    int min_len;              /* the seven fields of hlmi_phase_opts, same meaning and defaults                            */
+    double min_iden;
+    int min_cov;
+    int min_alt;
+    double min_frac;
+    int min_link;
+    double min_agree;
+    int min_side;             /* records a block needs on side A, and on side B, to be split (>= 1)                        */
+    int include_unpolished;   /* as in hlmi_polish_opts                                                                    */
+} hlmi_haplotig_opts;
+void hlmi_haplotig_opts_default(hlmi_haplotig_opts *o);   /* 0, 0.0, 3, 2, 0.2, 3, 0.8, 3, 1 */
+typedef struct {
+    hlmi_phase_stats phase;     /* of the phasing, with hlmi_phase's values; its ms_device ends where the phasing does      */
+    uint64_t blocks_split;
+    uint64_t contigs_split;     /* contigs with a split block: they give two records                                        */
+    uint64_t positions_split;   /* positions inside the extents of split blocks                                             */
+    uint64_t diff_positions;    /* ... that the two sides decided differently                                               */
+    uint64_t records;           /* records written to out_fa                                                                */
+    uint64_t substituted;       /* these four as in hlmi_polish_stats, summed over the records: a split contig gives both   */
+    uint64_t deleted;
+    uint64_t inserted_bases;
+    uint64_t slots_opened;
+    uint64_t ins_long;          /* these two as in hlmi_polish_stats, once per row                                          */
+    uint64_t ins_edge;
+    double ms_device;           /* wall time of the device part: uploads, kernels, read-backs                               */
+    double ms_total;
+} hlmi_haplotig_stats;
+/* contigs, reads, paf: as for hlmi_phase.  pairs_paf and out_blocks may be NULL.
+ * 1. Phasing: selection (the pair list included), rows, sites, links, blocks, phase bits and every row's hap_a / hap_b per block are
+ * hlmi_phase's, run by the same code.  A row's side in a block is A if hap_a > hap_b, B if hap_b > hap_a, none on a tie or without a
+ * record.
+ * 2. Split blocks: a block with at least two sites is split iff at least min_side of its (row, block) records have side A and at
+ * least min_side have side B.  Its extent is the positions [first site, last site] of its contig, both ends included; slot p (the
+ * gap in front of position p) lies inside the extent iff first < p <= last.  Extents of different blocks never overlap.
+ * 3. Who votes: row r takes part in side S at position or slot p unless p lies inside the extent of a split block and the row's side
+ * in that block is the other side.  A row votes on both sides wherever p is outside every extent, and a row with no side in a block
+ * votes on both sides inside that block's extent.  Where a row takes part it does so exactly as in hlmi_polish, unweighted: its
+ * column vote, its spanning of a slot, its insertion of 1..16 bases, ins_long, ins_edge.
+ * 4. Decisions: hlmi_polish's rules, once per side on that side's counters: a position keeps the contig's byte when the side's votes
+ * are below min_cov; a tie prefers the contig's own base; a slot opens when s >= min_cov and 2 i > s over the side's spanning and
+ * inserting rows; its length and bases come from the side's inserting rows.
+ * 5. out_fa (under a temporary name, renamed on success), contigs in file order.  A contig with selected rows and no split block
+ * gives one record, byte for byte what hlmi_polish writes for it (">name LN:i: RC:i: XC:f:").  A contig with a split block gives
+ * two records, ">name_hapA LN:i:<length> RC:i:<rows selected on the contig> XC:f:<that side's share of positions with votes >=
+ * min_cov> HB:i:<split blocks> HP:i:<positions inside their extents>" and the same for _hapB.  A contig without a selected row is
+ * written as it is when include_unpolished is set.  A record whose consensus is empty is not written.  Side A of a block is the
+ * side that holds the contig's own allele at the block's first site; the sides of different blocks of one contig are independent
+ * of each other (pseudo-haplotigs: _hapA joins the A sides of all blocks, which need not be one strain).
+ * 6. out_blocks (optional): the line "#contig\tblock\tstart\tend\tsites\trows_a\trows_b\tsplit\tdiff_positions", then one line per
+ * block with at least two sites, contigs in file order, blocks ascending: block is the block's id (the 1-based position of its
+ * first site), start and end its extent, 1-based; rows_a and rows_b the records with side A and B; split 1 or 0; diff_positions the
+ * number of positions of the extent whose decision (keep, a base, del) differs between the two sides, 0 when the block is not split.
+ * 7. Stats: substituted, deleted, inserted_bases and slots_opened are counted per record as hlmi_polish counts them for a contig (a
+ * consensus that turns out empty still counts) and summed.
+ * Consequence: with no split block in the call - min_side above the number of rows is enough - out_fa is byte for byte hlmi_polish's
+ * on the same input and options; the single-sided count pass produces it and no kernel of csrc/haplotigs.hip is launched.
+ * Out of scope: quality weights; links between sites that are not neighbours; joining blocks across a contig; insertion sites as
+ * phasing evidence.
+ * Refusals (HLMI_EINVAL unless said otherwise, nothing is written): hlmi_phase's option refusals, in its order; min_side < 1; then
+ * every refusal hlmi_phase makes about the files, the rows, the list and its tables, in its order; the rows' interval table does not
+ * fit the device's free memory; hlmi_polish's limits (2^28 bases in a sequence, 2^31 contig bases).
+ * Device: the records per (row, block) stay in device memory behind the phasing; 9 bytes per block go up (extent and split flag) and
+ * nothing per row comes down.  Two sides of counters live in LDS only (csrc/haplotigs.hip). */
+int hlmi_haplotigs(const char *contigs, const char *reads, const char *paf, const hlmi_haplotig_opts *o, const char *pairs_paf,
+                   const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st);
+/* The two calls hlmi_ava(contigs, reads, ao, P) and hlmi_haplotigs(contigs, reads, P, o, pairs_paf, ...) in one, without the PAF P:
+ * both files and every integer field of *st are byte for byte what that chain gives (ao NULL: the long constants).  The three stated
+ * differences of hlmi_polish_reads apply (a name twice - which hlmi_haplotigs refuses as well -, stub_oh >= 0, 2^32 rows). */
+int hlmi_haplotigs_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_haplotig_opts *o,
+                         const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st);
+
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
  * reads into a caller-owned device buffer (16 B per minimizer: two uint64), the caller
