@@ -529,40 +529,8 @@ void hlmi_polish_qopts_default(hlmi_polish_qopts *o) {
 
 namespace {
 hlmi_polish_opts polish_base_opts(const hlmi_polish_qopts &q) { return hlmi_polish_opts{q.min_len, q.min_iden, q.min_cov, q.include_unpolished}; }
-}  // namespace
 
-int hlmi_polish_q(const char *contigs, const char *reads, const char *paf, const hlmi_polish_qopts *o, const char *out_fa,
-                  hlmi_polish_qstats *st) {
-    return guarded([&] {
-        if (!contigs || !reads || !paf || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish_q: NULL argument");
-        require_device();
-        *st = hlmi_polish_qstats{};
-        pol::PolQualCall qc;
-        qc.qual_weight = o->qual_weight != 0;
-        qc.min_avg_qual = o->min_avg_qual;
-        polish_run(contigs, reads, paf, polish_base_opts(*o), out_fa, &st->base, &qc);
-        st->reads_with_qual = qc.reads_with_qual;
-        st->rows_low_qual = qc.rows_low_qual;
-    });
-}
-
-int hlmi_polish_reads_q(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_qopts *po,
-                        const char *out_fa, hlmi_polish_qstats *st) {
-    return guarded([&] {
-        if (!contigs || !reads || !po || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish_reads_q: NULL argument");
-        require_device();
-        *st = hlmi_polish_qstats{};
-        pol::PolQualCall qc;
-        qc.qual_weight = po->qual_weight != 0;
-        qc.min_avg_qual = po->min_avg_qual;
-        polish_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), polish_base_opts(*po), out_fa, &st->base, &qc);
-        st->reads_with_qual = qc.reads_with_qual;
-        st->rows_low_qual = qc.rows_low_qual;
-    });
-}
-
-namespace {
-// what the two _pairs calls hand polish_run / polish_reads_run, and how it comes back
+// what the _q and _pairs calls hand polish_run / polish_reads_run, and how it comes back
 struct PairsCall {
     pol::PolQualCall qc;
     pol::PolPairCall pc;
@@ -572,15 +540,42 @@ struct PairsCall {
         pc.path = pairs_paf;
     }
     pol::PolPairCall *list() { return pc.path ? &pc : nullptr; }      // no list: the _q call
+    void to(hlmi_polish_qstats *st) const {
+        st->reads_with_qual = qc.reads_with_qual;
+        st->rows_low_qual = qc.rows_low_qual;
+    }
     void to(hlmi_polish_pstats *st) const {
-        st->q.reads_with_qual = qc.reads_with_qual;
-        st->q.rows_low_qual = qc.rows_low_qual;
+        to(&st->q);
         st->pairs_listed = pc.pairs_listed;
         st->pairs_unknown = pc.pairs_unknown;
         st->rows_not_listed = pc.rows_not_listed;
     }
 };
 }  // namespace
+
+int hlmi_polish_q(const char *contigs, const char *reads, const char *paf, const hlmi_polish_qopts *o, const char *out_fa,
+                  hlmi_polish_qstats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish_q: NULL argument");
+        require_device();
+        *st = hlmi_polish_qstats{};
+        PairsCall c(*o, nullptr);
+        polish_run(contigs, reads, paf, polish_base_opts(*o), out_fa, &st->base, &c.qc);
+        c.to(st);
+    });
+}
+
+int hlmi_polish_reads_q(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_polish_qopts *po,
+                        const char *out_fa, hlmi_polish_qstats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !po || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_polish_reads_q: NULL argument");
+        require_device();
+        *st = hlmi_polish_qstats{};
+        PairsCall c(*po, nullptr);
+        polish_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), polish_base_opts(*po), out_fa, &st->base, &c.qc);
+        c.to(st);
+    });
+}
 
 int hlmi_polish_pairs(const char *contigs, const char *reads, const char *paf, const hlmi_polish_qopts *o, const char *pairs_paf,
                       const char *out_fa, hlmi_polish_pstats *st) {

@@ -1,6 +1,6 @@
 // haplotigs_host.cpp - the host part of hlmi_haplotigs and hlmi_haplotigs_reads (include/hylight_mi.h): the contigs polished once
-// per side of every split block.  Selection, layout, rows, compact CIGARs and reads are the polisher's (polish_select.h), sites and
-// phasing hlmi_phase's (phase_device, phase_emit for the statistics), called and not restated; the split rule, the blocks file and
+// per side of every split block.  The rows come from the pile-up calls' row front (polish_select.h), sites and phasing are
+// hlmi_phase's (phase_device, phase_emit for the statistics), called and not restated; the split rule, the blocks file and
 // the headers are haplotigs_text.h's, the exclusion intervals and the two-sided passes haplotigs.hip's.  With no split block the
 // single-sided polish_core gives the bytes and no kernel of haplotigs.hip runs.
 // PARITY UNPINNED: a function of the project's own; tests/haplotigs_model.py is the contract.
@@ -33,11 +33,18 @@ void check_opts(const char *who, const hlmi_haplotig_opts &o) {
     if (o.min_side < 1) fail(HLMI_EINVAL, "%s: min_side %d (< 1)", who, o.min_side);
 }
 
-// What both entry points do behind the rows' input: the phasing, the split rule, one or two sides of consensus, the statistics
-// and the two files.  core: the device's input, min_cov left to this function; L.contigs: the polished contigs' bytes.
-void haplotigs_finish(const char *who, const SeqSet &cs, const SeqSet &rs, const PolLayout &L, PolCoreIn core, const hlmi_haplotig_opts &o,
-                      double t_dev, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st) {
+// What both entry points do behind the rows: the phasing, the split rule, one or two sides of consensus, the statistics and the
+// two files.
+void haplotigs_body(const char *who, PileupRows &R, const hlmi_haplotig_opts &o, const char *out_fa, const char *out_blocks,
+                    hlmi_haplotig_stats *st) {
+    const SeqSet &cs = R.cs();
+    const PolLayout &L = R.L;
+    const double t_dev = R.t_dev;
     const hlmi_phase_opts po = phase_part(o);
+    set_row_stats(R, &st->phase);
+    st->ins_edge = R.ins_edge;
+    st->ins_long = R.ins_long;
+    PolCoreIn &core = R.up.core;
     core.min_cov = o.min_cov;
     core.quals = nullptr;
     Phased P;
@@ -46,7 +53,7 @@ void haplotigs_finish(const char *who, const SeqSet &cs, const SeqSet &rs, const
     bool any = false;
     {
         DevRecs keep;
-        phase_device(who, cs, L, core, po, P, &keep);
+        phase_device(who, R, po, P, &keep);
         st->phase.ms_device = now_ms() - t_dev;
         if (!haplotig_blocks(P.sites, P.dev.blocks, P.dev.recs, o.min_side, hb)) fail(HLMI_ESTATE, "%s: a row's record names no block", who);   // (never)
         for (const HBlock &h : hb) any |= h.split;
@@ -66,7 +73,7 @@ void haplotigs_finish(const char *who, const SeqSet &cs, const SeqSet &rs, const
         }
     }
     st->ms_device = now_ms() - t_dev;
-    phase_emit(who, cs, rs, L, P, po, []() { return std::vector<uint32_t>(); }, nullptr, nullptr, nullptr, &st->phase);
+    phase_emit(who, R, P, po, {}, nullptr, nullptr, nullptr, &st->phase);
 
     const size_t G = L.contigs.size(), n = L.cbase.size() - 1;
     if (out.start.size() != (any ? 2 * n : n) + 1 || out.sym.size() != (any ? 2 * G : G) || out.open_len.size() != out.open_pos.size())
@@ -92,18 +99,7 @@ void haplotigs_finish(const char *who, const SeqSet &cs, const SeqSet &rs, const
             }
         for (size_t side = 0; side < (n_split ? 2u : 1u); ++side) {
             const size_t g0 = side * G + b;
-            uint64_t covered = 0;
-            for (uint32_t p = 0; p < len; ++p) {
-                const uint8_t d = out.sym[g0 + p];
-                if (d == SYM_KEEP) continue;
-                ++covered;
-                if (d == SYM_DEL) ++st->deleted;
-                else if ("ACGT"[d & 3] != (char)((unsigned char)L.contigs[b + p] & 0xdfu)) ++st->substituted;
-            }
-            const auto s0 = std::lower_bound(out.open_pos.begin(), out.open_pos.end(), (uint32_t)g0);
-            const auto s1 = std::lower_bound(s0, out.open_pos.end(), (uint32_t)(g0 + len));
-            st->slots_opened += (uint64_t)(s1 - s0);
-            for (auto it = s0; it != s1; ++it) st->inserted_bases += out.open_len[it - out.open_pos.begin()];
+            const uint64_t covered = count_decisions(out, g0, L.contigs.data() + b, len, st);
             const uint64_t at = out.start[side * n + j], new_len = out.start[side * n + j + 1] - at;
             if (!new_len) continue;
             lines.push_back(haplotig_head(cs.names[c], n_split ? "AB"[side] : '\0', new_len, L.rc[c], covered, len, n_split, inside));
@@ -128,61 +124,23 @@ void haplotigs_finish(const char *who, const SeqSet &cs, const SeqSet &rs, const
 
 void haplotigs_run(const char *contigs, const char *reads, const char *paf, const hlmi_haplotig_opts &o, const char *pairs_paf,
                    const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st) {
-    const double t_begin = now_ms();
-    *st = hlmi_haplotig_stats{};
-    stat_reset();
-    check_opts("hlmi_haplotigs", o);
-    PolQualCall qc;                             // no floor and no weights: the quality strings are only checked, as hlmi_phase does
-    PolPairCall pc;
-    pc.path = pairs_paf;
-    PafSelection S;
-    select_paf_rows(contigs, reads, paf, o.min_len, o.min_iden, SelectNames{"hlmi_haplotigs", "hlmi_haplotigs", "hlmi_haplotigs", true}, &qc,
-                    pairs_paf ? &pc : nullptr, S);
-    st->phase.rows = S.pt.recs.size();
-    st->phase.contigs = S.cs.size();
-    st->phase.rows_selected = S.sel.size();
-    set_pair_stats(pc, pairs_paf != nullptr, &st->phase);
-    std::vector<PolSpan> spans;
-    spans.reserve(S.sel.size());
-    for (const PafSel &s : S.sel) spans.push_back(PolSpan{s.contig, S.pt.recs[s.line].ts, S.pt.recs[s.line].te});
-    PolLayout L;
-    polish_layout(S.cs, spans, "hlmi_haplotigs", L, nullptr);
-    PolDevIn in;
-    paf_rows_input(S, L, false, in, st->ins_edge, st->ins_long);
-    in.contigs = L.contigs;
-    in.cbase = L.cbase;
-    in.tiles = std::move(L.tiles);
-
-    const double t_dev = now_ms();
-    PolUploaded up;
-    polish_upload(in, up);
-    haplotigs_finish("hlmi_haplotigs", S.cs, S.rs, L, up.core, o, t_dev, out_fa, out_blocks, st);
-    st->ms_total = now_ms() - t_begin;
+    timed_call(st, true, [&] {
+        check_opts("hlmi_haplotigs", o);
+        PileupRows R;
+        rows_from_paf(contigs, reads, paf, plain_request("hlmi_haplotigs", o.min_len, o.min_iden, pairs_paf), R);
+        haplotigs_body("hlmi_haplotigs", R, o, out_fa, out_blocks, st);
+    });
     st->phase.ms_total = st->ms_total;
 }
 
 void haplotigs_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_haplotig_opts &o, const char *pairs_paf,
                          const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st) {
-    const double t_begin = now_ms();
-    *st = hlmi_haplotig_stats{};
-    stat_reset();
-    check_opts("hlmi_haplotigs_reads", o);
-    PolPairCall pc;
-    pc.path = pairs_paf;
-    RowSelection sel;
-    select_device_rows(contigs, reads, ao, o.min_len, o.min_iden,
-                       SelectNames{"hlmi_haplotigs_reads", "hlmi_haplotigs_reads", "hlmi_haplotigs_reads", true}, nullptr,
-                       pairs_paf ? &pc : nullptr, sel);
-    st->phase.rows = sel.n_rows;
-    st->phase.contigs = sel.cs.size();
-    st->phase.rows_selected = sel.n_sel;
-    set_pair_stats(pc, pairs_paf != nullptr, &st->phase);
-    DeviceRowsInput in;
-    device_rows_input(sel, "hlmi_haplotigs_reads", false, nullptr, in);
-    st->ins_edge = in.ins_edge;
-    st->ins_long = in.ins_long;
-    haplotigs_finish("hlmi_haplotigs_reads", sel.cs, sel.rs, in.L, in.core, o, sel.t_dev, out_fa, out_blocks, st);
-    st->ms_total = now_ms() - t_begin;
+    timed_call(st, true, [&] {
+        check_opts("hlmi_haplotigs_reads", o);
+        PileupRows R;
+        rows_from_reads(contigs, reads, ao, plain_request("hlmi_haplotigs_reads", o.min_len, o.min_iden, pairs_paf), R);
+        haplotigs_body("hlmi_haplotigs_reads", R, o, out_fa, out_blocks, st);
+    });
     st->phase.ms_total = st->ms_total;
 }
 

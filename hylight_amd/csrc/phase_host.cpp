@@ -1,11 +1,10 @@
 // phase_host.cpp - the host part of hlmi_phase and hlmi_phase_reads (include/hylight_mi.h): the variant sites of hlmi_variants
-// phased from the reads - links between neighbouring sites, blocks, and every read's side per block.  Selection, layout, rows,
-// compact CIGARs and reads are the polisher's (polish_select.h), the sites variants_core's, exactly as variants_host.cpp reaches
-// them; the allele table, the link counters and the records per (row, block) are phase.hip's, the rules' arithmetic and the
-// three files' text phase_text.h's.
+// phased from the reads - links between neighbouring sites, blocks, and every read's side per block.  The rows come from the
+// pile-up calls' row front (polish_select.h), the sites are variants_core's over them; the allele table, the link counters and the
+// records per (row, block) are phase.hip's, the rules' arithmetic and the three files' text phase_text.h's.  phase_device and
+// phase_emit are the two halves of the body that hlmi_haplotigs calls as well.
 // PARITY UNPINNED: a function of the project's own; tests/phase_model.py is the contract.
 #include <cmath>
-#include <functional>
 #include <string>
 #include <string_view>
 #include <vector>
@@ -38,32 +37,24 @@ void check_phase_opts(const char *who, const hlmi_phase_opts &o) {
     if (!(o.min_agree > 0.5 && o.min_agree <= 1.0)) fail(HLMI_EINVAL, "%s: min_agree %g (outside (0.5, 1] or not a number)", who, o.min_agree);
 }
 
-void set_pair_stats(const PolPairCall &pc, bool given, hlmi_phase_stats *st) {
-    if (!given) return;
-    st->pairs_listed = pc.pairs_listed;
-    st->pairs_unknown = pc.pairs_unknown;
-    st->rows_not_listed = pc.rows_not_listed;
-}
-
-void phase_device(const char *who, const SeqSet &cs, const PolLayout &L, const PolCoreIn &core, const hlmi_phase_opts &o, Phased &P,
-                  DevRecs *keep) {
-    variants_core(core, variant_part(o), P.var);
+void phase_device(const char *who, const PileupRows &R, const hlmi_phase_opts &o, Phased &P, DevRecs *keep) {
+    const SeqSet &cs = R.cs();
+    const PolLayout &L = R.L;
+    variants_core(R.up.core, variant_part(o), P.var);
     std::vector<std::string_view> seq(cs.size());
     for (size_t c = 0; c < cs.size(); ++c) seq[c] = std::string_view(cs.bases).substr(cs.off[c], cs.len(c));
     if (!phase_sites(seq, L.rc, L.slot_of_contig, L.cbase, P.var, P.sites))
         fail(HLMI_ESTATE, "%s: the sites' records do not fit the contigs", who);                                    // (never)
-    phase_core(who, core, P.sites, o, P.dev, keep);
+    phase_core(who, R.up.core, P.sites, o, P.dev, keep);
 }
 
-void phase_emit(const char *who, const SeqSet &cs, const SeqSet &rs, const PolLayout &L, const Phased &P, const hlmi_phase_opts &o,
-                const std::function<std::vector<uint32_t>()> &read_of_row, const char *out_sites, const char *out_links,
-                const char *out_reads, hlmi_phase_stats *st) {
-    std::vector<uint64_t> length(cs.size());
-    std::vector<std::string_view> seq(cs.size());
-    for (size_t c = 0; c < cs.size(); ++c) {
-        length[c] = cs.len(c);
-        seq[c] = std::string_view(cs.bases).substr(cs.off[c], cs.len(c));
-    }
+void phase_emit(const char *who, const PileupRows &R, const Phased &P, const hlmi_phase_opts &o, const std::vector<uint32_t> &rows_read,
+                const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st) {
+    const SeqSet &cs = R.cs();
+    const PolLayout &L = R.L;
+    std::vector<uint64_t> length;
+    std::vector<std::string_view> seq;
+    contig_views(cs, length, seq);
     VariantTotals tot;                          // the shared stats, by the code hlmi_variants counts them with
     contig_records(cs.names, length, L.rc, L.slot_of_contig, P.var, &tot);
     std::vector<std::string> unused;
@@ -90,9 +81,7 @@ void phase_emit(const char *who, const SeqSet &cs, const SeqSet &rs, const PolLa
     if (out_sites) sites = phase_site_lines(cs.names, P.sites, B);
     if (out_links) links = phase_link_lines(cs.names, P.sites, P.dev.links, o.min_link, o.min_agree);
     ReadTotals rt;
-    std::vector<uint32_t> rows_read;
-    if (out_reads && !P.dev.recs.empty()) rows_read = read_of_row();
-    if (!phase_read_lines(cs.names, rs.names, rows_read, P.sites, B, P.dev.recs, out_reads ? &reads : nullptr, &rt))
+    if (!phase_read_lines(cs.names, R.rs().names, rows_read, P.sites, B, P.dev.recs, out_reads ? &reads : nullptr, &rt))
         fail(HLMI_ESTATE, "%s: a row's record names no block or no read", who);                                     // (never)
     st->read_records = rt.records;
     st->reads_a = rt.a;
@@ -105,77 +94,40 @@ void phase_emit(const char *who, const SeqSet &cs, const SeqSet &rs, const PolLa
 
 }  // namespace ph
 
+namespace {
+
+// what both entry points do behind the rows: sites and phasing, the statistics and the three files
+void phase_body(const char *who, const PileupRows &R, const hlmi_phase_opts &o, const char *out_sites, const char *out_links,
+                const char *out_reads, hlmi_phase_stats *st) {
+    set_row_stats(R, st);
+    Phased P;
+    phase_device(who, R, o, P);
+    std::vector<uint32_t> rows_read;            // when a record needs its read's name (aligned rows: 4 bytes per row come down)
+    if (out_reads && !P.dev.recs.empty()) rows_read = R.read_of_row();
+    st->ms_device = now_ms() - R.t_dev;
+    phase_emit(who, R, P, o, rows_read, out_sites, out_links, out_reads, st);
+}
+
+}  // namespace
+
 void phase_run(const char *contigs, const char *reads, const char *paf, const hlmi_phase_opts &o, const char *pairs_paf,
                const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st) {
-    const double t_begin = now_ms();
-    *st = hlmi_phase_stats{};
-    stat_reset();
-    check_phase_opts("hlmi_phase", o);
-    PolQualCall qc;                             // no floor and no weights: the quality strings are only checked, as hlmi_variants does
-    PolPairCall pc;
-    pc.path = pairs_paf;
-    PafSelection S;
-    select_paf_rows(contigs, reads, paf, o.min_len, o.min_iden, SelectNames{"hlmi_phase", "hlmi_phase", "hlmi_phase", true}, &qc,
-                    pairs_paf ? &pc : nullptr, S);
-    st->rows = S.pt.recs.size();
-    st->contigs = S.cs.size();
-    st->rows_selected = S.sel.size();
-    set_pair_stats(pc, pairs_paf != nullptr, st);
-    std::vector<PolSpan> spans;
-    spans.reserve(S.sel.size());
-    for (const PafSel &s : S.sel) spans.push_back(PolSpan{s.contig, S.pt.recs[s.line].ts, S.pt.recs[s.line].te});
-    PolLayout L;
-    polish_layout(S.cs, spans, "hlmi_phase", L, nullptr);
-    PolDevIn in;
-    uint64_t ins_edge = 0, ins_long = 0;        // insertions take no part
-    paf_rows_input(S, L, false, in, ins_edge, ins_long);
-    in.contigs = std::move(L.contigs);
-    in.cbase = L.cbase;
-    in.tiles = std::move(L.tiles);
-
-    const double t_dev = now_ms();
-    Phased P;
-    {
-        PolUploaded up;
-        polish_upload(in, up);
-        phase_device("hlmi_phase", S.cs, L, up.core, o, P);
-    }
-    st->ms_device = now_ms() - t_dev;
-    phase_emit("hlmi_phase", S.cs, S.rs, L, P, o, [&]() {
-        std::vector<uint32_t> r(S.sel.size());
-        for (size_t i = 0; i < S.sel.size(); ++i) r[i] = S.sel[i].read;
-        return r;
-    }, out_sites, out_links, out_reads, st);
-    st->ms_total = now_ms() - t_begin;
+    timed_call(st, true, [&] {
+        check_phase_opts("hlmi_phase", o);
+        PileupRows R;
+        rows_from_paf(contigs, reads, paf, plain_request("hlmi_phase", o.min_len, o.min_iden, pairs_paf), R);
+        phase_body("hlmi_phase", R, o, out_sites, out_links, out_reads, st);
+    });
 }
 
 void phase_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_phase_opts &o, const char *pairs_paf,
                      const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st) {
-    const double t_begin = now_ms();
-    *st = hlmi_phase_stats{};
-    stat_reset();
-    check_phase_opts("hlmi_phase_reads", o);
-    PolPairCall pc;
-    pc.path = pairs_paf;
-    RowSelection sel;
-    select_device_rows(contigs, reads, ao, o.min_len, o.min_iden, SelectNames{"hlmi_phase_reads", "hlmi_phase_reads", "hlmi_phase_reads", true},
-                       nullptr, pairs_paf ? &pc : nullptr, sel);
-    st->rows = sel.n_rows;
-    st->contigs = sel.cs.size();
-    st->rows_selected = sel.n_sel;
-    set_pair_stats(pc, pairs_paf != nullptr, st);
-    DeviceRowsInput in;
-    device_rows_input(sel, "hlmi_phase_reads", false, nullptr, in);
-    Phased P;
-    phase_device("hlmi_phase_reads", sel.cs, in.L, in.core, o, P);
-    std::vector<uint32_t> rows_read;            // 4 bytes per selected row, when a record needs its read's name
-    if (out_reads && !P.dev.recs.empty()) {
-        rows_read = selected_query_ranks(sel.rows.recs.p, sel.idx.p, sel.n_sel);
-        for (uint32_t &q : rows_read) q = q < sel.qrec_of_rank.size() ? sel.qrec_of_rank[q] : 0xffffffffu;
-    }
-    st->ms_device = now_ms() - sel.t_dev;
-    phase_emit("hlmi_phase_reads", sel.cs, sel.rs, in.L, P, o, [&]() { return rows_read; }, out_sites, out_links, out_reads, st);
-    st->ms_total = now_ms() - t_begin;
+    timed_call(st, true, [&] {
+        check_phase_opts("hlmi_phase_reads", o);
+        PileupRows R;
+        rows_from_reads(contigs, reads, ao, plain_request("hlmi_phase_reads", o.min_len, o.min_iden, pairs_paf), R);
+        phase_body("hlmi_phase_reads", R, o, out_sites, out_links, out_reads, st);
+    });
 }
 
 }  // namespace hlmi

@@ -1,12 +1,12 @@
 // phase_internal.h - what phase_host.cpp (the two entry points, the files) and phase.hip (the kernels) share.  The rules are those
 // of include/hylight_mi.h (hlmi_phase, hlmi_phase_reads); tests/phase_model.py restates them.
 #pragma once
-#include <functional>
 #include <vector>
 
 #include "common.h"
 #include "phase_text.h"
 #include "polish_internal.h"
+#include "polish_select.h"
 #include "variants_internal.h"
 
 namespace hlmi {
@@ -37,23 +37,20 @@ void phase_core(const char *who, const pol::PolCoreIn &in, const std::vector<PSi
 // the query name rank of every selected row of the overlapper's rows (recs[idx[j]].qid): 4 bytes per row come down
 std::vector<uint32_t> selected_query_ranks(const PafRec *recs, const uint32_t *idx, size_t n_sel);
 
-// ---- what the entry points do around phase_core (phase_host.cpp); hlmi_haplotigs calls the same functions -------------------------
+// ---- what the entry points do around phase_core (phase_host.cpp); hlmi_haplotigs calls the same functions -----------------------
 // the option refusals, in the header's order: hlmi_variants's (check_variant_opts), min_link, min_agree
 void check_phase_opts(const char *who, const hlmi_phase_opts &o);
-void set_pair_stats(const pol::PolPairCall &pc, bool given, hlmi_phase_stats *st);
 struct Phased {
     var::DeviceVariants var;
     std::vector<PSite> sites;
     DevicePhase dev;
 };
-// the device part of the entry points over the same input: hlmi_variants's sites, then the phasing
-void phase_device(const char *who, const SeqSet &cs, const pol::PolLayout &L, const pol::PolCoreIn &core, const hlmi_phase_opts &o,
-                  Phased &P, DevRecs *keep = nullptr);
-// what the entry points do behind the device part: the statistics and the three files.  read_of_row: the read record of every
-// selected row, asked for only when out_reads has a line to write.  out_sites == nullptr (hlmi_haplotigs): the statistics alone
-void phase_emit(const char *who, const SeqSet &cs, const SeqSet &rs, const pol::PolLayout &L, const Phased &P, const hlmi_phase_opts &o,
-                const std::function<std::vector<uint32_t>()> &read_of_row, const char *out_sites, const char *out_links,
-                const char *out_reads, hlmi_phase_stats *st);
+// the device part over the rows of the front (R.up.core): hlmi_variants's sites, then the phasing
+void phase_device(const char *who, const pol::PileupRows &R, const hlmi_phase_opts &o, Phased &P, DevRecs *keep = nullptr);
+// what follows the device part: the statistics and the three files.  rows_read: R.read_of_row(), needed (and asked for) only when
+// out_reads has a line to write.  out_sites == nullptr (hlmi_haplotigs): the statistics alone
+void phase_emit(const char *who, const pol::PileupRows &R, const Phased &P, const hlmi_phase_opts &o, const std::vector<uint32_t> &rows_read,
+                const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st);
 
 }  // namespace ph
 

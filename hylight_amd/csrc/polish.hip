@@ -13,8 +13,8 @@
 // ninth LDS counter per position - the number of voting columns, which the coverage test and the slot's span still are - and the
 // five symbol counters hold weight sums; the slot passes add weights where they added 1.  QW = false is the kernels as they
 // were: no quality byte is read, eight counters.
-// polish_device uploads what polish_host.cpp built and runs polish_core; hlmi_polish_reads (polish_rows.hip) runs polish_core
-// over rows, CIGARs and reads that are in device memory already - its reads as the overlapper's codes (column_symbol).
+// polish_upload sends up what polish_host.cpp built from a PAF; hlmi_polish_reads (polish_rows.hip) runs polish_core over
+// rows, CIGARs and reads that are in device memory already - its reads as the overlapper's codes (column_symbol).
 // column_symbol, walk_row and the lane / wave switch of the vote loop are polish_walk.h's, shared with variants.hip.
 // polish_tail is everything behind the count pass - slot index, slot passes, lengths, scan, write - over any position space:
 // hlmi_haplotigs (haplotigs.hip) runs it over two sides side by side with slot votes of its own.
@@ -248,12 +248,6 @@ void polish_upload(const PolDevIn &in, PolUploaded &up) {
     c.tiles = up.tiles.p; c.n_tiles = in.tiles.size();
     c.cbase = up.cbase.p; c.n_cbase = in.cbase.size();
     c.min_cov = in.min_cov;
-}
-
-void polish_device(const PolDevIn &in, PolDevOut &out) {
-    PolUploaded up;
-    polish_upload(in, up);
-    polish_core(up.core, out);
 }
 
 void polish_core(const PolCoreIn &in, PolDevOut &out) {

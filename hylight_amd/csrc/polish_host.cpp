@@ -1,9 +1,9 @@
-// polish_host.cpp - the host part of hlmi_polish (include/hylight_mi.h): reading, the refusals, row selection, the rows and
-// tiles the device works on (sorted by contig and start), the statistics, the headers and the file.  The votes, the
-// decisions and the bases are polish.hip's.  The layout (contigs side by side, tiles) and the output (statistics, headers,
-// file) are functions of their own: hlmi_polish_reads (polish_rows.hip) selects its rows on the device and shares them.
-// The reading, the refusals and the row selection are pol::select_paf_rows (polish_select.h), which hlmi_depth (depth_host.cpp)
-// calls as well.
+// polish_host.cpp - two things (include/hylight_mi.h):
+//   pol::rows_from_paf (polish_select.h), the PAF half of every pile-up call's row front: reading, the refusals, the row selection
+//   (select_paf_rows), the layout (polish_layout: contigs side by side, tiles; rows_from_reads in polish_rows.hip calls it too),
+//   the rows the device works on (sorted by contig and start) and their upload;
+//   hlmi_polish and hlmi_polish_reads with their _q and _pairs forms: the option check, the request, one front each, and one
+//   body - polish_core (polish.hip: the votes, the decisions and the bases), the statistics, the headers and the file.
 // PARITY UNPINNED: racon is not part of the reference tree; tests/polish_model.py is the contract.
 #include <algorithm>
 #include <cstdio>
@@ -144,7 +144,9 @@ void select_paf_rows(const char *contigs, const char *reads, const char *paf, in
     });
 }
 
-void paf_rows_input(const PafSelection &S, const PolLayout &L, bool weighted, PolDevIn &in, uint64_t &ins_edge, uint64_t &ins_long) {
+// in.rows, in.ops, in.reads and, when weighted, in.quals from the selection, in its order; L is polish_layout's over the same
+// rows.  Adds the rows' ins_edge and ins_long to the two counters.
+static void paf_rows_input(const PafSelection &S, const PolLayout &L, bool weighted, PolDevIn &in, uint64_t &ins_edge, uint64_t &ins_long) {
     const PafText &pt = S.pt;
     const SeqSet &rs = S.rs;
     in.rows.reserve(S.sel.size());
@@ -172,44 +174,101 @@ void paf_rows_input(const PafSelection &S, const PolLayout &L, bool weighted, Po
     }
 }
 
-}  // namespace pol
-
-void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
-                hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
-    const double t_begin = now_ms();
-    *st = hlmi_polish_stats{};
-    if (o.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish: min_cov %d (< 1)", o.min_cov);
-    PafSelection S;
-    select_paf_rows(contigs, reads, paf, o.min_len, o.min_iden, SelectNames{}, qc, pc, S);
-    const SeqSet &cs = S.cs;
-    const PafText &pt = S.pt;
-    const std::vector<PafSel> &sel = S.sel;
-    const bool weighted = qc && qc->qual_weight;
-    st->rows = pt.recs.size();
-    st->contigs = cs.size();
-    st->rows_selected = sel.size();
-    polish_check_weight_width("hlmi_polish_q", qc, sel.size());
+void rows_from_paf(const char *contigs, const char *reads, const char *paf, const RowsRequest &q, PileupRows &R) {
+    PafSelection &S = R.paf;
+    PolQualCall checked;                        // check_quals: no floor and no weights, the quality strings are only checked
+    R.pc.path = q.pairs_paf;
+    select_paf_rows(contigs, reads, paf, q.min_len, q.min_iden, q.who, q.qc ? q.qc : q.check_quals ? &checked : nullptr,
+                    q.pairs_paf ? &R.pc : nullptr, S);
+    R.n_rows = S.pt.recs.size();
+    R.n_sel = S.sel.size();
+    polish_check_weight_width(q.who.quals, q.qc, R.n_sel);
 
     // the device's input: polished contigs side by side, the aligned stretch of every read, compact CIGARs, tiles
     std::vector<PolSpan> spans;
-    spans.reserve(sel.size());
-    for (const PafSel &s : sel) spans.push_back(PolSpan{s.contig, pt.recs[s.line].ts, pt.recs[s.line].te});
-    PolLayout L;
-    polish_layout(cs, spans, "hlmi_polish", L, st);
+    spans.reserve(S.sel.size());
+    for (const PafSel &s : S.sel) spans.push_back(PolSpan{s.contig, S.pt.recs[s.line].ts, S.pt.recs[s.line].te});
+    PolLayout &L = R.L;
+    polish_layout(S.cs, spans, q.who.seqs, L, !q.spans_only);
+    if (q.spans_only) {
+        R.t_dev = now_ms();
+        if (spans.empty()) return;
+        R.d_spans.upload(spans);
+        return R.upload_tiles();
+    }
     PolDevIn in;
-    in.min_cov = o.min_cov;
-    paf_rows_input(S, L, weighted, in, st->ins_edge, st->ins_long);
+    paf_rows_input(S, L, q.qc && q.qc->qual_weight, in, R.ins_edge, R.ins_long);
     in.contigs = std::move(L.contigs);
     in.cbase = L.cbase;
     in.tiles = std::move(L.tiles);
-
-    const double t_dev = now_ms();
-    PolDevOut out;
-    polish_device(in, out);
-    st->ms_device = now_ms() - t_dev;
+    R.t_dev = now_ms();
+    polish_upload(in, R.up);
     L.contigs = std::move(in.contigs);
-    polish_emit(cs, L, out, o, out_fa, st);
-    st->ms_total = now_ms() - t_begin;
+}
+
+}  // namespace pol
+
+namespace {
+
+// what both entry points do behind the rows: the votes, the decisions and the bases (polish.hip), the statistics, the headers
+// and the file
+void polish_body(PileupRows &R, const hlmi_polish_opts &o, const char *out_fa, hlmi_polish_stats *st) {
+    const SeqSet &cs = R.cs();
+    const PolLayout &L = R.L;
+    set_row_stats(R, st);
+    st->contigs_polished = L.cbase.size() - 1;
+    st->ins_edge = R.ins_edge;
+    st->ins_long = R.ins_long;
+    R.up.core.min_cov = o.min_cov;
+    PolDevOut out;
+    polish_core(R.up.core, out);
+    st->ms_device = now_ms() - R.t_dev;
+
+    std::vector<std::string> lines;
+    for (uint32_t c = 0; c < cs.size(); ++c) {
+        if (!L.rc[c]) {
+            if (o.include_unpolished && cs.len(c)) {
+                lines.push_back(">" + cs.names[c]);
+                lines.push_back(cs.bases.substr(cs.off[c], cs.len(c)));
+            }
+            continue;
+        }
+        const uint32_t j = L.slot_of_contig[c], b = L.cbase[j], len = cs.len(c);
+        const uint64_t covered = count_decisions(out, b, L.contigs.data() + b, len, st);
+        const uint64_t new_len = out.start[j + 1] - out.start[j];
+        if (!new_len) continue;
+        char head[96];
+        snprintf(head, sizeof head, " LN:i:%llu RC:i:%u XC:f:%.6f", (unsigned long long)new_len, L.rc[c], (double)covered / (double)len);
+        lines.push_back(">" + cs.names[c] + head);
+        lines.push_back(out.bases.substr(out.start[j], new_len));
+    }
+    write_lines(out_fa, lines);
+}
+
+}  // namespace
+
+void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
+                hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
+    timed_call(st, false, [&] {                 // false: hlmi_polish, _q and _pairs alone leave hlmi_last_stats_json's stats as they are
+        if (o.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish: min_cov %d (< 1)", o.min_cov);
+        PileupRows R;
+        rows_from_paf(contigs, reads, paf, RowsRequest{SelectNames{}, o.min_len, o.min_iden, qc, pc ? pc->path : nullptr}, R);
+        if (pc) *pc = R.pc;
+        polish_body(R, o, out_fa, st);
+    });
+}
+
+void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &o, const char *out_fa,
+                      hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
+    timed_call(st, true, [&] {
+        if (o.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish_reads: min_cov %d (< 1)", o.min_cov);
+        PileupRows R;
+        rows_from_reads(contigs, reads, ao,
+                        RowsRequest{SelectNames{"hlmi_polish_reads", "hlmi_polish_reads_q", "hlmi_polish_reads_pairs", true}, o.min_len,
+                                    o.min_iden, qc, pc ? pc->path : nullptr}, R);
+        if (pc) *pc = R.pc;
+        polish_body(R, o, out_fa, st);
+    });
 }
 
 namespace pol {
@@ -234,7 +293,7 @@ void polish_check_weight_width(const char *who, const PolQualCall *qc, uint64_t 
         fail(HLMI_EINVAL, "%s: %llu selected rows of weight 93 at the most do not fit the 32-bit sums", who, (unsigned long long)rows_selected);
 }
 
-void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, hlmi_polish_stats *st, bool with_bytes) {
+void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, bool with_bytes) {
     L = PolLayout{};
     L.rc.assign(cs.size(), 0);
     L.slot_of_contig.assign(cs.size(), 0);
@@ -250,7 +309,6 @@ void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char
             total += cs.len(c);
         }
     L.cbase.push_back((uint32_t)total);
-    if (st) st->contigs_polished = n_polished;
     for (size_t r0 = 0; r0 < sel.size();) {
         size_t r1 = r0;
         while (r1 < sel.size() && sel[r1].contig == sel[r0].contig) ++r1;
@@ -264,38 +322,6 @@ void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char
         }
         r0 = r1;
     }
-}
-
-void polish_emit(const SeqSet &cs, const PolLayout &L, const PolDevOut &out, const hlmi_polish_opts &o, const char *out_fa,
-                 hlmi_polish_stats *st) {
-    st->slots_opened = out.open_pos.size();
-    for (uint8_t l : out.open_len) st->inserted_bases += l;
-    std::vector<std::string> lines;
-    for (uint32_t c = 0; c < cs.size(); ++c) {
-        if (!L.rc[c]) {
-            if (o.include_unpolished && cs.len(c)) {
-                lines.push_back(">" + cs.names[c]);
-                lines.push_back(cs.bases.substr(cs.off[c], cs.len(c)));
-            }
-            continue;
-        }
-        const uint32_t j = L.slot_of_contig[c], b = L.cbase[j], len = cs.len(c);
-        uint64_t covered = 0;
-        for (uint32_t p = 0; p < len; ++p) {
-            const uint8_t d = out.sym[b + p];
-            if (d == SYM_KEEP) continue;
-            ++covered;
-            if (d == SYM_DEL) ++st->deleted;
-            else if ("ACGT"[d] != (char)((unsigned char)L.contigs[b + p] & 0xdfu)) ++st->substituted;
-        }
-        const uint64_t new_len = out.start[j + 1] - out.start[j];
-        if (!new_len) continue;
-        char head[96];
-        snprintf(head, sizeof head, " LN:i:%llu RC:i:%u XC:f:%.6f", (unsigned long long)new_len, L.rc[c], (double)covered / (double)len);
-        lines.push_back(">" + cs.names[c] + head);
-        lines.push_back(out.bases.substr(out.start[j], new_len));
-    }
-    write_lines(out_fa, lines);
 }
 
 }  // namespace pol

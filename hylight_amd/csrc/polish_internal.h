@@ -2,6 +2,7 @@
 // The rules are those of include/hylight_mi.h (hlmi_polish, hlmi_polish_q); tests/polish_model.py and
 // tests/polish_qual_model.py restate them.
 #pragma once
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <vector>
@@ -48,10 +49,9 @@ struct PolDevOut {
     std::vector<uint32_t> open_pos;     // opened slots, ascending, and the length each one got
     std::vector<uint8_t> open_len;
 };
-void polish_device(const PolDevIn &in, PolDevOut &out);        // uploads `in`, then polish_core
 
-// The device part over what is already in HBM: hlmi_polish reaches it through polish_device, hlmi_polish_reads (polish_rows.hip)
-// with the rows, compact CIGARs and reads where its own kernels and the overlapper left them.
+// The device part over what is already in HBM: hlmi_polish reaches it behind polish_upload (rows_from_paf), hlmi_polish_reads
+// (rows_from_reads) with the rows, compact CIGARs and reads where its own kernels and the overlapper left them.
 enum ReadEnc : int { READS_ASCII = 0, READS_CODES = 1 };       // PolRow::read_off counts bytes of ASCII, or of DevReads::codes()
 struct PolCoreIn {
     const PolRow *rows = nullptr;
@@ -87,7 +87,7 @@ using PolSlotVotes = std::function<void(int mode, const uint32_t *slot_of, const
 void polish_tail(const PolTailIn &in, const PolSlotVotes &votes, PolDevOut &out);
 constexpr uint32_t POLISH_NO_SLOT = 0xffffffffu;        // slot_of of a position whose slot stays shut
 
-// ---- what both entry points do on the host around the device part (polish_host.cpp) ----------------------------------------
+// ---- what the pile-up calls do on the host around the device part (polish_host.cpp) ----------------------------------------
 // a selected row as the layout sees it: contig record, [ts, te); in the order (contig, ts, line)
 struct PolSpan {
     uint32_t contig, ts, te;
@@ -99,13 +99,29 @@ struct PolLayout {
     std::string contigs;                    // PolDevIn::contigs
     std::vector<PolTile> tiles;
 };
-// who: the entry point's name for the refusal of 2^31 contig bases; sets contigs_polished (st may be nullptr).  with_bytes
+// who: the entry point's name for the refusal of 2^31 contig bases.  The polished contigs number L.cbase.size() - 1.  with_bytes
 // false: L.contigs stays empty (the depth call reads no contig byte)
-void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, hlmi_polish_stats *st,
-                   bool with_bytes = true);
-// slots_opened, inserted_bases, substituted, deleted, the headers and the file
-void polish_emit(const SeqSet &cs, const PolLayout &L, const PolDevOut &out, const hlmi_polish_opts &o, const char *out_fa,
-                 hlmi_polish_stats *st);
+void polish_layout(const SeqSet &cs, const std::vector<PolSpan> &sel, const char *who, PolLayout &L, bool with_bytes = true);
+
+// The decisions of one record: a polished contig of `len` positions whose bytes are `contig`, on the side whose decisions and
+// slots begin at g0 in out.sym / out.open_pos (hlmi_polish: the contig's cbase; hlmi_haplotigs: side * n_contig behind it).
+// Adds its deleted and substituted positions, opened slots and their bases to st; -> the positions with a decision (XC:f:).
+template <class Stats>
+uint64_t count_decisions(const PolDevOut &out, size_t g0, const char *contig, uint32_t len, Stats *st) {
+    uint64_t covered = 0;
+    for (uint32_t p = 0; p < len; ++p) {
+        const uint8_t d = out.sym[g0 + p];
+        if (d == SYM_KEEP) continue;
+        ++covered;
+        if (d == SYM_DEL) ++st->deleted;
+        else if ("ACGT"[d & 3] != (char)((unsigned char)contig[p] & 0xdfu)) ++st->substituted;
+    }
+    const auto s0 = std::lower_bound(out.open_pos.begin(), out.open_pos.end(), (uint32_t)g0);
+    const auto s1 = std::lower_bound(s0, out.open_pos.end(), (uint32_t)(g0 + len));
+    st->slots_opened += (uint64_t)(s1 - s0);
+    for (auto it = s0; it != s1; ++it) st->inserted_bases += out.open_len[it - out.open_pos.begin()];
+    return covered;
+}
 
 // The quality part of a _q call (nullptr: hlmi_polish / hlmi_polish_reads as they were).  In: the two options; out: the two
 // counters of hlmi_polish_qstats.
@@ -139,9 +155,10 @@ void pair_keys_device(const char *who, const std::vector<std::string> &name_of_r
 
 }  // namespace pol
 
+// qc, pc: the _q and _pairs parts (capi.cpp), nullptr without; pc's counters are set when the rows are there
 void polish_run(const char *contigs, const char *reads, const char *paf, const hlmi_polish_opts &o, const char *out_fa,
                 hlmi_polish_stats *st, pol::PolQualCall *qc = nullptr, pol::PolPairCall *pc = nullptr);
-// hlmi_polish_reads (polish_rows.hip): the overlapper's rows selected, ordered and compacted where they are
+// hlmi_polish_reads: the overlapper's rows selected, ordered and compacted where they are (polish_rows.hip)
 void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
                       const char *out_fa, hlmi_polish_stats *st, pol::PolQualCall *qc = nullptr, pol::PolPairCall *pc = nullptr);
 

@@ -9,14 +9,16 @@
 //                      ins_long, and the (contig, ts, te) the host lays the tiles out from - all that comes back of the rows
 //   pr_write_kernel    the same walk once more behind a scan: the compact ops and the PolRow table
 // The reads are voted from the overlapper's resident codes (PolRow::read_off points into DevReads::codes()); the votes, the
-// decisions and the bases are polish.hip's (polish_core), headers and file polish_host.cpp's (polish_layout, polish_emit).
+// decisions and the bases are polish.hip's (polish_core), layout, headers and file polish_host.cpp's (polish_layout, polish_body).
 // hlmi_polish_reads_q: the resident reads hold codes only, so the quality bytes go up as one array at the offsets of
 // DevReads::codes() (PolRow::read_off indexes both), and the read floor is one byte per name rank that pr_facts_kernel looks up.
 // hlmi_polish_reads_pairs: the list becomes a sorted array of keys qid << 32 | tid on the device (polish_pairs.hip), and
 // pr_facts_kernel looks a row's key up with the whole wave (wave_search.h) directly behind the floor.
 //
-// The first three kernels with the flag-select and the sort are pol::select_device_rows (polish_select.h): hlmi_depth_reads
-// (depth_host.cpp) selects its rows with the same call.
+// All of it is pol::rows_from_reads (polish_select.h), the aligned half of the row front of every pile-up call: the first three
+// kernels with the flag-select and the sort are select_device_rows, the last two with the layout's uploads device_rows_input.
+// hlmi_depth_reads asks for spans only: depth.hip's depth_spans_from_rows then stands in for the two CIGAR kernels.  No entry
+// point lives here: every _reads call is in its family's host file.
 //
 // Why a wave per row in the first kernel and a thread per row in the last two: the first reads the ops of EVERY row (all of
 // the CIGAR traffic of this file), needs two sums and nothing else of them, so 64 consecutive words per load and a DPP sum fit;
@@ -27,8 +29,10 @@
 
 #include "ava.h"
 #include "common.h"
+#include "depth_internal.h"
 #include "dev_prims.h"
 #include "paf_io.h"
+#include "phase_internal.h"
 #include "polish_internal.h"
 #include "polish_rows.h"
 #include "polish_select.h"
@@ -235,14 +239,18 @@ void select_device_rows(const char *contigs, const char *reads, const hlmi_ava_o
     }
 }
 
-void device_rows_input(const RowSelection &sel, const char *who, bool weighted, hlmi_polish_stats *st, DeviceRowsInput &out) {
+// The selected rows as PolRow, compact CIGARs and the layout, where the rows are.  R.dev is selected; weighted: the quality
+// bytes go up beside the overlapper's codes.
+static void device_rows_input(PileupRows &R, const char *who, bool weighted) {
+    const RowSelection &sel = R.dev;
     const SeqSet &cs = sel.cs, &rs = sel.rs;
     const SeqQual &rq = sel.rq;
     const AvaPairCall &call = sel.call;
     const AvaRows &rows = sel.rows;
     const DBuf<uint32_t> &idx = sel.idx, &d_crec_of_rank = sel.d_crec_of_rank, &d_qrec_of_rank = sel.d_qrec_of_rank;
     const size_t S = sel.n_sel;
-    PolLayout &L = out.L;
+    PolLayout &L = R.L;
+    PolUploaded &out = R.up;
 
     // ---- the compact CIGARs' sizes and the spans --------------------------------------------------------------------------------
     std::vector<PolSpan> spans;
@@ -260,13 +268,13 @@ void device_rows_input(const RowSelection &sel, const char *who, bool weighted, 
         exclusive_scan_u32_to_u64(cig_n.p, cig_off.p, S);
         n_ops = download_one(cig_off.p + (S - 1)) + download_one(cig_n.p + (S - 1));
         const std::vector<unsigned long long> t = totals.download(2);
-        out.ins_edge = t[0];
-        out.ins_long = t[1];
+        R.ins_edge = t[0];
+        R.ins_long = t[1];
         spans = d_span.download(S);
         for (const PolSpan &s : spans)
             if (s.contig >= cs.size()) fail(HLMI_EINVAL, "%s: a row names a target that is no contig", who);    // (never)
     }
-    polish_layout(cs, spans, who, L, st);
+    polish_layout(cs, spans, who, L);
 
     // ---- CIGARs and rows ----------------------------------------------------------------------------------------------------------
     DBuf<PolRow> &d_rows = out.rows;
@@ -303,38 +311,45 @@ void device_rows_input(const RowSelection &sel, const char *who, bool weighted, 
     c.cbase = out.cbase.p; c.n_cbase = L.cbase.size();
 }
 
-}  // namespace pol
+void rows_from_reads(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const RowsRequest &q, PileupRows &R) {
+    RowSelection &sel = R.dev;
+    R.aligned = true;
+    R.pc.path = q.pairs_paf;
+    select_device_rows(contigs, reads, ao, q.min_len, q.min_iden, q.who, q.qc, q.pairs_paf ? &R.pc : nullptr, sel);
+    const size_t S = R.n_sel = sel.n_sel;
+    R.n_rows = sel.n_rows;
+    R.t_dev = sel.t_dev;
+    polish_check_weight_width(q.who.quals, q.qc, S);
+    if (!q.spans_only) return device_rows_input(R, q.who.seqs, q.qc && q.qc->qual_weight);
 
-void polish_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_polish_opts &po,
-                      const char *out_fa, hlmi_polish_stats *st, PolQualCall *qc, PolPairCall *pc) {
-    const double t_begin = now_ms();
-    *st = hlmi_polish_stats{};
-    stat_reset();
-    if (po.min_cov < 1) fail(HLMI_EINVAL, "hlmi_polish_reads: min_cov %d (< 1)", po.min_cov);
-    RowSelection sel;
-    select_device_rows(contigs, reads, ao, po.min_len, po.min_iden,
-                       SelectNames{"hlmi_polish_reads", "hlmi_polish_reads_q", "hlmi_polish_reads_pairs", true}, qc, pc, sel);
-    const SeqSet &cs = sel.cs;
-    const bool weighted = qc && qc->qual_weight;
-    const double t_dev = sel.t_dev;
-    const size_t S = sel.n_sel;
-    st->rows = sel.n_rows;
-    st->contigs = cs.size();
-    st->rows_selected = S;
-    polish_check_weight_width("hlmi_polish_reads_q", qc, S);
-
-    DeviceRowsInput in;
-    device_rows_input(sel, "hlmi_polish_reads", weighted, st, in);
-    st->ins_edge = in.ins_edge;
-    st->ins_long = in.ins_long;
-    const PolLayout &L = in.L;
-    PolCoreIn &c = in.core;
-    c.min_cov = po.min_cov;
-    PolDevOut out;
-    polish_core(c, out);
-    st->ms_device = now_ms() - t_dev;
-    polish_emit(cs, L, out, po, out_fa, st);
-    st->ms_total = now_ms() - t_begin;
+    // the spans: all that is read of the selected rows, and all that comes back of them for the layout
+    R.d_spans.alloc(std::max<size_t>(S, 1));
+    depth::depth_spans_from_rows(sel.rows.recs.p, sel.idx.p, S, sel.d_crec_of_rank.p, R.d_spans.p);
+    const std::vector<PolSpan> spans = R.d_spans.download(S);
+    for (const PolSpan &s : spans)
+        if (s.contig >= sel.cs.size()) fail(HLMI_EINVAL, "%s: a row names a target that is no contig", q.who.seqs);      // (never)
+    polish_layout(sel.cs, spans, q.who.seqs, R.L, false);
+    if (S) R.upload_tiles();
 }
+
+void PileupRows::upload_tiles() {
+    up.tiles.upload(L.tiles);
+    up.cbase.upload(L.cbase);
+    up.core.tiles = up.tiles.p; up.core.n_tiles = L.tiles.size();
+    up.core.cbase = up.cbase.p; up.core.n_cbase = L.cbase.size();
+}
+
+std::vector<uint32_t> PileupRows::read_of_row() const {
+    std::vector<uint32_t> r(n_sel);
+    if (aligned) {
+        r = ph::selected_query_ranks(dev.rows.recs.p, dev.idx.p, n_sel);
+        for (uint32_t &q : r) q = q < dev.qrec_of_rank.size() ? dev.qrec_of_rank[q] : 0xffffffffu;
+    } else {
+        for (size_t i = 0; i < n_sel; ++i) r[i] = paf.sel[i].read;
+    }
+    return r;
+}
+
+}  // namespace pol
 
 }  // namespace hlmi

@@ -1,11 +1,13 @@
-// polish_select.h - the row selection of include/hylight_mi.h (hlmi_polish_pairs: qname == tname, the read floor, the pair
-// list, te == ts / min_len, min_iden, one row per read) as two functions, one per kind of entry point, so that every caller
-// runs one implementation: the polisher (polish_host.cpp: polish_run, polish_rows.hip: polish_reads_run) and the depth call
-// (depth_host.cpp) and the variant call (variants_host.cpp).  What a caller does with the selected rows is its own: spans
-// alone (depth), or PolRow + compact CIGARs + reads, built by the second pair of functions below for the polisher and the
-// variant call alike.
+// polish_select.h - the row front of every pile-up call (hlmi_polish*, hlmi_depth, hlmi_variants, hlmi_phase, hlmi_haplotigs and
+// their _reads forms): the row selection of include/hylight_mi.h (hlmi_polish_pairs: qname == tname, the read floor, the pair
+// list, te == ts / min_len, min_iden, one row per read), the layout of the covered contigs and the selected rows as the device
+// part's input.  An entry point fills a RowsRequest and calls one of two functions - rows_from_paf (polish_host.cpp) over a PAF
+// file, rows_from_reads (polish_rows.hip) over the rows the overlapper leaves in HBM - and hands the PileupRows to its family's
+// body, which does not know which of the two filled it.  The selection itself stays one function per kind of rows
+// (select_paf_rows, select_device_rows), each called by its front alone.
 #pragma once
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "ava.h"
@@ -18,13 +20,13 @@ namespace pol {
 
 // who names the entry point in the refusals; the older calls keep the names their messages always had
 struct SelectNames {
-    const char *seqs = "hlmi_polish";           // a sequence of 2^28 bases, a name twice
-    const char *quals = "hlmi_polish_q";        // polish_read_quals
+    const char *seqs = "hlmi_polish";           // a sequence of 2^28 bases, a name twice, 2^31 contig bases (polish_layout)
+    const char *quals = "hlmi_polish_q";        // polish_read_quals, polish_check_weight_width
     const char *list = "hlmi_polish_pairs";     // the pair list
     bool unique_names = false;                  // two records of one name in `contigs` or in `reads` are HLMI_EINVAL
 };
 
-// ---- over a PAF file (hlmi_polish*, hlmi_depth) -------------------------------------------------------------------------------
+// ---- over a PAF file ------------------------------------------------------------------------------------------------------------
 struct PafSel {
     size_t line;            // 0-based PAF line
     uint32_t contig, read;  // records
@@ -40,7 +42,7 @@ struct PafSelection {
 void select_paf_rows(const char *contigs, const char *reads, const char *paf, int min_len, double min_iden, const SelectNames &who,
                      PolQualCall *qc, PolPairCall *pc, PafSelection &out);
 
-// ---- over the overlapper's rows in HBM (hlmi_polish_reads*, hlmi_depth_reads) ------------------------------------------------
+// ---- over the overlapper's rows in HBM ------------------------------------------------------------------------------------------
 struct RowSelection {
     SeqSet cs, rs;
     SeqQual rq;             // with qc
@@ -57,14 +59,24 @@ struct RowSelection {
 void select_device_rows(const char *contigs, const char *reads, const hlmi_ava_opts &ao, int min_len, double min_iden,
                         const SelectNames &who, PolQualCall *qc, PolPairCall *pc, RowSelection &out);
 
-// ---- the selected rows as the device part's input (hlmi_polish*, hlmi_variants*) ----------------------------------------------
-// PolRow, compact CIGARs (polish_rows.h), the aligned read stretches, tiles: what polish_core and variants_core read.  One
-// implementation per kind of entry point, as for the selection.
-//
-// Over a PAF (polish_host.cpp): in.rows, in.ops, in.reads and, when weighted, in.quals from the selection, in its order; L is
-// polish_layout's over the same rows.  Adds the rows' ins_edge and ins_long to the two counters.
-void paf_rows_input(const PafSelection &S, const PolLayout &L, bool weighted, PolDevIn &in, uint64_t &ins_edge, uint64_t &ins_long);
-// PolDevIn in device memory (polish.hip); core.min_cov is in.min_cov
+// ---- the selected rows, ready for a device part ---------------------------------------------------------------------------------
+// what an entry point asks of the front
+struct RowsRequest {
+    SelectNames who;
+    int min_len = 0;
+    double min_iden = 0.0;
+    PolQualCall *qc = nullptr;          // the _q part: floor, counters, and with qual_weight the quality bytes travel with the reads
+    const char *pairs_paf = nullptr;    // nullptr: no list
+    bool spans_only = false;            // hlmi_depth: no contig bytes, no PolRow, no CIGAR, no reads - spans, tiles and cbase only
+    bool check_quals = false;           // rows_from_paf with no qc: read the quality strings all the same and refuse bad ones (no
+                                        // floor, no weights).  rows_from_reads reads none without qc, whatever this says
+};
+// the request of the calls that have one name in every refusal, no _q part and checked quality strings: all but hlmi_polish*
+inline RowsRequest plain_request(const char *who, int min_len, double min_iden, const char *pairs_paf, bool spans_only = false) {
+    return RowsRequest{SelectNames{who, who, who, true}, min_len, min_iden, nullptr, pairs_paf, spans_only, true};
+}
+
+// device memory behind a PolCoreIn (polish.hip fills it from a PolDevIn, polish_rows.hip where the overlapper's rows are)
 struct PolUploaded {
     DBuf<uint8_t> contig, reads, quals;
     DBuf<PolRow> rows;
@@ -72,21 +84,58 @@ struct PolUploaded {
     DBuf<PolTile> tiles;
     PolCoreIn core;
 };
-void polish_upload(const PolDevIn &in, PolUploaded &up);
+void polish_upload(const PolDevIn &in, PolUploaded &up);        // core.min_cov is in.min_cov
 
-// Over the overlapper's rows (polish_rows.hip): pr_count_kernel, the scan, polish_layout (who: the entry point's name in its
-// refusal; st: contigs_polished, may be nullptr), pr_unvote_kernel, pr_write_kernel and the uploads of the layout.  The reads
-// stay the overlapper's codes (sel.call.dQ, which core points into); core.min_cov is left to the caller.
-struct DeviceRowsInput {
-    PolLayout L;
-    DBuf<PolRow> rows;
-    DBuf<uint32_t> ops, cbase;
-    DBuf<PolTile> tiles;
-    DBuf<uint8_t> contig, quals;
-    PolCoreIn core;
+struct PileupRows {
+    bool aligned = false;               // filled by rows_from_reads
+    PafSelection paf;                   // whichever of the two backs it
+    RowSelection dev;
+    const SeqSet &cs() const { return aligned ? dev.cs : paf.cs; }
+    const SeqSet &rs() const { return aligned ? dev.rs : paf.rs; }
+    PolLayout L;                        // L.contigs: the polished contigs' bytes (empty with spans_only)
+    PolUploaded up;                     // up.core: min_cov is left to the body; with spans_only tiles and cbase alone are set
+    DBuf<PolSpan> d_spans;              // with spans_only: the selected rows in their order
+    size_t n_rows = 0, n_sel = 0;
+    PolPairCall pc;                     // the list's counters; path == nullptr: no list was given
     uint64_t ins_edge = 0, ins_long = 0;
+    double t_dev = 0;                   // where ms_device starts: before the uploads (PAF), where the overlapper starts (aligned)
+    // The read record of every selected row (0xffffffff: none).  Over the overlapper's rows 4 bytes per row come down for it, so a
+    // body asks only when it has a line to write.
+    std::vector<uint32_t> read_of_row() const;
+    void upload_tiles();                // with spans_only, of both fronts: L.tiles and L.cbase go up, up.core points at them
 };
-void device_rows_input(const RowSelection &sel, const char *who, bool weighted, hlmi_polish_stats *st, DeviceRowsInput &out);
+// Selection, polish_check_weight_width, polish_layout (its refusal names who.seqs), then the device part's input: PolRow, compact
+// CIGARs (polish_rows.h), the aligned read stretches as ASCII, contig bytes, tiles and cbase, uploaded.
+void rows_from_paf(const char *contigs, const char *reads, const char *paf, const RowsRequest &q, PileupRows &R);
+// The same over the overlapper's rows: pr_count_kernel, the scan, polish_layout, pr_unvote_kernel, pr_write_kernel and the uploads
+// of the layout; the reads stay the overlapper's codes (dev.call.dQ, which core points into).  With spans_only
+// depth_spans_from_rows takes the place of the CIGAR kernels.
+void rows_from_reads(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const RowsRequest &q, PileupRows &R);
+
+// rows, contigs, rows_selected and, when a list was given, its three counters (hlmi_polish_stats has none: those of the _pairs
+// calls reach hlmi_polish_pstats through capi.cpp)
+template <class Stats>
+void set_row_stats(const PileupRows &R, Stats *st) {
+    st->rows = R.n_rows;
+    st->contigs = R.cs().size();
+    st->rows_selected = R.n_sel;
+    if constexpr (!std::is_same_v<Stats, hlmi_polish_stats>) {
+        if (!R.pc.path) return;
+        st->pairs_listed = R.pc.pairs_listed;
+        st->pairs_unknown = R.pc.pairs_unknown;
+        st->rows_not_listed = R.pc.rows_not_listed;
+    }
+}
+
+// The frame of an entry point: zeroed statistics, the stats of hlmi_last_stats_json reset, ms_total around everything.
+template <class Stats, class Call>
+void timed_call(Stats *st, bool reset_stats, Call &&call) {
+    const double t_begin = now_ms();
+    *st = Stats{};
+    if (reset_stats) stat_reset();
+    call();
+    st->ms_total = now_ms() - t_begin;
+}
 
 }  // namespace pol
 }  // namespace hlmi

@@ -1,7 +1,7 @@
 // variants_host.cpp - the host part of hlmi_variants and hlmi_variants_reads (include/hylight_mi.h): variant sites and a summary
-// per contig from the selected rows' votes.  The selection is the polisher's own (polish_select.h), and so are the layout of the
-// covered contigs and their tiles (polish_layout) and the rows, compact CIGARs and reads the device works on (paf_rows_input /
-// device_rows_input); the votes, the site rule and the records are variants.hip's, the text variants_text.h's.
+// per contig from the selected rows' votes.  The rows come from the pile-up calls' row front (polish_select.h: rows_from_paf or
+// rows_from_reads), selected, laid out and in device memory; the votes, the site rule and the records are variants.hip's, the
+// text variants_text.h's.
 // PARITY UNPINNED: a function of the project's own; tests/variants_model.py is the contract.
 #include <string>
 #include <string_view>
@@ -25,17 +25,30 @@ void var::check_variant_opts(const char *who, const hlmi_variant_opts &o) {
     if (!(o.min_frac >= 0.0 && o.min_frac <= 1.0)) fail(HLMI_EINVAL, "%s: min_frac %g (outside [0, 1] or not a number)", who, o.min_frac);
 }
 
-namespace {
-
-// what both entry points do behind the device part: the records, the statistics and the two files
-void variants_emit(const char *who, const SeqSet &cs, const PolLayout &L, const DeviceVariants &dev, const char *out_sites,
-                   const char *out_summary, hlmi_variant_stats *st) {
-    std::vector<uint64_t> length(cs.size());
-    std::vector<std::string_view> seq(cs.size());
+void var::contig_views(const SeqSet &cs, std::vector<uint64_t> &length, std::vector<std::string_view> &seq) {
+    length.resize(cs.size());
+    seq.resize(cs.size());
     for (size_t c = 0; c < cs.size(); ++c) {
         length[c] = cs.len(c);
         seq[c] = std::string_view(cs.bases).substr(cs.off[c], cs.len(c));
     }
+}
+
+namespace {
+
+// what both entry points do behind the rows: the votes and the site rule, the records, the statistics and the two files
+void variants_body(const char *who, const PileupRows &R, const hlmi_variant_opts &o, const char *out_sites, const char *out_summary,
+                   hlmi_variant_stats *st) {
+    const SeqSet &cs = R.cs();
+    const PolLayout &L = R.L;
+    set_row_stats(R, st);
+    DeviceVariants dev;
+    variants_core(R.up.core, o, dev);
+    st->ms_device = now_ms() - R.t_dev;
+
+    std::vector<uint64_t> length;
+    std::vector<std::string_view> seq;
+    contig_views(cs, length, seq);
     VariantTotals tot;
     const std::vector<ContigVariants> recs = contig_records(cs.names, length, L.rc, L.slot_of_contig, dev, &tot);
     std::vector<std::string> sites;
@@ -56,78 +69,26 @@ void variants_emit(const char *who, const SeqSet &cs, const PolLayout &L, const 
     if (out_summary) write_lines(out_summary, summary);
 }
 
-void set_pair_stats(const PolPairCall &pc, bool given, hlmi_variant_stats *st) {
-    if (!given) return;
-    st->pairs_listed = pc.pairs_listed;
-    st->pairs_unknown = pc.pairs_unknown;
-    st->rows_not_listed = pc.rows_not_listed;
-}
-
 }  // namespace
 
 void variants_run(const char *contigs, const char *reads, const char *paf, const hlmi_variant_opts &o, const char *pairs_paf,
                   const char *out_sites, const char *out_summary, hlmi_variant_stats *st) {
-    const double t_begin = now_ms();
-    *st = hlmi_variant_stats{};
-    stat_reset();
-    check_variant_opts("hlmi_variants", o);
-    PolQualCall qc;                             // no floor and no weights: the quality strings are only checked, as hlmi_depth does
-    PolPairCall pc;
-    pc.path = pairs_paf;
-    PafSelection S;
-    select_paf_rows(contigs, reads, paf, o.min_len, o.min_iden, SelectNames{"hlmi_variants", "hlmi_variants", "hlmi_variants", true}, &qc,
-                    pairs_paf ? &pc : nullptr, S);
-    st->rows = S.pt.recs.size();
-    st->contigs = S.cs.size();
-    st->rows_selected = S.sel.size();
-    set_pair_stats(pc, pairs_paf != nullptr, st);
-    std::vector<PolSpan> spans;
-    spans.reserve(S.sel.size());
-    for (const PafSel &s : S.sel) spans.push_back(PolSpan{s.contig, S.pt.recs[s.line].ts, S.pt.recs[s.line].te});
-    PolLayout L;
-    polish_layout(S.cs, spans, "hlmi_variants", L, nullptr);
-    PolDevIn in;
-    uint64_t ins_edge = 0, ins_long = 0;        // insertions take no part
-    paf_rows_input(S, L, false, in, ins_edge, ins_long);
-    in.contigs = std::move(L.contigs);
-    in.cbase = L.cbase;
-    in.tiles = std::move(L.tiles);
-
-    const double t_dev = now_ms();
-    DeviceVariants dev;
-    {
-        PolUploaded up;
-        polish_upload(in, up);
-        variants_core(up.core, o, dev);
-    }
-    st->ms_device = now_ms() - t_dev;
-    variants_emit("hlmi_variants", S.cs, L, dev, out_sites, out_summary, st);
-    st->ms_total = now_ms() - t_begin;
+    timed_call(st, true, [&] {
+        check_variant_opts("hlmi_variants", o);
+        PileupRows R;
+        rows_from_paf(contigs, reads, paf, plain_request("hlmi_variants", o.min_len, o.min_iden, pairs_paf), R);
+        variants_body("hlmi_variants", R, o, out_sites, out_summary, st);
+    });
 }
 
 void variants_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_variant_opts &o,
                         const char *pairs_paf, const char *out_sites, const char *out_summary, hlmi_variant_stats *st) {
-    const double t_begin = now_ms();
-    *st = hlmi_variant_stats{};
-    stat_reset();
-    check_variant_opts("hlmi_variants_reads", o);
-    PolPairCall pc;
-    pc.path = pairs_paf;
-    RowSelection sel;
-    select_device_rows(contigs, reads, ao, o.min_len, o.min_iden,
-                       SelectNames{"hlmi_variants_reads", "hlmi_variants_reads", "hlmi_variants_reads", true}, nullptr,
-                       pairs_paf ? &pc : nullptr, sel);
-    st->rows = sel.n_rows;
-    st->contigs = sel.cs.size();
-    st->rows_selected = sel.n_sel;
-    set_pair_stats(pc, pairs_paf != nullptr, st);
-    DeviceRowsInput in;
-    device_rows_input(sel, "hlmi_variants_reads", false, nullptr, in);
-    DeviceVariants dev;
-    variants_core(in.core, o, dev);
-    st->ms_device = now_ms() - sel.t_dev;
-    variants_emit("hlmi_variants_reads", sel.cs, in.L, dev, out_sites, out_summary, st);
-    st->ms_total = now_ms() - t_begin;
+    timed_call(st, true, [&] {
+        check_variant_opts("hlmi_variants_reads", o);
+        PileupRows R;
+        rows_from_reads(contigs, reads, ao, plain_request("hlmi_variants_reads", o.min_len, o.min_iden, pairs_paf), R);
+        variants_body("hlmi_variants_reads", R, o, out_sites, out_summary, st);
+    });
 }
 
 }  // namespace hlmi

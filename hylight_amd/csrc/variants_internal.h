@@ -1,6 +1,9 @@
 // variants_internal.h - what variants_host.cpp (the two entry points, the files) and variants.hip (the kernels) share.  The rules
 // are those of include/hylight_mi.h (hlmi_variants, hlmi_variants_reads); tests/variants_model.py restates them.
 #pragma once
+#include <string_view>
+#include <vector>
+
 #include "common.h"
 #include "polish_internal.h"
 #include "variants_text.h"
@@ -13,6 +16,8 @@ namespace var {
 void variants_core(const pol::PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &out);
 // the option refusals of both entry points, in the header's order (hlmi_phase makes them first, under its own name)
 void check_variant_opts(const char *who, const hlmi_variant_opts &o);
+// every contig record's length and bytes, as variants_text.h's and phase_text.h's functions take them
+void contig_views(const SeqSet &cs, std::vector<uint64_t> &length, std::vector<std::string_view> &seq);
 
 }  // namespace var
 
