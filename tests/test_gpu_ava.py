@@ -160,6 +160,8 @@ def test_ava_noisy_reads(tmp_path, seed, errs):
     dict(gap_open=4, gap_ext=3, gap_open2=21, gap_ext2=2),              # second piece cheaper from 18 bases on
     dict(k=15, w=8, bandwidth=300, max_gap=2000, min_chain_score=40),     # other seeds, byte-table gap costs
     dict(bandwidth=3000),                                 # gap-cost table too small: costs computed in the chain DP
+    dict(k=27, w=64),                                     # the largest seeds the sketch admits (the oracle alone: 407 rows)
+    dict(k=11, w=1, hpc=0),                               # every k-mer a minimizer, no compression (the oracle alone: 593 rows)
 ])
 def test_ava_other_constants(tmp_path, changes):
     """Constants other than the two presets go through the same kernels (or their fallback forms)."""
