@@ -178,6 +178,13 @@ class VariantStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in VARIANT_STATS] + [(k, C.c_double) for k in POLISH_MS]
 
 
+VARIANT_INS_STATS = VARIANT_STATS + ("slots_callable", "ins_sites", "ins_long", "ins_edge")
+
+
+class VariantInsStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in VARIANT_INS_STATS] + [(k, C.c_double) for k in POLISH_MS]
+
+
 class PhaseOpts(C.Structure):
     _fields_ = list(VariantOpts._fields_) + [("min_link", C.c_int), ("min_agree", C.c_double)]
 
@@ -305,6 +312,11 @@ SYMBOLS = {
                                 C.POINTER(VariantStats)]),
     "hlmi_variants_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(VariantOpts), C.c_char_p, C.c_char_p,
                                       C.c_char_p, C.POINTER(VariantStats)]),
+    # ... with insertion sites
+    "hlmi_variants_ins": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VariantOpts), C.c_char_p, C.c_char_p, C.c_char_p,
+                                    C.c_char_p, C.POINTER(VariantInsStats)]),
+    "hlmi_variants_reads_ins": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(VariantOpts), C.c_char_p, C.c_char_p,
+                                          C.c_char_p, C.c_char_p, C.POINTER(VariantInsStats)]),
     # phased variant sites
     "hlmi_phase_opts_default": (None, [C.POINTER(PhaseOpts)]),
     "hlmi_phase": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PhaseOpts), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
@@ -874,6 +886,31 @@ def variants_reads(contigs, reads, out_sites, out_summary=None, ava_opts=None, p
     _check(load().hlmi_variants_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), _b(pairs),
                                       _b(out_sites), _b(out_summary), C.byref(st)))
     return {k: getattr(st, k) for k in VARIANT_STATS + POLISH_MS}
+
+
+def variants_ins(contigs, reads, paf, out_sites, out_ins, out_summary=None, pairs=None, **opts):
+    """hlmi_variants_ins: api.variants with the insertion sites beside it.  out_sites is the file api.variants writes.  A slot (the
+    gap in front of a contig position, as api.polish defines it) that min_cov selected rows span is an insertion site when the rows
+    that insert there - 1..16 bases, or more (long rows) - number min_alt and make min_frac of the spanning rows, whether or not
+    api.polish would open it.  Writes out_ins (contig, pos, ref, span, ins, ins_long, ins_frac, len, len_count, seq: the most
+    frequent length among the inserting rows and the most frequent base per index among the rows of that length, '*' when only
+    long rows insert) and, when given, out_summary with three columns more (slots, ins_sites, ins_rate).  Options: api.variants's.
+    A function of this project's own: include/hylight_mi.h states it, tests/variants_ins_model.py is its contract.
+    -> dict of the stats (hlmi_variant_ins_stats)."""
+    o, st = _variant_opts("variants_ins", opts), VariantInsStats()
+    _check(load().hlmi_variants_ins(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(pairs), _b(out_sites), _b(out_summary), _b(out_ins),
+                                    C.byref(st)))
+    return {k: getattr(st, k) for k in VARIANT_INS_STATS + POLISH_MS}
+
+
+def variants_ins_reads(contigs, reads, out_sites, out_ins, out_summary=None, ava_opts=None, pairs=None, **opts):
+    """hlmi_variants_reads_ins: `ava(contigs, reads, P, ava_opts)` and `variants_ins(contigs, reads, P, ...)` in one call without
+    the PAF P: the same files and the same integer stats.  ava_opts None: the long constants.  Refused besides what variants_ins
+    refuses: ava_opts.stub_oh >= 0.  -> dict of the stats (hlmi_variant_ins_stats)."""
+    o, st = _variant_opts("variants_ins_reads", opts), VariantInsStats()
+    _check(load().hlmi_variants_reads_ins(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
+                                          _b(pairs), _b(out_sites), _b(out_summary), _b(out_ins), C.byref(st)))
+    return {k: getattr(st, k) for k in VARIANT_INS_STATS + POLISH_MS}
 
 
 def _phase_opts(who, opts):

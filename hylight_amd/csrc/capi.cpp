@@ -645,6 +645,27 @@ int hlmi_variants_reads(const char *contigs, const char *reads, const hlmi_ava_o
     });
 }
 
+int hlmi_variants_ins(const char *contigs, const char *reads, const char *paf, const hlmi_variant_opts *o, const char *pairs_paf,
+                      const char *out_sites, const char *out_summary, const char *out_ins, hlmi_variant_ins_stats *st) {
+    return guarded([&] {
+        if (!out_ins) fail(HLMI_EINVAL, "hlmi_variants_ins: out_ins is NULL");
+        if (!contigs || !reads || !paf || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_variants_ins: NULL argument");
+        require_device();
+        variants_ins_run(contigs, reads, paf, *o, pairs_paf, out_sites, out_summary, out_ins, st);
+    });
+}
+
+int hlmi_variants_reads_ins(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_variant_opts *o,
+                            const char *pairs_paf, const char *out_sites, const char *out_summary, const char *out_ins,
+                            hlmi_variant_ins_stats *st) {
+    return guarded([&] {
+        if (!out_ins) fail(HLMI_EINVAL, "hlmi_variants_reads_ins: out_ins is NULL");
+        if (!contigs || !reads || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_variants_reads_ins: NULL argument");
+        require_device();
+        variants_reads_ins_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_sites, out_summary, out_ins, st);
+    });
+}
+
 void hlmi_phase_opts_default(hlmi_phase_opts *o) {
     if (o) *o = hlmi_phase_opts{0, 0.0, 3, 2, 0.2, 3, 0.8};
 }

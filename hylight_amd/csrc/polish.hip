@@ -17,7 +17,8 @@
 // rows, CIGARs and reads that are in device memory already - its reads as the overlapper's codes (column_symbol).
 // column_symbol, walk_row and the lane / wave switch of the vote loop are polish_walk.h's, shared with variants.hip.
 // polish_tail is everything behind the count pass - slot index, slot passes, lengths, scan, write - over any position space:
-// hlmi_haplotigs (haplotigs.hip) runs it over two sides side by side with slot votes of its own.
+// hlmi_haplotigs (haplotigs.hip) runs it over two sides side by side with slot votes of its own.  polish_slot_votes is the slot
+// passes alone over slots the caller chose: hlmi_variants_ins (variants.hip) votes the lengths and bases of its insertion sites.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
@@ -227,7 +228,31 @@ void launch_slot_for(const PolCoreIn &in, const uint32_t *d_slot_of, const uint8
     }
 }
 
+// the slots at pos[0, n) get their index in slot_of; length votes, the winning lengths, base votes (counters zeroed by the caller)
+void slot_passes(const PolSlotVotes &votes, const uint32_t *d_pos, size_t n, uint32_t *d_slot_of, uint8_t *d_win_len, uint32_t *d_len_cnt,
+                 uint32_t *d_base_cnt) {
+    constexpr int B = 256;
+    hipLaunchKernelGGL(slot_index_kernel, dim3(cdiv(n, B)), dim3(B), 0, stream(), d_pos, (uint32_t)n, d_slot_of);
+    votes(0, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+    hipLaunchKernelGGL(slot_len_kernel, dim3(cdiv(n, B)), dim3(B), 0, stream(), d_len_cnt, (uint32_t)n, d_win_len);
+    votes(1, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+    HIP_CHECK(hipGetLastError());
+}
+
+// polish_core's votes: polish_slot_kernel over every row of `in`
+PolSlotVotes row_votes_of(const PolCoreIn &in) {
+    return [&in](int mode, const uint32_t *d_slot_of, const uint8_t *d_win_len, uint32_t *d_len_cnt, uint32_t *d_base_cnt) {
+        if (mode == 0) launch_slot_for<0>(in, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+        else launch_slot_for<1>(in, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+    };
+}
+
 }  // namespace
+
+void polish_slot_votes(const PolCoreIn &in, const uint32_t *d_pos, size_t n, uint32_t *d_slot_of, uint8_t *d_win_len, uint32_t *d_len_cnt,
+                       uint32_t *d_base_cnt) {
+    if (n) slot_passes(row_votes_of(in), d_pos, n, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+}
 
 void polish_upload(const PolDevIn &in, PolUploaded &up) {
     up.contig.upload((const uint8_t *)in.contigs.data(), in.contigs.size());
@@ -270,12 +295,7 @@ void polish_core(const PolCoreIn &in, PolDevOut &out) {
         }
         HIP_CHECK(hipGetLastError());
     }
-    polish_tail(PolTailIn{in.contig, G, &d_sym, &d_open, in.cbase, in.n_cbase, "polish_slots"},
-                [&](int mode, const uint32_t *d_slot_of, const uint8_t *d_win_len, uint32_t *d_len_cnt, uint32_t *d_base_cnt) {
-                    if (mode == 0) launch_slot_for<0>(in, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
-                    else launch_slot_for<1>(in, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
-                },
-                out);
+    polish_tail(PolTailIn{in.contig, G, &d_sym, &d_open, in.cbase, in.n_cbase, "polish_slots"}, row_votes_of(in), out);
 }
 
 void polish_tail(const PolTailIn &in, const PolSlotVotes &votes, PolDevOut &out) {
@@ -291,11 +311,7 @@ void polish_tail(const PolTailIn &in, const PolSlotVotes &votes, PolDevOut &out)
         KTimer kt(in.slots_timer);
         d_len_cnt.zero();
         d_base_cnt.zero();
-        hipLaunchKernelGGL(slot_index_kernel, dim3(cdiv(n_open, B)), dim3(B), 0, stream(), d_open_pos.p, (uint32_t)n_open, d_slot_of.p);
-        votes(0, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
-        hipLaunchKernelGGL(slot_len_kernel, dim3(cdiv(n_open, B)), dim3(B), 0, stream(), d_len_cnt.p, (uint32_t)n_open, d_win_len.p);
-        votes(1, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
-        HIP_CHECK(hipGetLastError());
+        slot_passes(votes, d_open_pos.p, n_open, d_slot_of.p, d_win_len.p, d_len_cnt.p, d_base_cnt.p);
     }
     DBuf<uint32_t> d_out_len(G + 1);
     DBuf<uint64_t> d_off(G + 1), d_start(in.n_cbase);

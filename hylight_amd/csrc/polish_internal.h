@@ -86,6 +86,12 @@ struct PolTailIn {
 using PolSlotVotes = std::function<void(int mode, const uint32_t *slot_of, const uint8_t *win_len, uint32_t *len_cnt, uint32_t *base_cnt)>;
 void polish_tail(const PolTailIn &in, const PolSlotVotes &votes, PolDevOut &out);
 constexpr uint32_t POLISH_NO_SLOT = 0xffffffffu;        // slot_of of a position whose slot stays shut
+// polish_core's slot passes alone, for a caller with slots of its own (hlmi_variants_ins: its insertion sites): the n slots at the
+// ascending positions d_pos get their index in d_slot_of (one entry per position of in.contig, POLISH_NO_SLOT everywhere), every
+// row of `in` votes as in polish_core - lengths into d_len_cnt, the winning lengths into d_win_len (a tie: the smaller), bases
+// into d_base_cnt, laid out as polish_tail's votes are.  The caller zeroes the counters.  in.quals != nullptr: weighted.
+void polish_slot_votes(const PolCoreIn &in, const uint32_t *d_pos, size_t n, uint32_t *d_slot_of, uint8_t *d_win_len, uint32_t *d_len_cnt,
+                       uint32_t *d_base_cnt);
 
 // ---- what the pile-up calls do on the host around the device part (polish_host.cpp) ----------------------------------------
 // a selected row as the layout sees it: contig record, [ts, te); in the order (contig, ts, line)

@@ -1,9 +1,10 @@
-// variants_host.cpp - the host part of hlmi_variants and hlmi_variants_reads (include/hylight_mi.h): variant sites and a summary
-// per contig from the selected rows' votes.  The rows come from the pile-up calls' row front (polish_select.h: rows_from_paf or
+// variants_host.cpp - the host part of hlmi_variants, hlmi_variants_reads and their _ins forms (include/hylight_mi.h): variant sites,
+// insertion sites (_ins) and a summary per contig from the selected rows' votes.  The rows come from the pile-up calls' row front (polish_select.h: rows_from_paf or
 // rows_from_reads), selected, laid out and in device memory; the votes, the site rule and the records are variants.hip's, the
-// text variants_text.h's.
-// PARITY UNPINNED: a function of the project's own; tests/variants_model.py is the contract.
+// text variants_text.h's and variants_ins_text.h's.
+// PARITY UNPINNED: a function of the project's own; tests/variants_model.py and tests/variants_ins_model.py are the contract.
 #include <string>
+#include <type_traits>
 #include <string_view>
 #include <vector>
 
@@ -36,14 +37,20 @@ void var::contig_views(const SeqSet &cs, std::vector<uint64_t> &length, std::vec
 
 namespace {
 
-// what both entry points do behind the rows: the votes and the site rule, the records, the statistics and the two files
+// what every entry point does behind the rows: the votes and the site rule, the records, the statistics and the files.  Stats is
+// hlmi_variant_ins_stats for the _ins calls (out_ins is their file): one count pass with the slots' counters, the insertion
+// sites' records, the third file and a summary of three columns more; out_sites and the thirteen shared fields are the same.
+template <class Stats>
 void variants_body(const char *who, const PileupRows &R, const hlmi_variant_opts &o, const char *out_sites, const char *out_summary,
-                   hlmi_variant_stats *st) {
+                   const char *out_ins, Stats *st) {
+    constexpr bool INS = std::is_same_v<Stats, hlmi_variant_ins_stats>;
     const SeqSet &cs = R.cs();
     const PolLayout &L = R.L;
     set_row_stats(R, st);
     DeviceVariants dev;
-    variants_core(R.up.core, o, dev);
+    DeviceInsertions dins;
+    if constexpr (INS) variants_ins_core(R.up.core, o, dev, dins);
+    else variants_core(R.up.core, o, dev);
     st->ms_device = now_ms() - R.t_dev;
 
     std::vector<uint64_t> length;
@@ -63,32 +70,68 @@ void variants_body(const char *who, const PileupRows &R, const hlmi_variant_opts
     st->sites_del = tot.sites_del;
     stat_set("variants_tiles", (double)dev.tiles);
     stat_set("variants_tiles_revisited", (double)dev.tiles_revisited);
-    std::vector<std::string> summary;
-    if (out_summary) summary = summary_lines(recs);
+    std::vector<std::string> summary, ins;
+    if constexpr (INS) {
+        InsTotals itot;
+        const std::vector<ContigInsertions> irecs = contig_insertions(L.rc, L.slot_of_contig, dins, &itot);
+        if (!ins_lines(cs.names, seq, L.rc, L.slot_of_contig, L.cbase, dins, ins) || itot.ins_sites != dins.recs.size())
+            fail(HLMI_ESTATE, "%s: the insertion sites' records do not fit the contigs", who);                      // (never)
+        st->slots_callable = itot.slots_callable;
+        st->ins_sites = itot.ins_sites;
+        st->ins_long = R.ins_long;
+        st->ins_edge = R.ins_edge;
+        stat_set("variants_ins_slot_sites", (double)dins.slot_sites);
+        if (out_summary) summary = ins_summary_lines(recs, irecs);
+    } else if (out_summary)
+        summary = summary_lines(recs);
     write_lines(out_sites, sites);
+    if constexpr (INS) write_lines(out_ins, ins);
     if (out_summary) write_lines(out_summary, summary);
+}
+
+// the two kinds of rows in front of the body; who: the entry point's name in every refusal
+template <class Stats>
+void run_paf(const char *who, const char *contigs, const char *reads, const char *paf, const hlmi_variant_opts &o, const char *pairs_paf,
+             const char *out_sites, const char *out_summary, const char *out_ins, Stats *st) {
+    timed_call(st, true, [&] {
+        check_variant_opts(who, o);
+        PileupRows R;
+        rows_from_paf(contigs, reads, paf, plain_request(who, o.min_len, o.min_iden, pairs_paf), R);
+        variants_body(who, R, o, out_sites, out_summary, out_ins, st);
+    });
+}
+template <class Stats>
+void run_reads(const char *who, const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_variant_opts &o,
+               const char *pairs_paf, const char *out_sites, const char *out_summary, const char *out_ins, Stats *st) {
+    timed_call(st, true, [&] {
+        check_variant_opts(who, o);
+        PileupRows R;
+        rows_from_reads(contigs, reads, ao, plain_request(who, o.min_len, o.min_iden, pairs_paf), R);
+        variants_body(who, R, o, out_sites, out_summary, out_ins, st);
+    });
 }
 
 }  // namespace
 
 void variants_run(const char *contigs, const char *reads, const char *paf, const hlmi_variant_opts &o, const char *pairs_paf,
                   const char *out_sites, const char *out_summary, hlmi_variant_stats *st) {
-    timed_call(st, true, [&] {
-        check_variant_opts("hlmi_variants", o);
-        PileupRows R;
-        rows_from_paf(contigs, reads, paf, plain_request("hlmi_variants", o.min_len, o.min_iden, pairs_paf), R);
-        variants_body("hlmi_variants", R, o, out_sites, out_summary, st);
-    });
+    run_paf("hlmi_variants", contigs, reads, paf, o, pairs_paf, out_sites, out_summary, nullptr, st);
 }
 
 void variants_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_variant_opts &o,
                         const char *pairs_paf, const char *out_sites, const char *out_summary, hlmi_variant_stats *st) {
-    timed_call(st, true, [&] {
-        check_variant_opts("hlmi_variants_reads", o);
-        PileupRows R;
-        rows_from_reads(contigs, reads, ao, plain_request("hlmi_variants_reads", o.min_len, o.min_iden, pairs_paf), R);
-        variants_body("hlmi_variants_reads", R, o, out_sites, out_summary, st);
-    });
+    run_reads("hlmi_variants_reads", contigs, reads, ao, o, pairs_paf, out_sites, out_summary, nullptr, st);
+}
+
+void variants_ins_run(const char *contigs, const char *reads, const char *paf, const hlmi_variant_opts &o, const char *pairs_paf,
+                      const char *out_sites, const char *out_summary, const char *out_ins, hlmi_variant_ins_stats *st) {
+    run_paf("hlmi_variants_ins", contigs, reads, paf, o, pairs_paf, out_sites, out_summary, out_ins, st);
+}
+
+void variants_reads_ins_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_variant_opts &o,
+                            const char *pairs_paf, const char *out_sites, const char *out_summary, const char *out_ins,
+                            hlmi_variant_ins_stats *st) {
+    run_reads("hlmi_variants_reads_ins", contigs, reads, ao, o, pairs_paf, out_sites, out_summary, out_ins, st);
 }
 
 }  // namespace hlmi

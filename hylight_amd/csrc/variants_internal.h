@@ -1,11 +1,13 @@
 // variants_internal.h - what variants_host.cpp (the two entry points, the files) and variants.hip (the kernels) share.  The rules
-// are those of include/hylight_mi.h (hlmi_variants, hlmi_variants_reads); tests/variants_model.py restates them.
+// are those of include/hylight_mi.h (hlmi_variants, hlmi_variants_reads and their _ins forms); tests/variants_model.py and
+// tests/variants_ins_model.py restate them.
 #pragma once
 #include <string_view>
 #include <vector>
 
 #include "common.h"
 #include "polish_internal.h"
+#include "variants_ins_text.h"
 #include "variants_text.h"
 
 namespace hlmi {
@@ -14,6 +16,10 @@ namespace var {
 // The device part over the polisher's input (rows, compact CIGARs, reads as ASCII or codes, contig bytes, tiles, cbase - in.quals
 // and in.min_cov are not read): the three counters per slot and the sites' records, ascending.  o: validated by the caller.
 void variants_core(const pol::PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &out);
+// The same with the slots' counters in the one count pass (hlmi_variants_ins): `out` is what variants_core gives, except that
+// tiles_revisited counts the tiles with a site of either kind; ins: slots_callable and ins_sites per slot, the insertion sites'
+// records, ascending, finished on the device (variants_ins_text.h: InsRec).
+void variants_ins_core(const pol::PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &out, DeviceInsertions &ins);
 // the option refusals of both entry points, in the header's order (hlmi_phase makes them first, under its own name)
 void check_variant_opts(const char *who, const hlmi_variant_opts &o);
 // every contig record's length and bytes, as variants_text.h's and phase_text.h's functions take them
@@ -26,5 +32,11 @@ void variants_run(const char *contigs, const char *reads, const char *paf, const
                   const char *out_sites, const char *out_summary, hlmi_variant_stats *st);
 void variants_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_variant_opts &o,
                         const char *pairs_paf, const char *out_sites, const char *out_summary, hlmi_variant_stats *st);
+// the _ins forms: out_ins is not nullptr
+void variants_ins_run(const char *contigs, const char *reads, const char *paf, const hlmi_variant_opts &o, const char *pairs_paf,
+                      const char *out_sites, const char *out_summary, const char *out_ins, hlmi_variant_ins_stats *st);
+void variants_reads_ins_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_variant_opts &o,
+                            const char *pairs_paf, const char *out_sites, const char *out_summary, const char *out_ins,
+                            hlmi_variant_ins_stats *st);
 
 }  // namespace hlmi

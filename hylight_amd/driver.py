@@ -212,13 +212,15 @@ def depth_tables(final, long_reads, short_reads, outdir, device=None):
     return out
 
 
-def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None):
+def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None, ins=False):
     """`--variants`: the variant sites of the final contigs (hlmi_variants_reads: the reads are aligned to the contigs in the
     call, every pair, one row per read) - is each contig one strain?  The long reads - the filtered ones the overlap stage read -
     with the overlapper's long constants give outdir/final_contigs.long.variants.tsv and .long.variants.summary.tsv; short reads,
     when there are any, with the short constants give the .short. pair.  long_pairs / short_pairs (`--polish_strain`: the run's
     ov_long_ref.paf / shortr1.paf): only the (read, contig) pairs the list names vote; a list row whose names this call does not
     know counts in pairs_unknown.  `device`: the GPU to initialise the library on (None: the caller has done so).
+    ins (`--variants_ins`): hlmi_variants_reads_ins takes the call's place - the same two files (the summary with three columns
+    more) and the insertion sites in .variants.ins.tsv beside them; still one call per read set.
     -> {"long": stats, "short": stats}."""
     if device is not None:
         api.init(device)
@@ -229,7 +231,10 @@ def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pai
         o = api.ava_opts_short() if kind == "short" else api.ava_opts_long()
         o.pair_once = 0
         stem = os.path.join(outdir, f"final_contigs.{kind}.variants")
-        out[kind] = api.variants_reads(final, reads, stem + ".tsv", stem + ".summary.tsv", o, pairs=pairs)
+        if ins:
+            out[kind] = api.variants_ins_reads(final, reads, stem + ".tsv", stem + ".ins.tsv", stem + ".summary.tsv", o, pairs=pairs)
+        else:
+            out[kind] = api.variants_reads(final, reads, stem + ".tsv", stem + ".summary.tsv", o, pairs=pairs)
     return out
 
 
@@ -342,6 +347,10 @@ def build_parser():
                    help="(extension) when final_contigs.fa is written: the variant sites of its contigs and a summary per contig "
                         "(hlmi_variants_reads) into final_contigs.long.variants.tsv and .long.variants.summary.tsv, and with -s "
                         "also the .short. pair; with --polish_strain only the pairs of ov_long_ref.paf / shortr1.paf vote")
+    p.add_argument("--variants_ins", action="store_true",
+                   help="(extension) as --variants, with the insertion sites of the contigs beside the two files "
+                        "(hlmi_variants_reads_ins) in final_contigs.long.variants.ins.tsv, and with -s also the .short. one; the "
+                        "summary gains slots, ins_sites and ins_rate; with --variants too, still one call per read set")
     p.add_argument("--phase", action="store_true",
                    help="(extension) when final_contigs.fa is written: its variant sites phased from the reads (hlmi_phase_reads) "
                         "into final_contigs.long.phase.sites.tsv, .links.tsv and .reads.tsv, and with -s also the .short. triple; "
@@ -597,9 +606,10 @@ def _pipeline(args, pool):
         rc = _short_branch(args, tmp, outdir, long_con3, pool)
         if rc == 0 and args.depth:
             depth_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir)
-        if rc == 0 and args.variants:
+        if rc == 0 and (args.variants or args.variants_ins):
             variant_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
-                           long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None)
+                           long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None,
+                           **({"ins": True} if args.variants_ins else {}))
         if rc == 0 and args.phase:
             phase_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
                          long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None)
@@ -642,9 +652,9 @@ def _pipeline(args, pool):
         return EXIT_NO_FINAL
     if args.depth:
         depth_tables(final, infile, short_reads, outdir)
-    if args.variants:
+    if args.variants or args.variants_ins:
         variant_tables(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
-                       short_pairs=ov_short if args.polish_strain else None)
+                       short_pairs=ov_short if args.polish_strain else None, **({"ins": True} if args.variants_ins else {}))
     if args.phase:
         phase_tables(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
                      short_pairs=ov_short if args.polish_strain else None)

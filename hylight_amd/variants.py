@@ -14,6 +14,9 @@ order - with the overlap stage's filtered rows a read votes only on the contig t
 strain's alleles no longer show as sites).
 --out: the sites (contig, pos, ref, depth, A, C, G, T, del, alt, alt_count, alt_frac); --summary: one line per contig (contig,
 length, reads, callable, sites, site_rate).  Prints the stats as one JSON line.  Exit status 0 on success.
+--ins FILE: the insertion sites too (hlmi_variants_ins / hlmi_variants_reads_ins) - the slots where rows that insert bases the
+contig lacks number --min_alt and make --min_frac of the --min_cov or more rows that span the slot (contig, pos, ref, span, ins,
+ins_long, ins_frac, len, len_count, seq); --out stays the same file, --summary gains slots, ins_sites and ins_rate.
 """
 from __future__ import annotations
 
@@ -36,6 +39,8 @@ def build_parser():
                    help="PAF-like list (fields 1 and 6): only rows of a listed (read, contig) pair vote (not given: every row may)")
     p.add_argument("--out", required=True, help="the sites, one line each (TSV)")
     p.add_argument("--summary", default=None, help="one line per contig (TSV; not given: not written)")
+    p.add_argument("--ins", default=None, metavar="FILE",
+                   help="also the insertion sites, one line each (TSV; hlmi_variants_ins; not given: insertions take no part)")
     p.add_argument("--short", action="store_true", help="without --paf: the overlapper's short-read constants")
     p.add_argument("--min_len", type=int, default=0, help="drop rows that cover fewer contig bases")
     p.add_argument("--min_iden", type=float, default=0.0, help="drop rows with a smaller share of '=' columns")
@@ -49,9 +54,14 @@ def main(argv=None):
     parser = build_parser()
     a = parser.parse_args(argv)
     opts = dict(min_len=a.min_len, min_iden=a.min_iden, min_cov=a.min_cov, min_alt=a.min_alt, min_frac=a.min_frac)
-    if a.paf is not None:
-        if a.short:
-            parser.error("--short chooses the alignment of a call without --paf")
+    if a.paf is not None and a.short:
+        parser.error("--short chooses the alignment of a call without --paf")
+    if a.ins is not None:
+        if a.paf is not None:
+            st = api.variants_ins(a.contigs, a.reads, a.paf, a.out, a.ins, a.summary, pairs=a.pairs, **opts)
+        else:
+            st = api.variants_ins_reads(a.contigs, a.reads, a.out, a.ins, a.summary, read_ava_opts(a.short), pairs=a.pairs, **opts)
+    elif a.paf is not None:
         st = api.variants(a.contigs, a.reads, a.paf, a.out, a.summary, pairs=a.pairs, **opts)
     else:
         st = api.variants_reads(a.contigs, a.reads, a.out, a.summary, read_ava_opts(a.short), pairs=a.pairs, **opts)

@@ -964,6 +964,69 @@ int hlmi_variants(const char *contigs, const char *reads, const char *paf, const
 int hlmi_variants_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_variant_opts *o,
                         const char *pairs_paf, const char *out_sites, const char *out_summary, hlmi_variant_stats *st);
 
+/* ---- variant sites with insertion sites: hlmi_variants reports nothing where the reads carry bases the contig lacks; these calls
+ * add the slots' votes - hlmi_polish's slots - and list the slots where inserting rows have real support, whether or not
+ * hlmi_polish would open them (it opens a slot only when 2 i > s).  hlmi_variants_ins reads a PAF as hlmi_variants does,
+ * hlmi_variants_reads_ins aligns in the call as hlmi_variants_reads does.  New symbols: the older calls keep their signatures and
+ * their bytes, and HLMI_ABI_VERSION stays where it is.  Options: hlmi_variant_opts unchanged; min_cov, min_alt and min_frac rule
+ * the slots as they rule the positions.  A function of the project's own: PARITY UNPINNED; tests/variants_ins_model.py is the
+ * contract, byte for byte. */
+typedef struct {
+    uint64_t rows;              /* the thirteen integer fields of hlmi_variant_stats, with hlmi_variants's values         */
+    uint64_t rows_selected;
+    uint64_t contigs;
+    uint64_t contigs_covered;
+    uint64_t positions;
+    uint64_t callable;
+    uint64_t ref_other;
+    uint64_t sites;
+    uint64_t sites_base;
+    uint64_t sites_del;
+    uint64_t pairs_listed;
+    uint64_t pairs_unknown;
+    uint64_t rows_not_listed;
+    uint64_t slots_callable;    /* slots with s >= min_cov                                                                  */
+    uint64_t ins_sites;         /* ... that are insertion sites                                                             */
+    uint64_t ins_long;          /* as hlmi_polish_stats counts them: (row, slot) with more than 16 inserted bases           */
+    uint64_t ins_edge;          /* ... and I ops at a row's ts or te                                                        */
+    double ms_device;           /* wall time of the device part: uploads, kernels, read-backs                               */
+    double ms_total;
+} hlmi_variant_ins_stats;
+/* contigs, reads, paf, o, pairs_paf, out_sites, out_summary: as for hlmi_variants; out_ins must not be NULL.
+ * Selection, position votes, out_sites: exactly hlmi_variants's, run by the same code; out_sites is byte for byte the file
+ * hlmi_variants writes for the same arguments.  With a pair list an unlisted row neither votes nor spans nor inserts.
+ * Slots: hlmi_polish's definition, unweighted.  Slot p, 0 < p < length, is the gap in front of 0-based position p.  A selected row
+ * with ts < p < te spans it; s counts the spanning rows.  A row's I ops there are concatenated (one op of the compact CIGAR: I ops
+ * with nothing or only zero-length ops between them).  A row with 1..16 bases there inserts; i counts the inserting rows.  A row
+ * with more than 16 bases there is a long row; l counts the long rows, and such a row also counts in ins_long.  I ops at p == ts or
+ * p == te belong to no slot and count in ins_edge.  A row whose column at p votes nothing (an N) still spans; a row that starts at
+ * p does not span.
+ * Insertion site rule: a slot is callable iff s >= min_cov and counts in slots_callable; a callable slot is an insertion site iff
+ * i + l >= min_alt and (double)(i + l) / (double)s >= min_frac (one IEEE division).  The contig's own byte at p or p - 1 plays no
+ * part: a slot next to an N can be a site.
+ * Per site: len is the most frequent length among the i inserting rows, on a tie the smallest, 0 when i == 0; len_count the number
+ * of rows with that length; seq[j] the most frequent of A, C, G, T at index j among the rows that insert exactly len bases, on a
+ * tie the first of A, C, G, T, with none N - hlmi_polish's slot decisions.  Strand '-' rows insert the reverse complement.
+ * out_ins (under a temporary name, renamed on success): the line
+ * "#contig\tpos\tref\tspan\tins\tins_long\tins_frac\tlen\tlen_count\tseq", then one line per insertion site, contigs in file
+ * order, slots ascending: pos = p, the 1-based position of the base in front of the inserted bases (VCF's convention), ref that
+ * base, upper-cased, span = s, ins = i, ins_long = l, ins_frac the quotient above as %.6f, len and len_count as above, seq the len
+ * bases or '*' when len is 0.  With no insertion site the file is the header line alone.
+ * out_summary (optional): hlmi_variants's line plus three columns:
+ * "#contig\tlength\treads\tcallable\tsites\tsite_rate\tslots\tins_sites\tins_rate": slots = callable slots, ins_rate =
+ * (double)ins_sites / (double)slots as %.6f, 0.000000 when slots is 0; the first six columns are byte for byte hlmi_variants's.
+ * Refusals (HLMI_EINVAL, nothing is written): out_ins == NULL first, then hlmi_variants's refusals in its order.
+ * One count pass holds the five symbol counters and four slot counters per position (csrc/variants.hip); the lengths and bases of
+ * the insertion sites are voted by hlmi_polish's slot kernels, and 40 bytes per insertion site come to the host. */
+int hlmi_variants_ins(const char *contigs, const char *reads, const char *paf, const hlmi_variant_opts *o, const char *pairs_paf,
+                      const char *out_sites, const char *out_summary, const char *out_ins, hlmi_variant_ins_stats *st);
+/* The two calls hlmi_ava(contigs, reads, ao, P) and hlmi_variants_ins(contigs, reads, P, o, pairs_paf, ...) in one, without the PAF
+ * P: the three files and every integer field of *st are byte for byte what that chain gives (ao NULL: the long constants).  It
+ * refuses as hlmi_variants_reads does, behind out_ins == NULL. */
+int hlmi_variants_reads_ins(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_variant_opts *o,
+                            const char *pairs_paf, const char *out_sites, const char *out_summary, const char *out_ins,
+                            hlmi_variant_ins_stats *st);
+
 /* ---- phased variant sites: do the minor alleles of neighbouring sites ride on the same reads (a collapsed sister strain that can
  * be separated) or not (noise, a mis-join, a polishing error), and which read belongs to which side.  hlmi_phase reads a PAF as
  * hlmi_variants does, hlmi_phase_reads aligns in the call as hlmi_variants_reads does.  New symbols: the older calls keep their
