@@ -48,6 +48,8 @@ def lib():
         l.oracle_ava.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Opts), C.c_char_p]
         l.oracle_last_counts.restype = None
         l.oracle_last_counts.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
+        l.oracle_chain_pieces.restype = C.c_long
+        l.oracle_chain_pieces.argtypes = [C.c_void_p, C.c_int, C.POINTER(Opts), C.c_void_p, C.c_long]
         _lib = l
     return _lib
 
@@ -71,6 +73,24 @@ def ava(target_fa, query_fa, out_paf, opts=None):
     if rc != 0:
         raise RuntimeError(f"oracle_ava failed: {rc}")
     return out_paf
+
+
+def chain_pieces(anchors, opts):
+    """The oracle's own chain_group on one (query, target, strand) group: `anchors` is a list of (tpos, qpos, qspan) in chaining
+    order.  Returns [(chain start, piece index, [(q, t), ...fixed points])] in the order align_chain closes the pieces; nothing
+    is aligned and no sequence is read."""
+    a = np.ascontiguousarray(np.asarray(anchors, dtype=np.uint32).reshape(-1, 3))
+    n = a.shape[0]
+    out = np.zeros(16 * n + 16, dtype=np.int32)
+    w = lib().oracle_chain_pieces(a.ctypes.data, n, C.byref(opts), out.ctypes.data, out.size)
+    if w < 0:
+        raise RuntimeError("oracle_chain_pieces: output buffer too small")
+    res, x = [], 0
+    while x < w:
+        chain, piece, nf = int(out[x]), int(out[x + 1]), int(out[x + 2])
+        res.append((chain, piece, [(int(out[x + 3 + 2 * i]), int(out[x + 4 + 2 * i])) for i in range(nf)]))
+        x += 3 + 2 * nf
+    return res
 
 
 def last_counts():

@@ -451,6 +451,17 @@ static int band_dp(const ava_opts_t *o, const uint8_t *q, int qstride, int m, co
     return score;
 }
 
+/* Recording switch (oracle_chain_pieces below): with g_rec set, align_chain's calls note coordinates instead of aligning - one
+ * event of five ints each: {0, q0, t0, q1, t1} a block, {1, qs, ts, qe, te} a closed piece, {2, start anchor, members, 0, 0} a
+ * chain.  Unset (always, inside oracle_ava) nothing changes. */
+typedef struct { int32_t *ev; long n, cap; } rec_t;
+static __thread rec_t *g_rec;
+static void rec_push(int kind, int a, int b, int c, int d) {
+    rec_t *r = g_rec;
+    if (r->n + 5 <= r->cap) { int32_t *e = r->ev + r->n; e[0] = kind; e[1] = a; e[2] = b; e[3] = c; e[4] = d; }
+    r->n += 5;
+}
+
 typedef struct {
     int qs, qe, ts, te;   /* aligned-orientation query coords, target coords */
     int score;
@@ -467,6 +478,7 @@ static int block_ok(int q0, int t0, int q1, int t1) {
 
 static void align_block(const ava_opts_t *o, const uint8_t *q, const uint8_t *t, int q0, int t0, int q1, int t1,
                         piece_t *p) {
+    if (g_rec) { rec_push(0, q0, t0, q1, t1); return; }
     int m = q1 - q0, n = t1 - t0, delta = n - m, nr;
     uint32_t *scratch = (uint32_t *)malloc((size_t)(m + n + 2) * 4);
     /* band rule: near-diagonal blocks get the narrow band, the rest the wide one */
@@ -582,6 +594,7 @@ static int is_stub(const ava_opts_t *o, const piece_t *p, int ql, int tl) {
 
 static void close_piece(FILE *out, const ava_opts_t *o, const seqset_t *Q, int qi, const uint8_t *qa, const seqset_t *T, int ti,
                         int strand, piece_t *p) {
+    if (g_rec) { rec_push(1, p->qs, p->ts, p->qe, p->te); return; }
     const int ql = Q->len[qi], tl = T->len[ti];
     const int cand = is_stub_candidate(o, p, ql, tl);      /* (on the unextended piece, as the stub test itself) */
     const int stub = is_stub(o, p, ql, tl);
@@ -598,9 +611,10 @@ static void close_piece(FILE *out, const ava_opts_t *o, const seqset_t *Q, int q
 
 static void align_chain(FILE *out, const ava_opts_t *o, const seqset_t *Q, int qi, const uint8_t *qa /* aligned orientation */,
                         const seqset_t *T, int ti, int strand, const anchor_t *a, const int *chain, int m) {
-    const uint8_t *t = T->code[ti];
+    const uint8_t *t = g_rec ? 0 : T->code[ti];
     piece_t p;
     memset(&p, 0, sizeof p);
+    if (g_rec) rec_push(2, chain[0], m, 0, 0);
     int open = 0, cq = 0, ct = 0;   /* current fixed point */
     for (int x = 0; x < m; ++x) {
         const anchor_t *an = &a[chain[x]];
@@ -717,6 +731,46 @@ static void assign_ranks(seqset_t *T, seqset_t *Q) {
         }
     }
     free(all);
+}
+
+/* The chains of ONE (query, target, strand) group and the alignment pieces align_chain would bound, without aligning anything
+ * (tests/test_gpu_chain_direct.py holds the plain reference of tests/capi/chain_gpu_check.cpp to it).  anchors: n x 3 values
+ * (tpos, qpos, qspan) in chaining order - ascending aligned query position, as oracle_ava's sort leaves a group.  out receives, per
+ * piece in the order align_chain closes them: chain start (index of its first anchor), piece index inside the chain, number of
+ * fixed points F, then F pairs (q, t).  Returns the number of ints written, or -1 when cap is too small.  Reads no sequence. */
+long oracle_chain_pieces(const uint32_t *anchors, int n, const ava_opts_t *o, int32_t *out, long cap) {
+    anchor_t *a = (anchor_t *)calloc((size_t)(n ? n : 1), sizeof(anchor_t));
+    for (int i = 0; i < n; ++i) { a[i].tpos = anchors[3 * i]; a[i].qpos = anchors[3 * i + 1]; a[i].qspan = anchors[3 * i + 2]; a[i].gen = (uint32_t)i; }
+    rec_t r;
+    r.cap = 16 * (long)n + 16;               /* a chain event per chain; per member at most one block and one piece */
+    r.ev = (int32_t *)malloc((size_t)r.cap * 4);
+    r.n = 0;
+    read_switches();
+    g_ungapped = o->bandwidth == 0;
+    g_rec = &r;
+    chain_group(0, o, 0, 0, 0, 0, a, n);
+    g_rec = 0;
+    free(a);
+    long w = 0, head = -1;
+    int chain = 0, piece = 0, bad = r.n > r.cap;
+    for (long x = 0; x + 5 <= r.n && !bad; x += 5) {
+        const int32_t *e = r.ev + x;
+        if (e[0] == 2) { chain = e[1]; piece = 0; }
+        else if (e[0] == 0) {
+            if (head < 0) {                  /* first block of a piece: its header and both corners */
+                if (w + 7 > cap) { bad = 1; break; }
+                head = w;
+                out[w++] = chain; out[w++] = piece; out[w++] = 2;
+                out[w++] = e[1]; out[w++] = e[2]; out[w++] = e[3]; out[w++] = e[4];
+            } else {
+                if (w + 2 > cap) { bad = 1; break; }
+                out[w++] = e[3]; out[w++] = e[4];
+                ++out[head + 2];
+            }
+        } else { head = -1; ++piece; }
+    }
+    free(r.ev);
+    return bad ? -1 : w;
 }
 
 void oracle_last_counts(long *pieces, long *stubs) { *pieces = g_n_pieces; *stubs = g_n_stubs; }
