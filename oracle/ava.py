@@ -50,6 +50,9 @@ def lib():
         l.oracle_last_counts.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
         l.oracle_chain_pieces.restype = C.c_long
         l.oracle_chain_pieces.argtypes = [C.c_void_p, C.c_int, C.POINTER(Opts), C.c_void_p, C.c_long]
+        l.oracle_align_pieces.restype = C.c_long
+        l.oracle_align_pieces.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(Opts),
+                                          C.c_char_p, C.c_long]
         _lib = l
     return _lib
 
@@ -91,6 +94,33 @@ def chain_pieces(anchors, opts):
         res.append((chain, piece, [(int(out[x + 3 + 2 * i]), int(out[x + 4 + 2 * i])) for i in range(nf)]))
         x += 3 + 2 * nf
     return res
+
+
+_CODE = np.full(256, 4, dtype=np.uint8)
+for _i, _c in enumerate("ACGT"):
+    _CODE[ord(_c)] = _CODE[ord(_c.lower())] = _i
+
+
+def align_pieces(qseq, tseq, strand, fixed_points, opts):
+    """The oracle's own align_block / extend_left / extend_right / close_piece on ONE alignment piece: `qseq` (as in its file) and
+    `tseq` are base strings or code arrays, `fixed_points` a list of (q, t) in aligned orientation (on the query's reverse
+    complement when strand is 1).  Returns the PAF row as a list of columns (names "q" and "t"), or None when the piece is
+    dropped."""
+    def codes(s):
+        if isinstance(s, str):
+            s = s.encode()
+        if isinstance(s, (bytes, bytearray)):
+            return np.ascontiguousarray(_CODE[np.frombuffer(s, dtype=np.uint8)])
+        return np.ascontiguousarray(np.asarray(s, dtype=np.uint8))
+    q, t = codes(qseq), codes(tseq)
+    fp = np.ascontiguousarray(np.asarray(fixed_points, dtype=np.int32).reshape(-1, 2))
+    cap = 4096 + 16 * (q.size + t.size)
+    buf = C.create_string_buffer(cap)
+    n = lib().oracle_align_pieces(q.ctypes.data, q.size, t.ctypes.data, t.size, int(strand), fp.ctypes.data, fp.shape[0],
+                                  C.byref(opts), buf, cap)
+    if n < 0:
+        raise RuntimeError("oracle_align_pieces: fixed points outside the contract, or the row does not fit")
+    return buf.raw[:n].decode().rstrip("\n").split("\t") if n else None
 
 
 def last_counts():

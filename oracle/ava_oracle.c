@@ -773,6 +773,49 @@ long oracle_chain_pieces(const uint32_t *anchors, int n, const ava_opts_t *o, in
     return bad ? -1 : w;
 }
 
+/* The row of ONE alignment piece given by its fixed points, without sketch, index or chain (tests/test_gpu_align_direct.py holds
+ * the plain reference of tests/capi/align_gpu_check.cpp to it): the counterpart of oracle_chain_pieces.  qcodes / tcodes: codes
+ * 0..4 of the query as it stands in its file and of the target; strand 1: the fixed points count on the query's reverse
+ * complement.  fps: n_fp pairs (q, t), n_fp >= 2, inside what align_chain hands on (strictly increasing, every block passes
+ * block_ok).  Runs align_block over consecutive fixed points and close_piece (stub rule, end extensions, min_dp_score) as
+ * align_chain does, and writes the PAF line (names "q" and "t") to out.  Returns its length, 0 when the piece is dropped, -1
+ * when cap is too small or the fixed points are outside the contract. */
+long oracle_align_pieces(const uint8_t *qcodes, int ql, const uint8_t *tcodes, int tl, int strand, const int32_t *fps, int n_fp,
+                         const ava_opts_t *o, char *out, long cap) {
+    if (n_fp < 2 || ql < 0 || tl < 0) return -1;
+    read_switches();
+    g_ungapped = o->bandwidth == 0;
+    for (int x = 0; x < n_fp; ++x) {
+        if (fps[2 * x] < 0 || fps[2 * x] > ql || fps[2 * x + 1] < 0 || fps[2 * x + 1] > tl) return -1;
+        if (x && (fps[2 * x] <= fps[2 * x - 2] || fps[2 * x + 1] <= fps[2 * x - 1] ||
+                  !block_ok(fps[2 * x - 2], fps[2 * x - 1], fps[2 * x], fps[2 * x + 1]))) return -1;
+    }
+    char qn[] = "q", tn[] = "t", *qnp = qn, *tnp = tn;
+    uint8_t *qa = (uint8_t *)malloc((size_t)ql + 1), *tc = (uint8_t *)tcodes;
+    for (int i = 0; i < ql; ++i) { uint8_t c = strand ? qcodes[ql - 1 - i] : qcodes[i]; qa[i] = strand ? (c < 4 ? 3 - c : 4) : c; }
+    seqset_t Q, T;
+    memset(&Q, 0, sizeof Q); memset(&T, 0, sizeof T);
+    Q.n = 1; Q.name = &qnp; Q.len = &ql;
+    T.n = 1; T.name = &tnp; T.len = &tl; T.code = &tc;
+    piece_t p;
+    memset(&p, 0, sizeof p);
+    p.qs = fps[0]; p.ts = fps[1];
+    for (int x = 1; x < n_fp; ++x) align_block(o, qa, tcodes, fps[2 * x - 2], fps[2 * x - 1], fps[2 * x], fps[2 * x + 1], &p);
+    p.qe = fps[2 * n_fp - 2]; p.te = fps[2 * n_fp - 1];
+    char *buf = 0;
+    size_t len = 0;
+    FILE *f = open_memstream(&buf, &len);
+    close_piece(f, o, &Q, 0, qa, &T, 0, strand, &p);
+    fclose(f);
+    free(p.cg.op);
+    free(qa);
+    long r = (long)len;
+    if (r + 1 > cap) r = -1;
+    else { memcpy(out, buf, len); out[len] = 0; }
+    free(buf);
+    return r;
+}
+
 void oracle_last_counts(long *pieces, long *stubs) { *pieces = g_n_pieces; *stubs = g_n_stubs; }
 
 int oracle_ava(const char *target_fa, const char *query_fa, const ava_opts_t *o, const char *out_paf) {
