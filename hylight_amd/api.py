@@ -197,6 +197,14 @@ class PhaseStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in PHASE_STATS] + [(k, C.c_double) for k in POLISH_MS]
 
 
+PHASE_REACH_MAX = 8      # include/hylight_mi.h: HLMI_PHASE_REACH_MAX
+PHASE_REACH_STATS = ("links_far", "links_far_phased", "joins_far", "sites_bridged", "links_conflict")
+
+
+class PhaseReachStats(C.Structure):
+    _fields_ = [("base", PhaseStats)] + [(k, C.c_uint64) for k in PHASE_REACH_STATS]
+
+
 class HaplotigOpts(C.Structure):
     _fields_ = list(PhaseOpts._fields_) + [("min_side", C.c_int), ("include_unpolished", C.c_int)]
 
@@ -323,12 +331,20 @@ SYMBOLS = {
                              C.POINTER(PhaseStats)]),
     "hlmi_phase_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PhaseOpts), C.c_char_p, C.c_char_p, C.c_char_p,
                                    C.c_char_p, C.POINTER(PhaseStats)]),
+    "hlmi_phase_reach": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PhaseOpts), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p,
+                                   C.c_char_p, C.POINTER(PhaseReachStats)]),
+    "hlmi_phase_reads_reach": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PhaseOpts), C.c_int, C.c_char_p, C.c_char_p,
+                                         C.c_char_p, C.c_char_p, C.POINTER(PhaseReachStats)]),
     # haplotigs
     "hlmi_haplotig_opts_default": (None, [C.POINTER(HaplotigOpts)]),
     "hlmi_haplotigs": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(HaplotigOpts), C.c_char_p, C.c_char_p, C.c_char_p,
                                  C.POINTER(HaplotigStats)]),
     "hlmi_haplotigs_reads": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(HaplotigOpts), C.c_char_p, C.c_char_p,
                                        C.c_char_p, C.POINTER(HaplotigStats)]),
+    "hlmi_haplotigs_reach": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(HaplotigOpts), C.c_int, C.c_char_p, C.c_char_p,
+                                       C.c_char_p, C.POINTER(HaplotigStats)]),
+    "hlmi_haplotigs_reads_reach": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(HaplotigOpts), C.c_int, C.c_char_p,
+                                             C.c_char_p, C.c_char_p, C.POINTER(HaplotigStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -949,6 +965,36 @@ def phase_reads(contigs, reads, out_sites, out_links=None, out_reads=None, ava_o
     return {k: getattr(st, k) for k in PHASE_STATS + POLISH_MS}
 
 
+def _phase_reach_stats(st):
+    out = {k: getattr(st.base, k) for k in PHASE_STATS + POLISH_MS}
+    out.update({k: getattr(st, k) for k in PHASE_REACH_STATS})
+    return out
+
+
+def phase_reach(contigs, reads, paf, out_sites, out_links=None, out_reads=None, pairs=None, reach=1, **opts):
+    """hlmi_phase_reach: api.phase with links between sites up to `reach` (1 .. PHASE_REACH_MAX) apart, so that one noisy site does
+    not cut a block.  Sites, selection and alleles are api.phase's; every pair of sites (i, i + d), d <= reach, of a contig has a
+    link under api.phase's link rule; a site joins the block in front of it through the nearest member within reach that has a
+    phased link to it; a site inside a block that did not join is bridged: its block's id, phase ".", counted in a record's
+    spanned alone.  out_links has one line per link of any distance.  With reach 1 the files and the shared stats are
+    api.phase's.  include/hylight_mi.h states it, tests/phase_reach_model.py is its contract.
+    -> dict of the stats (hlmi_phase_reach_stats: api.phase's keys, links_far, links_far_phased, joins_far, sites_bridged,
+    links_conflict)."""
+    o, st = _phase_opts("phase_reach", opts), PhaseReachStats()
+    _check(load().hlmi_phase_reach(_b(contigs), _b(reads), _b(paf), C.byref(o), int(reach), _b(pairs), _b(out_sites), _b(out_links),
+                                   _b(out_reads), C.byref(st)))
+    return _phase_reach_stats(st)
+
+
+def phase_reads_reach(contigs, reads, out_sites, out_links=None, out_reads=None, ava_opts=None, pairs=None, reach=1, **opts):
+    """hlmi_phase_reads_reach: `ava(contigs, reads, P, ava_opts)` and `phase_reach(contigs, reads, P, ...)` in one call without the
+    PAF P, as phase_reads is for phase.  -> dict of the stats (hlmi_phase_reach_stats)."""
+    o, st = _phase_opts("phase_reads_reach", opts), PhaseReachStats()
+    _check(load().hlmi_phase_reads_reach(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), int(reach),
+                                         _b(pairs), _b(out_sites), _b(out_links), _b(out_reads), C.byref(st)))
+    return _phase_reach_stats(st)
+
+
 def _haplotig_opts(who, opts):
     o = HaplotigOpts()
     load().hlmi_haplotig_opts_default(C.byref(o))
@@ -986,6 +1032,25 @@ def haplotigs_reads(contigs, reads, out_fa, out_blocks=None, ava_opts=None, pair
     o, st = _haplotig_opts("haplotigs_reads", opts), HaplotigStats()
     _check(load().hlmi_haplotigs_reads(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), _b(pairs),
                                        _b(out_fa), _b(out_blocks), C.byref(st)))
+    return _haplotig_stats(st)
+
+
+def haplotigs_reach(contigs, reads, paf, out_fa, out_blocks=None, pairs=None, reach=1, **opts):
+    """hlmi_haplotigs_reach: api.haplotigs over the blocks of api.phase_reach (reach 1 .. PHASE_REACH_MAX): a block's extent runs
+    from its first to its last site, bridged sites included; a row's side comes from its record.  With reach 1 it is
+    api.haplotigs byte for byte.  tests/haplotigs_reach_model.py is its contract.  -> dict of the stats (hlmi_haplotig_stats)."""
+    o, st = _haplotig_opts("haplotigs_reach", opts), HaplotigStats()
+    _check(load().hlmi_haplotigs_reach(_b(contigs), _b(reads), _b(paf), C.byref(o), int(reach), _b(pairs), _b(out_fa), _b(out_blocks),
+                                       C.byref(st)))
+    return _haplotig_stats(st)
+
+
+def haplotigs_reads_reach(contigs, reads, out_fa, out_blocks=None, ava_opts=None, pairs=None, reach=1, **opts):
+    """hlmi_haplotigs_reads_reach: `ava(contigs, reads, P, ava_opts)` and `haplotigs_reach(contigs, reads, P, ...)` in one call
+    without the PAF P.  -> dict of the stats (hlmi_haplotig_stats)."""
+    o, st = _haplotig_opts("haplotigs_reads_reach", opts), HaplotigStats()
+    _check(load().hlmi_haplotigs_reads_reach(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
+                                             int(reach), _b(pairs), _b(out_fa), _b(out_blocks), C.byref(st)))
     return _haplotig_stats(st)
 
 

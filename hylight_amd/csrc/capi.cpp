@@ -688,6 +688,25 @@ int hlmi_phase_reads(const char *contigs, const char *reads, const hlmi_ava_opts
     });
 }
 
+int hlmi_phase_reach(const char *contigs, const char *reads, const char *paf, const hlmi_phase_opts *o, int reach, const char *pairs_paf,
+                     const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_reach_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_phase_reach: NULL argument");
+        require_device();
+        phase_reach_run(contigs, reads, paf, *o, reach, pairs_paf, out_sites, out_links, out_reads, st);
+    });
+}
+
+int hlmi_phase_reads_reach(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_phase_opts *o, int reach,
+                           const char *pairs_paf, const char *out_sites, const char *out_links, const char *out_reads,
+                           hlmi_phase_reach_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_phase_reads_reach: NULL argument");
+        require_device();
+        phase_reads_reach_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, reach, pairs_paf, out_sites, out_links, out_reads, st);
+    });
+}
+
 void hlmi_haplotig_opts_default(hlmi_haplotig_opts *o) {
     if (o) *o = hlmi_haplotig_opts{0, 0.0, 3, 2, 0.2, 3, 0.8, 3, 1};
 }
@@ -707,6 +726,24 @@ int hlmi_haplotigs_reads(const char *contigs, const char *reads, const hlmi_ava_
         if (!contigs || !reads || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_haplotigs_reads: NULL argument");
         require_device();
         haplotigs_reads_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_fa, out_blocks, st);
+    });
+}
+
+int hlmi_haplotigs_reach(const char *contigs, const char *reads, const char *paf, const hlmi_haplotig_opts *o, int reach,
+                         const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_haplotigs_reach: NULL argument");
+        require_device();
+        haplotigs_reach_run(contigs, reads, paf, *o, reach, pairs_paf, out_fa, out_blocks, st);
+    });
+}
+
+int hlmi_haplotigs_reads_reach(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_haplotig_opts *o, int reach,
+                               const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_haplotigs_reads_reach: NULL argument");
+        require_device();
+        haplotigs_reads_reach_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, reach, pairs_paf, out_fa, out_blocks, st);
     });
 }
 

@@ -2,7 +2,8 @@
 // per side of every split block.  The rows come from the pile-up calls' row front (polish_select.h), sites and phasing are
 // hlmi_phase's (phase_device, phase_emit for the statistics), called and not restated; the split rule, the blocks file and
 // the headers are haplotigs_text.h's, the exclusion intervals and the two-sided passes haplotigs.hip's.  With no split block the
-// single-sided polish_core gives the bytes and no kernel of haplotigs.hip runs.
+// single-sided polish_core gives the bytes and no kernel of haplotigs.hip runs.  The _reach calls hand `reach` down to the
+// phasing and are the same body otherwise: blocks stay runs of consecutive sites, a row's side comes from its record.
 // PARITY UNPINNED: a function of the project's own; tests/haplotigs_model.py is the contract.
 #include <algorithm>
 #include <string>
@@ -33,10 +34,10 @@ void check_opts(const char *who, const hlmi_haplotig_opts &o) {
     if (o.min_side < 1) fail(HLMI_EINVAL, "%s: min_side %d (< 1)", who, o.min_side);
 }
 
-// What both entry points do behind the rows: the phasing, the split rule, one or two sides of consensus, the statistics and the
-// two files.
+// What the entry points do behind the rows: the phasing, the split rule, one or two sides of consensus, the statistics and the
+// two files.  reach 0: the plain calls
 void haplotigs_body(const char *who, PileupRows &R, const hlmi_haplotig_opts &o, const char *out_fa, const char *out_blocks,
-                    hlmi_haplotig_stats *st) {
+                    hlmi_haplotig_stats *st, int reach = 0) {
     const SeqSet &cs = R.cs();
     const PolLayout &L = R.L;
     const double t_dev = R.t_dev;
@@ -53,7 +54,7 @@ void haplotigs_body(const char *who, PileupRows &R, const hlmi_haplotig_opts &o,
     bool any = false;
     {
         DevRecs keep;
-        phase_device(who, R, po, P, &keep);
+        phase_device(who, R, po, P, &keep, reach);
         st->phase.ms_device = now_ms() - t_dev;
         if (!haplotig_blocks(P.sites, P.dev.blocks, P.dev.recs, o.min_side, hb)) fail(HLMI_ESTATE, "%s: a row's record names no block", who);   // (never)
         for (const HBlock &h : hb) any |= h.split;
@@ -140,6 +141,30 @@ void haplotigs_reads_run(const char *contigs, const char *reads, const hlmi_ava_
         PileupRows R;
         rows_from_reads(contigs, reads, ao, plain_request("hlmi_haplotigs_reads", o.min_len, o.min_iden, pairs_paf), R);
         haplotigs_body("hlmi_haplotigs_reads", R, o, out_fa, out_blocks, st);
+    });
+    st->phase.ms_total = st->ms_total;
+}
+
+void haplotigs_reach_run(const char *contigs, const char *reads, const char *paf, const hlmi_haplotig_opts &o, int reach, const char *pairs_paf,
+                         const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st) {
+    timed_call(st, true, [&] {
+        check_opts("hlmi_haplotigs_reach", o);
+        check_reach("hlmi_haplotigs_reach", reach);
+        PileupRows R;
+        rows_from_paf(contigs, reads, paf, plain_request("hlmi_haplotigs_reach", o.min_len, o.min_iden, pairs_paf), R);
+        haplotigs_body("hlmi_haplotigs_reach", R, o, out_fa, out_blocks, st, reach);
+    });
+    st->phase.ms_total = st->ms_total;
+}
+
+void haplotigs_reads_reach_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_haplotig_opts &o, int reach,
+                               const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st) {
+    timed_call(st, true, [&] {
+        check_opts("hlmi_haplotigs_reads_reach", o);
+        check_reach("hlmi_haplotigs_reads_reach", reach);
+        PileupRows R;
+        rows_from_reads(contigs, reads, ao, plain_request("hlmi_haplotigs_reads_reach", o.min_len, o.min_iden, pairs_paf), R);
+        haplotigs_body("hlmi_haplotigs_reads_reach", R, o, out_fa, out_blocks, st, reach);
     });
     st->phase.ms_total = st->ms_total;
 }

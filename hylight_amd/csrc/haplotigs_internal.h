@@ -34,5 +34,10 @@ void haplotigs_run(const char *contigs, const char *reads, const char *paf, cons
                    const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st);
 void haplotigs_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_haplotig_opts &o, const char *pairs_paf,
                          const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st);
+// ... over the blocks of hlmi_phase_reach's rule
+void haplotigs_reach_run(const char *contigs, const char *reads, const char *paf, const hlmi_haplotig_opts &o, int reach, const char *pairs_paf,
+                         const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st);
+void haplotigs_reads_reach_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_haplotig_opts &o, int reach,
+                               const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st);
 
 }  // namespace hlmi

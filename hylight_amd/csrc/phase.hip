@@ -14,7 +14,9 @@
 //                         no link across a junction is ever counted
 //   (host)                blocks and phase bits from the link counters (phase_text.h: build_blocks); 5 B per site go back up
 //   phase_slots_kernel    a thread per row: the blocks it touches, block_index[s_hi - 1] - block_index[s_lo] + 1; a scan
-//   phase_assign_kernel   a thread per row walks its allele bytes once and writes one 24-byte record per block into its slots
+//   phase_assign_kernel   a thread per row walks its allele bytes once and writes one 24-byte record per block into its slots;
+//                         <true> (hlmi_phase_reach): a site whose bit byte is BIT_BRIDGED counts in spanned alone
+// With reach >= 1 (hlmi_phase_reach and its kin) the link pass is phase_reach.hip's and the blocks are build_blocks_reach's.
 // Every loop is bounded by a count known at its head; the searches are counted.
 #include <hip/hip_runtime.h>
 
@@ -104,10 +106,6 @@ __global__ __launch_bounds__(WG) void phase_allele_kernel(const AlleleArgs A) {
     }
 }
 
-struct LinkTile {
-    uint32_t row_lo, row_hi;
-};
-
 __global__ __launch_bounds__(WG) void phase_link_kernel(const LinkTile *__restrict__ tiles, uint32_t n_tiles, uint32_t n_links, uint32_t n_rows,
                                                         const uint32_t *__restrict__ s_lo, const uint32_t *__restrict__ cnt,
                                                         const uint64_t *__restrict__ off, const uint8_t *__restrict__ table,
@@ -148,6 +146,7 @@ __global__ __launch_bounds__(WG) void phase_slots_kernel(uint32_t n_rows, const 
     }
 }
 
+template <bool REACH>
 __global__ __launch_bounds__(WG) void phase_assign_kernel(uint32_t n_rows, const uint32_t *__restrict__ s_lo, const uint32_t *__restrict__ cnt,
                                                           const uint64_t *__restrict__ off, const uint8_t *__restrict__ table,
                                                           const uint32_t *__restrict__ block_index, const uint8_t *__restrict__ bit,
@@ -169,6 +168,7 @@ __global__ __launch_bounds__(WG) void phase_assign_kernel(uint32_t n_rows, const
             }
             const uint32_t al = a[i];
             ++cur.spanned;
+            if (REACH && bit[lo + i] == BIT_BRIDGED) continue;
             if (al < 2) ++((al ^ (uint32_t)(bit[lo + i] & 1u)) == 0 ? cur.a : cur.b);
             else if (al == AL_OTHER) ++cur.other;
         }
@@ -182,13 +182,26 @@ __global__ __launch_bounds__(WG) void phase_qrank_kernel(const PafRec *__restric
     for (size_t j = (size_t)blockIdx.x * WG + threadIdx.x; j < n_sel; j += step) out[j] = recs[idx[j]].qid;
 }
 
+}  // namespace
+
 void check_fits(const char *who, const char *what, uint64_t bytes) {
     const size_t avail = dev_available_bytes();             // 0: unknown
     if (avail && bytes > avail)
         fail(HLMI_EINVAL, "%s: %s of %llu bytes does not fit the device's free memory (%zu)", who, what, (unsigned long long)bytes, avail);
 }
 
-}  // namespace
+std::vector<LinkTile> link_tiles(const std::vector<uint32_t> &s_lo, const std::vector<uint32_t> &cnt, size_t n_links, size_t tile) {
+    const size_t R = s_lo.size(), n_tiles = (n_links + tile - 1) / tile;
+    std::vector<LinkTile> tiles(n_tiles);
+    size_t lo = 0, hi = 0;
+    for (size_t t = 0; t < n_tiles; ++t) {
+        const uint64_t l0 = (uint64_t)t * tile, l1 = std::min<uint64_t>(l0 + tile, n_links);
+        while (hi < R && s_lo[hi] < l1) ++hi;
+        while (lo < hi && (uint64_t)s_lo[lo] + cnt[lo] < l0 + 2) ++lo;
+        tiles[t] = LinkTile{(uint32_t)lo, (uint32_t)hi};
+    }
+    return tiles;
+}
 
 std::vector<uint32_t> selected_query_ranks(const PafRec *recs, const uint32_t *idx, size_t n_sel) {
     if (!n_sel) return {};
@@ -199,17 +212,33 @@ std::vector<uint32_t> selected_query_ranks(const PafRec *recs, const uint32_t *i
 }
 
 void phase_core(const char *who, const PolCoreIn &in, const std::vector<PSite> &sites, const hlmi_phase_opts &o, DevicePhase &out,
-                DevRecs *keep) {
+                DevRecs *keep, int reach) {
     out = DevicePhase{};
+    out.far.reach = reach;
     if (keep) *keep = DevRecs{};
     const size_t N = sites.size(), R = in.n_rows;
+    // the blocks from what the link pass left: neighbours alone (reach 0), or every distance up to reach
+    auto blocks = [&]() {
+        if (!reach) {
+            out.blocks = build_blocks(sites, out.links, o.min_link, o.min_agree);
+            return;
+        }
+        const ReachBlocks rb = build_blocks_reach(sites, out.far, o.min_link, o.min_agree);
+        out.blocks = rb.base;
+        out.links_far = rb.links_far;
+        out.links_far_phased = rb.links_far_phased;
+        out.joins_far = rb.joins_far;
+        out.sites_bridged = rb.sites_bridged;
+        out.links_conflict = rb.links_conflict;
+    };
     if (!N) {
-        out.blocks = build_blocks(sites, out.links, o.min_link, o.min_agree);
+        blocks();
         return;
     }
     if (N >= (1ull << 31)) fail(HLMI_EINVAL, "%s: %zu sites (2^31 and more)", who, N);              // (never: positions < 2^31)
     const size_t n_links = N - 1;
     out.links.assign(n_links, LinkCounts{0, 0, 0, 0});
+    if (reach) out.far.n.assign(n_links * (size_t)reach, LinkCounts{0, 0, 0, 0});
     DBuf<uint32_t> d_pos, d_lo(std::max<size_t>(R, 1)), d_cnt(std::max<size_t>(R, 1));
     DBuf<uint8_t> d_pack, d_table;
     DBuf<uint64_t> d_off(std::max<size_t>(R, 1));
@@ -240,21 +269,20 @@ void phase_core(const char *who, const PolCoreIn &in, const std::vector<PSite> &
             HIP_CHECK(hipGetLastError());
         }
     }
-    if (out.alleles && n_links) {
+    if (out.alleles && n_links && reach) {
+        KTimer kt("phase_link_reach");
+        s_lo = d_lo.download(R);
+        cnt = d_cnt.download(R);
+        link_reach(who, s_lo, cnt, n_links, d_lo.p, d_cnt.p, d_off.p, d_table.p, out.far);
+        for (size_t j = 0; j < n_links; ++j) out.links[j] = out.far.at(j, 1);
+    } else if (out.alleles && n_links) {
         KTimer kt("phase_link");
         s_lo = d_lo.download(R);
         cnt = d_cnt.download(R);
         // the rows of every tile of links as polish_layout finds a position tile's: from the first row that holds a link of the
         // tile or a later one to the last row that starts in front of the tile's end (s_lo ascends with the rows)
-        const size_t n_tiles = (n_links + PHASE_TILE - 1) / PHASE_TILE;
-        std::vector<LinkTile> tiles(n_tiles);
-        size_t lo = 0, hi = 0;
-        for (size_t t = 0; t < n_tiles; ++t) {
-            const uint64_t l0 = (uint64_t)t * PHASE_TILE, l1 = std::min<uint64_t>(l0 + PHASE_TILE, n_links);
-            while (hi < R && s_lo[hi] < l1) ++hi;
-            while (lo < hi && (uint64_t)s_lo[lo] + cnt[lo] < l0 + 2) ++lo;
-            tiles[t] = LinkTile{(uint32_t)lo, (uint32_t)hi};
-        }
+        const std::vector<LinkTile> tiles = link_tiles(s_lo, cnt, n_links, PHASE_TILE);
+        const size_t n_tiles = tiles.size();
         DBuf<LinkTile> d_tiles;
         d_tiles.upload(tiles);
         DBuf<LinkCounts> d_links(n_links);
@@ -263,7 +291,7 @@ void phase_core(const char *who, const PolCoreIn &in, const std::vector<PSite> &
         HIP_CHECK(hipGetLastError());
         out.links = d_links.download(n_links);
     }
-    out.blocks = build_blocks(sites, out.links, o.min_link, o.min_agree);
+    blocks();
     if (out.alleles) {
         KTimer kt("phase_assign");
         DBuf<uint32_t> d_index, d_slots(R);
@@ -280,8 +308,12 @@ void phase_core(const char *who, const PolCoreIn &in, const std::vector<PSite> &
         if (n_recs) {
             DBuf<ReadRec> d_recs(n_recs);
             d_recs.zero();
-            hipLaunchKernelGGL(phase_assign_kernel, grid1(R), dim3(WG), 0, stream(), (uint32_t)R, d_lo.p, d_cnt.p, d_off.p, d_table.p, d_index.p,
-                               d_bit.p, d_slots.p, d_rec_off.p, d_recs.p);
+            if (reach)
+                hipLaunchKernelGGL(phase_assign_kernel<true>, grid1(R), dim3(WG), 0, stream(), (uint32_t)R, d_lo.p, d_cnt.p, d_off.p, d_table.p,
+                                   d_index.p, d_bit.p, d_slots.p, d_rec_off.p, d_recs.p);
+            else
+                hipLaunchKernelGGL(phase_assign_kernel<false>, grid1(R), dim3(WG), 0, stream(), (uint32_t)R, d_lo.p, d_cnt.p, d_off.p, d_table.p,
+                                   d_index.p, d_bit.p, d_slots.p, d_rec_off.p, d_recs.p);
             HIP_CHECK(hipGetLastError());
             out.recs = d_recs.download(n_recs);
             if (keep) {

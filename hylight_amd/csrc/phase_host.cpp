@@ -2,8 +2,10 @@
 // phased from the reads - links between neighbouring sites, blocks, and every read's side per block.  The rows come from the
 // pile-up calls' row front (polish_select.h), the sites are variants_core's over them; the allele table, the link counters and the
 // records per (row, block) are phase.hip's, the rules' arithmetic and the three files' text phase_text.h's.  phase_device and
-// phase_emit are the two halves of the body that hlmi_haplotigs calls as well.
-// PARITY UNPINNED: a function of the project's own; tests/phase_model.py is the contract.
+// phase_emit are the two halves of the body that hlmi_haplotigs calls as well.  hlmi_phase_reach and hlmi_phase_reads_reach are
+// the same four statements with `reach` handed down: links of every distance up to it (phase_reach.hip), the block rule and the
+// two files that differ in phase_reach_text.h.
+// PARITY UNPINNED: a function of the project's own; tests/phase_model.py and tests/phase_reach_model.py are the contract.
 #include <cmath>
 #include <string>
 #include <string_view>
@@ -37,7 +39,11 @@ void check_phase_opts(const char *who, const hlmi_phase_opts &o) {
     if (!(o.min_agree > 0.5 && o.min_agree <= 1.0)) fail(HLMI_EINVAL, "%s: min_agree %g (outside (0.5, 1] or not a number)", who, o.min_agree);
 }
 
-void phase_device(const char *who, const PileupRows &R, const hlmi_phase_opts &o, Phased &P, DevRecs *keep) {
+void check_reach(const char *who, int reach) {
+    if (reach < 1 || reach > HLMI_PHASE_REACH_MAX) fail(HLMI_EINVAL, "%s: reach %d (outside [1, %d])", who, reach, HLMI_PHASE_REACH_MAX);
+}
+
+void phase_device(const char *who, const PileupRows &R, const hlmi_phase_opts &o, Phased &P, DevRecs *keep, int reach) {
     const SeqSet &cs = R.cs();
     const PolLayout &L = R.L;
     variants_core(R.up.core, variant_part(o), P.var);
@@ -45,13 +51,14 @@ void phase_device(const char *who, const PileupRows &R, const hlmi_phase_opts &o
     for (size_t c = 0; c < cs.size(); ++c) seq[c] = std::string_view(cs.bases).substr(cs.off[c], cs.len(c));
     if (!phase_sites(seq, L.rc, L.slot_of_contig, L.cbase, P.var, P.sites))
         fail(HLMI_ESTATE, "%s: the sites' records do not fit the contigs", who);                                    // (never)
-    phase_core(who, R.up.core, P.sites, o, P.dev, keep);
+    phase_core(who, R.up.core, P.sites, o, P.dev, keep, reach);
 }
 
 void phase_emit(const char *who, const PileupRows &R, const Phased &P, const hlmi_phase_opts &o, const std::vector<uint32_t> &rows_read,
-                const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st) {
+                const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st, hlmi_phase_reach_stats *far) {
     const SeqSet &cs = R.cs();
     const PolLayout &L = R.L;
+    const bool reach = P.dev.far.reach >= 1;
     std::vector<uint64_t> length;
     std::vector<std::string_view> seq;
     contig_views(cs, length, seq);
@@ -74,12 +81,21 @@ void phase_emit(const char *who, const PileupRows &R, const Phased &P, const hlm
     st->blocks_multi = B.blocks_multi;
     st->sites_phased = B.sites_phased;
     st->alleles = P.dev.alleles;
+    if (far) {
+        far->links_far = P.dev.links_far;
+        far->links_far_phased = P.dev.links_far_phased;
+        far->joins_far = P.dev.joins_far;
+        far->sites_bridged = P.dev.sites_bridged;
+        far->links_conflict = P.dev.links_conflict;
+    }
     stat_set("variants_tiles", (double)P.var.tiles);
     stat_set("variants_tiles_revisited", (double)P.var.tiles_revisited);
 
     std::vector<std::string> sites, links, reads;
-    if (out_sites) sites = phase_site_lines(cs.names, P.sites, B);
-    if (out_links) links = phase_link_lines(cs.names, P.sites, P.dev.links, o.min_link, o.min_agree);
+    if (out_sites) sites = reach ? phase_reach_site_lines(cs.names, P.sites, B) : phase_site_lines(cs.names, P.sites, B);
+    if (out_links)
+        links = reach ? phase_reach_link_lines(cs.names, P.sites, P.dev.far, o.min_link, o.min_agree)
+                      : phase_link_lines(cs.names, P.sites, P.dev.links, o.min_link, o.min_agree);
     ReadTotals rt;
     if (!phase_read_lines(cs.names, R.rs().names, rows_read, P.sites, B, P.dev.recs, out_reads ? &reads : nullptr, &rt))
         fail(HLMI_ESTATE, "%s: a row's record names no block or no read", who);                                     // (never)
@@ -96,16 +112,16 @@ void phase_emit(const char *who, const PileupRows &R, const Phased &P, const hlm
 
 namespace {
 
-// what both entry points do behind the rows: sites and phasing, the statistics and the three files
+// what the entry points do behind the rows: sites and phasing, the statistics and the three files.  reach 0: the plain calls
 void phase_body(const char *who, const PileupRows &R, const hlmi_phase_opts &o, const char *out_sites, const char *out_links,
-                const char *out_reads, hlmi_phase_stats *st) {
+                const char *out_reads, hlmi_phase_stats *st, int reach = 0, hlmi_phase_reach_stats *far = nullptr) {
     set_row_stats(R, st);
     Phased P;
-    phase_device(who, R, o, P);
+    phase_device(who, R, o, P, nullptr, reach);
     std::vector<uint32_t> rows_read;            // when a record needs its read's name (aligned rows: 4 bytes per row come down)
     if (out_reads && !P.dev.recs.empty()) rows_read = R.read_of_row();
     st->ms_device = now_ms() - R.t_dev;
-    phase_emit(who, R, P, o, rows_read, out_sites, out_links, out_reads, st);
+    phase_emit(who, R, P, o, rows_read, out_sites, out_links, out_reads, st, far);
 }
 
 }  // namespace
@@ -127,6 +143,31 @@ void phase_reads_run(const char *contigs, const char *reads, const hlmi_ava_opts
         PileupRows R;
         rows_from_reads(contigs, reads, ao, plain_request("hlmi_phase_reads", o.min_len, o.min_iden, pairs_paf), R);
         phase_body("hlmi_phase_reads", R, o, out_sites, out_links, out_reads, st);
+    });
+}
+
+void phase_reach_run(const char *contigs, const char *reads, const char *paf, const hlmi_phase_opts &o, int reach, const char *pairs_paf,
+                     const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_reach_stats *st) {
+    *st = hlmi_phase_reach_stats{};
+    timed_call(&st->base, true, [&] {
+        check_phase_opts("hlmi_phase_reach", o);
+        check_reach("hlmi_phase_reach", reach);
+        PileupRows R;
+        rows_from_paf(contigs, reads, paf, plain_request("hlmi_phase_reach", o.min_len, o.min_iden, pairs_paf), R);
+        phase_body("hlmi_phase_reach", R, o, out_sites, out_links, out_reads, &st->base, reach, st);
+    });
+}
+
+void phase_reads_reach_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_phase_opts &o, int reach,
+                           const char *pairs_paf, const char *out_sites, const char *out_links, const char *out_reads,
+                           hlmi_phase_reach_stats *st) {
+    *st = hlmi_phase_reach_stats{};
+    timed_call(&st->base, true, [&] {
+        check_phase_opts("hlmi_phase_reads_reach", o);
+        check_reach("hlmi_phase_reads_reach", reach);
+        PileupRows R;
+        rows_from_reads(contigs, reads, ao, plain_request("hlmi_phase_reads_reach", o.min_len, o.min_iden, pairs_paf), R);
+        phase_body("hlmi_phase_reads_reach", R, o, out_sites, out_links, out_reads, &st->base, reach, st);
     });
 }
 

@@ -125,21 +125,32 @@ inline Blocks build_blocks(const std::vector<PSite> &sites, const std::vector<Li
 // rule 5
 inline char hap_of(uint32_t a, uint32_t b) { return a > b ? 'A' : b > a ? 'B' : '-'; }
 
+// one line of out_sites; first: the first site of the site's block, phase: the text of the last column
+inline std::string phase_site_line(const std::vector<std::string> &names, const PSite &s, const PSite &first, const char *phase) {
+    uint64_t depth = 0;
+    for (int q = 0; q < var::N_SYM; ++q) depth += s.v[q];
+    char buf[160];
+    snprintf(buf, sizeof buf, "\t%llu\t%c\t%c\t%llu\t%u\t%u\t%llu\t%s", (unsigned long long)s.pos + 1, "ACGT"[s.own], "ACGT*"[s.alt],
+             (unsigned long long)depth, s.v[s.own], s.v[s.alt], (unsigned long long)first.pos + 1, phase);
+    return names[s.contig] + buf;
+}
+
 inline std::vector<std::string> phase_site_lines(const std::vector<std::string> &names, const std::vector<PSite> &sites, const Blocks &B) {
     std::vector<std::string> lines;
     lines.reserve(sites.size() + 1);
     lines.push_back("#contig\tpos\tref\talt\tdepth\tref_count\talt_count\tblock\tphase");
-    for (size_t i = 0; i < sites.size(); ++i) {
-        const PSite &s = sites[i];
-        uint64_t depth = 0;
-        for (int q = 0; q < var::N_SYM; ++q) depth += s.v[q];
-        char buf[160];
-        snprintf(buf, sizeof buf, "\t%llu\t%c\t%c\t%llu\t%u\t%u\t%llu\t%s", (unsigned long long)s.pos + 1, "ACGT"[s.own], "ACGT*"[s.alt],
-                 (unsigned long long)depth, s.v[s.own], s.v[s.alt], (unsigned long long)sites[B.first[B.index[i]]].pos + 1,
-                 B.bit[i] ? "1|0" : "0|1");
-        lines.push_back(names[s.contig] + buf);
-    }
+    for (size_t i = 0; i < sites.size(); ++i) lines.push_back(phase_site_line(names, sites[i], sites[B.first[B.index[i]]], B.bit[i] ? "1|0" : "0|1"));
     return lines;
+}
+
+// one line of out_links: the link between the sites a and b (a in front of b, one contig) with the counters c
+inline std::string phase_link_line(const std::vector<std::string> &names, const PSite &a, const PSite &b, const LinkCounts &c, int min_link,
+                                   double min_agree) {
+    const LinkCall k = link_call(c, min_link, min_agree);
+    char buf[192];
+    snprintf(buf, sizeof buf, "\t%llu\t%llu\t%u\t%u\t%u\t%u\t%llu\t%.6f\t%s", (unsigned long long)a.pos + 1, (unsigned long long)b.pos + 1, c.n00,
+             c.n01, c.n10, c.n11, (unsigned long long)k.inf, k.agree, k.phased == LINK_CIS ? "cis" : k.phased == LINK_TRANS ? "trans" : "-");
+    return names[a.contig] + buf;
 }
 
 inline std::vector<std::string> phase_link_lines(const std::vector<std::string> &names, const std::vector<PSite> &sites,
@@ -148,13 +159,7 @@ inline std::vector<std::string> phase_link_lines(const std::vector<std::string> 
     lines.push_back("#contig\tpos1\tpos2\tn00\tn01\tn10\tn11\tinformative\tagree\tphased");
     for (size_t i = 0; i + 1 < sites.size() && i < links.size(); ++i) {
         if (sites[i].contig != sites[i + 1].contig) continue;
-        const LinkCounts &c = links[i];
-        const LinkCall k = link_call(c, min_link, min_agree);
-        char buf[192];
-        snprintf(buf, sizeof buf, "\t%llu\t%llu\t%u\t%u\t%u\t%u\t%llu\t%.6f\t%s", (unsigned long long)sites[i].pos + 1,
-                 (unsigned long long)sites[i + 1].pos + 1, c.n00, c.n01, c.n10, c.n11, (unsigned long long)k.inf, k.agree,
-                 k.phased == LINK_CIS ? "cis" : k.phased == LINK_TRANS ? "trans" : "-");
-        lines.push_back(names[sites[i].contig] + buf);
+        lines.push_back(phase_link_line(names, sites[i], sites[i + 1], links[i], min_link, min_agree));
     }
     return lines;
 }

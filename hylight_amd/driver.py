@@ -238,12 +238,13 @@ def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pai
     return out
 
 
-def phase_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None):
+def phase_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None, reach=1):
     """`--phase`: the variant sites of the final contigs phased from the reads (hlmi_phase_reads: the reads are aligned to the
     contigs in the call, every pair, one row per read).  The long reads with the overlapper's long constants give
     outdir/final_contigs.long.phase.sites.tsv, .links.tsv and .reads.tsv; short reads, when there are any, with the short
     constants give the .short. triple.  long_pairs / short_pairs: as for variant_tables.  `device`: the GPU to initialise the
-    library on (None: the caller has done so).  -> {"long": stats, "short": stats}."""
+    library on (None: the caller has done so).  reach (`--phase_reach`) above 1: hlmi_phase_reads_reach, links between sites up to
+    `reach` apart.  -> {"long": stats, "short": stats}."""
     if device is not None:
         api.init(device)
     out = {}
@@ -253,16 +254,19 @@ def phase_tables(final, long_reads, short_reads, outdir, device=None, long_pairs
         o = api.ava_opts_short() if kind == "short" else api.ava_opts_long()
         o.pair_once = 0
         stem = os.path.join(outdir, f"final_contigs.{kind}.phase")
-        out[kind] = api.phase_reads(final, reads, stem + ".sites.tsv", stem + ".links.tsv", stem + ".reads.tsv", o, pairs=pairs)
+        files = (stem + ".sites.tsv", stem + ".links.tsv", stem + ".reads.tsv")
+        out[kind] = (api.phase_reads(final, reads, *files, o, pairs=pairs) if reach == 1 else
+                     api.phase_reads_reach(final, reads, *files, o, pairs=pairs, reach=reach))
     return out
 
 
-def haplotig_files(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None):
+def haplotig_files(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None, reach=1):
     """`--haplotigs`: the final contigs polished once per side of every phased block the reads split (hlmi_haplotigs_reads: the
     reads are aligned to the contigs in the call, every pair, one row per read).  The long reads with the overlapper's long
     constants give outdir/final_contigs.long.haplotigs.fa and .long.haplotigs.blocks.tsv; short reads, when there are any, with
     the short constants give the .short. pair.  long_pairs / short_pairs: as for phase_tables.  `device`: the GPU to initialise
-    the library on (None: the caller has done so).  -> {"long": stats, "short": stats}."""
+    the library on (None: the caller has done so).  reach (`--phase_reach`) above 1: hlmi_haplotigs_reads_reach.
+    -> {"long": stats, "short": stats}."""
     if device is not None:
         api.init(device)
     out = {}
@@ -272,7 +276,8 @@ def haplotig_files(final, long_reads, short_reads, outdir, device=None, long_pai
         o = api.ava_opts_short() if kind == "short" else api.ava_opts_long()
         o.pair_once = 0
         stem = os.path.join(outdir, f"final_contigs.{kind}.haplotigs")
-        out[kind] = api.haplotigs_reads(final, reads, stem + ".fa", stem + ".blocks.tsv", o, pairs=pairs)
+        out[kind] = (api.haplotigs_reads(final, reads, stem + ".fa", stem + ".blocks.tsv", o, pairs=pairs) if reach == 1 else
+                     api.haplotigs_reads_reach(final, reads, stem + ".fa", stem + ".blocks.tsv", o, pairs=pairs, reach=reach))
     return out
 
 
@@ -360,6 +365,9 @@ def build_parser():
                         "the reads split (hlmi_haplotigs_reads) into final_contigs.long.haplotigs.fa and "
                         ".long.haplotigs.blocks.tsv, and with -s also the .short. pair; independent of --phase; with "
                         "--polish_strain only the pairs of ov_long_ref.paf / shortr1.paf vote")
+    p.add_argument("--phase_reach", type=int, default=1, metavar="K",
+                   help="(extension) with --phase and --haplotigs: link variant sites up to K sites apart (hlmi_phase_reads_reach, "
+                        "hlmi_haplotigs_reads_reach; 1: neighbours alone, at most 8), so that one noisy site does not cut a block")
     return p
 
 
@@ -612,10 +620,12 @@ def _pipeline(args, pool):
                            **({"ins": True} if args.variants_ins else {}))
         if rc == 0 and args.phase:
             phase_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
-                         long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None)
+                         long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None,
+                         **({"reach": args.phase_reach} if args.phase_reach != 1 else {}))
         if rc == 0 and args.haplotigs:
             haplotig_files(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
-                           long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None)
+                           long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None,
+                           **({"reach": args.phase_reach} if args.phase_reach != 1 else {}))
         return rc
     # HyLight.py:211-262 (read clustering, POLYTE per cluster) is the short-read branch: not part of this path.  Its
     # contigs can be handed in; the contig-overlap half of extend_con runs either way (HyLight.py:264-280).
@@ -657,10 +667,10 @@ def _pipeline(args, pool):
                        short_pairs=ov_short if args.polish_strain else None, **({"ins": True} if args.variants_ins else {}))
     if args.phase:
         phase_tables(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
-                     short_pairs=ov_short if args.polish_strain else None)
+                     short_pairs=ov_short if args.polish_strain else None, **({"reach": args.phase_reach} if args.phase_reach != 1 else {}))
     if args.haplotigs:
         haplotig_files(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
-                       short_pairs=ov_short if args.polish_strain else None)
+                       short_pairs=ov_short if args.polish_strain else None, **({"reach": args.phase_reach} if args.phase_reach != 1 else {}))
     return 0
 
 

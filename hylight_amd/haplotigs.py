@@ -14,6 +14,8 @@ constants, --short: its short-read ones; every pair, pair_once = 0) and no PAF e
 of different blocks are independent of each other), every other contig as the polish module writes it; --blocks: one line per
 block of two or more sites (contig, block, start, end, sites, rows_a, rows_b, split, diff_positions).  Prints the stats as one
 JSON line.  Exit status 0 on success.
+--reach K (2 .. 8; hlmi_haplotigs_reach): the blocks of `python -m hylight_amd.phase --reach K`, whose extents cover their bridged
+sites.  The default 1 is the call without it.
 """
 from __future__ import annotations
 
@@ -46,6 +48,7 @@ def build_parser():
     p.add_argument("--min_agree", type=float, default=0.8, help="share of the informative rows on the link's majority side")
     p.add_argument("--min_side", type=int, default=3, help="rows a block needs on either side to be split")
     p.add_argument("--include_unpolished", type=int, default=1, choices=(0, 1), help="write contigs without a selected row as they are")
+    p.add_argument("--reach", type=int, default=1, metavar="K", help="link sites up to K sites apart (1: neighbours alone; at most 8)")
     return p
 
 
@@ -57,7 +60,12 @@ def main(argv=None):
     if a.paf is not None:
         if a.short:
             parser.error("--short chooses the alignment of a call without --paf")
-        st = api.haplotigs(a.contigs, a.reads, a.paf, a.out, a.blocks, pairs=a.pairs, **opts)
+        if a.reach != 1:
+            st = api.haplotigs_reach(a.contigs, a.reads, a.paf, a.out, a.blocks, pairs=a.pairs, reach=a.reach, **opts)
+        else:
+            st = api.haplotigs(a.contigs, a.reads, a.paf, a.out, a.blocks, pairs=a.pairs, **opts)
+    elif a.reach != 1:
+        st = api.haplotigs_reads_reach(a.contigs, a.reads, a.out, a.blocks, read_ava_opts(a.short), pairs=a.pairs, reach=a.reach, **opts)
     else:
         st = api.haplotigs_reads(a.contigs, a.reads, a.out, a.blocks, read_ava_opts(a.short), pairs=a.pairs, **opts)
     print(json.dumps(st))

@@ -13,6 +13,9 @@ constants, --short: its short-read ones; every pair, pair_once = 0) and no PAF e
 --out: the sites (contig, pos, ref, alt, depth, ref_count, alt_count, block, phase); --links: one line per pair of consecutive
 sites (contig, pos1, pos2, n00, n01, n10, n11, informative, agree, phased); --read-haps: one line per read and block (read, contig,
 block, spanned, hap_a, hap_b, other, hap).  Prints the stats as one JSON line.  Exit status 0 on success.
+--reach K (2 .. 8; hlmi_phase_reach) also links sites up to K sites apart, so that one noisy site does not cut a block: a site
+inside a block that joined nothing is bridged (its block's id, phase "."), --links has one line per link of any distance.  The
+default 1 is the call without it.
 """
 from __future__ import annotations
 
@@ -45,6 +48,7 @@ def build_parser():
     p.add_argument("--min_frac", type=float, default=0.2, help="share of the position's votes the alternative symbol needs")
     p.add_argument("--min_link", type=int, default=3, help="informative rows a link needs")
     p.add_argument("--min_agree", type=float, default=0.8, help="share of the informative rows on the link's majority side")
+    p.add_argument("--reach", type=int, default=1, metavar="K", help="link sites up to K sites apart (1: neighbours alone; at most 8)")
     return p
 
 
@@ -56,7 +60,12 @@ def main(argv=None):
     if a.paf is not None:
         if a.short:
             parser.error("--short chooses the alignment of a call without --paf")
-        st = api.phase(a.contigs, a.reads, a.paf, a.out, a.links, a.read_haps, pairs=a.pairs, **opts)
+        if a.reach != 1:
+            st = api.phase_reach(a.contigs, a.reads, a.paf, a.out, a.links, a.read_haps, pairs=a.pairs, reach=a.reach, **opts)
+        else:
+            st = api.phase(a.contigs, a.reads, a.paf, a.out, a.links, a.read_haps, pairs=a.pairs, **opts)
+    elif a.reach != 1:
+        st = api.phase_reads_reach(a.contigs, a.reads, a.out, a.links, a.read_haps, read_ava_opts(a.short), pairs=a.pairs, reach=a.reach, **opts)
     else:
         st = api.phase_reads(a.contigs, a.reads, a.out, a.links, a.read_haps, read_ava_opts(a.short), pairs=a.pairs, **opts)
     print(json.dumps(st))

@@ -1108,6 +1108,50 @@ int hlmi_phase(const char *contigs, const char *reads, const char *paf, const hl
 int hlmi_phase_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_phase_opts *o, const char *pairs_paf,
                      const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_stats *st);
 
+/* ---- phasing across a noisy site: links between sites up to `reach` apart.  hlmi_phase joins sites through the link between
+ * neighbours only, so one unreliable site - a homopolymer error called as a site, a site with few informative rows - cuts a block in
+ * two although the reads that span it say that the sites on either side belong together.  These calls read that evidence.  New
+ * symbols: the older calls keep their signatures and their bytes, and HLMI_ABI_VERSION stays where it is.  A function of the
+ * project's own: PARITY UNPINNED; tests/phase_reach_model.py is the contract, byte for byte. */
+#define HLMI_PHASE_REACH_MAX 8
+typedef struct {
+    hlmi_phase_stats base;      /* as hlmi_phase's; links and links_phased count the links of distance 1, blocks_multi the blocks
+                                   of two or more sites, sites_phased the members of such blocks (bridged sites are not included) */
+    uint64_t links_far;         /* links of distance 2 .. reach inside one contig                                           */
+    uint64_t links_far_phased;
+    uint64_t joins_far;         /* members that joined their block through a link of distance >= 2                          */
+    uint64_t sites_bridged;     /* sites inside a block that are no member of it                                            */
+    uint64_t links_conflict;    /* phased links between two members of one block that contradict their bits                 */
+} hlmi_phase_reach_stats;
+/* contigs, reads, paf, o, pairs_paf and the three files: as for hlmi_phase.  reach = K, 1 <= K <= HLMI_PHASE_REACH_MAX.
+ * Everything up to and including a row's allele at a site is hlmi_phase's, run by the same code.
+ * Links: one per pair of sites (i, i + d) of one contig, 1 <= d <= K, the sites counted in ascending order.  The four counters, inf,
+ * agree and the phased / cis / trans decision are hlmi_phase's link rule, over the rows whose allele is 0 or 1 at both sites; what
+ * the rows read at the sites in between plays no part.
+ * Blocks, per contig, sites ascending: a block starts at its first site b, a member with bit 0.  Going up from b + 1, site i joins
+ * the block iff one of the members j with i - K <= j < i has a phased link (j, i); the nearest such member decides: bit[i] = bit[j]
+ * XOR (the link is trans).  The walk ends at the first site more than K sites behind the last member, or with the contig.  The block
+ * is the sites b .. last member - still a run of consecutive sites, its id the 1-based position of its first site - and the next
+ * block starts behind it.  The sites among them that did not join are bridged: a bridged site has no phase bit.  With K = 1 this is
+ * hlmi_phase's rule.
+ * Conflicts: a phased link (j, i), i - j <= K, between two members of one block whose direction is not bit[j] XOR bit[i] is
+ * counted in links_conflict and changes nothing.
+ * Reads: hlmi_phase's records over these blocks; a bridged site counts in spanned and in none of hap_a, hap_b, other.
+ * Files: the three files of hlmi_phase, same header lines and columns.  out_sites: a bridged site has its block's id in the block
+ * column and "." in the phase column.  out_links: one line per link of any distance, ordered by (left site, right site).
+ * With reach = 1 the three files are byte for byte hlmi_phase's and the integer fields of base equal hlmi_phase's.
+ * Refusals: hlmi_phase's option refusals, in its order; reach < 1 or > HLMI_PHASE_REACH_MAX; then every other refusal of hlmi_phase,
+ * in its order; the link counters do not fit the device's free memory.
+ * The counters of 64 K bytes at the most per tile of left sites live in LDS (csrc/phase_reach.hip); 16 K bytes per site come to
+ * the host. */
+int hlmi_phase_reach(const char *contigs, const char *reads, const char *paf, const hlmi_phase_opts *o, int reach, const char *pairs_paf,
+                     const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_reach_stats *st);
+/* hlmi_phase_reads with the rule above: the two calls hlmi_ava(contigs, reads, ao, P) and hlmi_phase_reach(contigs, reads, P, o,
+ * reach, pairs_paf, ...) in one, without the PAF P; the stated differences of hlmi_phase_reads apply. */
+int hlmi_phase_reads_reach(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_phase_opts *o, int reach,
+                           const char *pairs_paf, const char *out_sites, const char *out_links, const char *out_reads,
+                           hlmi_phase_reach_stats *st);
+
 /* ---- haplotigs: polish each side of a phased block on its own.  hlmi_polish lets every read vote in every column, so inside a phased
  * block the majority strain wins; these calls give two consensus sequences where the reads prove two sides, and hlmi_polish's bytes
  * everywhere else.  hlmi_haplotigs reads a PAF as hlmi_phase does, hlmi_haplotigs_reads aligns in the call as hlmi_phase_reads does.
@@ -1170,8 +1214,8 @@ typedef struct {
  * consensus that turns out empty still counts) and summed.
  * Consequence: with no split block in the call - min_side above the number of rows is enough - out_fa is byte for byte hlmi_polish's
  * on the same input and options; the single-sided count pass produces it and no kernel of csrc/haplotigs.hip is launched.
- * Out of scope: quality weights; links between sites that are not neighbours; joining blocks across a contig; insertion sites as
- * phasing evidence.
+ * Out of scope: quality weights; joining blocks across a contig; insertion sites as phasing evidence.  (Links between sites that
+ * are not neighbours: hlmi_haplotigs_reach below.)
  * Refusals (HLMI_EINVAL unless said otherwise, nothing is written): hlmi_phase's option refusals, in its order; min_side < 1; then
  * every refusal hlmi_phase makes about the files, the rows, the list and its tables, in its order; the rows' interval table does not
  * fit the device's free memory; hlmi_polish's limits (2^28 bases in a sequence, 2^31 contig bases).
@@ -1184,6 +1228,16 @@ int hlmi_haplotigs(const char *contigs, const char *reads, const char *paf, cons
  * differences of hlmi_polish_reads apply (a name twice - which hlmi_haplotigs refuses as well -, stub_oh >= 0, 2^32 rows). */
 int hlmi_haplotigs_reads(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_haplotig_opts *o,
                          const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st);
+/* hlmi_haplotigs over the blocks of hlmi_phase_reach's rule, 1 <= reach <= HLMI_PHASE_REACH_MAX: the phasing is hlmi_phase_reach's
+ * (st->phase holds its base), every rule of hlmi_haplotigs stands as it is.  A block's extent runs from its first to its last
+ * site, the sites column of out_blocks counts every site in that range, bridged ones included, and a row's side comes from its
+ * record (which leaves bridged sites out).  With reach = 1 both files and the integer stats equal hlmi_haplotigs's byte for byte.
+ * Refusals: hlmi_haplotigs's option refusals, in its order; reach < 1 or > HLMI_PHASE_REACH_MAX; then the rest as hlmi_haplotigs. */
+int hlmi_haplotigs_reach(const char *contigs, const char *reads, const char *paf, const hlmi_haplotig_opts *o, int reach,
+                         const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st);
+/* hlmi_haplotigs_reads in the same way: hlmi_ava and hlmi_haplotigs_reach in one call, without the PAF. */
+int hlmi_haplotigs_reads_reach(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_haplotig_opts *o, int reach,
+                               const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st);
 
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
