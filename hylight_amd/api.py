@@ -205,6 +205,13 @@ class PhaseReachStats(C.Structure):
     _fields_ = [("base", PhaseStats)] + [(k, C.c_uint64) for k in PHASE_REACH_STATS]
 
 
+PHASE_INS_STATS = ("slots_callable", "ins_sites", "ins_long", "ins_edge", "ins_sites_phasing", "ins_sites_left_out", "ins_sites_phased")
+
+
+class PhaseInsStats(C.Structure):
+    _fields_ = [("reach", PhaseReachStats)] + [(k, C.c_uint64) for k in PHASE_INS_STATS]
+
+
 class HaplotigOpts(C.Structure):
     _fields_ = list(PhaseOpts._fields_) + [("min_side", C.c_int), ("include_unpolished", C.c_int)]
 
@@ -335,6 +342,10 @@ SYMBOLS = {
                                    C.c_char_p, C.POINTER(PhaseReachStats)]),
     "hlmi_phase_reads_reach": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PhaseOpts), C.c_int, C.c_char_p, C.c_char_p,
                                          C.c_char_p, C.c_char_p, C.POINTER(PhaseReachStats)]),
+    "hlmi_phase_ins": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PhaseOpts), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p,
+                                 C.c_char_p, C.POINTER(PhaseInsStats)]),
+    "hlmi_phase_reads_ins": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(PhaseOpts), C.c_int, C.c_char_p, C.c_char_p,
+                                       C.c_char_p, C.c_char_p, C.POINTER(PhaseInsStats)]),
     # haplotigs
     "hlmi_haplotig_opts_default": (None, [C.POINTER(HaplotigOpts)]),
     "hlmi_haplotigs": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(HaplotigOpts), C.c_char_p, C.c_char_p, C.c_char_p,
@@ -993,6 +1004,37 @@ def phase_reads_reach(contigs, reads, out_sites, out_links=None, out_reads=None,
     _check(load().hlmi_phase_reads_reach(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), int(reach),
                                          _b(pairs), _b(out_sites), _b(out_links), _b(out_reads), C.byref(st)))
     return _phase_reach_stats(st)
+
+
+def _phase_ins_stats(st):
+    out = _phase_reach_stats(st.reach)
+    out.update({k: getattr(st, k) for k in PHASE_INS_STATS})
+    return out
+
+
+def phase_ins(contigs, reads, paf, out_sites, out_links=None, out_reads=None, pairs=None, reach=1, **opts):
+    """hlmi_phase_ins: api.phase_reach over the merged list of api.variants's position sites and the insertion sites of
+    api.variants_ins that take part (len >= 1 and len_count >= min_alt); slot p sorts directly in front of position p.  At an
+    insertion site a row that spans the slot reads 0 if it inserts nothing there, 1 if it inserts the site's called length (by
+    length alone), 2 for any other length.  Links, blocks, bridged sites and read records are api.phase_reach's over the merged
+    list.  An insertion site's line has pos = p, the base in front of the slot, alt "+" and the called bases; a slot endpoint of a
+    link, and the id of a block that starts at an insertion site, carry a trailing "+".  Where no insertion site takes part the
+    files and the shared stats are api.phase_reach's.  include/hylight_mi.h states it, tests/phase_ins_model.py is its contract.
+    -> dict of the stats (hlmi_phase_ins_stats: api.phase_reach's keys, slots_callable, ins_sites, ins_long, ins_edge,
+    ins_sites_phasing, ins_sites_left_out, ins_sites_phased)."""
+    o, st = _phase_opts("phase_ins", opts), PhaseInsStats()
+    _check(load().hlmi_phase_ins(_b(contigs), _b(reads), _b(paf), C.byref(o), int(reach), _b(pairs), _b(out_sites), _b(out_links),
+                                 _b(out_reads), C.byref(st)))
+    return _phase_ins_stats(st)
+
+
+def phase_reads_ins(contigs, reads, out_sites, out_links=None, out_reads=None, ava_opts=None, pairs=None, reach=1, **opts):
+    """hlmi_phase_reads_ins: `ava(contigs, reads, P, ava_opts)` and `phase_ins(contigs, reads, P, ...)` in one call without the PAF
+    P, as phase_reads_reach is for phase_reach.  -> dict of the stats (hlmi_phase_ins_stats)."""
+    o, st = _phase_opts("phase_reads_ins", opts), PhaseInsStats()
+    _check(load().hlmi_phase_reads_ins(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o), int(reach),
+                                       _b(pairs), _b(out_sites), _b(out_links), _b(out_reads), C.byref(st)))
+    return _phase_ins_stats(st)
 
 
 def _haplotig_opts(who, opts):

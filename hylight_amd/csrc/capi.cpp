@@ -707,6 +707,25 @@ int hlmi_phase_reads_reach(const char *contigs, const char *reads, const hlmi_av
     });
 }
 
+int hlmi_phase_ins(const char *contigs, const char *reads, const char *paf, const hlmi_phase_opts *o, int reach, const char *pairs_paf,
+                   const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_ins_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_phase_ins: NULL argument");
+        require_device();
+        phase_ins_run(contigs, reads, paf, *o, reach, pairs_paf, out_sites, out_links, out_reads, st);
+    });
+}
+
+int hlmi_phase_reads_ins(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_phase_opts *o, int reach,
+                         const char *pairs_paf, const char *out_sites, const char *out_links, const char *out_reads,
+                         hlmi_phase_ins_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !o || !out_sites || !st) fail(HLMI_EINVAL, "hlmi_phase_reads_ins: NULL argument");
+        require_device();
+        phase_reads_ins_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, reach, pairs_paf, out_sites, out_links, out_reads, st);
+    });
+}
+
 void hlmi_haplotig_opts_default(hlmi_haplotig_opts *o) {
     if (o) *o = hlmi_haplotig_opts{0, 0.0, 3, 2, 0.2, 3, 0.8, 3, 1};
 }

@@ -16,7 +16,7 @@
 //   phase_slots_kernel    a thread per row: the blocks it touches, block_index[s_hi - 1] - block_index[s_lo] + 1; a scan
 //   phase_assign_kernel   a thread per row walks its allele bytes once and writes one 24-byte record per block into its slots;
 //                         <true> (hlmi_phase_reach): a site whose bit byte is BIT_BRIDGED counts in spanned alone
-// With reach >= 1 (hlmi_phase_reach and its kin) the link pass is phase_reach.hip's and the blocks are build_blocks_reach's.
+// With reach >= 1 the link pass is phase_reach.hip's, the blocks build_blocks_reach's; phase_ins.hip has a front of its own.
 // Every loop is bounded by a count known at its head; the searches are counted.
 #include <hip/hip_runtime.h>
 
@@ -217,33 +217,14 @@ void phase_core(const char *who, const PolCoreIn &in, const std::vector<PSite> &
     out.far.reach = reach;
     if (keep) *keep = DevRecs{};
     const size_t N = sites.size(), R = in.n_rows;
-    // the blocks from what the link pass left: neighbours alone (reach 0), or every distance up to reach
-    auto blocks = [&]() {
-        if (!reach) {
-            out.blocks = build_blocks(sites, out.links, o.min_link, o.min_agree);
-            return;
-        }
-        const ReachBlocks rb = build_blocks_reach(sites, out.far, o.min_link, o.min_agree);
-        out.blocks = rb.base;
-        out.links_far = rb.links_far;
-        out.links_far_phased = rb.links_far_phased;
-        out.joins_far = rb.joins_far;
-        out.sites_bridged = rb.sites_bridged;
-        out.links_conflict = rb.links_conflict;
-    };
-    if (!N) {
-        blocks();
-        return;
-    }
-    if (N >= (1ull << 31)) fail(HLMI_EINVAL, "%s: %zu sites (2^31 and more)", who, N);              // (never: positions < 2^31)
-    const size_t n_links = N - 1;
-    out.links.assign(n_links, LinkCounts{0, 0, 0, 0});
-    if (reach) out.far.n.assign(n_links * (size_t)reach, LinkCounts{0, 0, 0, 0});
-    DBuf<uint32_t> d_pos, d_lo(std::max<size_t>(R, 1)), d_cnt(std::max<size_t>(R, 1));
+    DBuf<uint32_t> d_pos, d_lo, d_cnt;
     DBuf<uint8_t> d_pack, d_table;
-    DBuf<uint64_t> d_off(std::max<size_t>(R, 1));
-    std::vector<uint32_t> s_lo, cnt;
-    if (R) {
+    DBuf<uint64_t> d_off;
+    if (N >= (1ull << 31)) fail(HLMI_EINVAL, "%s: %zu sites (2^31 and more)", who, N);              // (never: positions < 2^31)
+    if (N && R) {
+        d_lo.alloc(R);
+        d_cnt.alloc(R);
+        d_off.alloc(R);
         KTimer kt("phase_allele");
         std::vector<uint32_t> pos(N);
         std::vector<uint8_t> pack(N);
@@ -269,6 +250,29 @@ void phase_core(const char *who, const PolCoreIn &in, const std::vector<PSite> &
             HIP_CHECK(hipGetLastError());
         }
     }
+    phase_tail(who, R, sites, o, out, keep, reach, d_lo, d_cnt, d_off, d_table);
+}
+
+void phase_tail(const char *who, size_t R, const std::vector<PSite> &sites, const hlmi_phase_opts &o, DevicePhase &out, DevRecs *keep, int reach,
+                const DBuf<uint32_t> &d_lo, const DBuf<uint32_t> &d_cnt, const DBuf<uint64_t> &d_off, const DBuf<uint8_t> &d_table) {
+    const size_t N = sites.size(), n_links = N ? N - 1 : 0;
+    std::vector<uint32_t> s_lo, cnt;
+    // the blocks from what the link pass left: neighbours alone (reach 0), or every distance up to reach
+    auto blocks = [&]() {
+        if (!reach) {
+            out.blocks = build_blocks(sites, out.links, o.min_link, o.min_agree);
+            return;
+        }
+        const ReachBlocks rb = build_blocks_reach(sites, out.far, o.min_link, o.min_agree);
+        out.blocks = rb.base;
+        out.links_far = rb.links_far;
+        out.links_far_phased = rb.links_far_phased;
+        out.joins_far = rb.joins_far;
+        out.sites_bridged = rb.sites_bridged;
+        out.links_conflict = rb.links_conflict;
+    };
+    out.links.assign(n_links, LinkCounts{0, 0, 0, 0});
+    if (reach) out.far.n.assign(n_links * (size_t)reach, LinkCounts{0, 0, 0, 0});
     if (out.alleles && n_links && reach) {
         KTimer kt("phase_link_reach");
         s_lo = d_lo.download(R);

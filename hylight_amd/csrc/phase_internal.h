@@ -1,10 +1,12 @@
-// phase_internal.h - what phase_host.cpp (the entry points, the files), phase.hip and phase_reach.hip (the kernels) share.  The
-// rules are those of include/hylight_mi.h (hlmi_phase, hlmi_phase_reads, hlmi_phase_reach, hlmi_phase_reads_reach);
-// tests/phase_model.py and tests/phase_reach_model.py restate them.
+// phase_internal.h - what phase_host.cpp, phase_ins_host.cpp (the entry points, the files), phase.hip, phase_reach.hip and
+// phase_ins.hip (the kernels) share.  The
+// rules are those of include/hylight_mi.h (hlmi_phase, hlmi_phase_reads, hlmi_phase_reach, hlmi_phase_reads_reach, hlmi_phase_ins,
+// hlmi_phase_reads_ins); tests/phase_model.py, tests/phase_reach_model.py and tests/phase_ins_model.py restate them.
 #pragma once
 #include <vector>
 
 #include "common.h"
+#include "phase_ins_text.h"
 #include "phase_reach_text.h"
 #include "phase_text.h"
 #include "polish_internal.h"
@@ -56,6 +58,14 @@ struct DevRecs {
 void phase_core(const char *who, const pol::PolCoreIn &in, const std::vector<PSite> &sites, const hlmi_phase_opts &o, DevicePhase &out,
                 DevRecs *keep = nullptr, int reach = 0);
 
+// phase_core behind its allele table, shared with phase_ins_core: the link pass over the table (s_lo, cnt, off, table of the R
+// rows in device memory; no site or no allele: not read), the blocks, the records.  out.alleles and out.far.reach are the caller's
+void phase_tail(const char *who, size_t R, const std::vector<PSite> &sites, const hlmi_phase_opts &o, DevicePhase &out, DevRecs *keep, int reach,
+                const DBuf<uint32_t> &s_lo, const DBuf<uint32_t> &cnt, const DBuf<uint64_t> &off, const DBuf<uint8_t> &table);
+// phase_ins.hip (hlmi_phase_ins): phase_core over the merged list of position and insertion sites, 1 <= reach <= PHASE_REACH_MAX:
+// the table's front by kind (an I op's length against the site's at a slot), then phase_tail
+void phase_ins_core(const char *who, const pol::PolCoreIn &in, const MergedSites &M, const hlmi_phase_opts &o, DevicePhase &out, int reach);
+
 // the query name rank of every selected row of the overlapper's rows (recs[idx[j]].qid): 4 bytes per row come down
 std::vector<uint32_t> selected_query_ranks(const PafRec *recs, const uint32_t *idx, size_t n_sel);
 
@@ -91,5 +101,11 @@ void phase_reach_run(const char *contigs, const char *reads, const char *paf, co
 void phase_reads_reach_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_phase_opts &o, int reach,
                            const char *pairs_paf, const char *out_sites, const char *out_links, const char *out_reads,
                            hlmi_phase_reach_stats *st);
+// phase_ins_host.cpp
+void phase_ins_run(const char *contigs, const char *reads, const char *paf, const hlmi_phase_opts &o, int reach, const char *pairs_paf,
+                   const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_ins_stats *st);
+void phase_reads_ins_run(const char *contigs, const char *reads, const hlmi_ava_opts &ao, const hlmi_phase_opts &o, int reach,
+                         const char *pairs_paf, const char *out_sites, const char *out_links, const char *out_reads,
+                         hlmi_phase_ins_stats *st);
 
 }  // namespace hlmi

@@ -238,13 +238,14 @@ def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pai
     return out
 
 
-def phase_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None, reach=1):
+def phase_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None, reach=1, ins=False):
     """`--phase`: the variant sites of the final contigs phased from the reads (hlmi_phase_reads: the reads are aligned to the
     contigs in the call, every pair, one row per read).  The long reads with the overlapper's long constants give
     outdir/final_contigs.long.phase.sites.tsv, .links.tsv and .reads.tsv; short reads, when there are any, with the short
     constants give the .short. triple.  long_pairs / short_pairs: as for variant_tables.  `device`: the GPU to initialise the
     library on (None: the caller has done so).  reach (`--phase_reach`) above 1: hlmi_phase_reads_reach, links between sites up to
-    `reach` apart.  -> {"long": stats, "short": stats}."""
+    `reach` apart.  ins (`--phase_ins`): hlmi_phase_reads_ins takes the call's place at any reach - the same three files with the
+    insertion sites that take part among the sites.  -> {"long": stats, "short": stats}."""
     if device is not None:
         api.init(device)
     out = {}
@@ -255,7 +256,8 @@ def phase_tables(final, long_reads, short_reads, outdir, device=None, long_pairs
         o.pair_once = 0
         stem = os.path.join(outdir, f"final_contigs.{kind}.phase")
         files = (stem + ".sites.tsv", stem + ".links.tsv", stem + ".reads.tsv")
-        out[kind] = (api.phase_reads(final, reads, *files, o, pairs=pairs) if reach == 1 else
+        out[kind] = (api.phase_reads_ins(final, reads, *files, o, pairs=pairs, reach=reach) if ins else
+                     api.phase_reads(final, reads, *files, o, pairs=pairs) if reach == 1 else
                      api.phase_reads_reach(final, reads, *files, o, pairs=pairs, reach=reach))
     return out
 
@@ -360,6 +362,10 @@ def build_parser():
                    help="(extension) when final_contigs.fa is written: its variant sites phased from the reads (hlmi_phase_reads) "
                         "into final_contigs.long.phase.sites.tsv, .links.tsv and .reads.tsv, and with -s also the .short. triple; "
                         "independent of --variants; with --polish_strain only the pairs of ov_long_ref.paf / shortr1.paf vote")
+    p.add_argument("--phase_ins", action="store_true",
+                   help="(extension) with --phase: insertion sites as phasing evidence - the same three files from "
+                        "hlmi_phase_reads_ins, whose sites are the variant sites and the insertion sites with a supported length; "
+                        "honours --phase_reach; refused without --phase")
     p.add_argument("--haplotigs", action="store_true",
                    help="(extension) when final_contigs.fa is written: its contigs polished once per side of every phased block "
                         "the reads split (hlmi_haplotigs_reads) into final_contigs.long.haplotigs.fa and "
@@ -478,6 +484,8 @@ def refuse_polyte_workers(args):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = build_parser().parse_args(argv)
+    if args.phase_ins and not args.phase:
+        raise SystemExit("--phase_ins adds insertion sites to the files of --phase: give --phase as well")
     if args.polyte_native and args.polyte_cmd:
         raise SystemExit("--polyte_native and --polyte_cmd are two ways to run the same step: give one of them")
     if args.polish_qual and not (args.polish_native or args.polish_direct):
@@ -621,7 +629,7 @@ def _pipeline(args, pool):
         if rc == 0 and args.phase:
             phase_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
                          long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None,
-                         **({"reach": args.phase_reach} if args.phase_reach != 1 else {}))
+                         **({"reach": args.phase_reach} if args.phase_reach != 1 else {}), **({"ins": True} if args.phase_ins else {}))
         if rc == 0 and args.haplotigs:
             haplotig_files(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
                            long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None,
@@ -667,7 +675,8 @@ def _pipeline(args, pool):
                        short_pairs=ov_short if args.polish_strain else None, **({"ins": True} if args.variants_ins else {}))
     if args.phase:
         phase_tables(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
-                     short_pairs=ov_short if args.polish_strain else None, **({"reach": args.phase_reach} if args.phase_reach != 1 else {}))
+                     short_pairs=ov_short if args.polish_strain else None, **({"reach": args.phase_reach} if args.phase_reach != 1 else {}),
+                     **({"ins": True} if args.phase_ins else {}))
     if args.haplotigs:
         haplotig_files(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
                        short_pairs=ov_short if args.polish_strain else None, **({"reach": args.phase_reach} if args.phase_reach != 1 else {}))

@@ -16,6 +16,9 @@ block, spanned, hap_a, hap_b, other, hap).  Prints the stats as one JSON line.  
 --reach K (2 .. 8; hlmi_phase_reach) also links sites up to K sites apart, so that one noisy site does not cut a block: a site
 inside a block that joined nothing is bridged (its block's id, phase "."), --links has one line per link of any distance.  The
 default 1 is the call without it.
+--ins (hlmi_phase_ins, with --reach K as well) adds the insertion sites of `python -m hylight_amd.variants --ins` whose called length
+has --min_alt rows as phasing evidence: a site line with pos of the base in front, alt "+" and the called bases; a slot endpoint of
+a link and the id of a block that starts at an insertion site carry a trailing "+".  Without --ins the module calls what it called.
 """
 from __future__ import annotations
 
@@ -49,6 +52,7 @@ def build_parser():
     p.add_argument("--min_link", type=int, default=3, help="informative rows a link needs")
     p.add_argument("--min_agree", type=float, default=0.8, help="share of the informative rows on the link's majority side")
     p.add_argument("--reach", type=int, default=1, metavar="K", help="link sites up to K sites apart (1: neighbours alone; at most 8)")
+    p.add_argument("--ins", action="store_true", help="insertion sites as phasing evidence (hlmi_phase_ins; --reach applies)")
     return p
 
 
@@ -60,10 +64,14 @@ def main(argv=None):
     if a.paf is not None:
         if a.short:
             parser.error("--short chooses the alignment of a call without --paf")
-        if a.reach != 1:
+        if a.ins:
+            st = api.phase_ins(a.contigs, a.reads, a.paf, a.out, a.links, a.read_haps, pairs=a.pairs, reach=a.reach, **opts)
+        elif a.reach != 1:
             st = api.phase_reach(a.contigs, a.reads, a.paf, a.out, a.links, a.read_haps, pairs=a.pairs, reach=a.reach, **opts)
         else:
             st = api.phase(a.contigs, a.reads, a.paf, a.out, a.links, a.read_haps, pairs=a.pairs, **opts)
+    elif a.ins:
+        st = api.phase_reads_ins(a.contigs, a.reads, a.out, a.links, a.read_haps, read_ava_opts(a.short), pairs=a.pairs, reach=a.reach, **opts)
     elif a.reach != 1:
         st = api.phase_reads_reach(a.contigs, a.reads, a.out, a.links, a.read_haps, read_ava_opts(a.short), pairs=a.pairs, reach=a.reach, **opts)
     else:

@@ -1152,6 +1152,60 @@ int hlmi_phase_reads_reach(const char *contigs, const char *reads, const hlmi_av
                            const char *pairs_paf, const char *out_sites, const char *out_links, const char *out_reads,
                            hlmi_phase_reach_stats *st);
 
+/* ---- insertion sites as phasing evidence: hlmi_phase and its _reach forms phase the sites hlmi_variants calls, which carry the five
+ * symbols A C G T del; a slot where a share of the rows inserts bases (hlmi_variants_ins) is a site of a third kind that no row's
+ * allele was ever read at.  These calls read it: two strains that differ by an insertion and a SNP are one block, and strains that
+ * differ by insertions alone are phased at all.  hlmi_phase_ins reads a PAF as hlmi_phase_reach does, hlmi_phase_reads_ins aligns in
+ * the call as hlmi_phase_reads_reach does.  New symbols: the older calls keep their signatures and their bytes, and
+ * HLMI_ABI_VERSION stays where it is.  A function of the project's own: PARITY UNPINNED; tests/phase_ins_model.py is the contract,
+ * byte for byte. */
+typedef struct {
+    hlmi_phase_reach_stats reach;   /* as hlmi_phase_reach's, over the merged list of sites: links, blocks, alleles and the rest
+                                       count sites of both kinds; the thirteen variant fields (sites among them) stay hlmi_variants's */
+    uint64_t slots_callable;        /* the four slot fields of hlmi_variant_ins_stats, with hlmi_variants_ins's values            */
+    uint64_t ins_sites;
+    uint64_t ins_long;
+    uint64_t ins_edge;
+    uint64_t ins_sites_phasing;     /* insertion sites that take part                                                           */
+    uint64_t ins_sites_left_out;    /* ... and those that do not: ins_sites = ins_sites_phasing + ins_sites_left_out            */
+    uint64_t ins_sites_phased;      /* insertion sites that are members of blocks of two or more sites                          */
+} hlmi_phase_ins_stats;
+/* contigs, reads, paf, o, reach, pairs_paf and the three files: as for hlmi_phase_reach.  reach = K, 1 <= K <= HLMI_PHASE_REACH_MAX;
+ * with K = 1 the links are those between neighbours, counted by the kernel of the _reach calls.
+ * Sites: the merged list of two kinds.  Position sites: exactly hlmi_variants's.  Insertion sites: those of hlmi_variants_ins under
+ * the same options (both kinds come from its one count pass) that take part: an insertion site at slot p - the gap in front of
+ * 0-based position p, 0 < p < length, printed as pos = p - takes part iff len >= 1 and len_count >= min_alt, so that its called
+ * length has the support a position site's alt needs.  The others count in ins_sites_left_out and appear in none of the three
+ * files.  Order inside a contig: slot p sorts directly in front of position p (key 2 p for the slot, 2 p + 1 for the position);
+ * with the printed 1-based positions, a position site and an insertion site that print the same pos come position site first.
+ * Alleles: at a position site hlmi_phase's, run by the same code.  At an insertion site at slot p a row spans the slot iff
+ * ts < p < te (hlmi_variants_ins's span); with b what the row inserts at p as hlmi_variants_ins counts it (the one I op of the
+ * compact CIGAR at that slot, never an edge op), the row's allele is 0 (own) if it inserts nothing there, 1 (alt) if the length of
+ * b is the site's len, 2 (other) for any other length, more than 16 bases included.  The alt is matched by length alone: the
+ * inserted bases, N included, play no part.  "None" does not occur inside the span.  A row's sites are the keys in
+ * [2 ts + 1, 2 te): one run of the merged list, so alleles and its 2^32 refusal are hlmi_phase's over both kinds.
+ * Links, blocks, phase bits, conflicts, bridged sites, read records: hlmi_phase_reach's rules over the merged list, run by the same
+ * code.
+ * Files: the three files of hlmi_phase_reach, same header lines.  out_sites, at an insertion site: pos = p, ref the upper-cased
+ * base in front of the slot (as out_ins of hlmi_variants_ins has it), alt '+' followed by the site's seq, depth = span, ref_count =
+ * span - ins - ins_long, alt_count = len_count.  out_links: pos1 and pos2 are the printed positions; a slot endpoint carries a
+ * trailing '+'.  A block's id is the printed pos of its first site, with a trailing '+' when that site is an insertion site
+ * (otherwise a position site and an insertion site that print the same pos could start two blocks with one id); the same id
+ * stands in out_reads.
+ * On an input where no insertion site takes part the three files are byte for byte hlmi_phase_reach's at the same reach and
+ * st->reach equals hlmi_phase_reach's stats in every integer field.
+ * Refusals: hlmi_phase_reach's, in its order, under these names.  The doubled key needs none of its own: hlmi_polish's limit of 2^31
+ * contig bases, which these calls make as hlmi_phase does, keeps 2 p + 1 below 2^32.
+ * The merged list lives in device memory as 5 bytes per site; the table is filled by kind and written by csrc/phase_ins.hip, and
+ * everything behind it is hlmi_phase_reach's device code. */
+int hlmi_phase_ins(const char *contigs, const char *reads, const char *paf, const hlmi_phase_opts *o, int reach, const char *pairs_paf,
+                   const char *out_sites, const char *out_links, const char *out_reads, hlmi_phase_ins_stats *st);
+/* hlmi_phase_reads_reach with the rules above: the two calls hlmi_ava(contigs, reads, ao, P) and hlmi_phase_ins(contigs, reads, P, o,
+ * reach, pairs_paf, ...) in one, without the PAF P; the stated differences of hlmi_phase_reads apply. */
+int hlmi_phase_reads_ins(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_phase_opts *o, int reach,
+                         const char *pairs_paf, const char *out_sites, const char *out_links, const char *out_reads,
+                         hlmi_phase_ins_stats *st);
+
 /* ---- haplotigs: polish each side of a phased block on its own.  hlmi_polish lets every read vote in every column, so inside a phased
  * block the majority strain wins; these calls give two consensus sequences where the reads prove two sides, and hlmi_polish's bytes
  * everywhere else.  hlmi_haplotigs reads a PAF as hlmi_phase does, hlmi_haplotigs_reads aligns in the call as hlmi_phase_reads does.
