@@ -224,6 +224,13 @@ class HaplotigStats(C.Structure):
     _fields_ = [("phase", PhaseStats)] + [(k, C.c_uint64) for k in HAPLOTIG_STATS] + [(k, C.c_double) for k in POLISH_MS]
 
 
+HAPLOTIG_INS_STATS = PHASE_INS_STATS + ("diff_slots",)
+
+
+class HaplotigInsStats(C.Structure):
+    _fields_ = [("base", HaplotigStats)] + [(k, C.c_uint64) for k in HAPLOTIG_INS_STATS]
+
+
 ABI_VERSION = 7          # include/hylight_mi.h: HLMI_ABI_VERSION
 
 # every symbol include/hylight_mi.h declares: name -> (restype, argtypes)
@@ -356,6 +363,10 @@ SYMBOLS = {
                                        C.c_char_p, C.POINTER(HaplotigStats)]),
     "hlmi_haplotigs_reads_reach": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(HaplotigOpts), C.c_int, C.c_char_p,
                                              C.c_char_p, C.c_char_p, C.POINTER(HaplotigStats)]),
+    "hlmi_haplotigs_ins": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(HaplotigOpts), C.c_int, C.c_char_p, C.c_char_p,
+                                     C.c_char_p, C.POINTER(HaplotigInsStats)]),
+    "hlmi_haplotigs_reads_ins": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(HaplotigOpts), C.c_int, C.c_char_p,
+                                           C.c_char_p, C.c_char_p, C.POINTER(HaplotigInsStats)]),
     "hlmi_job_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "hlmi_job_close": (None, [C.c_void_p]),
     "hlmi_job_num_queries": (C.c_int64, [C.c_void_p]),
@@ -1094,6 +1105,37 @@ def haplotigs_reads_reach(contigs, reads, out_fa, out_blocks=None, ava_opts=None
     _check(load().hlmi_haplotigs_reads_reach(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
                                              int(reach), _b(pairs), _b(out_fa), _b(out_blocks), C.byref(st)))
     return _haplotig_stats(st)
+
+
+def _haplotig_ins_stats(st):
+    out = _haplotig_stats(st.base)
+    out.update({k: getattr(st, k) for k in HAPLOTIG_INS_STATS})        # ins_long and ins_edge: the same values as base's
+    return out
+
+
+def haplotigs_ins(contigs, reads, paf, out_fa, out_blocks=None, pairs=None, reach=1, **opts):
+    """hlmi_haplotigs_ins: api.haplotigs_reach over the blocks of api.phase_ins, whose first or last site may be an insertion site.
+    A block's extent lies in key space (slot p: 2 p, position p: 2 p + 1) and runs from the key of its first site to the key of its
+    last: one that starts at an insertion site shuts the other side's rows out of that slot too, one that ends at slot p shuts them
+    out of slot p and not out of position p.  An insertion site inside a split block is decided per side: two strains that differ
+    by insertions alone give name_hapA and name_hapB.  out_blocks has a tenth column, diff_slots (slots inside the extent whose
+    opened length differs between the sides); block, start and end carry a trailing "+" at an insertion site.  Where no insertion
+    site takes part out_fa and the shared stats are api.haplotigs_reach's.  include/hylight_mi.h states it,
+    tests/haplotigs_ins_model.py is its contract.  -> dict of the stats (hlmi_haplotig_ins_stats: api.haplotigs_reach's keys, the
+    seven insertion counters of api.phase_ins, diff_slots)."""
+    o, st = _haplotig_opts("haplotigs_ins", opts), HaplotigInsStats()
+    _check(load().hlmi_haplotigs_ins(_b(contigs), _b(reads), _b(paf), C.byref(o), int(reach), _b(pairs), _b(out_fa), _b(out_blocks),
+                                     C.byref(st)))
+    return _haplotig_ins_stats(st)
+
+
+def haplotigs_reads_ins(contigs, reads, out_fa, out_blocks=None, ava_opts=None, pairs=None, reach=1, **opts):
+    """hlmi_haplotigs_reads_ins: `ava(contigs, reads, P, ava_opts)` and `haplotigs_ins(contigs, reads, P, ...)` in one call without
+    the PAF P.  -> dict of the stats (hlmi_haplotig_ins_stats)."""
+    o, st = _haplotig_opts("haplotigs_reads_ins", opts), HaplotigInsStats()
+    _check(load().hlmi_haplotigs_reads_ins(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
+                                           int(reach), _b(pairs), _b(out_fa), _b(out_blocks), C.byref(st)))
+    return _haplotig_ins_stats(st)
 
 
 DEVICE = "cuda"          # where the buffers that cross the C ABI live (stage.py allocates them with torch)

@@ -766,6 +766,24 @@ int hlmi_haplotigs_reads_reach(const char *contigs, const char *reads, const hlm
     });
 }
 
+int hlmi_haplotigs_ins(const char *contigs, const char *reads, const char *paf, const hlmi_haplotig_opts *o, int reach,
+                       const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_ins_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !paf || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_haplotigs_ins: NULL argument");
+        require_device();
+        haplotigs_ins_run(contigs, reads, paf, *o, reach, pairs_paf, out_fa, out_blocks, st);
+    });
+}
+
+int hlmi_haplotigs_reads_ins(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_haplotig_opts *o, int reach,
+                             const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_ins_stats *st) {
+    return guarded([&] {
+        if (!contigs || !reads || !o || !out_fa || !st) fail(HLMI_EINVAL, "hlmi_haplotigs_reads_ins: NULL argument");
+        require_device();
+        haplotigs_reads_ins_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, reach, pairs_paf, out_fa, out_blocks, st);
+    });
+}
+
 hlmi_job *hlmi_job_open(const char *reads_fa, const char *ref_fa, int nsplit, int long_mode) {
     hlmi_job *j = nullptr;
     guarded([&] {

@@ -17,9 +17,34 @@
 //                         insertion's position looked up in the row's interval list in global memory
 // The rest is polish.hip's polish_tail over both sides side by side.  Every loop is bounded by a count known at its head; the
 // searches are counted.
+//
+// The key-space form (KEYS, hlmi_haplotigs_ins: blocks of hlmi_phase_ins, whose first or last site may be a slot).  An extent is
+// [kf, kl] in ph::site_key's space - slot g has key 2 g, position g key 2 g + 1 - and holds every key in between: position g is
+// inside iff kf <= 2 g + 1 <= kl, slot g iff kf <= 2 g <= kl.  With both ends odd that is the rule above.  The interval is
+// KeyInterval, 12 bytes (two 32-bit keys and the shut side are 65 bits: the record grows, no call refuses more than before).
+//   LDS entry   klo | khi << 11 | shut << 22: the extent clipped to the tile's 2 HAP_TILE keys, as offsets from key 2 g0.  That is the
+//               position form's lo and hi with one more bit each, the keys' low bits: klo even - the slot in front of the first
+//               inside position is inside; khi even - the slot behind the last inside position is inside while that position is
+//               not.  key_sides finds both answers a column needs, its position's and its slot's, with one counted search.
+//   the bound   An extent holds a position and one more site, so two keys at the least, and extents do not overlap.  One that
+//               touches the tile has a key in it; all but two - the one across the tile's lower border and the one across its
+//               upper - lie inside with both.  2 (n - 2) + 2 <= 2 HAP_TILE: n <= HAP_TILE + 1 = IV_CAP_KEYS (reached by an
+//               extent that ends at the slot of offset 0 - it touches the tile by that slot alone - and HAP_TILE extents of a
+//               position with the slot behind it).  One word per extent: 4 x 1025 x 4 = 16 400 bytes next to the 64 KiB of
+//               counters, 81 936 bytes, 16 more than half a CU's LDS: a workgroup per CU for this form, where the position form
+//               has two.  The choice is the plain list over a packed entry or a smaller tile; it is untimed beyond DESIGN 7
+//   the span    The flush takes a slot's span from the counters of the position behind it: c + C_OTHER - C_START.  A row has
+//               one column at position x.  Per side S it takes part in position x (P) or not, and in slot x (L) or not, and the
+//               column adds: P and L - its vote, counted in c; L alone (the extent starts at position x) - C_OTHER; P alone (the
+//               extent ended at slot x: the row votes at x and must not span the slot) - C_START, which the flush subtracts;
+//               neither - nothing.  The two corrections are made only behind the row's first column; on its first column a row
+//               spans no slot and lane 0 adds the C_START that takes its vote out, on the sides of P.  So a row moves a slot's
+//               span on a side by one or by nothing, and the cases exclude each other: at most once per slot and side.
+//               An extent that starts at slot x has klo even: the slot's lookup needs no exception for the first offset
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "dev_prims.h"
@@ -45,6 +70,11 @@ constexpr uint32_t IV_NONE = 0xffffffffu, POS_MASK = 0x7fffffffu;
 static_assert(HAP_TILE == POLISH_TILE, "the count pass runs over polish_layout's tiles");
 static_assert(HAP_TILE <= 1024, "a tile offset has 10 bits in an LDS interval");
 static_assert(sizeof(ReadRec) == 24, "24 bytes per record");
+constexpr int IV_CAP_KEYS = HAP_TILE + 1;                              // ... in key space (the head comment's bound)
+constexpr uint32_t KEY_MASK = 2047u;
+static_assert(2 * HAP_TILE <= 2048, "a tile's key offset has 11 bits in an LDS interval");
+static_assert(2 * (IV_CAP_KEYS - 2) + 2 >= 2 * HAP_TILE, "the list holds every n with 2 (n - 2) + 2 <= 2 HAP_TILE");
+static_assert(IV_CAP_KEYS <= 2048, "key_sides's 12 steps");
 
 // A row's exclusion interval in the device's position space (positions < 2^31): the row takes no part in side `shut` at the
 // positions of [first, last] and at the slots of (first, last]
@@ -52,6 +82,12 @@ struct Interval {
     uint32_t first_shut;                // first | shut << 31
     uint32_t last;
 };
+// ... in key space (keys < 2^32): no part in side `shut` at every position and slot whose key lies in [kf, kl]
+struct KeyInterval {
+    uint32_t kf, kl, shut;
+};
+template <bool KEYS>
+using IvOf = std::conditional_t<KEYS, KeyInterval, Interval>;
 
 // the side a record shuts its row out of inside a split block: the other one than its own; 2: none (no side, or not split)
 __device__ __forceinline__ uint32_t shut_side(const ReadRec &r, const uint8_t *__restrict__ split, uint32_t n_blocks) {
@@ -73,22 +109,28 @@ __global__ __launch_bounds__(WG) void hap_iv_count_kernel(uint32_t n_rows, const
     }
 }
 
+// KEYS: gfirst and glast hold the blocks' kf and kl
+template <bool KEYS>
 __global__ __launch_bounds__(WG) void hap_iv_fill_kernel(uint32_t n_rows, const uint64_t *__restrict__ rec_off, const uint32_t *__restrict__ rec_cnt,
                                                          const ReadRec *__restrict__ recs, uint64_t n_recs, const uint8_t *__restrict__ split,
                                                          const uint32_t *__restrict__ gfirst, const uint32_t *__restrict__ glast, uint32_t n_blocks,
                                                          const uint64_t *__restrict__ iv_off, const uint32_t *__restrict__ iv_cnt,
-                                                         Interval *__restrict__ iv) {
+                                                         IvOf<KEYS> *__restrict__ iv) {
     const uint32_t step = gridDim.x * WG;
     for (uint32_t k = blockIdx.x * WG + threadIdx.x; k < n_rows; k += step) {
         const uint32_t n = rec_cnt[k], room = iv_cnt[k];
         const uint64_t off = rec_off[k];
-        Interval *out = iv + iv_off[k];
+        IvOf<KEYS> *out = iv + iv_off[k];
         uint32_t c = 0;
         for (uint32_t i = 0; i < n; ++i) {
             if (off + i >= n_recs) continue;
             const ReadRec r = recs[off + i];
             const uint32_t s = shut_side(r, split, n_blocks);
-            if (s < 2u && c < room) out[c++] = Interval{(gfirst[r.block] & POS_MASK) | s << 31, glast[r.block]};
+            if constexpr (KEYS) {
+                if (s < 2u && c < room) out[c++] = KeyInterval{gfirst[r.block], glast[r.block], s};
+            } else {
+                if (s < 2u && c < room) out[c++] = Interval{(gfirst[r.block] & POS_MASK) | s << 31, glast[r.block]};
+            }
         }
     }
 }
@@ -99,6 +141,16 @@ __device__ __forceinline__ uint32_t first_ending_at_or_behind(const Interval *__
     for (int it = 0; it < 33 && lo < hi; ++it) {
         const uint32_t m = lo + ((hi - lo) >> 1);
         if (a[m].last < g) lo = m + 1;
+        else hi = m;
+    }
+    return lo;
+}
+// ... whose kl is not below key k
+__device__ __forceinline__ uint32_t first_ending_at_or_behind(const KeyInterval *__restrict__ a, uint32_t n, uint32_t k) {
+    uint32_t lo = 0, hi = n;
+    for (int it = 0; it < 33 && lo < hi; ++it) {
+        const uint32_t m = lo + ((hi - lo) >> 1);
+        if (a[m].kl < k) lo = m + 1;
         else hi = m;
     }
     return lo;
@@ -126,14 +178,39 @@ __device__ __forceinline__ uint32_t slot_sides(uint32_t e, uint32_t x) {
     return position_sides(e);
 }
 
-template <int ENC>
+// The key-space entries (the head comment: klo | khi << 11 | shut << 22) of s[0, n), ascending: bits 0 and 1 - the row takes part in
+// side A, B at the position of tile offset x; bits 2 and 3 - at the slot in front of it.  One search for the last entry that
+// begins at or in front of the position's key; the slot's key, one below, lies in that entry, in the one in front of it when the
+// entry begins at the position itself, or in none.  n <= IV_CAP_KEYS <= 2048: 12 steps at the most
+__device__ __forceinline__ uint32_t key_sides(const uint32_t *s, uint32_t n, uint32_t x) {
+    if (!n) return 15u;
+    const uint32_t ks = 2u * x, kp = ks + 1u;
+    uint32_t lo = 0, hi = n;                    // the last entry whose klo is not behind kp lies in [lo, hi)
+    for (int it = 0; it < 12 && hi - lo > 1; ++it) {
+        const uint32_t m = lo + ((hi - lo) >> 1);
+        if ((s[m] & KEY_MASK) <= kp) lo = m;
+        else hi = m;
+    }
+    const uint32_t e = s[lo], klo = e & KEY_MASK, khi = e >> 11 & KEY_MASK, out = 3u & ~(1u << (e >> 22 & 1u));
+    const uint32_t mp = klo <= kp && kp <= khi ? out : 3u;
+    uint32_t ms = 3u;
+    if (klo <= ks) ms = ks <= khi ? out : 3u;
+    else if (klo == kp && lo > 0) {             // the entry in front ends below kp: at the slot's key or in front of it
+        const uint32_t f = s[lo - 1];
+        if ((f >> 11 & KEY_MASK) == ks) ms = 3u & ~(1u << (f >> 22 & 1u));
+    }
+    return mp | ms << 2;
+}
+
+template <int ENC, bool KEYS = false>
 __global__ __launch_bounds__(POLISH_WG) void hap_count_kernel(const PolRow *__restrict__ rows, const uint32_t *__restrict__ ops,
                                                               const uint8_t *__restrict__ reads, const uint8_t *__restrict__ contig,
                                                               const PolTile *__restrict__ tiles, int min_cov, const uint64_t *__restrict__ iv_off,
-                                                              const uint32_t *__restrict__ iv_cnt, const Interval *__restrict__ iv, size_t G,
+                                                              const uint32_t *__restrict__ iv_cnt, const IvOf<KEYS> *__restrict__ iv, size_t G,
                                                               uint8_t *__restrict__ sym, uint8_t *__restrict__ open) {
+    constexpr uint32_t CAP = KEYS ? IV_CAP_KEYS : IV_CAP;
     __shared__ uint32_t s_cnt[2][HAP_CNT][HAP_TILE];
-    __shared__ uint32_t s_iv[POLISH_WAVES][IV_CAP];
+    __shared__ uint32_t s_iv[POLISH_WAVES][CAP];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const PolTile t = tiles[blockIdx.x];
     const uint32_t t_end = t.t0 + t.n_pos;
@@ -148,18 +225,24 @@ __global__ __launch_bounds__(POLISH_WG) void hap_count_kernel(const PolRow *__re
         const uint32_t n_iv = iv_cnt[k];
         uint32_t n_t = 0;
         if (n_iv) {
-            const Interval *ri = iv + iv_off[k];
-            const uint32_t lo = first_ending_at_or_behind(ri, n_iv, g0);
-            for (uint32_t c = 0; c < (uint32_t)IV_CAP; c += 64) {
+            const IvOf<KEYS> *ri = iv + iv_off[k];
+            const uint32_t lo = first_ending_at_or_behind(ri, n_iv, KEYS ? 2u * g0 : g0);
+            for (uint32_t c = 0; c < CAP; c += 64) {
                 const uint32_t j = c + (uint32_t)lane;
-                bool ok = j < (uint32_t)IV_CAP && lo + j < n_iv;
-                Interval v{0, 0};
+                bool ok = j < CAP && lo + j < n_iv;
+                IvOf<KEYS> v{};
                 if (ok) v = ri[lo + j];
-                const uint32_t first = v.first_shut & POS_MASK;
-                ok = ok && first < g1 && v.last >= g0;
-                if (ok)
-                    siv[j] = (first > g0 ? first - g0 : 0u) | (min(v.last, g1 - 1) - g0) << 10 | (v.first_shut >> 31) << 20 |
-                             (uint32_t)(first < g0) << 21;
+                if constexpr (KEYS) {
+                    const uint32_t k0 = 2u * g0, k1 = 2u * g1 - 1u;    // the tile's first and last key (g1 < 2^31)
+                    ok = ok && v.kf <= k1 && v.kl >= k0;
+                    if (ok) siv[j] = (v.kf > k0 ? v.kf - k0 : 0u) | (min(v.kl, k1) - k0) << 11 | (v.shut & 1u) << 22;
+                } else {
+                    const uint32_t first = v.first_shut & POS_MASK;
+                    ok = ok && first < g1 && v.last >= g0;
+                    if (ok)
+                        siv[j] = (first > g0 ? first - g0 : 0u) | (min(v.last, g1 - 1) - g0) << 10 | (v.first_shut >> 31) << 20 |
+                                 (uint32_t)(first < g0) << 21;
+                }
                 const uint32_t n_ok = (uint32_t)__popcll(__ballot(ok));
                 n_t += n_ok;
                 if (n_ok < 64u) break;                                 // (the same in every lane)
@@ -168,27 +251,42 @@ __global__ __launch_bounds__(POLISH_WG) void hap_count_kernel(const PolRow *__re
             __builtin_amdgcn_wave_barrier();
         }
         if (lane == 0 && r.ts >= t.t0) {
-            const uint32_t x = r.ts - t.t0, m = position_sides(tile_interval_at(siv, n_t, x));
+            const uint32_t x = r.ts - t.t0, m = KEYS ? key_sides(siv, n_t, x) & 3u : position_sides(tile_interval_at(siv, n_t, x));
             if (m & 1u) atomicAdd(&s_cnt[0][C_START][x], 1u);
             if (m & 2u) atomicAdd(&s_cnt[1][C_START][x], 1u);
         }
         auto vote = [&](uint32_t p, uint32_t code, uint32_t tp0, uint32_t qc0, uint32_t) {
             const uint32_t x = p - t.t0;
             const uint32_t s = code == OP_D ? (uint32_t)SYM_DEL : column_symbol<ENC>(r, reads, qc0 + (p - tp0));
-            const uint32_t e = tile_interval_at(siv, n_t, x), m = position_sides(e);
-            if (m & 1u) atomicAdd(&s_cnt[0][s][x], 1u);
-            if (m & 2u) atomicAdd(&s_cnt[1][s][x], 1u);
-            // shut out of the position and still spanning the slot in front of it (the extent's first position): the span below
-            // counts the row as it counts a column that votes nothing
-            const uint32_t only_slot = slot_sides(e, x) & ~m;
-            if (only_slot && p > r.ts) {
-                if (only_slot & 1u) atomicAdd(&s_cnt[0][C_OTHER][x], 1u);
-                if (only_slot & 2u) atomicAdd(&s_cnt[1][C_OTHER][x], 1u);
+            if constexpr (KEYS) {
+                const uint32_t both = key_sides(siv, n_t, x), m = both & 3u, ms = both >> 2;
+                if (m & 1u) atomicAdd(&s_cnt[0][s][x], 1u);
+                if (m & 2u) atomicAdd(&s_cnt[1][s][x], 1u);
+                // behind the row's first column (the head comment's span): in the slot alone - a column that votes nothing; at
+                // the position alone - the vote above is taken out of the slot's span
+                if (m != ms && p > r.ts) {
+                    const uint32_t only_slot = ms & ~m, only_pos = m & ~ms;
+                    if (only_slot & 1u) atomicAdd(&s_cnt[0][C_OTHER][x], 1u);
+                    if (only_slot & 2u) atomicAdd(&s_cnt[1][C_OTHER][x], 1u);
+                    if (only_pos & 1u) atomicAdd(&s_cnt[0][C_START][x], 1u);
+                    if (only_pos & 2u) atomicAdd(&s_cnt[1][C_START][x], 1u);
+                }
+            } else {
+                const uint32_t e = tile_interval_at(siv, n_t, x), m = position_sides(e);
+                if (m & 1u) atomicAdd(&s_cnt[0][s][x], 1u);
+                if (m & 2u) atomicAdd(&s_cnt[1][s][x], 1u);
+                // shut out of the position and still spanning the slot in front of it (the extent's first position): the span
+                // below counts the row as it counts a column that votes nothing
+                const uint32_t only_slot = slot_sides(e, x) & ~m;
+                if (only_slot && p > r.ts) {
+                    if (only_slot & 1u) atomicAdd(&s_cnt[0][C_OTHER][x], 1u);
+                    if (only_slot & 2u) atomicAdd(&s_cnt[1][C_OTHER][x], 1u);
+                }
             }
         };
         walk_row(r, ops, lane, t_end, [&](uint32_t code, uint32_t len, uint32_t tp0, uint32_t qc0) {
             if (code == OP_I && len >= 1 && len <= (uint32_t)POLISH_INS_CAP && tp0 > r.ts && tp0 < r.te && tp0 >= t.t0 && tp0 < t_end) {
-                const uint32_t x = tp0 - t.t0, m = slot_sides(tile_interval_at(siv, n_t, x), x);
+                const uint32_t x = tp0 - t.t0, m = KEYS ? key_sides(siv, n_t, x) >> 2 : slot_sides(tile_interval_at(siv, n_t, x), x);
                 if (m & 1u) atomicAdd(&s_cnt[0][C_INS][x], 1u);
                 if (m & 2u) atomicAdd(&s_cnt[1][C_INS][x], 1u);
             }
@@ -224,10 +322,10 @@ __global__ __launch_bounds__(POLISH_WG) void hap_count_kernel(const PolRow *__re
 
 // MODE 0: the length every inserting row votes for at its opened slots of the sides it takes part in; MODE 1: its bases, where
 // its length won.  slot_of, and the counters behind it, run over (side, position): side B's positions lie G behind side A's
-template <int MODE, int ENC>
+template <int MODE, int ENC, bool KEYS = false>
 __global__ __launch_bounds__(POLISH_WG) void hap_slot_kernel(const PolRow *__restrict__ rows, uint32_t n_rows, const uint32_t *__restrict__ ops,
                                                              const uint8_t *__restrict__ reads, const uint64_t *__restrict__ iv_off,
-                                                             const uint32_t *__restrict__ iv_cnt, const Interval *__restrict__ iv, size_t G,
+                                                             const uint32_t *__restrict__ iv_cnt, const IvOf<KEYS> *__restrict__ iv, size_t G,
                                                              const uint32_t *__restrict__ slot_of, const uint8_t *__restrict__ win_len,
                                                              uint32_t *__restrict__ len_cnt, uint32_t *__restrict__ base_cnt) {
     const int lane = threadIdx.x & 63;
@@ -235,12 +333,17 @@ __global__ __launch_bounds__(POLISH_WG) void hap_slot_kernel(const PolRow *__res
     if (w >= n_rows) return;
     const PolRow r = rows[w];
     const uint32_t n_iv = iv_cnt[w];
-    const Interval *ri = iv + iv_off[w];
+    const IvOf<KEYS> *ri = iv + iv_off[w];
     walk_row(r, ops, lane, 0xffffffffu, [&](uint32_t code, uint32_t len, uint32_t tp0, uint32_t qc0) {
         if (code != OP_I || len < 1 || len > (uint32_t)POLISH_INS_CAP || tp0 <= r.ts || tp0 >= r.te) return;
         const uint32_t g = r.cbase + tp0;
-        uint32_t sides = 3u;                    // slot g lies inside an interval iff first < g <= last
-        if (n_iv) {
+        uint32_t sides = 3u;                    // slot g lies inside an interval iff first < g <= last; KEYS: iff kf <= 2 g <= kl
+        if constexpr (KEYS) {
+            if (n_iv) {
+                const uint32_t j = first_ending_at_or_behind(ri, n_iv, 2u * g);
+                if (j < n_iv && ri[j].kf <= 2u * g) sides = 3u & ~(1u << (ri[j].shut & 1u));
+            }
+        } else if (n_iv) {
             const uint32_t j = first_ending_at_or_behind(ri, n_iv, g);
             if (j < n_iv && (ri[j].first_shut & POS_MASK) < g) sides = 3u & ~(1u << (ri[j].first_shut >> 31));
         }
@@ -258,35 +361,36 @@ __global__ __launch_bounds__(POLISH_WG) void hap_slot_kernel(const PolRow *__res
     });
 }
 
+template <bool KEYS>
 struct IvTable {
     DBuf<uint64_t> off;
     DBuf<uint32_t> cnt;
-    DBuf<Interval> iv;
+    DBuf<IvOf<KEYS>> iv;
 };
 
-template <int MODE>
-void launch_slot(const PolCoreIn &in, const IvTable &T, const uint32_t *d_slot_of, const uint8_t *d_win_len, uint32_t *d_len_cnt,
+template <int MODE, bool KEYS>
+void launch_slot(const PolCoreIn &in, const IvTable<KEYS> &T, const uint32_t *d_slot_of, const uint8_t *d_win_len, uint32_t *d_len_cnt,
                  uint32_t *d_base_cnt) {
     const dim3 g(cdiv(in.n_rows, POLISH_WAVES));
     if (in.enc == READS_CODES)
-        hipLaunchKernelGGL((hap_slot_kernel<MODE, READS_CODES>), g, dim3(POLISH_WG), 0, stream(), in.rows, in.n_rows, in.ops, in.reads, T.off.p,
-                           T.cnt.p, T.iv.p, in.n_contig, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+        hipLaunchKernelGGL((hap_slot_kernel<MODE, READS_CODES, KEYS>), g, dim3(POLISH_WG), 0, stream(), in.rows, in.n_rows, in.ops, in.reads,
+                           T.off.p, T.cnt.p, T.iv.p, in.n_contig, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
     else
-        hipLaunchKernelGGL((hap_slot_kernel<MODE, READS_ASCII>), g, dim3(POLISH_WG), 0, stream(), in.rows, in.n_rows, in.ops, in.reads, T.off.p,
-                           T.cnt.p, T.iv.p, in.n_contig, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+        hipLaunchKernelGGL((hap_slot_kernel<MODE, READS_ASCII, KEYS>), g, dim3(POLISH_WG), 0, stream(), in.rows, in.n_rows, in.ops, in.reads,
+                           T.off.p, T.cnt.p, T.iv.p, in.n_contig, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
 }
 
-}  // namespace
-
-void haplotig_core(const char *who, const PolCoreIn &in, const std::vector<uint32_t> &cbase, const ph::DevRecs &recs,
-                   const HapBlocksUp &blocks, PolDevOut &out) {
+// haplotig_core in either form
+template <bool KEYS>
+void core_in_form(const char *who, const PolCoreIn &in, const std::vector<uint32_t> &cbase, const ph::DevRecs &recs, const HapBlocksUp &blocks,
+                  PolDevOut &out) {
     const size_t G = in.n_contig, R = in.n_rows, n_blocks = blocks.split.size();
     out = PolDevOut{};
     if (!G || !R || !in.n_tiles || cbase.empty() || blocks.gfirst.size() != n_blocks || blocks.glast.size() != n_blocks || recs.off.n < R ||
         recs.cnt.n < R)
         fail(HLMI_ESTATE, "%s: a split block without rows, tiles or records", who);                                  // (never)
     if (in.quals) fail(HLMI_ESTATE, "%s: the two-sided count pass takes no weights", who);                          // (never)
-    IvTable T;
+    IvTable<KEYS> T;
     {
         KTimer kt("hap_intervals");
         DBuf<uint32_t> d_gfirst, d_glast;
@@ -303,12 +407,12 @@ void haplotig_core(const char *who, const PolCoreIn &in, const std::vector<uint3
         const uint64_t n_iv = download_one(T.off.p + (R - 1)) + download_one(T.cnt.p + (R - 1));
         if (n_iv > recs.n) fail(HLMI_ESTATE, "%s: more intervals than (row, block) records", who);                   // (never)
         const size_t avail = dev_available_bytes();             // 0: unknown
-        if (avail && n_iv * sizeof(Interval) > avail)
+        if (avail && n_iv * sizeof(IvOf<KEYS>) > avail)
             fail(HLMI_EINVAL, "%s: the rows' interval table of %llu bytes does not fit the device's free memory (%zu)", who,
-                 (unsigned long long)(n_iv * sizeof(Interval)), avail);
+                 (unsigned long long)(n_iv * sizeof(IvOf<KEYS>)), avail);
         T.iv.alloc(std::max<uint64_t>(n_iv, 1));
         T.iv.zero();
-        hipLaunchKernelGGL(hap_iv_fill_kernel, grid1(R), dim3(WG), 0, stream(), (uint32_t)R, recs.off.p, recs.cnt.p, recs.recs.p, recs.n,
+        hipLaunchKernelGGL(hap_iv_fill_kernel<KEYS>, grid1(R), dim3(WG), 0, stream(), (uint32_t)R, recs.off.p, recs.cnt.p, recs.recs.p, recs.n,
                            d_split.p, d_gfirst.p, d_glast.p, (uint32_t)n_blocks, T.off.p, T.cnt.p, T.iv.p);
         HIP_CHECK(hipGetLastError());
     }
@@ -319,10 +423,10 @@ void haplotig_core(const char *who, const PolCoreIn &in, const std::vector<uint3
     {
         KTimer kt("hap_count");
         if (in.enc == READS_CODES)
-            hipLaunchKernelGGL((hap_count_kernel<READS_CODES>), dim3((unsigned)in.n_tiles), dim3(POLISH_WG), 0, stream(), in.rows, in.ops, in.reads,
+            hipLaunchKernelGGL((hap_count_kernel<READS_CODES, KEYS>), dim3((unsigned)in.n_tiles), dim3(POLISH_WG), 0, stream(), in.rows, in.ops, in.reads,
                                in.contig, in.tiles, in.min_cov, T.off.p, T.cnt.p, T.iv.p, G, d_sym.p, d_open.p);
         else
-            hipLaunchKernelGGL((hap_count_kernel<READS_ASCII>), dim3((unsigned)in.n_tiles), dim3(POLISH_WG), 0, stream(), in.rows, in.ops, in.reads,
+            hipLaunchKernelGGL((hap_count_kernel<READS_ASCII, KEYS>), dim3((unsigned)in.n_tiles), dim3(POLISH_WG), 0, stream(), in.rows, in.ops, in.reads,
                                in.contig, in.tiles, in.min_cov, T.off.p, T.cnt.p, T.iv.p, G, d_sym.p, d_open.p);
         HIP_CHECK(hipGetLastError());
     }
@@ -338,10 +442,18 @@ void haplotig_core(const char *who, const PolCoreIn &in, const std::vector<uint3
     d_cbase2.upload(cbase2);
     polish_tail(PolTailIn{d_contig.p, 2 * G, &d_sym, &d_open, d_cbase2.p, cbase2.size(), "hap_slots"},
                 [&](int mode, const uint32_t *d_slot_of, const uint8_t *d_win_len, uint32_t *d_len_cnt, uint32_t *d_base_cnt) {
-                    if (mode == 0) launch_slot<0>(in, T, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
-                    else launch_slot<1>(in, T, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+                    if (mode == 0) launch_slot<0, KEYS>(in, T, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
+                    else launch_slot<1, KEYS>(in, T, d_slot_of, d_win_len, d_len_cnt, d_base_cnt);
                 },
                 out);
+}
+
+}  // namespace
+
+void haplotig_core(const char *who, const PolCoreIn &in, const std::vector<uint32_t> &cbase, const ph::DevRecs &recs,
+                   const HapBlocksUp &blocks, PolDevOut &out) {
+    if (blocks.keys) core_in_form<true>(who, in, cbase, recs, blocks, out);
+    else core_in_form<false>(who, in, cbase, recs, blocks, out);
 }
 
 }  // namespace hap

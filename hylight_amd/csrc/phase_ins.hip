@@ -126,9 +126,11 @@ __global__ __launch_bounds__(WG) void phase_allele_ins_kernel(const AlleleInsArg
 
 }  // namespace
 
-void phase_ins_core(const char *who, const PolCoreIn &in, const MergedSites &M, const hlmi_phase_opts &o, DevicePhase &out, int reach) {
+void phase_ins_core(const char *who, const PolCoreIn &in, const MergedSites &M, const hlmi_phase_opts &o, DevicePhase &out, int reach,
+                    DevRecs *keep) {
     out = DevicePhase{};
     out.far.reach = reach;
+    if (keep) *keep = DevRecs{};
     const size_t N = M.sites.size(), R = in.n_rows;
     if (reach < 1 || M.key.size() != N || M.ins_of.size() != N) fail(HLMI_ESTATE, "%s: the merged sites in the allele pass", who);     // (never)
     DBuf<uint32_t> d_key, d_lo, d_cnt;
@@ -162,7 +164,7 @@ void phase_ins_core(const char *who, const PolCoreIn &in, const MergedSites &M, 
             HIP_CHECK(hipGetLastError());
         }
     }
-    phase_tail(who, R, M.sites, o, out, nullptr, reach, d_lo, d_cnt, d_off, d_table);
+    phase_tail(who, R, M.sites, o, out, keep, reach, d_lo, d_cnt, d_off, d_table);
 }
 
 }  // namespace ph

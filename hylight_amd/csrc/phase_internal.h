@@ -63,8 +63,10 @@ void phase_core(const char *who, const pol::PolCoreIn &in, const std::vector<PSi
 void phase_tail(const char *who, size_t R, const std::vector<PSite> &sites, const hlmi_phase_opts &o, DevicePhase &out, DevRecs *keep, int reach,
                 const DBuf<uint32_t> &s_lo, const DBuf<uint32_t> &cnt, const DBuf<uint64_t> &off, const DBuf<uint8_t> &table);
 // phase_ins.hip (hlmi_phase_ins): phase_core over the merged list of position and insertion sites, 1 <= reach <= PHASE_REACH_MAX:
-// the table's front by kind (an I op's length against the site's at a slot), then phase_tail
-void phase_ins_core(const char *who, const pol::PolCoreIn &in, const MergedSites &M, const hlmi_phase_opts &o, DevicePhase &out, int reach);
+// the table's front by kind (an I op's length against the site's at a slot), then phase_tail.  keep (hlmi_haplotigs_ins): as
+// phase_core's
+void phase_ins_core(const char *who, const pol::PolCoreIn &in, const MergedSites &M, const hlmi_phase_opts &o, DevicePhase &out, int reach,
+                    DevRecs *keep = nullptr);
 
 // the query name rank of every selected row of the overlapper's rows (recs[idx[j]].qid): 4 bytes per row come down
 std::vector<uint32_t> selected_query_ranks(const PafRec *recs, const uint32_t *idx, size_t n_sel);

@@ -262,13 +262,14 @@ def phase_tables(final, long_reads, short_reads, outdir, device=None, long_pairs
     return out
 
 
-def haplotig_files(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None, reach=1):
+def haplotig_files(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None, reach=1, ins=False):
     """`--haplotigs`: the final contigs polished once per side of every phased block the reads split (hlmi_haplotigs_reads: the
     reads are aligned to the contigs in the call, every pair, one row per read).  The long reads with the overlapper's long
     constants give outdir/final_contigs.long.haplotigs.fa and .long.haplotigs.blocks.tsv; short reads, when there are any, with
     the short constants give the .short. pair.  long_pairs / short_pairs: as for phase_tables.  `device`: the GPU to initialise
-    the library on (None: the caller has done so).  reach (`--phase_reach`) above 1: hlmi_haplotigs_reads_reach.
-    -> {"long": stats, "short": stats}."""
+    the library on (None: the caller has done so).  reach (`--phase_reach`) above 1: hlmi_haplotigs_reads_reach.  ins
+    (`--haplotigs_ins`): hlmi_haplotigs_reads_ins takes the call's place at any reach - the same two files over the blocks of
+    `--phase_ins`, the blocks file with its tenth column.  -> {"long": stats, "short": stats}."""
     if device is not None:
         api.init(device)
     out = {}
@@ -278,7 +279,8 @@ def haplotig_files(final, long_reads, short_reads, outdir, device=None, long_pai
         o = api.ava_opts_short() if kind == "short" else api.ava_opts_long()
         o.pair_once = 0
         stem = os.path.join(outdir, f"final_contigs.{kind}.haplotigs")
-        out[kind] = (api.haplotigs_reads(final, reads, stem + ".fa", stem + ".blocks.tsv", o, pairs=pairs) if reach == 1 else
+        out[kind] = (api.haplotigs_reads_ins(final, reads, stem + ".fa", stem + ".blocks.tsv", o, pairs=pairs, reach=reach) if ins else
+                     api.haplotigs_reads(final, reads, stem + ".fa", stem + ".blocks.tsv", o, pairs=pairs) if reach == 1 else
                      api.haplotigs_reads_reach(final, reads, stem + ".fa", stem + ".blocks.tsv", o, pairs=pairs, reach=reach))
     return out
 
@@ -371,6 +373,10 @@ def build_parser():
                         "the reads split (hlmi_haplotigs_reads) into final_contigs.long.haplotigs.fa and "
                         ".long.haplotigs.blocks.tsv, and with -s also the .short. pair; independent of --phase; with "
                         "--polish_strain only the pairs of ov_long_ref.paf / shortr1.paf vote")
+    p.add_argument("--haplotigs_ins", action="store_true",
+                   help="(extension) with --haplotigs: the blocks of --phase_ins - insertion sites are phasing evidence and are "
+                        "decided per side - the same two files from hlmi_haplotigs_reads_ins, the blocks file with a tenth column "
+                        "diff_slots; honours --phase_reach and --polish_strain; refused without --haplotigs")
     p.add_argument("--phase_reach", type=int, default=1, metavar="K",
                    help="(extension) with --phase and --haplotigs: link variant sites up to K sites apart (hlmi_phase_reads_reach, "
                         "hlmi_haplotigs_reads_reach; 1: neighbours alone, at most 8), so that one noisy site does not cut a block")
@@ -486,6 +492,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.phase_ins and not args.phase:
         raise SystemExit("--phase_ins adds insertion sites to the files of --phase: give --phase as well")
+    if args.haplotigs_ins and not args.haplotigs:
+        raise SystemExit("--haplotigs_ins adds insertion sites to the blocks of --haplotigs: give --haplotigs as well")
     if args.polyte_native and args.polyte_cmd:
         raise SystemExit("--polyte_native and --polyte_cmd are two ways to run the same step: give one of them")
     if args.polish_qual and not (args.polish_native or args.polish_direct):
@@ -633,7 +641,7 @@ def _pipeline(args, pool):
         if rc == 0 and args.haplotigs:
             haplotig_files(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
                            long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None,
-                           **({"reach": args.phase_reach} if args.phase_reach != 1 else {}))
+                           **({"reach": args.phase_reach} if args.phase_reach != 1 else {}), **({"ins": True} if args.haplotigs_ins else {}))
         return rc
     # HyLight.py:211-262 (read clustering, POLYTE per cluster) is the short-read branch: not part of this path.  Its
     # contigs can be handed in; the contig-overlap half of extend_con runs either way (HyLight.py:264-280).
@@ -679,7 +687,8 @@ def _pipeline(args, pool):
                      **({"ins": True} if args.phase_ins else {}))
     if args.haplotigs:
         haplotig_files(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
-                       short_pairs=ov_short if args.polish_strain else None, **({"reach": args.phase_reach} if args.phase_reach != 1 else {}))
+                       short_pairs=ov_short if args.polish_strain else None, **({"reach": args.phase_reach} if args.phase_reach != 1 else {}),
+                       **({"ins": True} if args.haplotigs_ins else {}))
     return 0
 
 

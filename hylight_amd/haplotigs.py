@@ -16,6 +16,9 @@ block of two or more sites (contig, block, start, end, sites, rows_a, rows_b, sp
 JSON line.  Exit status 0 on success.
 --reach K (2 .. 8; hlmi_haplotigs_reach): the blocks of `python -m hylight_amd.phase --reach K`, whose extents cover their bridged
 sites.  The default 1 is the call without it.
+--ins (hlmi_haplotigs_ins; honours --reach): the blocks of `python -m hylight_amd.phase --ins`, in which insertion sites are
+phasing evidence: a block may begin or end at an insertion site (block, start, end then carry a trailing +), a slot inside a
+split block is opened on the side whose rows insert, and --blocks has a tenth column, diff_slots.
 """
 from __future__ import annotations
 
@@ -49,6 +52,7 @@ def build_parser():
     p.add_argument("--min_side", type=int, default=3, help="rows a block needs on either side to be split")
     p.add_argument("--include_unpolished", type=int, default=1, choices=(0, 1), help="write contigs without a selected row as they are")
     p.add_argument("--reach", type=int, default=1, metavar="K", help="link sites up to K sites apart (1: neighbours alone; at most 8)")
+    p.add_argument("--ins", action="store_true", help="insertion sites take part in the phasing and are decided per side")
     return p
 
 
@@ -60,10 +64,14 @@ def main(argv=None):
     if a.paf is not None:
         if a.short:
             parser.error("--short chooses the alignment of a call without --paf")
-        if a.reach != 1:
+        if a.ins:
+            st = api.haplotigs_ins(a.contigs, a.reads, a.paf, a.out, a.blocks, pairs=a.pairs, reach=a.reach, **opts)
+        elif a.reach != 1:
             st = api.haplotigs_reach(a.contigs, a.reads, a.paf, a.out, a.blocks, pairs=a.pairs, reach=a.reach, **opts)
         else:
             st = api.haplotigs(a.contigs, a.reads, a.paf, a.out, a.blocks, pairs=a.pairs, **opts)
+    elif a.ins:
+        st = api.haplotigs_reads_ins(a.contigs, a.reads, a.out, a.blocks, read_ava_opts(a.short), pairs=a.pairs, reach=a.reach, **opts)
     elif a.reach != 1:
         st = api.haplotigs_reads_reach(a.contigs, a.reads, a.out, a.blocks, read_ava_opts(a.short), pairs=a.pairs, reach=a.reach, **opts)
     else:

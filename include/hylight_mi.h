@@ -1268,8 +1268,8 @@ typedef struct {
  * consensus that turns out empty still counts) and summed.
  * Consequence: with no split block in the call - min_side above the number of rows is enough - out_fa is byte for byte hlmi_polish's
  * on the same input and options; the single-sided count pass produces it and no kernel of csrc/haplotigs.hip is launched.
- * Out of scope: quality weights; joining blocks across a contig; insertion sites as phasing evidence.  (Links between sites that
- * are not neighbours: hlmi_haplotigs_reach below.)
+ * Out of scope: quality weights; joining blocks across a contig.  (Links between sites that are not neighbours:
+ * hlmi_haplotigs_reach below; insertion sites as phasing evidence: hlmi_haplotigs_ins below.)
  * Refusals (HLMI_EINVAL unless said otherwise, nothing is written): hlmi_phase's option refusals, in its order; min_side < 1; then
  * every refusal hlmi_phase makes about the files, the rows, the list and its tables, in its order; the rows' interval table does not
  * fit the device's free memory; hlmi_polish's limits (2^28 bases in a sequence, 2^31 contig bases).
@@ -1292,6 +1292,59 @@ int hlmi_haplotigs_reach(const char *contigs, const char *reads, const char *paf
 /* hlmi_haplotigs_reads in the same way: hlmi_ava and hlmi_haplotigs_reach in one call, without the PAF. */
 int hlmi_haplotigs_reads_reach(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_haplotig_opts *o, int reach,
                                const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_stats *st);
+
+/* ---- haplotigs over blocks with insertion sites: hlmi_haplotigs and its _reach form phase the position sites alone, so a strain
+ * that differs from the contig by insertions alone is phased by hlmi_phase_ins and written by nobody: the majority vote never opens
+ * its slots.  These calls polish each side of hlmi_phase_ins's split blocks.  hlmi_haplotigs_ins reads a PAF as hlmi_phase_ins does,
+ * hlmi_haplotigs_reads_ins aligns in the call as hlmi_phase_reads_ins does.  New symbols: the older calls keep their signatures and
+ * their bytes, and HLMI_ABI_VERSION stays where it is.  A function of the project's own: PARITY UNPINNED;
+ * tests/haplotigs_ins_model.py is the contract, byte for byte. */
+typedef struct {
+    hlmi_haplotig_stats base;       /* as hlmi_haplotigs_reach's; its phase part holds hlmi_phase_ins's values of the shared fields,
+                                       over the merged list of sites (the thirteen variant fields stay hlmi_variants's)            */
+    uint64_t slots_callable;        /* the seven insertion counters of hlmi_phase_ins_stats, with its values, by the same code      */
+    uint64_t ins_sites;
+    uint64_t ins_long;
+    uint64_t ins_edge;
+    uint64_t ins_sites_phasing;
+    uint64_t ins_sites_left_out;
+    uint64_t ins_sites_phased;
+    uint64_t diff_slots;            /* slots inside the extents of split blocks that the two sides opened to different lengths      */
+} hlmi_haplotig_ins_stats;
+/* contigs, reads, paf, o, reach, pairs_paf and the two files: as for hlmi_haplotigs_reach.  The rules of hlmi_haplotigs hold except
+ * where changed here.
+ * Phasing: hlmi_phase_ins's at the same reach, run by the same code: the merged list of position sites and the insertion sites that
+ * take part, alleles, links, blocks, bridged sites and records.  A row's side in a block is A if hap_a > hap_b of its record, B if
+ * hap_b > hap_a, none otherwise.  Side A holds the own allele at the block's first site; at an insertion site the own allele is
+ * "inserts nothing".
+ * Extent: a split block's extent lies in hlmi_phase_ins's key space - slot p has key 2 p, position p key 2 p + 1 - and is [kf, kl],
+ * the keys of its first and its last site.  Position p is inside iff kf <= 2 p + 1 <= kl, slot p iff kf <= 2 p <= kl.  Between two
+ * position sites that is hlmi_haplotigs's rule: positions [first, last], slots (first, last].  An extent that starts at an insertion
+ * site at slot p shuts the other side's rows out of slot p as well; one that ends at an insertion site at slot p shuts them out of
+ * slot p and not out of position p.  Every extent holds a position; extents never overlap.
+ * Who votes, decisions, out_fa: hlmi_haplotigs's rules 3, 4, 5 and 7 with these inside tests - so an insertion site inside a split
+ * block is decided per side: the side whose rows insert opens the slot, the other keeps it shut.  positions_split and HP:i: count
+ * the positions inside, ((kl - 1) >> 1) - (kf >> 1) + 1 per extent.
+ * out_blocks: the nine columns of hlmi_haplotigs and a tenth, diff_slots.  block is the id hlmi_phase_ins prints: the printed pos of
+ * the first site, with a trailing '+' where that is an insertion site.  start and end are the printed pos of the first and the last
+ * site, each with a trailing '+' when that site is an insertion site.  sites counts both kinds, bridged sites included.
+ * diff_positions runs over the positions inside.  diff_slots is the number of slots inside the extent whose opened length differs
+ * between the two sides - a shut slot has length 0, the bases play no part - and 0 when the block is not split; st->diff_slots is
+ * the sum over the blocks.
+ * Where no insertion site takes part, out_fa is byte for byte hlmi_haplotigs_reach's at the same reach, out_blocks is its file with
+ * the tenth column (0) added, and st->base equals its stats in every integer field.  With no split block hlmi_polish's count pass
+ * gives the bytes and no kernel of csrc/haplotigs.hip is launched, as in hlmi_haplotigs.
+ * Out of scope: quality weights; joining blocks across a contig; insertions of more than 16 bases (hlmi_polish's cap: such a row
+ * reads "other" at the site and opens no slot).
+ * Refusals: hlmi_haplotigs_reach's, in its order, under these names.  None of their own: a row's interval holds two 32-bit keys and
+ * the shut side in 12 bytes, and hlmi_polish's limit of 2^31 contig bases keeps 2 p + 1 below 2^32.
+ * Device: as hlmi_haplotigs; the records are hlmi_phase_ins's, 9 bytes per block go up (kf, kl, split flag), the count pass and the
+ * slot passes run in their key-space instantiations (csrc/haplotigs.hip). */
+int hlmi_haplotigs_ins(const char *contigs, const char *reads, const char *paf, const hlmi_haplotig_opts *o, int reach,
+                       const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_ins_stats *st);
+/* hlmi_haplotigs_reads_reach in the same way: hlmi_ava and hlmi_haplotigs_ins in one call, without the PAF. */
+int hlmi_haplotigs_reads_ins(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_haplotig_opts *o, int reach,
+                             const char *pairs_paf, const char *out_fa, const char *out_blocks, hlmi_haplotig_ins_stats *st);
 
 /* ---- staged multi-GPU job: sketch shard -> (RCCL all-gather by the caller) -> run -------- */
 /* One process per GPU.  Every rank opens the same files, sketches its slice of the query
