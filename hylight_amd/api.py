@@ -185,6 +185,17 @@ class VariantInsStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in VARIANT_INS_STATS] + [(k, C.c_double) for k in POLISH_MS]
 
 
+class VariantQOpts(C.Structure):
+    _fields_ = list(VariantOpts._fields_) + [("min_base_qual", C.c_int), ("min_avg_qual", C.c_double)]
+
+
+VARIANT_QCOUNTS = ("reads_with_qual", "rows_low_qual", "columns_low_qual")
+
+
+class VariantQCounts(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in VARIANT_QCOUNTS]
+
+
 class PhaseOpts(C.Structure):
     _fields_ = list(VariantOpts._fields_) + [("min_link", C.c_int), ("min_agree", C.c_double)]
 
@@ -339,6 +350,16 @@ SYMBOLS = {
                                     C.c_char_p, C.POINTER(VariantInsStats)]),
     "hlmi_variants_reads_ins": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(VariantOpts), C.c_char_p, C.c_char_p,
                                           C.c_char_p, C.c_char_p, C.POINTER(VariantInsStats)]),
+    # ... with base qualities: a per-base floor and a read floor
+    "hlmi_variant_qopts_default": (None, [C.POINTER(VariantQOpts)]),
+    "hlmi_variants_q": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VariantQOpts), C.c_char_p, C.c_char_p, C.c_char_p,
+                                  C.POINTER(VariantStats), C.POINTER(VariantQCounts)]),
+    "hlmi_variants_reads_q": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(VariantQOpts), C.c_char_p, C.c_char_p,
+                                        C.c_char_p, C.POINTER(VariantStats), C.POINTER(VariantQCounts)]),
+    "hlmi_variants_ins_q": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(VariantQOpts), C.c_char_p, C.c_char_p, C.c_char_p,
+                                      C.c_char_p, C.POINTER(VariantInsStats), C.POINTER(VariantQCounts)]),
+    "hlmi_variants_reads_ins_q": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(AvaOpts), C.POINTER(VariantQOpts), C.c_char_p, C.c_char_p,
+                                            C.c_char_p, C.c_char_p, C.POINTER(VariantInsStats), C.POINTER(VariantQCounts)]),
     # phased variant sites
     "hlmi_phase_opts_default": (None, [C.POINTER(PhaseOpts)]),
     "hlmi_phase": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(PhaseOpts), C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
@@ -949,6 +970,61 @@ def variants_ins_reads(contigs, reads, out_sites, out_ins, out_summary=None, ava
     _check(load().hlmi_variants_reads_ins(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
                                           _b(pairs), _b(out_sites), _b(out_summary), _b(out_ins), C.byref(st)))
     return {k: getattr(st, k) for k in VARIANT_INS_STATS + POLISH_MS}
+
+
+def _variant_qopts(who, opts):
+    o = VariantQOpts()
+    load().hlmi_variant_qopts_default(C.byref(o))
+    for k, v in opts.items():
+        if k not in dict(VariantQOpts._fields_):
+            raise TypeError(f"{who}: unknown option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def _variant_qstats(st, qc, keys):
+    return {**{k: getattr(st, k) for k in keys + POLISH_MS}, **{k: getattr(qc, k) for k in VARIANT_QCOUNTS}}
+
+
+def variants_q(contigs, reads, paf, out_sites, out_summary=None, pairs=None, **opts):
+    """hlmi_variants_q: api.variants with base qualities - a column whose Phred is below min_base_qual (default 10; 0: off) casts no
+    vote, as an N column casts none, and the rows of a read whose mean Phred is below min_avg_qual (default 10.0; 0.0: off) are
+    dropped as api.polish_q drops them.  The counts stay counts of reads.  FASTA records pass every floor; both floors 0 give
+    api.variants's files.  include/hylight_mi.h states it, tests/variants_qual_model.py is its contract.
+    -> dict of the stats (hlmi_variant_stats) with reads_with_qual, rows_low_qual and columns_low_qual (hlmi_variant_qcounts)."""
+    o, st, qc = _variant_qopts("variants_q", opts), VariantStats(), VariantQCounts()
+    _check(load().hlmi_variants_q(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(pairs), _b(out_sites), _b(out_summary), C.byref(st),
+                                  C.byref(qc)))
+    return _variant_qstats(st, qc, VARIANT_STATS)
+
+
+def variants_reads_q(contigs, reads, out_sites, out_summary=None, ava_opts=None, pairs=None, **opts):
+    """hlmi_variants_reads_q: `ava(contigs, reads, P, ava_opts)` and `variants_q(contigs, reads, P, ...)` in one call without the
+    PAF P: the same files and the same integer stats.  -> as variants_q."""
+    o, st, qc = _variant_qopts("variants_reads_q", opts), VariantStats(), VariantQCounts()
+    _check(load().hlmi_variants_reads_q(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
+                                        _b(pairs), _b(out_sites), _b(out_summary), C.byref(st), C.byref(qc)))
+    return _variant_qstats(st, qc, VARIANT_STATS)
+
+
+def variants_ins_q(contigs, reads, paf, out_sites, out_ins, out_summary=None, pairs=None, **opts):
+    """hlmi_variants_ins_q: api.variants_ins with the floors of variants_q.  out_sites is the file variants_q writes; a column
+    below the base floor still spans its slot, and the slots' own counts take no quality into account: out_ins differs from
+    api.variants_ins's only through rows the read floor dropped.  -> dict of the stats (hlmi_variant_ins_stats) with the three
+    counters of hlmi_variant_qcounts."""
+    o, st, qc = _variant_qopts("variants_ins_q", opts), VariantInsStats(), VariantQCounts()
+    _check(load().hlmi_variants_ins_q(_b(contigs), _b(reads), _b(paf), C.byref(o), _b(pairs), _b(out_sites), _b(out_summary),
+                                      _b(out_ins), C.byref(st), C.byref(qc)))
+    return _variant_qstats(st, qc, VARIANT_INS_STATS)
+
+
+def variants_ins_reads_q(contigs, reads, out_sites, out_ins, out_summary=None, ava_opts=None, pairs=None, **opts):
+    """hlmi_variants_reads_ins_q: `ava(contigs, reads, P, ava_opts)` and `variants_ins_q(contigs, reads, P, ...)` in one call
+    without the PAF P: the same files and the same integer stats.  -> as variants_ins_q."""
+    o, st, qc = _variant_qopts("variants_ins_reads_q", opts), VariantInsStats(), VariantQCounts()
+    _check(load().hlmi_variants_reads_ins_q(_b(contigs), _b(reads), C.byref(ava_opts) if ava_opts is not None else None, C.byref(o),
+                                            _b(pairs), _b(out_sites), _b(out_summary), _b(out_ins), C.byref(st), C.byref(qc)))
+    return _variant_qstats(st, qc, VARIANT_INS_STATS)
 
 
 def _phase_opts(who, opts):

@@ -666,6 +666,57 @@ int hlmi_variants_reads_ins(const char *contigs, const char *reads, const hlmi_a
     });
 }
 
+void hlmi_variant_qopts_default(hlmi_variant_qopts *o) {
+    if (o) *o = hlmi_variant_qopts{0, 0.0, 3, 2, 0.2, 10, 10.0};
+}
+
+// the _q forms refuse in the header's order: the floors (they need o), then out_ins == NULL (ins), then the other arguments
+static void variant_q_arguments(const char *who, const hlmi_variant_qopts *o, bool ins, const char *out_ins, bool others) {
+    if (!o) fail(HLMI_EINVAL, "%s: NULL argument", who);
+    var::check_variant_qfloors(who, *o);
+    if (ins && !out_ins) fail(HLMI_EINVAL, "%s: out_ins is NULL", who);
+    if (!others) fail(HLMI_EINVAL, "%s: NULL argument", who);
+}
+
+int hlmi_variants_q(const char *contigs, const char *reads, const char *paf, const hlmi_variant_qopts *o, const char *pairs_paf,
+                    const char *out_sites, const char *out_summary, hlmi_variant_stats *st, hlmi_variant_qcounts *qc) {
+    return guarded([&] {
+        variant_q_arguments("hlmi_variants_q", o, false, nullptr, contigs && reads && paf && out_sites && st && qc);
+        require_device();
+        variants_q_run(contigs, reads, paf, *o, pairs_paf, out_sites, out_summary, st, qc);
+    });
+}
+
+int hlmi_variants_reads_q(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_variant_qopts *o,
+                          const char *pairs_paf, const char *out_sites, const char *out_summary, hlmi_variant_stats *st,
+                          hlmi_variant_qcounts *qc) {
+    return guarded([&] {
+        variant_q_arguments("hlmi_variants_reads_q", o, false, nullptr, contigs && reads && out_sites && st && qc);
+        require_device();
+        variants_reads_q_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_sites, out_summary, st, qc);
+    });
+}
+
+int hlmi_variants_ins_q(const char *contigs, const char *reads, const char *paf, const hlmi_variant_qopts *o, const char *pairs_paf,
+                        const char *out_sites, const char *out_summary, const char *out_ins, hlmi_variant_ins_stats *st,
+                        hlmi_variant_qcounts *qc) {
+    return guarded([&] {
+        variant_q_arguments("hlmi_variants_ins_q", o, true, out_ins, contigs && reads && paf && out_sites && st && qc);
+        require_device();
+        variants_ins_q_run(contigs, reads, paf, *o, pairs_paf, out_sites, out_summary, out_ins, st, qc);
+    });
+}
+
+int hlmi_variants_reads_ins_q(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_variant_qopts *o,
+                              const char *pairs_paf, const char *out_sites, const char *out_summary, const char *out_ins,
+                              hlmi_variant_ins_stats *st, hlmi_variant_qcounts *qc) {
+    return guarded([&] {
+        variant_q_arguments("hlmi_variants_reads_ins_q", o, true, out_ins, contigs && reads && out_sites && st && qc);
+        require_device();
+        variants_reads_ins_q_run(contigs, reads, ao ? *ao : ava_opts_long(), *o, pairs_paf, out_sites, out_summary, out_ins, st, qc);
+    });
+}
+
 void hlmi_phase_opts_default(hlmi_phase_opts *o) {
     if (o) *o = hlmi_phase_opts{0, 0.0, 3, 2, 0.2, 3, 0.8};
 }

@@ -197,7 +197,8 @@ void rows_from_paf(const char *contigs, const char *reads, const char *paf, cons
         return R.upload_tiles();
     }
     PolDevIn in;
-    paf_rows_input(S, L, q.qc && q.qc->qual_weight, in, R.ins_edge, R.ins_long);
+    refill_missing_quals(q, S.rs, S.rq);
+    paf_rows_input(S, L, quals_travel(q), in, R.ins_edge, R.ins_long);
     in.contigs = std::move(L.contigs);
     in.cbase = L.cbase;
     in.tiles = std::move(L.tiles);

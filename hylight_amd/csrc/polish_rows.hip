@@ -320,7 +320,10 @@ void rows_from_reads(const char *contigs, const char *reads, const hlmi_ava_opts
     R.n_rows = sel.n_rows;
     R.t_dev = sel.t_dev;
     polish_check_weight_width(q.who.quals, q.qc, S);
-    if (!q.spans_only) return device_rows_input(R, q.who.seqs, q.qc && q.qc->qual_weight);
+    if (!q.spans_only) {
+        refill_missing_quals(q, sel.rs, sel.rq);
+        return device_rows_input(R, q.who.seqs, quals_travel(q));
+    }
 
     // the spans: all that is read of the selected rows, and all that comes back of them for the layout
     R.d_spans.alloc(std::max<size_t>(S, 1));

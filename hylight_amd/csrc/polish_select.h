@@ -70,7 +70,18 @@ struct RowsRequest {
     bool spans_only = false;            // hlmi_depth: no contig bytes, no PolRow, no CIGAR, no reads - spans, tiles and cbase only
     bool check_quals = false;           // rows_from_paf with no qc: read the quality strings all the same and refuse bad ones (no
                                         // floor, no weights).  rows_from_reads reads none without qc, whatever this says
+    uint8_t quals_fill = 0;             // with qc, not 0: the quality bytes travel with the reads though no vote is weighted (no
+                                        // polish_check_weight_width: that is qual_weight's), and a record without a quality
+                                        // string travels as this byte, not as SeqQual's '!' (the variant calls' base floor)
 };
+// do the quality bytes go to the device?
+inline bool quals_travel(const RowsRequest &q) { return q.qc && (q.qc->qual_weight || q.quals_fill); }
+// quals_fill: the records without a quality string, refilled in place (the read floor was judged before: such a read is never low)
+inline void refill_missing_quals(const RowsRequest &q, const SeqSet &rs, SeqQual &rq) {
+    if (!q.qc || !q.quals_fill) return;
+    for (size_t i = 0; i < rs.size() && i < rq.has_qual.size(); ++i)
+        if (!rq.has_qual[i]) std::fill(rq.quals.begin() + rs.off[i], rq.quals.begin() + rs.off[i + 1], (char)q.quals_fill);
+}
 // the request of the calls that have one name in every refusal, no _q part and checked quality strings: all but hlmi_polish*
 inline RowsRequest plain_request(const char *who, int min_len, double min_iden, const char *pairs_paf, bool spans_only = false) {
     return RowsRequest{SelectNames{who, who, who, true}, min_len, min_iden, nullptr, pairs_paf, spans_only, true};

@@ -22,12 +22,19 @@
 // site, their order is the order of the selected flags - ascending by construction, whatever order the atomics ran in.  The
 // price is that the tiles with a site are counted twice (DESIGN.md section 4.3j has the byte formula).  With no site the select
 // over the tiles and the second pass are not launched.  Every loop is bounded by a count known at its head.
+// QF (hlmi_variants_q and its forms with min_base_qual > 0): a column whose Phred lies below the floor casts no vote, as an N
+// column casts none (variants_qual.h has the judgement; with INS it still spans: C_OTHER).  The quality byte is fetched at the
+// index column_symbol fetches the base at; a D op's pass or fail is its lane's, once per op, and travels as wd through
+// vote_columns<true>.  The withheld votes are counted per lane, summed per wave, then in one LDS word, and reach one 64-bit
+// counter of the call with one global atomic per workgroup - in pass 1 only.  No LDS plane is added.  QF = false is the kernel
+// as it was: no quality byte is read.
 #include <hip/hip_runtime.h>
 
 #include "common.h"
 #include "dev_prims.h"
 #include "polish_walk.h"
 #include "variants_internal.h"
+#include "variants_qual.h"
 #include "wave_ops.h"
 
 namespace hlmi {
@@ -81,13 +88,18 @@ struct VarArgs {
     uint32_t n_ins;
     InsRec *ins_recs;
     uint8_t *ins_voted;
+    // QF: the quality bytes, indexed exactly like `reads` by PolRow::read_off; the floor (1..93); pass 1 out: the withheld votes
+    const uint8_t *quals;
+    uint32_t min_base_qual;
+    unsigned long long *low_count;
 };
 
-template <int ENC, bool EMIT, bool INS>
+template <int ENC, bool EMIT, bool INS, bool QF>
 __global__ __launch_bounds__(POLISH_WG) void var_tile_kernel(const VarArgs A) {
     constexpr int N_CNT = INS ? N_CNT_INS : N_SYM, N_TOT = INS ? 5 : 3;
+    constexpr int N_WORDS = N_TOT + (QF && !EMIT ? 1 : 0);         // QF, pass 1: the workgroup's withheld votes behind the totals
     __shared__ uint32_t s_cnt[N_CNT][POLISH_TILE];
-    __shared__ uint32_t s_tot[N_TOT];
+    __shared__ uint32_t s_tot[N_WORDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint32_t tile = blockIdx.x;
     if constexpr (EMIT) {
@@ -98,16 +110,30 @@ __global__ __launch_bounds__(POLISH_WG) void var_tile_kernel(const VarArgs A) {
     const PolTile t = A.tiles[tile];
     const uint32_t n_pos = min(t.n_pos, (uint32_t)POLISH_TILE), t_end = t.t0 + n_pos;
     for (int i = tid; i < N_CNT * POLISH_TILE; i += POLISH_WG) (&s_cnt[0][0])[i] = 0;
-    if (tid < N_TOT) s_tot[tid] = 0;
+    if (tid < N_WORDS) s_tot[tid] = 0;
     __syncthreads();
+    uint32_t n_low = 0;                         // QF: the votes this lane withheld (a tile has at most POLISH_TILE x rows columns)
     const uint32_t row_hi = min(t.row_hi, A.n_rows);
     for (uint32_t k = t.row_lo + (uint32_t)wave; k < row_hi; k += POLISH_WAVES) {
         const PolRow r = A.rows[k];
         if (r.te <= t.t0 || r.ts >= t_end) continue;
         if constexpr (INS)
             if (lane == 0 && r.ts >= t.t0) atomicAdd(&s_cnt[C_START][r.ts - t.t0], 1u);        // r.ts < t_end
-        auto vote = [&](uint32_t p, uint32_t code, uint32_t tp0, uint32_t qc0, uint32_t) {
-            const uint32_t s = code == OP_D ? (uint32_t)SYM_DEL : column_symbol<ENC>(r, A.reads, qc0 + (p - tp0));
+        auto vote = [&](uint32_t p, uint32_t code, uint32_t tp0, uint32_t qc0, uint32_t wd) {
+            uint32_t s = code == OP_D ? (uint32_t)SYM_DEL : column_symbol<ENC>(r, A.reads, qc0 + (p - tp0));
+            if constexpr (QF) {
+                // A column that votes anyway (an N, another byte: s == C_OTHER) is not judged.  s < 4: column_symbol found
+                // col < r.qn, so vq_index(...) < r.qn and the byte lies inside [read_off, read_off + qn) - the argument that
+                // covers the base fetch.  A D column carries its op's verdict (wd: 1 passes, 0 fails).
+                if (s < (uint32_t)N_SYM) {
+                    const bool pass = code == OP_D ? wd != 0u
+                                                   : vq_byte_passes(A.quals[r.read_off + vq_index(r.qn, r.rev, qc0 + (p - tp0))], A.min_base_qual);
+                    if (!pass) {
+                        s = (uint32_t)C_OTHER;
+                        if constexpr (!EMIT) ++n_low;
+                    }
+                }
+            }
             // t.t0 <= p < t_end: [a, b) is clipped.  INS counts the column that votes nothing too (s == C_OTHER): it spans
             if (s < (uint32_t)(INS ? C_OTHER + 1 : N_SYM)) atomicAdd(&s_cnt[s][p - t.t0], 1u);
         };
@@ -120,7 +146,10 @@ __global__ __launch_bounds__(POLISH_WG) void var_tile_kernel(const VarArgs A) {
                 a = max(tp0, t.t0);
                 b = max(a, min(tp0 + len, t_end));
             }
-            vote_columns<false>(a, b, code, tp0, qc0, 1u, lane, vote);
+            uint32_t wd = 1u;                   // QF: a D op's pass or fail, once per op, by its lane; its flanks are tested
+            if constexpr (QF)                   // against [0, r.qn) inside vq_del_passes, whose bytes are the row's stretch
+                if (code == OP_D && b > a) wd = vq_del_passes(A.quals + r.read_off, r.qn, r.rev, qc0, A.min_base_qual) ? 1u : 0u;
+            vote_columns<QF>(a, b, code, tp0, qc0, wd, lane, vote);
         });
     }
     __syncthreads();
@@ -193,8 +222,14 @@ __global__ __launch_bounds__(POLISH_WG) void var_tile_kernel(const VarArgs A) {
                 if (w_ins) atomicAdd(&s_tot[4], w_ins);
             }
         }
+        if constexpr (QF) {
+            const uint32_t w_low = (uint32_t)__builtin_amdgcn_readlane((int)wave_prefix_sum_incl_dpp(n_low), 63);
+            if (lane == 0 && w_low) atomicAdd(&s_tot[N_TOT], w_low);
+        }
         __syncthreads();
         if (tid == 0) {
+            if constexpr (QF)
+                if (s_tot[N_TOT]) atomicAdd(A.low_count, (unsigned long long)s_tot[N_TOT]);
             const uint32_t j = slot_of_position(A.cbase, A.n_slots, t.cbase);
             if (s_tot[0]) atomicAdd(&A.slot_counts[j], (unsigned long long)s_tot[0]);
             if (s_tot[1]) atomicAdd(&A.slot_counts[A.n_slots + j], (unsigned long long)s_tot[1]);
@@ -243,12 +278,18 @@ __global__ void gather_u32_kernel(const uint32_t *__restrict__ from, const uint3
     if (i < n) out[i] = from[at[i]];
 }
 
+template <bool EMIT, bool INS, bool QF>
+void launch_tiles_of(ReadEnc enc, const VarArgs &a, uint32_t n_blocks) {
+    if (enc == READS_CODES)
+        hipLaunchKernelGGL((var_tile_kernel<READS_CODES, EMIT, INS, QF>), dim3(n_blocks), dim3(POLISH_WG), 0, stream(), a);
+    else hipLaunchKernelGGL((var_tile_kernel<READS_ASCII, EMIT, INS, QF>), dim3(n_blocks), dim3(POLISH_WG), 0, stream(), a);
+    HIP_CHECK(hipGetLastError());
+}
+// a.quals == nullptr: no floor, the kernel as it always was
 template <bool EMIT, bool INS>
 void launch_tiles(ReadEnc enc, const VarArgs &a, uint32_t n_blocks) {
-    if (enc == READS_CODES)
-        hipLaunchKernelGGL((var_tile_kernel<READS_CODES, EMIT, INS>), dim3(n_blocks), dim3(POLISH_WG), 0, stream(), a);
-    else hipLaunchKernelGGL((var_tile_kernel<READS_ASCII, EMIT, INS>), dim3(n_blocks), dim3(POLISH_WG), 0, stream(), a);
-    HIP_CHECK(hipGetLastError());
+    if (a.quals) launch_tiles_of<EMIT, INS, true>(enc, a, n_blocks);
+    else launch_tiles_of<EMIT, INS, false>(enc, a, n_blocks);
 }
 
 // The slot passes of the _ins calls over the n_ins insertion sites at d_ins_pos, whose records hold (pos, s, i, l) and whose
@@ -276,9 +317,11 @@ size_t ins_slot_passes(const PolCoreIn &in, const uint32_t *d_ins_pos, size_t n_
     return n_v;
 }
 
-// ins == nullptr: hlmi_variants's device part as it always was
+// ins == nullptr: hlmi_variants's device part as it always was.  min_base_qual > 0 (the _q calls; in.quals is then set unless
+// there is no read byte at all): the floor, and *low gets the withheld votes; 0: no quality byte is read, *low stays 0.
 template <bool INS>
-void core_impl(const PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &out, DeviceInsertions *ins) {
+void core_impl(const PolCoreIn &in, const hlmi_variant_opts &o, int min_base_qual, DeviceVariants &out, DeviceInsertions *ins,
+               uint64_t *low) {
     constexpr size_t N_COUNTS = INS ? 5 : 3;
     out = DeviceVariants{};
     const size_t G = in.n_contig;               // < 2^31 (polish_layout)
@@ -295,10 +338,11 @@ void core_impl(const PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &
     if (!G || !n_slots || !in.n_tiles) return;
     if (in.n_tiles >= (1ull << 32)) fail(HLMI_EINVAL, "hlmi_variants: %zu tiles (2^32 and more)", in.n_tiles);      // (never: G < 2^31)
     DBuf<uint8_t> d_flag(G), d_tile_flag(in.n_tiles), d_ins_flag(INS ? G : 0);
-    DBuf<unsigned long long> d_counts(N_COUNTS * (size_t)n_slots);
+    DBuf<unsigned long long> d_counts(N_COUNTS * (size_t)n_slots), d_low(1);
     d_flag.zero();                              // positions of a covered contig that no tile holds: no site
     d_ins_flag.zero();
     d_counts.zero();
+    d_low.zero();
     VarArgs a{};
     a.rows = in.rows; a.n_rows = in.n_rows;
     a.ops = in.ops;
@@ -308,11 +352,15 @@ void core_impl(const PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &
     a.min_cov = (uint32_t)o.min_cov; a.min_alt = (uint32_t)o.min_alt; a.min_frac = o.min_frac;
     a.flag = d_flag.p; a.tile_flag = d_tile_flag.p; a.slot_counts = d_counts.p;
     a.ins_flag = d_ins_flag.p;
+    if (min_base_qual > 0 && in.quals) {
+        a.quals = in.quals; a.min_base_qual = (uint32_t)min_base_qual; a.low_count = d_low.p;
+    }
     {
         KTimer kt("variants_tile");
         launch_tiles<false, INS>(in.enc, a, (uint32_t)in.n_tiles);
     }
     const std::vector<unsigned long long> counts = d_counts.download(N_COUNTS * (size_t)n_slots);
+    if (low && a.quals) *low = download_one(d_low.p);
     uint64_t n_sites = 0, n_ins = 0;
     for (uint32_t j = 0; j < n_slots; ++j) {
         out.callable[j] = counts[j];
@@ -360,10 +408,23 @@ void core_impl(const PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &
 
 }  // namespace
 
-void variants_core(const PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &out) { core_impl<false>(in, o, out, nullptr); }
+void variants_core(const PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &out) {
+    core_impl<false>(in, o, 0, out, nullptr, nullptr);
+}
 
 void variants_ins_core(const PolCoreIn &in, const hlmi_variant_opts &o, DeviceVariants &out, DeviceInsertions &ins) {
-    core_impl<true>(in, o, out, &ins);
+    core_impl<true>(in, o, 0, out, &ins, nullptr);
+}
+
+void variants_q_core(const PolCoreIn &in, const hlmi_variant_opts &o, int min_base_qual, DeviceVariants &out, uint64_t &columns_low_qual) {
+    columns_low_qual = 0;
+    core_impl<false>(in, o, min_base_qual, out, nullptr, &columns_low_qual);
+}
+
+void variants_ins_q_core(const PolCoreIn &in, const hlmi_variant_opts &o, int min_base_qual, DeviceVariants &out, DeviceInsertions &ins,
+                         uint64_t &columns_low_qual) {
+    columns_low_qual = 0;
+    core_impl<true>(in, o, min_base_qual, out, &ins, &columns_low_qual);
 }
 
 }  // namespace var

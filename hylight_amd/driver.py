@@ -212,7 +212,7 @@ def depth_tables(final, long_reads, short_reads, outdir, device=None):
     return out
 
 
-def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None, ins=False):
+def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None, ins=False, qual=None):
     """`--variants`: the variant sites of the final contigs (hlmi_variants_reads: the reads are aligned to the contigs in the
     call, every pair, one row per read) - is each contig one strain?  The long reads - the filtered ones the overlap stage read -
     with the overlapper's long constants give outdir/final_contigs.long.variants.tsv and .long.variants.summary.tsv; short reads,
@@ -221,6 +221,8 @@ def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pai
     know counts in pairs_unknown.  `device`: the GPU to initialise the library on (None: the caller has done so).
     ins (`--variants_ins`): hlmi_variants_reads_ins takes the call's place - the same two files (the summary with three columns
     more) and the insertion sites in .variants.ins.tsv beside them; still one call per read set.
+    qual (`--variants_qual`): dict(min_base_qual=, min_avg_qual=) - the _q form of either call takes its place, the file names
+    stay; FASTA reads pass every floor (the identity), FASTQ reads are where it bites.
     -> {"long": stats, "short": stats}."""
     if device is not None:
         api.init(device)
@@ -231,11 +233,22 @@ def variant_tables(final, long_reads, short_reads, outdir, device=None, long_pai
         o = api.ava_opts_short() if kind == "short" else api.ava_opts_long()
         o.pair_once = 0
         stem = os.path.join(outdir, f"final_contigs.{kind}.variants")
-        if ins:
+        if qual is not None and ins:
+            out[kind] = api.variants_ins_reads_q(final, reads, stem + ".tsv", stem + ".ins.tsv", stem + ".summary.tsv", o, pairs=pairs, **qual)
+        elif qual is not None:
+            out[kind] = api.variants_reads_q(final, reads, stem + ".tsv", stem + ".summary.tsv", o, pairs=pairs, **qual)
+        elif ins:
             out[kind] = api.variants_ins_reads(final, reads, stem + ".tsv", stem + ".ins.tsv", stem + ".summary.tsv", o, pairs=pairs)
         else:
             out[kind] = api.variants_reads(final, reads, stem + ".tsv", stem + ".summary.tsv", o, pairs=pairs)
     return out
+
+
+def variants_qual_args(args):
+    """`--variants_qual` as variant_tables takes it (nothing without the flag: the calls made before it existed are made)"""
+    if not args.variants_qual:
+        return {}
+    return {"qual": dict(min_base_qual=args.variants_min_base_qual, min_avg_qual=args.variants_min_avg_qual)}
 
 
 def phase_tables(final, long_reads, short_reads, outdir, device=None, long_pairs=None, short_pairs=None, reach=1, ins=False):
@@ -360,6 +373,15 @@ def build_parser():
                    help="(extension) as --variants, with the insertion sites of the contigs beside the two files "
                         "(hlmi_variants_reads_ins) in final_contigs.long.variants.ins.tsv, and with -s also the .short. one; the "
                         "summary gains slots, ins_sites and ins_rate; with --variants too, still one call per read set")
+    p.add_argument("--variants_qual", action="store_true",
+                   help="(extension) with --variants / --variants_ins: base qualities take part (hlmi_variants_reads_q, "
+                        "hlmi_variants_reads_ins_q) - a column below --variants_min_base_qual casts no vote, the rows of a read whose "
+                        "mean quality is below --variants_min_avg_qual are dropped; the same file names; FASTA reads pass every "
+                        "floor, so it is the short-read FASTQ where this bites; refused without --variants or --variants_ins")
+    p.add_argument("--variants_min_base_qual", type=int, default=10, metavar="Q",
+                   help="with --variants_qual: the per-base floor, a Phred of 0..93 (0: off); no real data stands behind the default")
+    p.add_argument("--variants_min_avg_qual", type=float, default=10.0, metavar="Q",
+                   help="with --variants_qual: the read floor, --polish_min_avg_qual's rule and default (0: off)")
     p.add_argument("--phase", action="store_true",
                    help="(extension) when final_contigs.fa is written: its variant sites phased from the reads (hlmi_phase_reads) "
                         "into final_contigs.long.phase.sites.tsv, .links.tsv and .reads.tsv, and with -s also the .short. triple; "
@@ -490,6 +512,8 @@ def refuse_polyte_workers(args):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     args = build_parser().parse_args(argv)
+    if args.variants_qual and not (args.variants or args.variants_ins):
+        raise SystemExit("--variants_qual puts quality floors into the calls of --variants / --variants_ins: give one of them as well")
     if args.phase_ins and not args.phase:
         raise SystemExit("--phase_ins adds insertion sites to the files of --phase: give --phase as well")
     if args.haplotigs_ins and not args.haplotigs:
@@ -633,7 +657,7 @@ def _pipeline(args, pool):
         if rc == 0 and (args.variants or args.variants_ins):
             variant_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
                            long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None,
-                           **({"ins": True} if args.variants_ins else {}))
+                           **({"ins": True} if args.variants_ins else {}), **variants_qual_args(args))
         if rc == 0 and args.phase:
             phase_tables(os.path.join(outdir, "final_contigs.fa"), infile, short_reads, outdir,
                          long_pairs=ov_long_ref if args.polish_strain else None, short_pairs=ov_short if args.polish_strain else None,
@@ -680,7 +704,8 @@ def _pipeline(args, pool):
         depth_tables(final, infile, short_reads, outdir)
     if args.variants or args.variants_ins:
         variant_tables(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
-                       short_pairs=ov_short if args.polish_strain else None, **({"ins": True} if args.variants_ins else {}))
+                       short_pairs=ov_short if args.polish_strain else None, **({"ins": True} if args.variants_ins else {}),
+                       **variants_qual_args(args))
     if args.phase:
         phase_tables(final, infile, short_reads, outdir, long_pairs=ov_long_ref if args.polish_strain else None,
                      short_pairs=ov_short if args.polish_strain else None, **({"reach": args.phase_reach} if args.phase_reach != 1 else {}),

@@ -17,6 +17,9 @@ length, reads, callable, sites, site_rate).  Prints the stats as one JSON line. 
 --ins FILE: the insertion sites too (hlmi_variants_ins / hlmi_variants_reads_ins) - the slots where rows that insert bases the
 contig lacks number --min_alt and make --min_frac of the --min_cov or more rows that span the slot (contig, pos, ref, span, ins,
 ins_long, ins_frac, len, len_count, seq); --out stays the same file, --summary gains slots, ins_sites and ins_rate.
+--min_base_qual N / --min_avg_qual X: base qualities take part (hlmi_variants_q and its _reads and _ins forms) - a column whose
+Phred is below N casts no vote, as an N column casts none, and the rows of a read whose mean Phred is below X are dropped; the
+counts stay counts of reads.  Giving either selects the _q call; without both the calls above are made.  FASTA records pass.
 """
 from __future__ import annotations
 
@@ -47,6 +50,12 @@ def build_parser():
     p.add_argument("--min_cov", type=int, default=3, help="votes a position needs to be callable")
     p.add_argument("--min_alt", type=int, default=2, help="votes the alternative symbol needs")
     p.add_argument("--min_frac", type=float, default=0.2, help="share of the position's votes the alternative symbol needs")
+    p.add_argument("--min_base_qual", type=int, default=None, metavar="N",
+                   help="a column whose Phred is below N (0..93) casts no vote (hlmi_variants_q and its forms; 0: off; given alone, "
+                        "--min_avg_qual is 0; neither given: base qualities take no part)")
+    p.add_argument("--min_avg_qual", type=float, default=None, metavar="X",
+                   help="drop the rows of a read whose mean Phred is below X, as the polisher's --min_avg_qual does (0: off; given "
+                        "alone, --min_base_qual is 0)")
     return p
 
 
@@ -56,7 +65,17 @@ def main(argv=None):
     opts = dict(min_len=a.min_len, min_iden=a.min_iden, min_cov=a.min_cov, min_alt=a.min_alt, min_frac=a.min_frac)
     if a.paf is not None and a.short:
         parser.error("--short chooses the alignment of a call without --paf")
-    if a.ins is not None:
+    if a.min_base_qual is not None or a.min_avg_qual is not None:       # either selects the _q call, with or without --ins
+        opts.update(min_base_qual=a.min_base_qual or 0, min_avg_qual=a.min_avg_qual or 0.0)
+        if a.ins is not None and a.paf is not None:
+            st = api.variants_ins_q(a.contigs, a.reads, a.paf, a.out, a.ins, a.summary, pairs=a.pairs, **opts)
+        elif a.ins is not None:
+            st = api.variants_ins_reads_q(a.contigs, a.reads, a.out, a.ins, a.summary, read_ava_opts(a.short), pairs=a.pairs, **opts)
+        elif a.paf is not None:
+            st = api.variants_q(a.contigs, a.reads, a.paf, a.out, a.summary, pairs=a.pairs, **opts)
+        else:
+            st = api.variants_reads_q(a.contigs, a.reads, a.out, a.summary, read_ava_opts(a.short), pairs=a.pairs, **opts)
+    elif a.ins is not None:
         if a.paf is not None:
             st = api.variants_ins(a.contigs, a.reads, a.paf, a.out, a.ins, a.summary, pairs=a.pairs, **opts)
         else:

@@ -1027,6 +1027,62 @@ int hlmi_variants_reads_ins(const char *contigs, const char *reads, const hlmi_a
                             const char *pairs_paf, const char *out_sites, const char *out_summary, const char *out_ins,
                             hlmi_variant_ins_stats *st);
 
+/* ---- variant calls with base qualities: in the four calls above every vote counts the same, a Q3 base like a Q40 base, which on
+ * noisy reads is the main source of false sites.  The _q forms add what pile-up callers have (samtools mpileup -Q / -q): a
+ * per-base floor - a column below it casts no vote, exactly as an N column casts none - and hlmi_polish_q's read floor.  A floor
+ * and not hlmi_polish_q's weights: min_alt, depth, alt_count and alt_frac are counts of reads and stay counts.  New symbols: the
+ * older calls keep their signatures and their bytes, and HLMI_ABI_VERSION stays where it is.  The default floors 10 and 10.0 are
+ * --polish_min_avg_qual's value; no real data in this repository supports either figure.  A function of the project's own: PARITY
+ * UNPINNED; tests/variants_qual_model.py is the contract, byte for byte. */
+typedef struct {
+    int min_len;              /* the five fields of hlmi_variant_opts, same meaning                                          */
+    double min_iden;
+    int min_cov;
+    int min_alt;
+    double min_frac;
+    int min_base_qual;        /* 0: off; 1..93: a column whose Phred is below it casts no vote                               */
+    double min_avg_qual;      /* 0.0: off; else hlmi_polish_q's read floor, word for word                                    */
+} hlmi_variant_qopts;
+void hlmi_variant_qopts_default(hlmi_variant_qopts *o);   /* 0, 0.0, 3, 2, 0.2, 10, 10.0 */
+typedef struct {
+    uint64_t reads_with_qual;   /* as hlmi_polish_qstats                                                                    */
+    uint64_t rows_low_qual;
+    uint64_t columns_low_qual;  /* (selected row, column) votes withheld by the base floor                                  */
+} hlmi_variant_qcounts;
+/* Where a rule below is silent, the rule of hlmi_variants / hlmi_variants_ins holds.
+ * Qualities: validation, reads_with_qual, the read floor and rows_low_qual follow hlmi_polish_q, run by the same code: a record's
+ * quality string must be as long as its bases and hold bytes of 33..126 only (HLMI_EINVAL naming the record); a read whose mean
+ * Phred is below min_avg_qual is low, and a row whose query is a low read is dropped directly behind the qname == tname skip - in
+ * front of the pair list - and counted in rows_low_qual.  On strand '-', column i has the quality of read[qe - 1 - i].
+ * Column Phred: q = byte - 33.  An '=' / 'X' column whose base is A C G T passes iff q >= min_base_qual.
+ * D op: its q is the lower q of query columns qc - 1 and qc, qc the first query column behind the op, only the columns that exist
+ * inside [0, qe - qs) counting; with neither present the op passes.  All columns of the op pass or fail together.
+ * A failing column casts no vote and counts once in columns_low_qual (in the first pass over the tiles only, never again when a
+ * tile is revisited for its records).  A column that would have voted nothing anyway (N, other bytes) counts nowhere new.  c,
+ * depth, the five counts, callable, ref_other and the site rule then follow from the remaining votes unchanged.
+ * FASTA records have no qualities: every column of such a read passes every floor, and the read is never low.
+ * Slots (the _ins_q forms): a failing column still spans - it is counted where an N column is counted.  span, ins, ins_long,
+ * len, len_count and seq take no quality into account: they differ from hlmi_variants_ins's only through rows the read floor
+ * dropped.  out_sites of an _ins_q call is byte for byte the _q call's.
+ * Refusals (HLMI_EINVAL, nothing is written): min_base_qual outside 0..93, or min_avg_qual negative or not a number, before
+ * anything is read; then out_ins == NULL for the _ins_q forms; then the older call's refusals, in its order.  There is no
+ * rows_selected x 93 refusal: the counters hold counts.
+ * Identities: the calls give the older calls' files and every integer stat byte for byte with min_base_qual = 0 and min_avg_qual =
+ * 0.0; on a FASTA `reads` file at any floors; and on a FASTQ whose bytes all pass and whose reads are all above the read floor.
+ * The _reads_q forms: the files and the integer fields equal the chain hlmi_ava -> hlmi_variants_q (or hlmi_variants_ins_q); the
+ * three stated differences of hlmi_variants_reads still apply. */
+int hlmi_variants_q(const char *contigs, const char *reads, const char *paf, const hlmi_variant_qopts *o, const char *pairs_paf,
+                    const char *out_sites, const char *out_summary, hlmi_variant_stats *st, hlmi_variant_qcounts *qc);
+int hlmi_variants_reads_q(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_variant_qopts *o,
+                          const char *pairs_paf, const char *out_sites, const char *out_summary, hlmi_variant_stats *st,
+                          hlmi_variant_qcounts *qc);
+int hlmi_variants_ins_q(const char *contigs, const char *reads, const char *paf, const hlmi_variant_qopts *o, const char *pairs_paf,
+                        const char *out_sites, const char *out_summary, const char *out_ins, hlmi_variant_ins_stats *st,
+                        hlmi_variant_qcounts *qc);
+int hlmi_variants_reads_ins_q(const char *contigs, const char *reads, const hlmi_ava_opts *ao, const hlmi_variant_qopts *o,
+                              const char *pairs_paf, const char *out_sites, const char *out_summary, const char *out_ins,
+                              hlmi_variant_ins_stats *st, hlmi_variant_qcounts *qc);
+
 /* ---- phased variant sites: do the minor alleles of neighbouring sites ride on the same reads (a collapsed sister strain that can
  * be separated) or not (noise, a mis-join, a polishing error), and which read belongs to which side.  hlmi_phase reads a PAF as
  * hlmi_variants does, hlmi_phase_reads aligns in the call as hlmi_variants_reads does.  New symbols: the older calls keep their
